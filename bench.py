@@ -14,10 +14,16 @@ partition): by default N x the config's block (weak scaling, N x 1800 RFMIP colu
 a 1800-column block); with --global the config's fixed global size (C5: 1e6 synthetic columns x 137
 layers, strong scaling), each rank streaming its range through the step in chunks of at most
 125 000 columns.  No collective in the data path; barrier + synchronize around the timed region, max
-over ranks.  After timing, the broadband fluxes are all-gathered once with shard.gather_columns over
+over ranks.  With --full, after timing, the broadband fluxes are all-gathered once with shard.gather_columns over
 RCCL (the final flux reduction the north star names), timed as "gather_ms" and folded into
 "end_to_end" (all columns / (timed steps + gather)), never into `value`; every rank then checks the
 gathered array against every rank's own slab ("gather_check"; a failure exits non-zero).
+
+A plain run does what the headline figure needs and no more: it builds the step, settles, warms up, times the
+--steps steps, writes the step's outputs when --dump-outputs is given, and prints the line (metric, value, unit,
+ms_per_step, ...).  Everything else the benchmark measures or checks -- the unsettled figure, block_stream,
+host_resident, the per-stage times and rooflines, the final flux all-gather and its check, c5_global and the CPU
+baseline -- runs with --full only, and the line then carries those blocks as well.
 
 Prints ONE JSON line on rank 0.
 """
@@ -42,6 +48,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: ms_per_step_unsettled, "
+                         "block_stream, host_resident, stages_ms / rooflines, the flux all-gather (N > 1), c5_global "
+                         "and the CPU baseline (a plain run skips them all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the fluxes the last timed step left (what a caller of the step "
+                         "receives: lw_up, lw_dn, sw_up, sw_dn, sw_dir, each (columns, levels)) as DIR/<name>.npy in "
+                         "float32; above 64 MB in all, a fixed seeded sample of the columns")
     ap.add_argument("--settle-s", type=float, default=1.0,
                     help="untimed steps for this many seconds before the warmup steps (the GPU's clocks ramp up over "
                          "the first ~0.1 s of steps: 20 steps after 5 warmup steps ran 0.53 ms/step at C3 where "
@@ -76,10 +90,10 @@ def parse():
     ap.add_argument("--fortran-block", type=int, default=1800, help="--fortran: columns per block")
     ap.add_argument("--fortran-threads", type=int, default=1, help="--fortran: OpenMP threads over blocks")
     ap.add_argument("--c5-steps", type=int, default=3,
-                    help="timed steps of the c5_global block every line carries (BASELINE configs[4]: 1e6 synthetic "
+                    help="timed steps of the c5_global block every --full line carries (BASELINE configs[4]: 1e6 synthetic "
                          "columns x 137 layers split over the ranks, streamed in 125 000-column chunks); 0: skip it")
     ap.add_argument("--c5-warmup", type=int, default=1, help="untimed steps of the c5_global block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline work")
     ap.add_argument("--cpu-kind", default="auto", choices=["auto", "reference", "port"],
                     help="auto: the reference's own Fortran (oracle/_ref) when built, else the C restatement")
@@ -162,9 +176,15 @@ def fortran_bench(args):
         data.write_problem(prob, pin)
         r = subprocess.run([exe, pin, pout, data.DATA_DIR, str(args.fortran_block), str(args.steps + 1)],
                            capture_output=True, text=True, env=env, timeout=600)
-    m = re.search(r"timing:\s*([0-9.]+) ms per block loop", r.stdout)
-    if r.returncode != 0 or not m:
-        raise SystemExit("bench --fortran: host program failed: " + (r.stdout + r.stderr)[-600:])
+        m = re.search(r"timing:\s*([0-9.]+) ms per block loop", r.stdout)
+        if r.returncode != 0 or not m:
+            raise SystemExit("bench --fortran: host program failed: " + (r.stdout + r.stderr)[-600:])
+        dumped = None
+        if args.dump_outputs:  # the five fluxes the host program wrote after its last block loop, under the step's names
+            from rrtmgpnn import rbin
+            got = rbin.read(pout)
+            dumped = dump_outputs(args.dump_outputs,
+                                  {k: np.asarray(got[k[:2] + "_flux" + k[2:]]) for k in FLUX_NAMES})
     ms = float(m.group(1))
     nblocks = (1800 + args.fortran_block - 1) // args.fortran_block
     print(json.dumps({
@@ -176,7 +196,7 @@ def fortran_bench(args):
                                "rte_lw, gas_optics + rte_sw per block; host arrays in, fluxes out)",
                    "global_columns": 1800, "nlay": 60, "block_size": args.fortran_block, "blocks": nblocks,
                    "threads": args.fortran_threads, "parallelism": "OpenMP over blocks, a device context per thread"},
-        "column_layers_per_s": round(1800 * 60 / (ms * 1e-3), 1)}), flush=True)
+        "column_layers_per_s": round(1800 * 60 / (ms * 1e-3), 1), "dump_outputs": dumped}), flush=True)
 
 
 def result_stream():
@@ -187,6 +207,50 @@ def result_stream():
     out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
     return out
+
+
+FLUX_NAMES = ("lw_up", "lw_dn", "sw_up", "sw_dn", "sw_dir")
+# the result line's keys: a plain run prints PLAIN_KEYS (N > 1: and "ranks"); --full adds FULL_KEYS, one per block it
+# measures or checks beside the headline figure (tests/test_gpu_bench_line.py runs both and compares)
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "settle_s", "settle_steps", "ms_per_step",
+              "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "column_layers_per_s", "full",
+              "dump_outputs")
+FULL_KEYS = ("ms_per_step_unsettled", "value_unsettled", "roofline", "cpu_baseline", "stages_ms",
+             "stages_overlapped_ms", "stage_roofline", "gather_ms", "gather_check", "end_to_end", "host_resident",
+             "block_stream", "c5_global")
+DUMP_MAX_BYTES = 63 * 1000 * 1000  # --dump-outputs writes less than 64 MB in all, .npy headers included
+DUMP_SEED = 20251015
+
+
+def dump_rows(ncol, row_bytes):
+    """--dump-outputs: the columns written.  None (all of them) while ncol x row_bytes fits DUMP_MAX_BYTES; else a
+    fixed sample, the sorted draw without replacement of a PCG64 stream seeded by DUMP_SEED -- a function of ncol and
+    row_bytes alone, so two builds write the same columns."""
+    keep = DUMP_MAX_BYTES // row_bytes
+    if ncol <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ncol, size=keep, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write {name: (columns, ...) array or tensor} as dirname/<name>.npy in float32 (the step's own
+    precision), the same dump_rows() columns of every array.  Returns the note the result line carries."""
+    os.makedirs(dirname, exist_ok=True)
+    first = next(iter(arrays.values()))
+    ncol = int(first.shape[0])
+    rows = dump_rows(ncol, sum(4 * int(np.prod(a.shape[1:])) for a in arrays.values()))
+    for name, a in arrays.items():
+        if not isinstance(a, np.ndarray):  # a device tensor: take the sample there, copy only that
+            if rows is not None:
+                import torch
+                a = a.index_select(0, torch.as_tensor(rows, device=a.device))
+            a = a.detach().cpu().numpy()
+        elif rows is not None:
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": dirname, "arrays": list(arrays), "dtype": "float32", "columns": ncol,
+            "columns_written": ncol if rows is None else int(rows.size),
+            "sample": None if rows is None else "sorted PCG64 draw without replacement, seed %d" % DUMP_SEED}
 
 
 def main():
@@ -316,8 +380,8 @@ def main():
         return el
 
     # unsettled: the first W + K steps of the process, exactly as the driver's command would time them without the
-    # settle phase (reported beside `value` as ms_per_step_unsettled, for comparison with rounds 1-2)
-    elapsed_unsettled = warm_and_time() if args.settle_s > 0 else None
+    # settle phase (--full: reported beside `value` as ms_per_step_unsettled, for comparison with rounds 1-2)
+    elapsed_unsettled = warm_and_time() if (args.full and args.settle_s > 0) else None
     # settle: untimed steps until the GPU runs at its steady clocks (reported in the line), then the warmup steps
     settle_steps, ts0 = 0, time.perf_counter()
     while time.perf_counter() - ts0 < args.settle_s:
@@ -330,6 +394,91 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     total_cols = global_cols * args.steps
     value = total_cols / elapsed
+
+    # ---- --dump-outputs: the rank's flux slab as the last timed step left it (N > 1: the all-gathered global array,
+    # below), before anything else runs the step again ----
+    dumped = None
+    if args.dump_outputs and world == 1:
+        dumped = dump_outputs(args.dump_outputs, dict(list(zip(FLUX_NAMES, rank_run.flux))[:5 if step.sw else 2]))
+
+    config = {"workload": workload, "global_columns": global_cols, "ncol_per_gpu": hi - lo,
+              "chunk_columns": ncol, "nlay": nlay, "ngpt_lw": step.ng_lw,
+              "ngpt_sw": step.ng_sw if step.sw else None,
+              "parallelism": "column-sharded (shard.column_range), 1 process per GPU",
+              "launch": ("hipGraph replay" if use_graph else "eager") +
+                        (", LW and SW chains on two streams" if step.overlap else "") +
+                        (", the LW chain after %s" % step.lw_after if step.lw_after else "") +
+                        (" (LW network on %d CUs)" % step.lw_net_cus if step.lw_net_cus else "") +
+                        (", the SW solver after %s" % step.sw_after if step.sw_after else "") +
+                        (", SW stream priority %d" % step.sw_priority if getattr(step, "sw_priority", 0) else ""),
+              "kernels": ("class-layer sequence" if not step.fused else
+                          "fused Planck-in-LW-solver, g=0 elided" +
+                          (", cloud increments fused into both solvers" if step.allsky else ""))}
+    # the headline figure: all a plain run reports; --full adds its blocks to it below
+    line = {"metric": metric, "value": round(value, 1), "unit": "columns/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "settle_s": round(settle_s, 3) if args.settle_s > 0 else 0.0,
+            "settle_steps": settle_steps, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": data_desc, "config": config,
+            "column_layers_per_s": round(value * nlay, 1), "full": args.full}
+    if world > 1:
+        line["ranks"] = {"launcher": ("bench.py --gpus %d (torch.distributed.run child)" % world
+                                      if os.environ.get("RRTMGPNN_VISIBLE_DEVICES") else "outer launcher"),
+                         "world_size": world, "visible_devices": ndev, "backend": backend,
+                         "ranks_per_device": -(-world // ndev)}
+
+    if not args.full:
+        # ---- a plain run ends here: (N > 1 with --dump-outputs: one all-gather, for the dump alone) the line, and
+        # the step released in order ----
+        if args.dump_outputs and world > 1:
+            full = shard.gather_columns(torch.stack(list(rank_run.flux), dim=1), global_cols, world)
+            if rank == 0:
+                dumped = dump_outputs(args.dump_outputs,
+                                      {k: full[:, i] for i, k in enumerate(FLUX_NAMES[:5 if step.sw else 2])})
+            del full
+        if rank == 0:
+            print(json.dumps(dict(line, dump_outputs=dumped)), file=result, flush=True)
+        torch.cuda.synchronize(dev)
+        torch.cuda.set_stream(torch.cuda.default_stream(dev))
+        rank_run.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- everything below: --full only ----
+
+    # ---- final flux all-gather over RCCL (outside the timed region): shard.gather_columns, the partition's
+    # tested exchange, of the rank's (ncol, 5, nlev) flux slab into the global (global_cols, 5, nlev) array ----
+    gather_ms = None
+    end_to_end = None
+    gather_check = None
+    if world > 1:
+        local_slab = torch.stack(list(rank_run.flux), dim=1)
+        torch.cuda.synchronize(dev)
+        dist.barrier()
+        g0 = time.perf_counter()
+        full = shard.gather_columns(local_slab, global_cols, world)
+        torch.cuda.synchronize(dev)
+        gather_ms = (time.perf_counter() - g0) * 1e3
+        t = torch.tensor([gather_ms], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        gather_ms = float(t.item())
+        assert full.shape[0] == global_cols
+        # every rank checks the gathered array: its own slab in place bit for bit, every rank's slab in place by an
+        # exact checksum of its bits, finite fluxes; the verdict is reduced over ranks
+        chk = shard.verify_gather(full, local_slab, global_cols, rank, world)
+        ok = torch.tensor([1 if chk["ok"] else 0], dtype=torch.int32, device=dev)
+        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+        gather_check = dict(chk, ok=bool(ok.item()), ranks_checked=world,
+                            note="rank 0's view; ok is the minimum over ranks of (own slab bitwise, every slab's "
+                                 "checksum in place, finite)")
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(args.dump_outputs,
+                                  {k: full[:, i] for i, k in enumerate(FLUX_NAMES[:5 if step.sw else 2])})
+        del full, local_slab
+        if not gather_check["ok"]:
+            sys.stderr.write("bench.py: flux all-gather check failed on some rank: %s\n" % chk)
+        end_to_end = {"value": round(total_cols / (elapsed + gather_ms * 1e-3), 1), "unit": "columns/s",
+                      "note": "all ranks' columns over the timed steps plus one final flux all-gather"}
 
     # ---- block stream (never `value`): the step's block streamed K times with its two chains free-running
     # (ClearSkyStep.run_blocks: block b+1's SW chain beside block b's LW chain, no per-block join) -- the rate of a
@@ -492,50 +641,6 @@ def main():
         if roof is not None and sq.get(name, {}).get("valu_busy") is not None:
             roof["valu_busy"] = sq[name]["valu_busy"]  # the solvers' binding limit: VALU issue
 
-    # ---- final flux all-gather over RCCL (outside the timed region): shard.gather_columns, the partition's
-    # tested exchange, of the rank's (ncol, 5, nlev) flux slab into the global (global_cols, 5, nlev) array ----
-    gather_ms = None
-    end_to_end = None
-    gather_check = None
-    if world > 1:
-        local_slab = torch.stack(list(rank_run.flux), dim=1)
-        torch.cuda.synchronize(dev)
-        dist.barrier()
-        g0 = time.perf_counter()
-        full = shard.gather_columns(local_slab, global_cols, world)
-        torch.cuda.synchronize(dev)
-        gather_ms = (time.perf_counter() - g0) * 1e3
-        t = torch.tensor([gather_ms], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        gather_ms = float(t.item())
-        assert full.shape[0] == global_cols
-        # every rank checks the gathered array: its own slab in place bit for bit, every rank's slab in place by an
-        # exact checksum of its bits, finite fluxes; the verdict is reduced over ranks
-        chk = shard.verify_gather(full, local_slab, global_cols, rank, world)
-        ok = torch.tensor([1 if chk["ok"] else 0], dtype=torch.int32, device=dev)
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        gather_check = dict(chk, ok=bool(ok.item()), ranks_checked=world,
-                            note="rank 0's view; ok is the minimum over ranks of (own slab bitwise, every slab's "
-                                 "checksum in place, finite)")
-        del full
-        if not gather_check["ok"]:
-            sys.stderr.write("bench.py: flux all-gather check failed on some rank: %s\n" % chk)
-        end_to_end = {"value": round(total_cols / (elapsed + gather_ms * 1e-3), 1), "unit": "columns/s",
-                      "note": "all ranks' columns over the timed steps plus one final flux all-gather"}
-
-    config = {"workload": workload, "global_columns": global_cols, "ncol_per_gpu": hi - lo,
-              "chunk_columns": ncol, "nlay": nlay, "ngpt_lw": step.ng_lw,
-              "ngpt_sw": step.ng_sw if step.sw else None,
-              "parallelism": "column-sharded (shard.column_range), 1 process per GPU",
-              "launch": ("hipGraph replay" if use_graph else "eager") +
-                        (", LW and SW chains on two streams" if step.overlap else "") +
-                        (", the LW chain after %s" % step.lw_after if step.lw_after else "") +
-                        (" (LW network on %d CUs)" % step.lw_net_cus if step.lw_net_cus else "") +
-                        (", the SW solver after %s" % step.sw_after if step.sw_after else "") +
-                        (", SW stream priority %d" % step.sw_priority if step.sw_priority else ""),
-              "kernels": ("class-layer sequence" if not step.fused else
-                          "fused Planck-in-LW-solver, g=0 elided" +
-                          (", cloud increments fused into both solvers" if step.allsky else ""))}
     step_sw = step.sw
     # the main line's steps, workspaces and chunk inputs are released before c5_global allocates its own (at C5 each
     # holds ~116 GB of the device's 288: both at once can exceed HBM)
@@ -558,18 +663,12 @@ def main():
         cpu = cpu_baseline(prob, clouds, args.cpu_seconds, args.cpu_kind, sw=step_sw, bind=args.cpu_bind)
 
     if rank == 0:
-        out = {
-            "metric": metric, "value": round(value, 1), "unit": "columns/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "settle_s": round(settle_s, 3) if args.settle_s > 0 else 0.0,
-            "settle_steps": settle_steps, "ms_per_step": round(ms_per_step, 4),
+        out = dict(line, **{
             "ms_per_step_unsettled": (None if elapsed_unsettled is None else
                                       round(elapsed_unsettled / args.steps * 1e3, 4)),
             "value_unsettled": (None if elapsed_unsettled is None else
                                 round(total_cols / elapsed_unsettled, 1)),
-            "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": "f32", "data": data_desc,
-            "config": config,
-            "column_layers_per_s": round(value * nlay, 1),
+            "dump_outputs": dumped,
             "roofline": roof,
             "cpu_baseline": cpu,
             "stages_ms": {k: round(v, 4) for k, v in stages.items()},
@@ -581,12 +680,7 @@ def main():
             "host_resident": pcie,
             "block_stream": block_stream,
             "c5_global": c5g,
-        }
-        if world > 1:
-            out["ranks"] = {"launcher": ("bench.py --gpus %d (torch.distributed.run child)" % world
-                                         if os.environ.get("RRTMGPNN_VISIBLE_DEVICES") else "outer launcher"),
-                            "world_size": world, "visible_devices": ndev, "backend": backend,
-                            "ranks_per_device": -(-world // ndev)}
+        })
         print(json.dumps(out), file=result, flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -4,16 +4,17 @@
   text attributes) reads back exactly;
 * the reference's own files -- the NN models (netCDF-4/HDF5), the cloud-optics coefficients (classic netCDF)
   and the RFMIP inputs (netCDF-4) -- read natively equal the committed RBIN conversions, and the RFMIP problem
-  built from the netCDF file equals the one built from RBIN, bit for bit (skipped where /root/reference is
-  absent, e.g. on the GPU box; the GPU side is tests/test_gpu_datafiles.py).
+  built from the netCDF file equals the one built from RBIN, bit for bit.  The files are byte-for-byte copies kept
+  under tests/golden/reference_files/ (the RFMIP file xz-compressed: it is unpacked into the test's tmp_path), so the
+  tests need nothing outside the repository; the GPU side is tests/test_gpu_datafiles.py.
 """
+import lzma
 import os
 
 import numpy as np
 import pytest
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+FILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_files")
 NN = {"lw_abs": "lw-g256-2018-12-04_absorption_58_58.nc", "lw_pfrac": "lw-g256-2018-12-04_planck_frac_16_16.nc",
       "sw_abs": "sw-g224-2018-12-04-absorption_16_16.nc", "sw_ray": "sw-g224-2018-12-04-rayleigh_16_16.nc"}
 ACT = ["linear", "softsign", "relu", "sigmoid", "hard_sigmoid", "tanh", "gaussian"]
@@ -76,12 +77,11 @@ def test_reader_errors(tmp_path):
         ncio.DataFile(str(tmp_path / "missing.nc"))
 
 
-@needs_ref
 @pytest.mark.parametrize("model", sorted(NN))
 def test_nn_netcdf4_equals_rbin(model):
     from rrtmgpnn import data, ncio, rbin
     m = data.load_model(model)
-    with ncio.DataFile(os.path.join(REF, "neural", "data", NN[model])) as f:
+    with ncio.DataFile(os.path.join(FILES, NN[model])) as f:
         dims = [f.read("nn_input_coeffs_min").size] + list(f.read("nn_dimsize"))
         np.testing.assert_array_equal(dims, m["dims"])
         assert [ACT.index(a) for a in f.strings("nn_activation_char")] == list(m["activation"])
@@ -98,22 +98,22 @@ def test_nn_netcdf4_equals_rbin(model):
         assert f.att("", "emulator_target").startswith("rrtmgp-data-")
 
 
-@needs_ref
 @pytest.mark.parametrize("which", ["lw", "sw"])
 def test_cloud_coefficients_classic_netcdf_equal_rbin(which):
     from rrtmgpnn import data, ncio
     co = data.load_cloud_optics(which)
-    got = ncio.read(os.path.join(REF, "extensions", "cloud_optics", "rrtmgp-cloud-optics-coeffs-%s.nc" % which))
+    got = ncio.read(os.path.join(FILES, "rrtmgp-cloud-optics-coeffs-%s.nc" % which))
     assert set(got) == set(co)
     for k, v in co.items():
         np.testing.assert_array_equal(np.atleast_1d(got[k]).astype(np.float32), v, err_msg=k)
 
 
-@needs_ref
-def test_rfmip_problem_from_netcdf_equals_rbin():
+def test_rfmip_problem_from_netcdf_equals_rbin(tmp_path):
     from rrtmgpnn import data, ncio
-    nc = os.path.join(REF, "examples", "rfmip-clear-sky",
-                      "multiple_input4MIPs_radiation_RFMIP_UColorado-RFMIP-1-2_none.nc")
+    name = "multiple_input4MIPs_radiation_RFMIP_UColorado-RFMIP-1-2_none.nc"
+    nc = str(tmp_path / name)
+    with lzma.open(os.path.join(FILES, name + ".xz")) as src, open(nc, "wb") as dst:
+        dst.write(src.read())
     a = data.rfmip_problem(fields=ncio.rfmip_fields(nc))
     b = data.rfmip_problem()
     for k in b:

@@ -86,7 +86,7 @@ def test_c5_shard_full_size_step_sampled_vs_oracle(dev, orc):
 
 
 def test_c5_global_rank_chunked_full_size_sampled_vs_oracle(dev, orc):
-    """BASELINE configs[4] as bench.py runs it (--global, and every line's c5_global block): the 1e6 x 137 problem
+    """BASELINE configs[4] as bench.py runs it (--global, and every --full line's c5_global block): the 1e6 x 137 problem
     split over 3 ranks, rank 1's range [333334, 666667) streamed through pipeline.ChunkedRank in 125 000-column chunks
     -- two full chunks through one captured step and a short last one (83 333 columns) through a second -- run twice
     (the slab refilled with nans in between), then a strided sample of the slab that includes every chunk's first and

@@ -260,6 +260,54 @@ def test_bench_result_stream_keeps_stdout_to_the_line():
     assert "[Gloo] chatter" in p.stderr and "raw fd write" in p.stderr
 
 
+def test_bench_plain_run_is_the_default_and_full_is_an_option():
+    """The options alone; what each mode runs and prints is tests/test_gpu_bench_line.py's."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert not set(bench.PLAIN_KEYS) & set(bench.FULL_KEYS)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(bench.PLAIN_KEYS)
+    argv, sys.argv = sys.argv, ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+    try:
+        args = bench.parse()
+        assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 2)
+        sys.argv += ["--full", "--dump-outputs", "d"]
+        args = bench.parse()
+        assert args.full and args.dump_outputs == "d"
+    finally:
+        sys.argv = argv
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32, all columns while they fit; above the cap the
+    same seeded sample of the columns for every array and every run, under 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    small = {k: rng.normal(size=(37, 61)).astype(np.float32) for k in bench.FLUX_NAMES}
+    note = bench.dump_outputs(str(tmp_path / "a"), small)
+    assert note["columns_written"] == note["columns"] == 37 and note["sample"] is None
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, v)
+    # C5's global slab: 1e6 columns x 5 fluxes x 138 levels is 2.76 GB, so a sample is written
+    assert bench.dump_rows(1800, 5 * 61 * 4) is None
+    rows = bench.dump_rows(1000000, 5 * 138 * 4)
+    assert rows.size * 5 * 138 * 4 + 5 * 128 < 64 * 1000 * 1000 and rows.size > 20000
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 1000000
+    np.testing.assert_array_equal(rows, bench.dump_rows(1000000, 5 * 138 * 4))
+    # the sampling path itself, with the cap lowered for the test: the same rows of every array
+    cap, bench.DUMP_MAX_BYTES = bench.DUMP_MAX_BYTES, 10 * 5 * 61 * 4
+    try:
+        note = bench.dump_outputs(str(tmp_path / "b"), small)
+        rows = bench.dump_rows(37, 5 * 61 * 4)
+    finally:
+        bench.DUMP_MAX_BYTES = cap
+    assert note["columns_written"] == 10 == rows.size and note["columns"] == 37
+    for k, v in small.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / (k + ".npy")), v[rows])
+
+
 def test_synthetic_problem_column_ranges_are_slices_of_the_whole():
     """bench.py builds each rank's shard (and each chunk of it) as a column range of one global synthetic problem:
     a range generated alone must equal the same columns of the whole, at 60 and 137 layers."""

@@ -4,7 +4,7 @@ profiles/pmc_sq.json (which bench.py reads for its roofline's `traffic`, `valu_b
 
 usage: publish_profiles.py <run_dir> <round> <config> [<config> ...]
 
-<run_dir> is what tools/profile_configs.sh leaves (gpurun_out/ merged back from the GPU box), per config:
+<run_dir> is what tools/profile_configs.sh leaves (its $OUT directory, bench_out by default), per config:
 <config>/pmc_traffic.txt (tools/pmc_traffic.py's stage table), <config>/pmc_sq.txt and <config>/pmc_mfma.txt
 (tools/pmc_counters.py's two passes, merged in that order as profile_configs.sh merges them into pmc_sq.json),
 <config>/prof/run_kernel_stats.csv (the bench command's kernel trace), <config>/prof_iso/run_kernel_stats.csv
