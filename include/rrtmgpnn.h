@@ -322,6 +322,34 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, const float *mu0,
                                    const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
                                    float *flux_dn, float *flux_dir);
+/* ---- by-band fluxes: ty_fluxes_byband (extensions/mo_fluxes_byband.F90:31-131) ------------------
+ * rrtmgpnn_solver_request_byband arms by-band outputs for the NEXT solver call on this context (any of the
+ * rrtmgpnn_lw_solver_* / rrtmgpnn_sw_solver_* entries); that call clears the request whether it succeeds or fails.
+ * bnd_flux_* are device arrays (nbnd, nlay+1, ncol), band fastest, NULL for "not wanted"; band_lims_gpt HOST
+ * (2, nbnd), 1-based, copied by this call: any widths >= 1, any start parity, and the bands need not cover every
+ * g-point.  Each value is the reference's sum_byband (extensions/mo_fluxes_byband_kernels.F90:31-50, called at
+ * mo_fluxes_byband.F90:103-115) -- start from the band's first g-point, add the others one by one in increasing g -- of
+ *   SW two-stream (also _inc and _rfmip): the g-point fluxes rte_sw saves: up, TOTAL down (diffuse + direct, rounded
+ *     once per g-point, then added) and direct;
+ *   SW no-scattering: the spectral direct beam (bnd_flux_dir only; up / dn are RRTMGPNN_ERR_ARGUMENT);
+ *   LW two-stream, and LW no-scattering / rescaled with several angles: the g-point fluxes, as the _gpt entries
+ *     return them;
+ *   LW no-scattering / rescaled with one angle (also with lw_Ds): the float32 terms the broadband sum adds,
+ *     fac * radiance with fac = 2 pi weight -- NOT sum_byband of the _gpt entries' output, which holds bare radiances
+ *     there (quirk B-5).  When ngpt % 4 != 0 the reference's broadband sum itself adds bare radiances (fac = 1,
+ *     rte/kernels/mo_rte_solver_kernels.F90:287-320), and the by-band values follow it.
+ * The sums are formed inside the solver from the LDS rows its ordered broadband sum walks; the call's broadband
+ * outputs are bit-identical to the same call without the request.  bnd_flux_dir on an LW entry is
+ * RRTMGPNN_ERR_ARGUMENT; a by-band request together with g-point outputs (the _gpt entries) is
+ * RRTMGPNN_ERR_UNSUPPORTED (reduce the g-point arrays with rrtmgpnn_sum_byband instead).  Nothing is allocated and
+ * the pointers are kernel arguments, so an armed call can be captured in a hipGraph.  bnd_flux_net
+ * (net_byband_precalc, mo_fluxes_byband_kernels.F90:54-70) = bnd_flux_dn - bnd_flux_up is left to the caller. */
+int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
+                                   float *bnd_flux_dn, float *bnd_flux_dir);
+/* sum_byband (extensions/mo_fluxes_byband_kernels.F90:31-50) of an existing g-point flux array: gpt_flux
+ * (ngpt, nlev, ncol) -> bnd_flux (nbnd, nlev, ncol), device arrays; band_lims_gpt HOST (2, nbnd) as above. */
+int rrtmgpnn_sum_byband(rrtmgpnn_context *ctx, int ngpt, int nlev, int ncol, int nbnd, const int *band_lims_gpt,
+                        const float *gpt_flux, float *bnd_flux);
 /* expand (rte/mo_rte_lw.F90:429-447): (nband,ncol) -> (ngpt,ncol).  band_lims_gpt HOST (2,nband). */
 int rrtmgpnn_expand_band_to_gpt(rrtmgpnn_context *ctx, int nband, int ngpt, int ncol, const int *band_lims_gpt,
                                 const float *arr_in, float *arr_out);

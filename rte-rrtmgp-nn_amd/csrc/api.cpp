@@ -108,6 +108,38 @@ static int bands_cover(const BandArgs &b, int ngpt)
   return RRTMGPNN_OK;
 }
 
+// A solver entry's hold on the context's by-band request (rrtmgpnn_solver_request_byband): the first entry of a call
+// takes the armed request into the per-call extras, validates it against the call's ngpt, and clears it when the
+// call returns, whatever the outcome; an entry reached from another (the _gpt entries call the plain ones) finds
+// nothing armed and leaves the extras alone.
+struct BybandScope {
+  rrtmgpnn_context *c;
+  bool owner = false;
+  int rc = RRTMGPNN_OK;
+  BybandScope(rrtmgpnn_context *ctx, int ngpt) : c(ctx)
+  {
+    if (!c || !c->byband.armed) return;
+    owner = true;
+    const auto rq = c->byband;
+    c->byband = rrtmgpnn_context::BybandRequest{};
+    rc = band_args(rq.nbnd, rq.lims, ngpt, c->extras.bnd);
+    if (rc) return;
+    c->extras.bnd_up = rq.up;
+    c->extras.bnd_dn = rq.dn;
+    c->extras.bnd_dir = rq.dir;
+  }
+  ~BybandScope()
+  {
+    if (!owner) return;
+    c->extras.bnd_up = c->extras.bnd_dn = c->extras.bnd_dir = nullptr;
+    c->extras.bnd = BandArgs{};
+  }
+};
+// first statement of every solver entry
+#define RRTMGPNN_BYBAND(ctx, ngpt)        \
+  ::rrtmgpnn::BybandScope byband_((ctx), (ngpt)); \
+  if (byband_.rc) return byband_.rc
+
 }  // namespace rrtmgpnn
 
 using namespace rrtmgpnn;
@@ -642,6 +674,7 @@ int rrtmgpnn_lw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int nco
                               const float *lay_source, const float *lev_source, const float *sfc_emis_gpt,
                               const float *sfc_source, float *flux_up, float *flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!Ds || !weights || !tau || !lay_source || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn ||
       ngpt < 1 || nlay < 1 || ncol < 0)
@@ -657,6 +690,7 @@ int rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      float temp_ref_min, float totplnk_delta, const float *totplnk,
                                      int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!Ds || !weights || !tau || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis || !flux_up ||
       !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 || sfc_lay < 1 || sfc_lay > nlay ||
@@ -679,6 +713,7 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          float totplnk_delta, const float *totplnk, int emis_by_band,
                                          const float *sfc_emis, float *flux_up, float *flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
       !flux_up || !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 || sfc_lay < 1 || sfc_lay > nlay ||
@@ -697,6 +732,7 @@ int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int nco
                               const float *ssa, const float *g, const float *lay_source, const float *lev_source,
                               const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!Ds || !weights || !tau || !ssa || !g || !lay_source || !lev_source || !sfc_emis_gpt || !sfc_source ||
       !flux_up || !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0)
@@ -710,6 +746,7 @@ int rrtmgpnn_lw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int nc
                                const float *lev_source, const float *sfc_emis_gpt, const float *sfc_source,
                                float *flux_up, float *flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!tau || !ssa || !g || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn || ngpt < 1 ||
       nlay < 1 || ncol < 0)
@@ -723,6 +760,7 @@ int rrtmgpnn_sw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int nc
                                const float *g, const float *mu0, const float *sfc_alb_dir_gpt,
                                const float *sfc_alb_dif_gpt, float *flux_up, float *flux_dn, float *flux_dir)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt || !flux_up || !flux_dn ||
       !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
@@ -759,6 +797,7 @@ int rrtmgpnn_lw_solver_noscat_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int
                                   const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn,
                                   float *gpt_flux_up, float *gpt_flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (int rc = lw_ds_check(nmus, lw_Ds)) return rc;
   ExtrasScope x(ctx, lw_Ds, gpt_flux_up, gpt_flux_dn, nullptr);
@@ -775,6 +814,7 @@ int rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_context *ctx, int ngpt, int nl
                                          const float *sfc_emis, float *flux_up, float *flux_dn, float *gpt_flux_up,
                                          float *gpt_flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (int rc = lw_ds_check(nmus, lw_Ds)) return rc;
   ExtrasScope x(ctx, lw_Ds, gpt_flux_up, gpt_flux_dn, nullptr);
@@ -789,6 +829,7 @@ int rrtmgpnn_sw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *sfc_alb_dif_gpt, float *flux_up, float *flux_dn, float *flux_dir,
                                    float *gpt_flux_up, float *gpt_flux_dn, float *gpt_flux_dir)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   ExtrasScope x(ctx, nullptr, gpt_flux_up, gpt_flux_dn, gpt_flux_dir);
   return rrtmgpnn_sw_solver_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0,
@@ -798,6 +839,7 @@ int rrtmgpnn_sw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, in
 int rrtmgpnn_sw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
                               const float *tau, const float *mu0, float *flux_dir)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !mu0 || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: bad argument");
@@ -810,6 +852,7 @@ int rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int
                                   const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn,
                                   float *gpt_flux_up, float *gpt_flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   ExtrasScope x(ctx, nullptr, gpt_flux_up, gpt_flux_dn, nullptr);
   return rrtmgpnn_lw_solver_1rescl(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, ssa, g,
@@ -821,6 +864,7 @@ int rrtmgpnn_lw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *lev_source, const float *sfc_emis_gpt, const float *sfc_source,
                                    float *flux_up, float *flux_dn, float *gpt_flux_up, float *gpt_flux_dn)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   ExtrasScope x(ctx, nullptr, gpt_flux_up, gpt_flux_dn, nullptr);
   return rrtmgpnn_lw_solver_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis_gpt,
@@ -831,6 +875,7 @@ int rrtmgpnn_sw_solver_noscat_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int
                                   const float *inc_flux, const float *tau, const float *mu0, float *flux_dir,
                                   float *gpt_flux_dir)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   ExtrasScope x(ctx, nullptr, nullptr, nullptr, gpt_flux_dir);
   return rrtmgpnn_sw_solver_noscat(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir);
@@ -843,6 +888,7 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
                                    float *flux_dn, float *flux_dir)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !tau_bnd || !ssa_bnd || !g_bnd || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt ||
       !flux_up || !flux_dn || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
@@ -852,6 +898,38 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
   if (int rc = bands_cover(b, ngpt)) return rc;
   return launch_sw_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
                            sfc_alb_dif_gpt, &b, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir);
+}
+
+int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
+                                   float *bnd_flux_dn, float *bnd_flux_dir)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->byband = rrtmgpnn_context::BybandRequest{};
+  if (!bnd_flux_up && !bnd_flux_dn && !bnd_flux_dir) return RRTMGPNN_OK;  // nothing wanted: nothing armed
+  if (nbnd < 1 || nbnd > kMaxBands || !band_lims_gpt)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband: band limits: need 1..64 bands");
+  for (int i = 0; i < nbnd; i++)
+    if (band_lims_gpt[2 * i] < 1 || band_lims_gpt[2 * i] > band_lims_gpt[2 * i + 1])
+      return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband: band limits out of range");
+  auto &rq = ctx->byband;
+  rq.armed = true;
+  rq.up = bnd_flux_up;
+  rq.dn = bnd_flux_dn;
+  rq.dir = bnd_flux_dir;
+  rq.nbnd = nbnd;
+  std::memcpy(rq.lims, band_lims_gpt, sizeof(int) * 2 * nbnd);
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_sum_byband(rrtmgpnn_context *ctx, int ngpt, int nlev, int ncol, int nbnd, const int *band_lims_gpt,
+                        const float *gpt_flux, float *bnd_flux)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!gpt_flux || !bnd_flux || ngpt < 1 || nlev < 0 || ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sum_byband: bad argument");
+  BandArgs b;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  return launch_sum_byband(ctx, ngpt, (long long)nlev * ncol, b, gpt_flux, bnd_flux);
 }
 
 int rrtmgpnn_expand_band_to_gpt(rrtmgpnn_context *ctx, int nband, int ngpt, int ncol, const int *band_lims_gpt,
@@ -1111,6 +1189,7 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      const float *g_bnd, float *toa_flux, float *sfc_alb_gpt, float *mu0,
                                      float *flux_up, float *flux_dn, float *flux_dir)
 {
+  RRTMGPNN_BYBAND(ctx, ngpt);
   if (int rc = check_ctx(ctx)) return rc;
   if (!solar_source || !tsi || !sfc_alb || !sza || !tau || !ssa || !toa_flux || !sfc_alb_gpt || !mu0 || !flux_up ||
       !flux_dn || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0 || nbnd < 0 ||

@@ -41,6 +41,12 @@ extern int g_mlp_kernel_default;  // rrtmgpnn_context_set_mlp_kernel(NULL, mode)
 // call for a (kernel, device) pair it makes no HIP call (hipGraph captures stay attribute-free).
 int raise_lds_limit(const void *kernel);
 
+// band limits as a kernel argument: 1-based inclusive (first, last) g-point per band
+struct BandArgs {
+  int lims[2 * kMaxBands];
+  int nbnd;
+};
+
 }  // namespace rrtmgpnn
 
 // Device workspace owned by a context: grown on demand, never shrunk, so steady-state calls
@@ -61,7 +67,20 @@ struct rrtmgpnn_context {
   struct SolverExtras {
     const float *lw_Ds = nullptr;
     float *gpt_up = nullptr, *gpt_dn = nullptr, *gpt_dir = nullptr;
+    // ty_fluxes_byband's by-band outputs, (nbnd, nlay+1, ncol) each, and their band limits: set from `byband` by the
+    // solver entry that consumes the request (rrtmgpnn_solver_request_byband); every solver launch has by-band
+    // instances
+    float *bnd_up = nullptr, *bnd_dn = nullptr, *bnd_dir = nullptr;
+    rrtmgpnn::BandArgs bnd{};
+    bool byband() const { return bnd_up || bnd_dn || bnd_dir; }
   } extras;
+  // rrtmgpnn_solver_request_byband: armed for the next solver call on this context, which clears it
+  struct BybandRequest {
+    bool armed = false;
+    float *up = nullptr, *dn = nullptr, *dir = nullptr;
+    int nbnd = 0;
+    int lims[2 * rrtmgpnn::kMaxBands] = {0};
+  } byband;
   void *ws = nullptr;
   size_t ws_bytes = 0;
   bool ws_pinned = false;
@@ -194,10 +213,6 @@ int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A,
                  long long nbatch, int ngpt, const float *x, const float *col_dry, float *out0, float *out1,
                  float *out2, const MlpInputs *in);
 // kernels_rte.hip
-struct BandArgs {
-  int lims[2 * kMaxBands];
-  int nbnd;
-};
 int launch_planck_source(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ntemp, const float *tlay,
                          const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
                          float temp_ref_min, float totplnk_delta, const float *totplnk, float *sfc_source,
@@ -247,4 +262,7 @@ int launch_lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
                       const float *sfc_emis, const float *sfc_source, float *flux_up, float *flux_dn);
 int launch_expand(rrtmgpnn_context *ctx, int nband, int ngpt, int ncol, const BandArgs &bands, const float *in,
                   float *out);
+// kernels_fluxes.hip: sum_byband of a g-point array (ngpt, nlev, ncol) into (nbnd, nlev, ncol)
+int launch_sum_byband(rrtmgpnn_context *ctx, int ngpt, long long nrow, const BandArgs &bands, const float *gpt_flux,
+                      float *bnd_flux);
 }  // namespace rrtmgpnn

@@ -21,10 +21,17 @@
 //             report's form): scaling * ((dn - up)(l+1) - (dn - up)(l)) / (p(l+1) - p(l)),
 //             scaling = -(24 * 3600 * grav / 1004) formed in fp32 on the host
 //
-// Elementwise and HBM-bound: one thread per (layer, column), layer fastest, so a wave reads 65 contiguous levels of
+//  * sum_byband_kernel   : sum_byband (extensions/mo_fluxes_byband_kernels.F90:31-50) of a g-point flux array
+//                          (ngpt, nlev, ncol) into (nbnd, nlev, ncol): each band starts from its first g-point and adds
+//                          the others one by one in increasing g.  A block stages a few (level, column) rows in LDS with
+//                          coalesced loads, then one lane per (row, band) walks its band.
+//
+// The others are elementwise and HBM-bound: one thread per (layer, column), layer fastest, so a wave reads 65 contiguous levels of
 // each array and writes 64 contiguous layers.  -ffp-contract=off keeps the reference's roundings.
 #include "internal.hpp"
 #include "libm_ref.hpp"
+
+#include <algorithm>
 
 namespace rrtmgpnn {
 
@@ -124,6 +131,47 @@ int launch_heating_rate(rrtmgpnn_context *ctx, int ncol, int nlay, int k_day, fl
   else
     hipLaunchKernelGGL(heating_rate_kernel<false>, grid, block, 0, ctx->stream, n, nlay, c0, c1, up, dn, plev, hr);
   RRTMGPNN_LAUNCH_CHECK("heating_rate_kernel");
+  return RRTMGPNN_OK;
+}
+
+constexpr int kSbLdsFloats = 12288;  // LDS floats a sum_byband block stages (48 KiB)
+constexpr int kSbMaxRows = 16;
+
+__global__ void __launch_bounds__(256) sum_byband_kernel(int ngpt, long long nrow, int rpb, BandArgs b,
+                                                         const float *__restrict__ gpt_flux,
+                                                         float *__restrict__ bnd_flux)
+{
+  extern __shared__ float rows[];  // [rpb][ngpt + 1]: odd row stride, the rows of one band start in different banks
+  const long long r0 = (long long)blockIdx.x * rpb;
+  const int nr = (int)min((long long)rpb, nrow - r0), rs = ngpt + 1;
+  const float *src = gpt_flux + (size_t)r0 * ngpt;
+  for (int i = threadIdx.x; i < nr * ngpt; i += blockDim.x) {
+    const int r = i / ngpt;
+    rows[r * rs + (i - r * ngpt)] = src[i];
+  }
+  __syncthreads();
+  const int nb = b.nbnd;
+  for (int i = threadIdx.x; i < nr * nb; i += blockDim.x) {
+    const int r = i / nb, ib = i - r * nb;
+    const float *w = rows + r * rs;
+    const int lo = b.lims[2 * ib] - 1, hi = b.lims[2 * ib + 1];
+    float s = w[lo];
+    for (int g = lo + 1; g < hi; g++) s = s + w[g];
+    bnd_flux[(size_t)(r0 + r) * nb + ib] = s;
+  }
+}
+
+int launch_sum_byband(rrtmgpnn_context *ctx, int ngpt, long long nrow, const BandArgs &bands, const float *gpt_flux,
+                      float *bnd_flux)
+{
+  if (nrow == 0) return RRTMGPNN_OK;
+  if (ngpt + 1 > kSbLdsFloats) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sum_byband: too many g-points for the LDS stage");
+  const int rpb = std::max(1, std::min(kSbMaxRows, kSbLdsFloats / (ngpt + 1)));
+  const long long nblk = (nrow + rpb - 1) / rpb;
+  if (nblk > 0x7fffffffLL) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sum_byband: too many (level, column) rows");
+  hipLaunchKernelGGL(sum_byband_kernel, dim3((unsigned)nblk), dim3(256), sizeof(float) * (size_t)rpb * (ngpt + 1),
+                     ctx->stream, ngpt, nrow, rpb, bands, gpt_flux, bnd_flux);
+  RRTMGPNN_LAUNCH_CHECK("sum_byband_kernel");
   return RRTMGPNN_OK;
 }
 

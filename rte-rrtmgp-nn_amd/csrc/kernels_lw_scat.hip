@@ -42,6 +42,10 @@ __device__ __forceinline__ RsLayer rs_layer(float tau, float ssal, float g, floa
   return r;
 }
 
+// kBand: also the by-band fluxes bo.up / bo.dn (ty_fluxes_byband, (nbnd, nlay+1, ncol)): with one angle summed from the
+// ring rows in the flush's barrier window (the terms the broadband sum adds: fac * radiance, the bare radiance when
+// ngpt % 4 != 0), with several angles from the per-g accumulators
+template <bool kBand = false>
 __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                                        const float *__restrict__ inc_flux,
                                                        const float *__restrict__ tau, const float *__restrict__ ssa,
@@ -49,7 +53,8 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
                                                        const float *__restrict__ lev, const float *__restrict__ emis,
                                                        const float *__restrict__ sfc, float *__restrict__ ws,
                                                        float *__restrict__ flux_up, float *__restrict__ flux_dn,
-                                                       float *__restrict__ gpt_up, float *__restrict__ gpt_dn)
+                                                       float *__restrict__ gpt_up, float *__restrict__ gpt_dn,
+                                                       BandOut bo)
 {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
@@ -97,7 +102,12 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
       }
     };
     auto flush = [&](float *pq, int n, int lev0, int dl) {
-      if (!multi) ring_flush<kScatRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
+      if (multi) return;
+      if constexpr (kBand)
+        ring_flush<kScatRing, true>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false, false, 0, &bo.b,
+                                    pq == pdn ? bo.dn : bo.up, nullptr, nullptr, icol);
+      else
+        ring_flush<kScatRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
     };
     // 1: no-scattering transport down with the rescaled optics (lw_transport_noscat_dn)
     const float I0 = inc / (2.0f * kPi * ang.w[imu]);
@@ -151,6 +161,18 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
   }
   if (multi) {
     __syncthreads();
+    if constexpr (kBand) {
+      // sum_byband of the angle-summed g-point fluxes: one lane per (quantity, level, band), band fastest
+      const int nb = bo.b.nbnd;
+      for (int t = g; t < 2 * nlev * nb; t += blockDim.x) {
+        const int r = t / nb, ib = t - r * nb;
+        float *o = r < nlev ? bo.dn : bo.up;
+        if (!o) continue;
+        const float *w = acc_base + (size_t)r * ngpt;
+        o[ib + (size_t)nb * ((r % nlev) + (size_t)nlev * icol)] =
+            band_walk(w, w, false, bo.b.lims[2 * ib] - 1, bo.b.lims[2 * ib + 1]);
+      }
+    }
     for (int t = g; t < 2 * nlev; t += blockDim.x) {
       const float *w = gpt ? (t < nlev ? gdn : gup) + (size_t)(t % nlev) * ngpt : acc_base + (size_t)t * ngpt;
       float s = 0.0f;
@@ -197,6 +219,8 @@ __device__ __forceinline__ L2Layer l2_layer(float tau, float w0, float g, float 
   return r;
 }
 
+// kBand: also the by-band fluxes bo.up / bo.dn, summed from the ring rows in the flush's barrier window
+template <bool kBand = false>
 __global__ void __launch_bounds__(256) lw_2stream_kernel(int ngpt, int nlay, int ncol, int top_at_1,
                                                          const float *__restrict__ inc_flux,
                                                          const float *__restrict__ tau, const float *__restrict__ ssa,
@@ -204,7 +228,8 @@ __global__ void __launch_bounds__(256) lw_2stream_kernel(int ngpt, int nlay, int
                                                          const float *__restrict__ emis,
                                                          const float *__restrict__ sfc, float *__restrict__ ws,
                                                          float *__restrict__ flux_up, float *__restrict__ flux_dn,
-                                                         float *__restrict__ gpt_up, float *__restrict__ gpt_dn)
+                                                         float *__restrict__ gpt_up, float *__restrict__ gpt_dn,
+                                                         BandOut bo)
 {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
@@ -260,7 +285,11 @@ __global__ void __launch_bounds__(256) lw_2stream_kernel(int ngpt, int nlay, int
     }
   };
   auto flush = [&](int n, int lev0, int dl) {
-    ring_flush<kScatRing>(ring, part, 2, n, lev0, dl, ngpt, nlev, false, true);
+    if constexpr (kBand)
+      ring_flush<kScatRing, true>(ring, part, 2, n, lev0, dl, ngpt, nlev, false, true, 0, &bo.b, bo.up, bo.dn, nullptr,
+                                  icol);
+    else
+      ring_flush<kScatRing>(ring, part, 2, n, lev0, dl, ngpt, nlev, false, true);
   };
   float Fdn = (on && inc_flux) ? inc_flux[g + (size_t)ngpt * icol] : 0.0f;
   put(Fdn * alb_b + src_b, Fdn, 0, top);
@@ -304,9 +333,18 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top
   const auto &ex = ctx->extras;
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
-  hipLaunchKernelGGL(lw_rescl_kernel, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1, a,
-                     inc_flux, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up,
-                     flux_dn, ex.gpt_up, ex.gpt_dn);
+  if (ex.byband() && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
+  if (ex.byband() && ex.gpt_up)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
+                                          "reduces g-point fluxes)");
+  if (ex.byband())
+    hipLaunchKernelGGL(lw_rescl_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
+                       a, inc_flux, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up,
+                       flux_dn, ex.gpt_up, ex.gpt_dn, band_out(ctx));
+  else
+    hipLaunchKernelGGL(lw_rescl_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
+                       a, inc_flux, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up,
+                       flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{});
   RRTMGPNN_LAUNCH_CHECK("lw_rescl_kernel");
   return RRTMGPNN_OK;
 }
@@ -325,9 +363,18 @@ int launch_lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
   const auto &ex = ctx->extras;
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
-  hipLaunchKernelGGL(lw_2stream_kernel, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
-                     inc_flux, tau, ssa, g, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up, flux_dn, ex.gpt_up,
-                     ex.gpt_dn);
+  if (ex.byband() && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
+  if (ex.byband() && ex.gpt_up)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
+                                          "reduces g-point fluxes)");
+  if (ex.byband())
+    hipLaunchKernelGGL(lw_2stream_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
+                       inc_flux, tau, ssa, g, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up, flux_dn,
+                       ex.gpt_up, ex.gpt_dn, band_out(ctx));
+  else
+    hipLaunchKernelGGL(lw_2stream_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol,
+                       top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up, flux_dn,
+                       ex.gpt_up, ex.gpt_dn, BandOut{});
   RRTMGPNN_LAUNCH_CHECK("lw_2stream_kernel");
   return RRTMGPNN_OK;
 }

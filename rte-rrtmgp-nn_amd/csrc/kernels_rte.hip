@@ -122,14 +122,19 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // kInc: tau is incremented by a band-resolved absorption optical depth tau_bnd (nbnd, nlay, ncol) as it is
 // read -- inc_1scalar_by_1scalar_bybnd (rte/kernels/mo_optical_props_kernels.F90:358-372), tau + tau_bnd(band),
 // the same single add -- so clouds%increment(atmos) never makes a pass over the g-point array.
-template <bool kFused, bool kInc, int kPF, bool kMulti>
+//
+// kBand: also the by-band fluxes bo.up / bo.dn (ty_fluxes_byband; (nbnd, nlay+1, ncol), null = not wanted).  With one
+// angle the band sums are formed from the ring rows in the flush's barrier window (band_flush), i.e. over the float32
+// terms the broadband sum adds: fac * radiance, or the bare radiance when ngpt % 4 != 0 (quirk B-5); with several
+// angles from the per-g accumulators in a by-band variant of the final loop.
+template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
                                            const float *__restrict__ emis, const float *__restrict__ sfc,
                                            LwPlanck pl, BandArgs bands, const float *__restrict__ tau_bnd,
                                            float *__restrict__ gdn, float *__restrict__ gup, long long gcs,
-                                           float *__restrict__ flux_up, float *__restrict__ flux_dn)
+                                           float *__restrict__ flux_up, float *__restrict__ flux_dn, BandOut bo)
 {
   static_assert(kRing % kPF == 0, "prefetch depth must divide the ring");
   // the fused down pass takes lev(l+1)'s Planck fraction from the neighbouring prefetch slot, py[(r+1) % kPF]: with
@@ -245,14 +250,24 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
       ring[(size_t)r * rs + g] = v;
     }
   };
-  auto flush = [&](float *pq, int n, int lev0, int dl) {
+  // bq: the by-band array of the quantity being flushed (kBand)
+  auto flush = [&](float *pq, int n, int lev0, int dl, float *bq) {
     if constexpr (!kMulti) {
-      if (rs != ngpt)
-        ring_flush_lanes(ring, rs, pq, n, lev0, dl, ngpt);
-      else
-        ring_flush<kRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
+      if constexpr (kBand) {
+        if (rs != ngpt)
+          ring_flush_lanes<true>(ring, rs, pq, n, lev0, dl, ngpt, 0, &bo.b, bq, nlev, icol);
+        else
+          ring_flush<kRing, true>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false, false, 0, &bo.b, bq, nullptr, nullptr,
+                                  icol);
+      } else {
+        if (rs != ngpt)
+          ring_flush_lanes(ring, rs, pq, n, lev0, dl, ngpt);
+        else
+          ring_flush<kRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
+      }
     }
   };
+  float *const bdn = kBand ? bo.dn : nullptr, *const bup = kBand ? bo.up : nullptr;
   // layer source and the level source on the side given by `li` (lev index, 0..nlay)
   auto lay_src = [&](float y, int l) { return kFused ? y * bl[l] : y; };
   auto lev_src = [&](float v, int li) { return kFused ? v * bl[nlay + li] : v; };
@@ -268,7 +283,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     const bool acc = imu > 0;
     float I = inc / (2.0f * kPi * ang.w[imu]);
     put(fac * I, I, 0, 0, top, acc);
-    flush(pdn, 1, top, 1);
+    flush(pdn, 1, top, 1, bdn);
     // downward: lw_transport_noscat_dn (:982-1009)
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
@@ -315,7 +330,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
       for (int j0 = 0; j0 < nlay; j0 += kRing) {
 #pragma unroll
         for (int r = 0; r < kRing; r++) step(j0 + r, r);
-        flush(pdn, min(kRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
+        flush(pdn, min(kRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn, bdn);
       }
     }
     // upward: lw_transport_noscat_up (:950-980); j-th layer from the surface is l = lay_up(j).  With one angle its first
@@ -334,7 +349,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // surface reflection and emission (:269)
     float U = I * (1.0f - e) + e * ss;
     put(fac * U, U, 0, 1, sfcl, acc);
-    flush(pup, 1, sfcl, 1);
+    flush(pup, 1, sfcl, 1, bup);
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
 #pragma unroll
@@ -368,12 +383,23 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
       for (int j0 = 0; j0 < nlay; j0 += kRing) {
 #pragma unroll
         for (int r = 0; r < kRing; r++) step(j0 + r, r);
-        flush(pup, min(kRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
+        flush(pup, min(kRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn, bup);
       }
     }
   }
   if constexpr (kMulti) {
     __syncthreads();
+    if constexpr (kBand) {
+      // sum_byband of the angle-summed g-point fluxes: one lane per (quantity, level, band), band fastest
+      const int nb = bo.b.nbnd;
+      for (int t = g; t < 2 * nlev * nb; t += blockDim.x) {
+        const int r = t / nb, ib = t - r * nb, l = r % nlev;
+        float *o = r < nlev ? bdn : bup;
+        if (!o) continue;
+        const float *w = (r < nlev ? wdn : wup) + (size_t)l * ngpt;
+        o[ib + (size_t)nb * (l + (size_t)nlev * icol)] = band_walk(w, w, false, bo.b.lims[2 * ib] - 1, bo.b.lims[2 * ib + 1]);
+      }
+    }
     for (int t = g; t < 2 * nlev; t += blockDim.x) {
       const int l = t % nlev;
       const float *w = (t < nlev ? wdn : wup) + (size_t)l * ngpt;
@@ -413,6 +439,11 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
   const bool gpt = ex.gpt_up != nullptr;
+  const bool bb = ex.byband();
+  if (bb && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
+  if (bb && gpt)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
+                                          "reduces g-point fluxes)");
   LwAngles a{};
   a.nmus = nmus;
   a.Dg = ex.lw_Ds;
@@ -435,14 +466,17 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
     gcs = 2 * nv;
   }
   constexpr int PF = kFused ? kLwfPf : kLwPf;
-  if (nmus > 1 || gpt)
-    hipLaunchKernelGGL((lw_noscat_kernel<kFused, kInc, PF, true>), dim3(ncol), dim3(threads), lds, ctx->stream, ngpt,
-                       nlay, ncol, top_at_1, a, inc_flux, tau, lay_or_pfrac, kFused ? lay_or_pfrac : lev_source,
-                       sfc_emis, sfc_source, pl, bands, tau_bnd, gdn, gup, gcs, flux_up, flux_dn);
-  else
-    hipLaunchKernelGGL((lw_noscat_kernel<kFused, kInc, PF, false>), dim3(ncol), dim3(threads), lds, ctx->stream, ngpt,
-                       nlay, ncol, top_at_1, a, inc_flux, tau, lay_or_pfrac, kFused ? lay_or_pfrac : lev_source,
-                       sfc_emis, sfc_source, pl, bands, tau_bnd, gdn, gup, gcs, flux_up, flux_dn);
+  const BandOut bo = bb ? band_out(ctx) : BandOut{};
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1, a, inc_flux, tau,
+                       lay_or_pfrac, kFused ? lay_or_pfrac : lev_source, sfc_emis, sfc_source, pl, bands, tau_bnd, gdn,
+                       gup, gcs, flux_up, flux_dn, bo);
+  };
+  const bool multi = nmus > 1 || gpt;
+  if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true>);
+  else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true>);
+  else if (multi)  go(lw_noscat_kernel<kFused, kInc, PF, true>);
+  else             go(lw_noscat_kernel<kFused, kInc, PF, false>);
   RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel");
   return RRTMGPNN_OK;
 }
@@ -570,7 +604,9 @@ __device__ __forceinline__ void inc_2str(float &t1, float &w1, float &g1, float 
 // a multiple of 4 radn_dn = radn_dn + radn_dir, :682) and direct, with the broadband down flux summed from the
 // total as sw_solver_2stream does when it saves them (:660-684).  This is the g-point kernel for odd ngpt; even ngpt
 // takes the checkpointed kernel's g-point instance.
-template <bool kHasG, bool kInc, int kPF, bool kGpt = false>
+// kBand: also the by-band fluxes bo.up / bo.dn / bo.dir (ty_fluxes_byband, (nbnd, nlay+1, ncol)), summed from the ring
+// rows in the flush's barrier window; the total down value is dif + dir, rounded once per g-point (band_flush).
+template <bool kHasG, bool kInc, int kPF, bool kGpt = false, bool kBand = false>
 __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int top_at_1,
                                             const float *__restrict__ inc_flux, const float *__restrict__ inc_dif,
                                             const float *__restrict__ tau, const float *__restrict__ ssa,
@@ -581,7 +617,7 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
                                             float *__restrict__ ws, float *__restrict__ flux_up,
                                             float *__restrict__ flux_dn, float *__restrict__ flux_dir,
                                             float *__restrict__ gpt_up, float *__restrict__ gpt_dn,
-                                            float *__restrict__ gpt_dir)
+                                            float *__restrict__ gpt_dir, BandOut bo)
 {
   static_assert(kRingSw % kPF == 0, "prefetch depth must divide the ring");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -720,7 +756,13 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
       }
     }
   };
-  auto flush = [&](int n, int lev0, int dl) { ring_flush<kRingSw>(ring, part, 3, n, lev0, dl, ngpt, nlev, !kGpt); };
+  auto flush = [&](int n, int lev0, int dl) {
+    if constexpr (kBand)
+      ring_flush<kRingSw, true>(ring, part, 3, n, lev0, dl, ngpt, nlev, !kGpt, false, 0, &bo.b, bo.up, bo.dn, bo.dir,
+                                icol);
+    else
+      ring_flush<kRingSw>(ring, part, 3, n, lev0, dl, ngpt, nlev, !kGpt);
+  };
   const int dl_dn = top_at_1 ? 1 : -1;
   float Fdn = (on && inc_dif) ? inc_dif[gcol] : 0.0f;
   put(Fdn * alb_b + src_b, Fdn, Ftop, 0, top);  // Eq 12 at the top; alb_b/src_b hold the top level's values
@@ -765,7 +807,7 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
   }
 }
 
-template <bool kHasG, bool kInc, bool kGpt = false>
+template <bool kHasG, bool kInc, bool kGpt = false, bool kBand = false>
 static void sw_launch(rrtmgpnn_context *ctx, size_t lds, int threads, int ngpt, int nlay, int ncol,
                       int top_at_1, const float *inc_flux, const float *inc_flux_dif, const float *tau,
                       const float *ssa, const float *g, const float *mu0, const float *alb_dir, const float *alb_dif,
@@ -773,10 +815,10 @@ static void sw_launch(rrtmgpnn_context *ctx, size_t lds, int threads, int ngpt, 
                       float *flux_up, float *flux_dn, float *flux_dir)
 {
   const auto &ex = ctx->extras;
-  hipLaunchKernelGGL((sw_2stream_kernel<kHasG, kInc, kSwPf, kGpt>), dim3(ncol), dim3(threads), lds,
+  hipLaunchKernelGGL((sw_2stream_kernel<kHasG, kInc, kSwPf, kGpt, kBand>), dim3(ncol), dim3(threads), lds,
                      ctx->stream, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, alb_dir,
                      alb_dif, bands, tau_bnd, ssa_bnd, g_bnd, (float *)ws, flux_up, flux_dn, flux_dir, ex.gpt_up,
-                     ex.gpt_dn, ex.gpt_dir);
+                     ex.gpt_dn, ex.gpt_dir, kBand ? band_out(ctx) : BandOut{});
 }
 
 int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
@@ -798,6 +840,10 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
   if (gpt && (!ctx->extras.gpt_up || !ctx->extras.gpt_dn || !ctx->extras.gpt_dir))
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: g-point outputs need gpt_flux_up, gpt_flux_dn and gpt_flux_dn_dir");
   if (gpt && inc) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: g-point outputs with a fused increment");
+  const bool bb = ctx->extras.byband();
+  if (bb && gpt)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
+                                          "reduces g-point fluxes)");
   const bool ck = (ngpt % 2) == 0 && (mode == 3 || mode == 0 || gpt);
   const bool x2 = !ck && (ngpt % 2) == 0 && mode != 1;
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
@@ -846,7 +892,23 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: too many layers for LDS partials");
   const BandArgs nob{};
   const BandArgs &b = inc ? *bands : nob;
-  if (gpt && g)
+  if (bb && inc && g)
+    sw_launch<true, true, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa,
+                                       g, mu0, alb_dir, alb_dif, b, tau_bnd, ssa_bnd, g_bnd, ws, flux_up, flux_dn,
+                                       flux_dir);
+  else if (bb && inc)
+    sw_launch<false, true, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau,
+                                        ssa, g, mu0, alb_dir, alb_dif, b, tau_bnd, ssa_bnd, g_bnd, ws, flux_up,
+                                        flux_dn, flux_dir);
+  else if (bb && g)
+    sw_launch<true, false, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau,
+                                        ssa, g, mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up,
+                                        flux_dn, flux_dir);
+  else if (bb)
+    sw_launch<false, false, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau,
+                                         ssa, g, mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up,
+                                         flux_dn, flux_dir);
+  else if (gpt && g)
     sw_launch<true, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
                                  mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up, flux_dn, flux_dir);
   else if (gpt)
@@ -878,10 +940,13 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
 // ------------------------------------------------------------------------------------------
 constexpr int kNsRing = 8;
 
+// kBand: also the by-band direct flux bo.dir (nbnd, nlay+1, ncol), summed from the ring rows (band_flush)
+template <bool kBand = false>
 __global__ void __launch_bounds__(1024) sw_noscat_kernel(int ngpt, int nlay, int top_at_1,
                                                          const float *__restrict__ inc_flux,
                                                          const float *__restrict__ tau, const float *__restrict__ mu0p,
-                                                         float *__restrict__ flux_dir, float *__restrict__ gpt_dir)
+                                                         float *__restrict__ flux_dir, float *__restrict__ gpt_dir,
+                                                         BandOut bo)
 {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   uint64_t *etab = (uint64_t *)(smem + kExpTabOff);
@@ -903,6 +968,8 @@ __global__ void __launch_bounds__(1024) sw_noscat_kernel(int ngpt, int nlay, int
       for (int i = 0; i < ngpt; i++) s = s + r[i];
       out[lev0 + (int)threadIdx.x * dl] = s;
     }
+    if constexpr (kBand)
+      band_flush(ring, ngpt, 0, 0, 1, 1, n, 0, lev0, dl, nlev, icol, icol + 1, -1, bo.dir, nullptr, nullptr, bo.b, 64);
     __syncthreads();
   };
   // g-point direct flux (ty_fluxes_flexible gpt_flux_dn_dir, (ngpt, nlev, ncol)) when asked for
@@ -938,8 +1005,18 @@ int launch_sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int to
   if (ngpt > 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw_solver_noscat: more than 1024 g-points");
   const int threads = (ngpt + 63) / 64 * 64;
   const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)kNsRing * ngpt);
-  hipLaunchKernelGGL(sw_noscat_kernel, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, top_at_1, inc_flux,
-                     tau, mu0, flux_dir, ctx->extras.gpt_dir);
+  const auto &ex = ctx->extras;
+  if (ex.byband() && (ex.bnd_up || ex.bnd_dn))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: only bnd_flux_dn_dir is an output of the direct-beam solver");
+  if (ex.byband() && ex.gpt_dir)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw_solver_noscat: by-band and g-point outputs in one call "
+                                          "(rrtmgpnn_sum_byband reduces g-point fluxes)");
+  if (ex.byband())
+    hipLaunchKernelGGL(sw_noscat_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, top_at_1,
+                       inc_flux, tau, mu0, flux_dir, ex.gpt_dir, band_out(ctx));
+  else
+    hipLaunchKernelGGL(sw_noscat_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, top_at_1,
+                       inc_flux, tau, mu0, flux_dir, ex.gpt_dir, BandOut{});
   RRTMGPNN_LAUNCH_CHECK("sw_noscat_kernel");
   return RRTMGPNN_OK;
 }

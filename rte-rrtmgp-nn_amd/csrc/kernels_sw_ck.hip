@@ -178,7 +178,8 @@ constexpr int kCkAheadSmall = 1;
 // (the RRTMGP g-point sets: 16 per band).  Round 4, C4: SW solver -1.7 % alone, steps -0.8 % (3 alternating pairs)
 template <bool kHasG, bool kInc, int K, bool kGpt = false, int R = kCkRing,
           int WAVES = (!kHasG && !kInc && !kGpt) ? kCkWavesNN : kCkWaves, bool kTn = false,
-          class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1>
+          class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1,
+          bool kBand = false>
 __global__ void __launch_bounds__(512, WAVES)
     sw_2stream_ck_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
@@ -187,7 +188,7 @@ __global__ void __launch_bounds__(512, WAVES)
                          const float *__restrict__ tau_bnd, const float *__restrict__ ssa_bnd,
                          const float *__restrict__ g_bnd, float *__restrict__ ws, float *__restrict__ flux_up,
                          float *__restrict__ flux_dn, float *__restrict__ flux_dir, float *__restrict__ gpt_up,
-                         float *__restrict__ gpt_dn, float *__restrict__ gpt_dir, SwBcDev bc)
+                         float *__restrict__ gpt_dn, float *__restrict__ gpt_dir, SwBcDev bc, BandOut bo)
 {
   static_assert(R % K == 0, "the flux ring must hold whole chunks");
   constexpr bool kG0 = !kHasG && !kInc;  // g is the literal 0 (the NN path)
@@ -470,12 +471,15 @@ __global__ void __launch_bounds__(512, WAVES)
     }
   };
   auto flush = [&](int n, int lev0, int dl, int slot0 = 0) {
+    // kBand: the by-band sums bo.up / bo.dn / bo.dir in the same barrier window; the ring keeps diffuse and direct
+    // apart (the broadband bits do not move) and the band walk forms dif + dir itself (band_flush)
+    const BandOut *pb = kBand ? &bo : nullptr;
     if (kCkFlushLanes && (ngpt & 3) == 0 && 3 * ncb * n * 4 <= (int)blockDim.x)
-      ring_flush_sw_lanes<R, kGpt>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up, flux_dn,
-                                   flux_dir, rs, slot0);
+      ring_flush_sw_lanes<R, kGpt, kBand>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up,
+                                          flux_dn, flux_dir, rs, slot0, pb);
     else
-      ring_flush_sw<R, kGpt>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up, flux_dn,
-                             flux_dir, rs, slot0);
+      ring_flush_sw<R, kGpt, kBand>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up, flux_dn,
+                                    flux_dir, rs, slot0, pb);
   };
   // the ring holds M = R / K chunks; the block flushes it when it is full (a barrier, the ordered sums, a barrier).
   // (Staggering the blocks' flush phases, so that blocks sharing a CU flush at different chunks, measured equal, round
@@ -588,6 +592,8 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
   const SwBcDev nobc{};  // tsi == NULL: the caller's inc_flux, mu0 and albedos
   const SwBcDev &bcd = bc ? *bc : nobc;
   const auto &ex = ctx->extras;
+  const bool bb = ex.byband();
+  const BandOut bo = bb ? band_out(ctx) : BandOut{};
   // npl g-points per lane, ncb columns per block
   auto go = [&](auto kern, const float *tb, const float *sb, const float *gb, int ring = kCkRing, int npl = 2) -> int {
     const int ncb = npl == 2 ? ncb2 : columns_per_block(ngpt);
@@ -601,7 +607,7 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, top_at_1, ncb, inc_flux, inc_flux_dif,
                        tau, ssa, g, mu0, alb_dir, alb_dif, b, tb, sb, gb, (float *)ws, flux_up, flux_dn, flux_dir,
-                       ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd);
+                       ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
@@ -611,6 +617,36 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
     if (bands) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: g-point outputs with a fused increment");
     if (g) return go(sw_2stream_ck_kernel<true, false, kCkK, true>, nullptr, nullptr, nullptr);
     return go(sw_2stream_ck_kernel<false, false, kCkK, true>, nullptr, nullptr, nullptr);
+  }
+  if (bb) {
+    // by-band instances: the small-grid clear-sky instance where it applies (as without the request), else the
+    // large-grid forms without workspace planes (the same bits as the others), the band-pair and the general
+    // increment, with and without g
+    if (!g && !bands && sw_ck_small(ctx, ngpt, ncol, false, false, false))
+      return go(sw_2stream_ck_kernel<false, false, kCkKSmall, false, kCkRingSmall, kCkWavesSmall, kCkTnSmall, VSmall,
+                                     kCkEmkSmall, false, kCkP1Small, kCkAheadSmall, true>,
+                nullptr, nullptr, nullptr, kCkRingSmall, (int)(sizeof(VSmall) / sizeof(float)));
+    bool pair = bands != nullptr;
+    for (int i = 0; bands && i < b.nbnd; i++) pair = pair && ((b.lims[2 * i] - 1) % 2 == 0);
+    constexpr int W = kCkWaves;
+    constexpr int P = kCkP1;
+    if (pair && g)
+      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (pair)
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (bands && g)
+      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (bands)
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true>,
+                tau_bnd, ssa_bnd, g_bnd);
+    if (g)
+      return go(sw_2stream_ck_kernel<true, false, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true>, nullptr,
+                nullptr, nullptr);
+    return go(sw_2stream_ck_kernel<false, false, kCkK, false, kCkRing, kCkWavesNN, false, f2, false, false, P, 1, true>,
+              nullptr, nullptr, nullptr);
   }
   if (bands) {
     bool pair = true;  // every band starts at an even (0-based) g-point

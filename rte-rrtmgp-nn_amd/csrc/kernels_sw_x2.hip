@@ -102,7 +102,9 @@ constexpr int kSw2Ring = 6;  // levels staged per ordered flush (2, 4, 8 were 2-
 // band-resolved cloud arrays (same expressions, same bits) instead of reading three g-resolved planes pass 2 would park
 // in workspace: 3 plane stores and 1 plane load fewer per launch (the band arrays are 16x smaller and stay in cache).
 
-template <bool kHasG, bool kInc, int kPF>
+// kBand: also the by-band fluxes bo.up / bo.dn / bo.dir (ty_fluxes_byband, (nbnd, nlay+1, ncol)), summed from the ring
+// rows in the flush's barrier window (band_flush, rte_device.hpp)
+template <bool kHasG, bool kInc, int kPF, bool kBand = false>
 __global__ void __launch_bounds__(512, kSw2Waves)
     sw_2stream_x2_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
@@ -110,7 +112,7 @@ __global__ void __launch_bounds__(512, kSw2Waves)
                          const float *__restrict__ alb_dir, const float *__restrict__ alb_dif, BandArgs bands,
                          const float *__restrict__ tau_bnd, const float *__restrict__ ssa_bnd,
                          const float *__restrict__ g_bnd, float *__restrict__ ws, float *__restrict__ flux_up,
-                         float *__restrict__ flux_dn, float *__restrict__ flux_dir)
+                         float *__restrict__ flux_dn, float *__restrict__ flux_dir, BandOut bo)
 {
   static_assert(kSw2Ring % kPF == 0, "prefetch depth must divide the ring");
   constexpr bool kRc = kInc ? kSw2RecompInc : kSw2Recomp;
@@ -237,8 +239,12 @@ __global__ void __launch_bounds__(512, kSw2Waves)
     }
   };
   auto flush = [&](int n, int lev0, int dl) {
-    ring_flush_sw<kSw2Ring>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up, flux_dn,
-                            flux_dir);
+    if constexpr (kBand)
+      ring_flush_sw<kSw2Ring, false, true>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up,
+                                           flux_dn, flux_dir, 0, 0, &bo);
+    else
+      ring_flush_sw<kSw2Ring>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up, flux_dn,
+                              flux_dir);
   };
   const int dl_dn = top_at_1 ? 1 : -1;
   f2 Fdn = inc_dif ? ld_col(inc_dif) : splat(0.0f);
@@ -316,15 +322,23 @@ int launch_sw_2stream_x2(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
   const BandArgs &b = bands ? *bands : nob;
   const dim3 grid((ncol + ncb - 1) / ncb), block(threads);
   constexpr int PF = kSw2Pf, PFN = kSw2PfNoG, PFI = kSw2PfInc;
+  const bool bb = ctx->extras.byband();
+  const BandOut bo = bb ? band_out(ctx) : BandOut{};
   auto go = [&](auto kern, const float *tb, const float *sb, const float *gb) -> int {
     // rings past 64 KiB (4 columns of 224 g-points: 64.5 KiB) need the dynamic-LDS limit raised (per device)
     if (lds > 64 * 1024)
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, top_at_1, ncb, inc_flux, inc_flux_dif,
-                       tau, ssa, g, mu0, alb_dir, alb_dif, b, tb, sb, gb, (float *)ws, flux_up, flux_dn, flux_dir);
+                       tau, ssa, g, mu0, alb_dir, alb_dif, b, tb, sb, gb, (float *)ws, flux_up, flux_dn, flux_dir, bo);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_x2_kernel");
     return RRTMGPNN_OK;
   };
+  if (bb) {
+    if (bands && g) return go(sw_2stream_x2_kernel<true, true, PF, true>, tau_bnd, ssa_bnd, g_bnd);
+    if (bands) return go(sw_2stream_x2_kernel<false, true, PFI, true>, tau_bnd, ssa_bnd, g_bnd);
+    if (g) return go(sw_2stream_x2_kernel<true, false, PF, true>, nullptr, nullptr, nullptr);
+    return go(sw_2stream_x2_kernel<false, false, PFN, true>, nullptr, nullptr, nullptr);
+  }
   if (bands && g) return go(sw_2stream_x2_kernel<true, true, PF>, tau_bnd, ssa_bnd, g_bnd);
   if (bands) return go(sw_2stream_x2_kernel<false, true, PFI>, tau_bnd, ssa_bnd, g_bnd);
   if (g) return go(sw_2stream_x2_kernel<true, false, PF>, nullptr, nullptr, nullptr);

@@ -86,6 +86,61 @@ struct LwAngles {
 };
 
 // ------------------------------------------------------------------------------------------
+// By-band fluxes (ty_fluxes_byband, extensions/mo_fluxes_byband.F90; sum_byband,
+// extensions/mo_fluxes_byband_kernels.F90:31-50): a band's flux starts from the band's first g-point value and adds
+// the others one by one in increasing g.  The solvers' by-band instances (template flag kBand) form these sums from the
+// LDS ring rows that the ordered broadband flush walks, inside that flush's barrier window, and store them to
+// (nbnd, nlev, ncol) arrays; a null array is not wanted.
+// ------------------------------------------------------------------------------------------
+struct BandOut {
+  float *up, *dn, *dir;
+  BandArgs b;
+};
+
+inline BandOut band_out(const rrtmgpnn_context *ctx)
+{
+  return BandOut{ctx->extras.bnd_up, ctx->extras.bnd_dn, ctx->extras.bnd_dir, ctx->extras.bnd};
+}
+
+// sum_byband over g-points [lo, hi) of one row; add2: the value is r[i] + r2[i], rounded once per g-point (the SW
+// total down flux from the diffuse and direct rows)
+__device__ __forceinline__ float band_walk(const float *r, const float *r2, bool add2, int lo, int hi)
+{
+  float s = add2 ? r[lo] + r2[lo] : r[lo];
+  if (add2) for (int i = lo + 1; i < hi; i++) s = s + (r[i] + r2[i]);
+  else      for (int i = lo + 1; i < hi; i++) s = s + r[i];
+  return s;
+}
+
+// The band sums of `n` staged levels of a ring [ncb][nq][rows][rs] (column stride cs, quantity stride qs floats; the
+// levels in rows slot0 .. slot0 + n - 1, row c holding level lev0 + c*dl).  One lane per (column, quantity, level, band),
+// band fastest, so a wave's stores are contiguous; the items are dealt out starting at lane t0, the first lane that the
+// broadband flush leaves idle (rounded up to a wave by the caller where whole waves are idle), and wrap around the
+// block.  o[q] is quantity q's output (null: skipped); dn_q: the quantity whose value is its own row plus quantity 2's
+// (-1: none).  Columns at or past ncol store nothing.  Call between the flush's two barriers.
+__device__ __forceinline__ void band_flush(const float *ring, int rs, int qs, int cs, int ncb, int nq, int n,
+                                           int slot0, int lev0, int dl, int nlev, int icol0, int ncol, int dn_q,
+                                           float *o0, float *o1, float *o2, const BandArgs &b, int t0)
+{
+  const int nb = b.nbnd, items = ncb * nq * n * nb, nt = (int)blockDim.x;
+  int first = (int)threadIdx.x - t0;
+  if (first < 0) first += nt;
+  for (int it = first; it < items; it += nt) {
+    const int row = it / nb, ib = it - row * nb;
+    const int cq = row / n, s = row - cq * n;
+    const int c = cq / nq, q = cq - c * nq;
+    float *o = q == 0 ? o0 : (q == 1 ? o1 : o2);
+    const int icol = icol0 + c;
+    if (!o || icol >= ncol) continue;
+    const float *rc = ring + (size_t)c * cs;
+    const float *r = rc + (size_t)q * qs + (size_t)(slot0 + s) * rs;
+    const float *r2 = rc + (size_t)2 * qs + (size_t)(slot0 + s) * rs;
+    const int lo = b.lims[2 * ib] - 1, hi = b.lims[2 * ib + 1];
+    o[ib + (size_t)nb * ((size_t)(lev0 + s * dl) + (size_t)nlev * icol)] = band_walk(r, r2, q == dn_q, lo, hi);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Ordered broadband reduction.  The reference sums g-points into 4 interleaved partial sums,
 // partial j accumulating g = j, j+4, j+8, ... in increasing g, then ((p0+p1)+p2)+p3
 // (rte/kernels/mo_rte_solver_kernels.F90:296-318 LW, :643-686 SW).  A float32 tree reduction
@@ -99,9 +154,12 @@ struct LwAngles {
 // dn_mode (SW): quantity 1 is accumulated as (s + ring1) + ring2, i.e. sums_dn + radn_dn + radn_dir.
 // ngpt % 4 != 0, or seq: the reference uses sum(radn, 1) instead (one sequential sum, kept in partial 0).
 // slot0: the first staged slot (the levels sit in slots slot0 .. slot0 + n - 1)
-template <int R>
+// kBand: also the by-band sums of column icol (band_flush; o0 / o1 / o2 are quantities 0 / 1 / 2's outputs)
+template <int R, bool kBand = false>
 __device__ __forceinline__ void ring_flush(const float *ring, float *part, int nq, int n, int lev0, int dl, int ngpt,
-                                           int nlev, bool dn_mode, bool seq = false, int slot0 = 0)
+                                           int nlev, bool dn_mode, bool seq = false, int slot0 = 0,
+                                           const BandArgs *b = nullptr, float *o0 = nullptr, float *o1 = nullptr,
+                                           float *o2 = nullptr, int icol = 0)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -134,6 +192,9 @@ __device__ __forceinline__ void ring_flush(const float *ring, float *part, int n
     float4 *p = (float4 *)(part + ((size_t)q * nlev + lev0 + c * dl) * 4);
     *p = make_float4(s0, s1, s2, s3);
   }
+  if constexpr (kBand)
+    band_flush(ring, ngpt, R * ngpt, 0, 1, nq, n, slot0, lev0, dl, nlev, icol, icol + 1, dn_mode ? 1 : -1, o0, o1, o2,
+               *b, (nq * n + 63) & ~63);
   __syncthreads();
 }
 
@@ -142,8 +203,11 @@ __device__ __forceinline__ void ring_flush(const float *ring, float *part, int n
 // ring_flush's float4 walk, in the same order, with a quarter of its instructions on the flushing wave.  With rows
 // padded to stride = ngpt + 4 the lanes' rows start in different LDS banks.
 // slot0: the first staged slot (the levels sit in slots slot0 .. slot0 + n - 1)
+// kBand: also the by-band sums of column icol into bnd (band_flush; null: not wanted)
+template <bool kBand = false>
 __device__ __forceinline__ void ring_flush_lanes(const float *ring, int stride, float *part, int n, int lev0, int dl,
-                                                 int ngpt, int slot0 = 0)
+                                                 int ngpt, int slot0 = 0, const BandArgs *b = nullptr,
+                                                 float *bnd = nullptr, int nlev = 0, int icol = 0)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -156,6 +220,8 @@ __device__ __forceinline__ void ring_flush_lanes(const float *ring, int stride, 
     for (int m = 0; m < n4; m++) sum = sum + r[4 * m];
     part[(size_t)(lev0 + sl * dl) * 4 + j] = sum;
   }
+  if constexpr (kBand)
+    band_flush(ring, stride, 0, 0, 1, 1, n, slot0, lev0, dl, nlev, icol, icol + 1, -1, bnd, nullptr, nullptr, *b, 64);
   __syncthreads();
 }
 
@@ -169,10 +235,11 @@ __device__ __forceinline__ float combine4(const float *p) { return ((p[0] + p[1]
 // saves g-point fluxes (:660-670): the down sum is s + total instead of (s + diffuse) + direct
 // stride: floats per ring row (ngpt, or ngpt padded so that the rows the flush threads walk together fall in different
 // LDS banks)
-template <int R, bool kTotal = false>
+// kBand: also the by-band sums (band_flush), the down value formed as dif + dir per g-point unless kTotal
+template <int R, bool kTotal = false, bool kBand = false>
 __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n, int lev0, int dl, int ngpt, int nlev,
                                               int icol0, int ncol, float *o_up, float *o_dn, float *o_dir,
-                                              int stride = 0, int slot0 = 0)
+                                              int stride = 0, int slot0 = 0, const BandOut *bo = nullptr)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -210,6 +277,9 @@ __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n,
       o[lev0 + s * dl + (size_t)nlev * icol] = ((s0 + s1) + s2) + s3;
     }
   }
+  if constexpr (kBand)
+    band_flush(ring, rs, R * rs, 3 * R * rs, ncb, 3, n, slot0, lev0, dl, nlev, icol0, ncol, kTotal ? -1 : 1, bo->up,
+               bo->dn, bo->dir, bo->b, (3 * ncb * n + 63) & ~63);
   __syncthreads();
 }
 
@@ -223,10 +293,11 @@ __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n,
 // (the SW launchers refuse more before launching)
 constexpr int kFlushLanesMaxCols = 4;
 
-template <int R, bool kTotal = false>
+template <int R, bool kTotal = false, bool kBand = false>
 __device__ __forceinline__ void ring_flush_sw_lanes(const float *ring, int ncb, int n, int lev0, int dl, int ngpt,
                                                     int nlev, int icol0, int ncol, float *o_up, float *o_dn,
-                                                    float *o_dir, int stride, int slot0 = 0)
+                                                    float *o_dir, int stride, int slot0 = 0,
+                                                    const BandOut *bo = nullptr)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -259,6 +330,9 @@ __device__ __forceinline__ void ring_flush_sw_lanes(const float *ring, int ncb, 
       o[lev0 + (dl > 0 ? sl : -sl) + (size_t)nlev * icol] = ((sum + p1) + p2) + p3;  // dl = +-1
     }
   }
+  if constexpr (kBand)
+    band_flush(ring, stride, R * stride, 3 * R * stride, ncb, 3, n, slot0, lev0, dl, nlev, icol0, ncol,
+               kTotal ? -1 : 1, bo->up, bo->dn, bo->dir, bo->b, (3 * per_q + 63) & ~63);
   __syncthreads();
 }
 

@@ -17,6 +17,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_compute_heating_rate
   public :: c_rrtmgpnn_lw_solver_noscat_gpt, c_rrtmgpnn_lw_solver_noscat_planck_gpt, c_rrtmgpnn_sw_solver_2stream_gpt
   public :: c_rrtmgpnn_lw_solver_1rescl_gpt, c_rrtmgpnn_lw_solver_2stream_gpt, c_rrtmgpnn_sw_solver_noscat_gpt
+  public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
   public :: c_rrtmgpnn_network_load, c_rrtmgpnn_compute_nn_inputs, c_rrtmgpnn_get_col_dry, &
             c_rrtmgpnn_interpolate_tlev, c_rrtmgpnn_predict_nn_lw, c_rrtmgpnn_predict_nn_sw, &
             c_rrtmgpnn_compute_planck_source_nn, c_rrtmgpnn_lw_solver_noscat, c_rrtmgpnn_sw_solver_2stream, &
@@ -273,6 +274,21 @@ module mo_rrtmgpnn_c
       type(c_ptr), value :: ctx, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt, sfc_alb_dif_gpt, &
                             flux_up, flux_dn, flux_dir
       integer(c_int), value :: ngpt, nlay, ncol, top_at_1
+    end function
+    ! ty_fluxes_byband: by-band outputs (nbnd, nlay+1, ncol) of the next solver call; sum_byband of g-point fluxes
+    integer(c_int) function c_rrtmgpnn_solver_request_byband(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, &
+        bnd_flux_dir) bind(C, name="rrtmgpnn_solver_request_byband")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, bnd_flux_up, bnd_flux_dn, bnd_flux_dir
+      integer(c_int), value :: nbnd
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
+    end function
+    integer(c_int) function c_rrtmgpnn_sum_byband(ctx, ngpt, nlev, ncol, nbnd, band_lims_gpt, gpt_flux, bnd_flux) &
+        bind(C, name="rrtmgpnn_sum_byband")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, gpt_flux, bnd_flux
+      integer(c_int), value :: ngpt, nlev, ncol, nbnd
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
     end function
     integer(c_int) function c_rrtmgpnn_expand_band_to_gpt(ctx, nband, ngpt, ncol, band_lims_gpt, arr_in, arr_out) &
         bind(C, name="rrtmgpnn_expand_band_to_gpt")

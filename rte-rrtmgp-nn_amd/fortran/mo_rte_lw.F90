@@ -9,12 +9,17 @@
 ! with one angle the g-point radiances (quirk B-5), with several the angle-summed fluxes; lw_solver_2stream the adding
 ! fluxes.  lw_Ds on 1scl properties; flux_up_Jac / flux_dn_Jac accepted and left untouched (compute_Jac = .false.),
 ! an error string only with use_2stream, as the reference.
+! ty_fluxes_byband (mo_fluxes_byband) is detected with select type: the solver forms the band sums itself
+! (rrtmgpnn_solver_request_byband).  Together with g-point outputs the g-point arrays are reduced with
+! rrtmgpnn_sum_byband -- except with one angle of the no-scattering / rescaled solution, whose g-point arrays hold
+! radiances (quirk B-5): there the solver runs a second time with the by-band request.
 module mo_rte_lw
   use, intrinsic :: iso_c_binding
   use mo_rte_kind,         only: wp
   use mo_optical_props,    only: ty_optical_props_arry, ty_optical_props_1scl, ty_optical_props_2str, dev_g_read
   use mo_source_functions, only: ty_source_func_lw
   use mo_fluxes,           only: ty_fluxes_flexible
+  use mo_fluxes_byband,    only: ty_fluxes_byband
   use mo_rte_rrtmgp_config, only: check_values
   use mo_rrtmgpnn_c
   implicit none
@@ -52,8 +57,10 @@ contains
     integer(c_long_long) :: ng, nv, nsfc, ngv
     integer(c_int), allocatable :: lims(:,:)
     type(c_ptr) :: d_tau, d_ssa, d_g, d_lay, d_lev, d_sfc, d_jac, d_emis, d_emis_gpt, d_inc, d_up, d_dn
-    type(c_ptr) :: d_ds, d_gup, d_gdn
-    logical :: two_str, use_2s, src_tmp, g_tmp, gpt, du, dd
+    type(c_ptr) :: d_ds, d_gup, d_gdn, d_bup, d_bdn
+    integer(c_long_long) :: nbv
+    integer(c_int) :: rc_drop
+    logical :: two_str, use_2s, src_tmp, g_tmp, gpt, du, dd, bb, one_angle
     real(wp), allocatable :: up(:,:), dn(:,:)
 
     ncol  = optical_props%get_ncol()
@@ -110,6 +117,13 @@ contains
         error_msg = "rte_lw: gpt_flux_dn inconsistently sized"; return
       end if
     end if
+    bb = .false.
+    select type (fluxes)
+    class is (ty_fluxes_byband)
+      bb = fluxes%are_desired_bnd()
+      if (bb) error_msg = fluxes%check_extents_bnd(nband, nlay + 1, ncol, .false.)
+      if (error_msg /= '') return
+    end select
     use_2s = .false.
     if (present(use_2stream)) use_2s = use_2stream
     two_str = .false.
@@ -169,53 +183,36 @@ contains
       d_gdn = dev_scratch(ngv)
     end if
     d_emis_gpt = c_null_ptr
-    if (.not. two_str .and. sources%planck_deferred) then
-      ! lw_solver_noscat_GaussQuad (:326-353) with compute_Planck_source_nn (gas_optics, :398-404) and expand(sfc_emis)
-      ! (:429-447) inside the solver
-      error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
-                    merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_ds, &
-                    d_inc, d_tau, dev_present(sources%lay_source, ng, PRESENT_READ), nband, sources%pk_ntemp, &
-                    dev_present(sources%pk_tlay, size(sources%pk_tlay, kind=c_long_long), PRESENT_READ), &
-                    dev_present(sources%pk_tlev, size(sources%pk_tlev, kind=c_long_long), PRESENT_READ), &
-                    dev_present(sources%pk_tsfc, size(sources%pk_tsfc, kind=c_long_long), PRESENT_READ), &
-                    sources%pk_sfc_lay, lims, sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, &
-                    d_up, d_dn, d_gup, d_gdn), "rte_lw: lw_solver_noscat")
+    d_bup = c_null_ptr
+    d_bdn = c_null_ptr
+    nbv = int(nband, c_long_long) * (nlay + 1) * ncol
+    one_angle = nmus == 1 .and. .not. (two_str .and. use_2s)
+    if (bb) then
+      select type (fluxes)
+      class is (ty_fluxes_byband)
+        if (associated(fluxes%bnd_flux_up)) d_bup = dev_scratch(nbv)
+        if (associated(fluxes%bnd_flux_dn)) d_bdn = dev_scratch(nbv)
+      end select
+    end if
+    if (.not. bb) then
+      call run_solver(d_gup, d_gdn)
     else
-      src_tmp = .false.
-      g_tmp = .false.
-      error_msg = sources%device_sources(d_lay, d_lev, d_sfc, d_jac, src_tmp)
-      if (error_msg == '') then
-        d_emis_gpt = dev_scratch(nsfc)
-        ! sfc_emis expanded to g-points (:429-447), then the solver (:326-387)
-        error_msg = rrtmgpnn_check(c_rrtmgpnn_expand_band_to_gpt(rrtmgpnn_ctx(), nband, ngpt, ncol, lims, d_emis, &
-                                                                 d_emis_gpt), "rte_lw: expand")
+      if (gpt) call run_solver(d_gup, d_gdn)
+      if (gpt .and. .not. one_angle) then
+        if (error_msg == '' .and. c_associated(d_bup)) &
+          error_msg = rrtmgpnn_check(c_rrtmgpnn_sum_byband(rrtmgpnn_ctx(), ngpt, nlay + 1, ncol, nband, lims, d_gup, &
+                                                           d_bup), "rte_lw: sum_byband")
+        if (error_msg == '' .and. c_associated(d_bdn)) &
+          error_msg = rrtmgpnn_check(c_rrtmgpnn_sum_byband(rrtmgpnn_ctx(), ngpt, nlay + 1, ncol, nband, lims, d_gdn, &
+                                                           d_bdn), "rte_lw: sum_byband")
+      else if (error_msg == '') then
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_solver_request_byband(rrtmgpnn_ctx(), nband, lims, d_bup, d_bdn, &
+                                                                    c_null_ptr), "rte_lw: solver_request_byband")
+        if (error_msg == '') call run_solver(c_null_ptr, c_null_ptr)
+        ! a request that no solver call consumed (the sources failed first) is dropped
+        if (error_msg /= '') rc_drop = c_rrtmgpnn_solver_request_byband(rrtmgpnn_ctx(), 0_c_int, lims, c_null_ptr, &
+                                                                        c_null_ptr, c_null_ptr)
       end if
-      if (error_msg == '') then
-        select type (optical_props)
-        type is (ty_optical_props_2str)
-          d_ssa = dev_present(optical_props%ssa, ng, PRESENT_READ)
-          d_g = dev_g_read(optical_props, g_tmp)
-        end select
-        if (two_str .and. use_2s) then
-          error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_2stream_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
-                                     merge(1_c_int, 0_c_int, top_at_1), d_inc, d_tau, d_ssa, d_g, d_lev, d_emis_gpt, &
-                                     d_sfc, d_up, d_dn, d_gup, d_gdn), "rte_lw: lw_solver_2stream")
-        else if (two_str) then
-          error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
-                                     merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), &
-                                     gauss_wts(1:nmus, nmus), d_inc, d_tau, d_ssa, d_g, d_lay, d_lev, d_emis_gpt, &
-                                     d_sfc, d_up, d_dn, d_gup, d_gdn), "rte_lw: lw_solver_noscat (rescaled)")
-        else
-          error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
-                                     merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), &
-                                     gauss_wts(1:nmus, nmus), d_ds, d_inc, d_tau, d_lay, d_lev, d_emis_gpt, d_sfc, &
-                                     d_up, d_dn, d_gup, d_gdn), "rte_lw: lw_solver_noscat")
-        end if
-      end if
-      if (src_tmp) then
-        call dev_release(d_lay); call dev_release(d_lev); call dev_release(d_sfc); call dev_release(d_jac)
-      end if
-      if (g_tmp) call dev_release(d_g)
     end if
     ! broadband fluxes go straight into the caller's arrays when they are contiguous (and no net flux is wanted from
     ! them); otherwise into temporaries copied after the sync
@@ -239,16 +236,85 @@ contains
         if (associated(fluxes%gpt_flux_up)) call dev_copy_out(fluxes%gpt_flux_up, d_gup, ngv)
         if (associated(fluxes%gpt_flux_dn)) call dev_copy_out(fluxes%gpt_flux_dn, d_gdn, ngv)
       end if
+      if (bb) then
+        select type (fluxes)
+        class is (ty_fluxes_byband)
+          if (associated(fluxes%bnd_flux_up)) call dev_copy_out(fluxes%bnd_flux_up, d_bup, nbv)
+          if (associated(fluxes%bnd_flux_dn)) call dev_copy_out(fluxes%bnd_flux_dn, d_bdn, nbv)
+        end select
+      end if
     end if
     call rrtmgpnn_sync(error_msg, "rte_lw")
     if (error_msg == '') then
       if (associated(fluxes%flux_up) .and. .not. du) fluxes%flux_up = up
       if (associated(fluxes%flux_dn) .and. .not. dd) fluxes%flux_dn = dn
       if (associated(fluxes%flux_net)) fluxes%flux_net = dn - up
+      if (bb) then
+        select type (fluxes)
+        class is (ty_fluxes_byband)  ! net_byband_precalc
+          if (associated(fluxes%bnd_flux_net)) fluxes%bnd_flux_net = fluxes%bnd_flux_dn - fluxes%bnd_flux_up
+        end select
+      end if
     end if
     call dev_release(d_emis); call dev_release(d_emis_gpt); call dev_release(d_inc)
     call dev_release(d_up); call dev_release(d_dn)
     call dev_release(d_ds); call dev_release(d_gup); call dev_release(d_gdn)
+    call dev_release(d_bup); call dev_release(d_bdn)
+
+  contains
+
+    ! the solver for these optical properties and sources, with g-point outputs gu / gd (NULL: none)
+    subroutine run_solver(gu, gd)
+      type(c_ptr), intent(in) :: gu, gd
+      if (.not. two_str .and. sources%planck_deferred) then
+        ! lw_solver_noscat_GaussQuad (:326-353) with compute_Planck_source_nn (gas_optics, :398-404) and expand(sfc_emis)
+        ! (:429-447) inside the solver
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                      merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_ds, &
+                      d_inc, d_tau, dev_present(sources%lay_source, ng, PRESENT_READ), nband, sources%pk_ntemp, &
+                      dev_present(sources%pk_tlay, size(sources%pk_tlay, kind=c_long_long), PRESENT_READ), &
+                      dev_present(sources%pk_tlev, size(sources%pk_tlev, kind=c_long_long), PRESENT_READ), &
+                      dev_present(sources%pk_tsfc, size(sources%pk_tsfc, kind=c_long_long), PRESENT_READ), &
+                      sources%pk_sfc_lay, lims, sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, &
+                      d_up, d_dn, gu, gd), "rte_lw: lw_solver_noscat")
+      else
+        src_tmp = .false.
+        g_tmp = .false.
+        error_msg = sources%device_sources(d_lay, d_lev, d_sfc, d_jac, src_tmp)
+        if (error_msg == '') then
+          d_emis_gpt = dev_scratch(nsfc)
+          ! sfc_emis expanded to g-points (:429-447), then the solver (:326-387)
+          error_msg = rrtmgpnn_check(c_rrtmgpnn_expand_band_to_gpt(rrtmgpnn_ctx(), nband, ngpt, ncol, lims, d_emis, &
+                                                                   d_emis_gpt), "rte_lw: expand")
+        end if
+        if (error_msg == '') then
+          select type (optical_props)
+          type is (ty_optical_props_2str)
+            d_ssa = dev_present(optical_props%ssa, ng, PRESENT_READ)
+            d_g = dev_g_read(optical_props, g_tmp)
+          end select
+          if (two_str .and. use_2s) then
+            error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_2stream_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                                       merge(1_c_int, 0_c_int, top_at_1), d_inc, d_tau, d_ssa, d_g, d_lev, d_emis_gpt, &
+                                       d_sfc, d_up, d_dn, gu, gd), "rte_lw: lw_solver_2stream")
+          else if (two_str) then
+            error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                                       merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), &
+                                       gauss_wts(1:nmus, nmus), d_inc, d_tau, d_ssa, d_g, d_lay, d_lev, d_emis_gpt, &
+                                       d_sfc, d_up, d_dn, gu, gd), "rte_lw: lw_solver_noscat (rescaled)")
+          else
+            error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                                       merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), &
+                                       gauss_wts(1:nmus, nmus), d_ds, d_inc, d_tau, d_lay, d_lev, d_emis_gpt, d_sfc, &
+                                       d_up, d_dn, gu, gd), "rte_lw: lw_solver_noscat")
+          end if
+        end if
+        if (src_tmp) then
+          call dev_release(d_lay); call dev_release(d_lev); call dev_release(d_sfc); call dev_release(d_jac)
+        end if
+        if (g_tmp) call dev_release(d_g)
+      end if
+    end subroutine run_solver
   end function rte_lw
 
   ! whether the device fluxes can be copied into f itself: associated, contiguous and n elements (the extents were

@@ -5,11 +5,15 @@
 ! flux_dn are left as they are, as in the reference).  ty_fluxes_flexible g-point fluxes on 2str properties
 ! (rrtmgpnn_sw_solver_2stream_gpt: up, total down, direct, :155-173, 228-234) and on 1scl properties the spectral
 ! direct beam into gpt_flux_dn_dir (rrtmgpnn_sw_solver_noscat_gpt, :155-163, 218-222).
+! ty_fluxes_byband (mo_fluxes_byband) is detected with select type: the solver forms the band sums itself
+! (rrtmgpnn_solver_request_byband); together with g-point outputs the g-point arrays, which hold what rte_sw saves
+! (up, total down, direct), are reduced with rrtmgpnn_sum_byband.
 module mo_rte_sw
   use, intrinsic :: iso_c_binding
   use mo_rte_kind,      only: wp
   use mo_optical_props, only: ty_optical_props_arry, ty_optical_props_2str
   use mo_fluxes,        only: ty_fluxes_flexible
+  use mo_fluxes_byband, only: ty_fluxes_byband
   use mo_rte_rrtmgp_config, only: check_values
   use mo_rrtmgpnn_c
   implicit none
@@ -31,7 +35,11 @@ contains
     integer(c_long_long) :: ng, nv, nsfc, ngv
     type(c_ptr) :: d_tau, d_ssa, d_g, d_mu0, d_inc, d_dif, d_adir, d_adif, d_up, d_dn, d_dir, d_gup, d_gdn, d_gdir
     real(wp), allocatable :: up(:,:), dn(:,:), dir(:,:)
-    logical :: two_str, gpt, du, dd, dr
+    logical :: two_str, gpt, du, dd, dr, bb
+    type(c_ptr) :: d_bup, d_bdn, d_bdir
+    integer(c_long_long) :: nbv
+    integer :: nband
+    integer(c_int), allocatable :: lims(:,:)
 
     ncol = atmos%get_ncol()
     nlay = atmos%get_nlay()
@@ -57,6 +65,14 @@ contains
         error_msg = "rte_sw: gpt_flux_dn_dir inconsistently sized"; return
       end if
     end if
+    bb = .false.
+    nband = atmos%get_nband()
+    select type (fluxes)
+    class is (ty_fluxes_byband)
+      bb = fluxes%are_desired_bnd()
+      if (bb) error_msg = fluxes%check_extents_bnd(nband, nlay + 1, ncol, .true.)
+      if (error_msg /= '') return
+    end select
     if (size(mu0) /= ncol) then
       error_msg = "rte_sw: mu0 inconsistently sized"; return
     end if
@@ -122,10 +138,31 @@ contains
     d_gup = c_null_ptr
     d_gdn = c_null_ptr
     d_gdir = c_null_ptr
+    d_bup = c_null_ptr
+    d_bdn = c_null_ptr
+    d_bdir = c_null_ptr
+    nbv = int(nband, c_long_long) * (nlay + 1) * ncol
     two_str = .false.
     select type (atmos)
     class is (ty_optical_props_2str)
       two_str = .true.
+    end select
+    if (bb) then
+      lims = atmos%get_band_lims_gpoint()
+      select type (fluxes)
+      class is (ty_fluxes_byband)  ! on 1scl properties only the direct beam is computed
+        if (two_str .and. associated(fluxes%bnd_flux_up)) d_bup = dev_scratch(nbv)
+        if (two_str .and. associated(fluxes%bnd_flux_dn)) d_bdn = dev_scratch(nbv)
+        if (associated(fluxes%bnd_flux_dn_dir)) d_bdir = dev_scratch(nbv)
+      end select
+      ! without g-point outputs the solver forms the band sums itself
+      if (.not. gpt .and. (c_associated(d_bup) .or. c_associated(d_bdn) .or. c_associated(d_bdir))) &
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_solver_request_byband(rrtmgpnn_ctx(), nband, lims, d_bup, d_bdn, d_bdir), &
+                                   "rte_sw: solver_request_byband")
+    end if
+    if (error_msg == '') then
+    select type (atmos)
+    class is (ty_optical_props_2str)
       d_ssa = dev_present(atmos%ssa, ng, PRESENT_READ)
       d_g = c_null_ptr  ! NULL: g is identically zero (the solver takes it as a literal 0, same fluxes)
       if (.not. atmos%g_zero) d_g = dev_present(atmos%g, ng, PRESENT_READ)
@@ -149,6 +186,18 @@ contains
                                  merge(1_c_int, 0_c_int, top_at_1), d_inc, d_tau, d_mu0, d_dir, d_gdir), &
                                  "rte_sw: sw_solver_noscat")
     end select
+    end if
+    if (bb .and. gpt .and. error_msg == '') then  ! reduce the g-point arrays
+      if (c_associated(d_bup) .and. c_associated(d_gup)) &
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_sum_byband(rrtmgpnn_ctx(), ngpt, nlay + 1, ncol, nband, lims, d_gup, &
+                                                         d_bup), "rte_sw: sum_byband")
+      if (error_msg == '' .and. c_associated(d_bdn) .and. c_associated(d_gdn)) &
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_sum_byband(rrtmgpnn_ctx(), ngpt, nlay + 1, ncol, nband, lims, d_gdn, &
+                                                         d_bdn), "rte_sw: sum_byband")
+      if (error_msg == '' .and. c_associated(d_bdir) .and. c_associated(d_gdir)) &
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_sum_byband(rrtmgpnn_ctx(), ngpt, nlay + 1, ncol, nband, lims, d_gdir, &
+                                                         d_bdir), "rte_sw: sum_byband")
+    end if
     ! broadband fluxes go straight into the caller's arrays when they are contiguous (and no net flux is wanted from
     ! them); otherwise into temporaries copied after the sync
     du = .false.; dd = .false.; dr = .false.
@@ -179,6 +228,14 @@ contains
         if (associated(fluxes%gpt_flux_dn)) call dev_copy_out(fluxes%gpt_flux_dn, d_gdn, ngv)
       end if
       if (gpt .and. associated(fluxes%gpt_flux_dn_dir)) call dev_copy_out(fluxes%gpt_flux_dn_dir, d_gdir, ngv)
+      if (bb) then
+        select type (fluxes)
+        class is (ty_fluxes_byband)
+          if (c_associated(d_bup)) call dev_copy_out(fluxes%bnd_flux_up, d_bup, nbv)
+          if (c_associated(d_bdn)) call dev_copy_out(fluxes%bnd_flux_dn, d_bdn, nbv)
+          if (c_associated(d_bdir)) call dev_copy_out(fluxes%bnd_flux_dn_dir, d_bdir, nbv)
+        end select
+      end if
     end if
     call rrtmgpnn_sync(error_msg, "rte_sw")
     if (error_msg == '') then
@@ -187,12 +244,19 @@ contains
         if (associated(fluxes%flux_up) .and. .not. du) fluxes%flux_up = up
         if (associated(fluxes%flux_dn) .and. .not. dd) fluxes%flux_dn = dn
         if (associated(fluxes%flux_net))  fluxes%flux_net = dn - up
+        if (bb) then
+          select type (fluxes)
+          class is (ty_fluxes_byband)  ! net_byband_precalc
+            if (associated(fluxes%bnd_flux_net)) fluxes%bnd_flux_net = fluxes%bnd_flux_dn - fluxes%bnd_flux_up
+          end select
+        end if
       end if
     end if
     call dev_release(d_mu0); call dev_release(d_inc); call dev_release(d_dif); call dev_release(d_adir)
     if (.not. same_array(sfc_alb_dir_gpt, sfc_alb_dif_gpt)) call dev_release(d_adif)
     call dev_release(d_up); call dev_release(d_dn); call dev_release(d_dir)
     call dev_release(d_gup); call dev_release(d_gdn); call dev_release(d_gdir)
+    call dev_release(d_bup); call dev_release(d_bdn); call dev_release(d_bdir)
   end function rte_sw
 
   ! whether the device fluxes can be copied into f itself: associated, contiguous and n elements

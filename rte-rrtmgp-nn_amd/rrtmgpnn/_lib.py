@@ -92,6 +92,8 @@ SIGNATURES = {
                                       + [c_vp] * 12),
     "rrtmgpnn_lw_solver_2stream_gpt": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 11),
     "rrtmgpnn_sw_solver_noscat_gpt": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 5),
+    "rrtmgpnn_solver_request_byband": (c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp]),
+    "rrtmgpnn_sum_byband": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp]),
     "rrtmgpnn_expand_band_to_gpt": (c_int, [c_vp, c_int, c_int, c_int, P(c_int), c_vp, c_vp]),
     "rrtmgpnn_compute_heating_rate": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_calc_heating_rate_k_day": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -436,6 +436,69 @@ class FluxesFlexible(FluxesBroadband):
         return any(x is not None for x in (self.gpt_flux_up, self.gpt_flux_dn, self.gpt_flux_dn_dir, self.gpt_flux_net))
 
 
+class FluxesByBand(FluxesFlexible):
+    """ty_fluxes_byband (extensions/mo_fluxes_byband.F90:31-131): the outputs above plus by-band fluxes, (ncol, nlay+1,
+    nband) float32 tensors the caller allocates (Fortran (nband, nlay+1, ncol): band fastest, this project's layout).
+    Each value is the reference's sum_byband of the g-point fluxes (mo_fluxes_byband_kernels.F90:31-50), formed inside
+    the solver (rrtmgpnn_solver_request_byband); with one LW quadrature angle the g-point fluxes are fac * radiance,
+    the terms the broadband sum adds.  bnd_flux_net = bnd_flux_dn - bnd_flux_up (net_byband_precalc) needs both of
+    those associated: the reference's net_byband_full order is not reproduced."""
+
+    def __init__(self, bnd_flux_up=None, bnd_flux_dn=None, bnd_flux_dn_dir=None, bnd_flux_net=None, **kw):
+        super().__init__(**kw)
+        self.bnd_flux_up, self.bnd_flux_dn = bnd_flux_up, bnd_flux_dn
+        self.bnd_flux_dn_dir, self.bnd_flux_net = bnd_flux_dn_dir, bnd_flux_net
+
+    def are_desired_byband(self):
+        return any(x is not None for x in (self.bnd_flux_up, self.bnd_flux_dn, self.bnd_flux_dn_dir,
+                                           self.bnd_flux_net))
+
+    def are_desired(self):
+        return super().are_desired() or self.are_desired_byband()
+
+
+BYBAND_NET_ERROR = "reduce: bnd_flux_net needs bnd_flux_up and bnd_flux_dn (net_byband_full is not provided)"
+
+
+def _byband_checks(fluxes, ncol, nlev, nbnd, have_beam):
+    """reduce_byband's checks (extensions/mo_fluxes_byband.F90:72-97): the last failing extent's message, then the
+    direct-beam consistency; and this layer's own condition on bnd_flux_net."""
+    e = ""
+    for name, tail in (("bnd_flux_up", " (can't compute net flux either)"),
+                       ("bnd_flux_dn", " (can't compute net flux either)"), ("bnd_flux_dn_dir", ""),
+                       ("bnd_flux_net", " (can't compute net flux either)")):
+        a = getattr(fluxes, name)
+        if a is not None and tuple(a.shape) != (ncol, nlev, nbnd):
+            e = "reduce: %s array incorrectly sized%s" % (name, tail)
+    if e:
+        return e
+    if fluxes.bnd_flux_dn_dir is not None and not have_beam:
+        return "reduce: requesting bnd_flux_dn_dir but direct flux hasn't been supplied"
+    if fluxes.bnd_flux_net is not None and (fluxes.bnd_flux_up is None or fluxes.bnd_flux_dn is None):
+        return BYBAND_NET_ERROR
+    return ""
+
+
+def _byband_arm(ctx, op, up, dn, dr):
+    """Arm by-band outputs for the next solver call on ctx; the band limits are the optical properties' own."""
+    check(_lib.lib().rrtmgpnn_solver_request_byband(ctx.h, op.get_nband(), int_array(op.band_lims_gpt.ravel()),
+                                                    _p(up), _p(dn), _p(dr)), "solver_request_byband")
+
+
+def _byband_disarm(ctx):
+    """Drop a request that no solver call consumed (an argument check returned first)."""
+    check(_lib.lib().rrtmgpnn_solver_request_byband(ctx.h, 0, None, None, None, None), "solver_request_byband")
+
+
+def _sum_byband(ctx, op, gpt_flux, bnd_flux):
+    if bnd_flux is None:
+        return
+    ncol, nlev, ngpt = gpt_flux.shape
+    check(_lib.lib().rrtmgpnn_sum_byband(ctx.h, ngpt, nlev, ncol, op.get_nband(),
+                                         int_array(op.band_lims_gpt.ravel()), _p(gpt_flux), _p(bnd_flux)),
+          "sum_byband")
+
+
 # ---------------------------------------------------------------------------------------------
 class GasOpticsRRTMGP(OpticalProps):
     """ty_gas_optics_rrtmgp, NN branch.  The lookup-table branch needs the k-distribution files that are
@@ -792,6 +855,11 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
             if a is not None and tuple(a.shape) != (ncol, nlay + 1, ngpt):
                 return "rte_lw: g-point flux arrays inconsistently sized"
     nband = optical_props.get_nband()
+    bb = isinstance(fluxes, FluxesByBand) and fluxes.are_desired_byband()
+    if bb:
+        e = _byband_checks(fluxes, ncol, nlay + 1, nband, have_beam=False)
+        if e:
+            return e
     if tuple(sfc_emis.shape) != (ncol, nband):
         return "rte_lw: sfc_emis inconsistently sized"
     if inc_flux is not None and tuple(inc_flux.shape) != (ncol, ngpt):
@@ -812,40 +880,70 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
             torch.empty((ncol, nlay + 1, ngpt), device=emis.device)
         gd = fluxes.gpt_flux_dn if fluxes.gpt_flux_dn is not None else \
             torch.empty((ncol, nlay + 1, ngpt), device=emis.device)
-    if is2 and use_2stream:  # lw_solver_2stream (rte/mo_rte_lw.F90:357-371); validate() runs unconditionally
-        e = op.validate()
-        if e:
-            return e
-        common = (ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux), _p(op.tau), _p(op.ssa), _p(op.g),
-                  _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source), _p(up), _p(dn))
-        if gpt:
-            check(L.rrtmgpnn_lw_solver_2stream_gpt(*common, _p(gu), _p(gd)), "lw_solver_2stream_gpt")
-        else:
-            check(L.rrtmgpnn_lw_solver_2stream(*common), "lw_solver_2stream")
-    elif is2:  # rescaled no-scattering solution (:372-387)
-        if check_values:
+    def solve(gpt, gu, gd):
+        if is2 and use_2stream:  # lw_solver_2stream (rte/mo_rte_lw.F90:357-371); validate() runs unconditionally
             e = op.validate()
             if e:
                 return e
-        common = (ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu, float_array(GAUSS_DS[nmu]),
-                  float_array(GAUSS_WTS[nmu]), _p(inc_flux), _p(op.tau), _p(op.ssa), _p(op.g), _p(sources.lay_source),
-                  _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source), _p(up), _p(dn))
-        if gpt:
-            check(L.rrtmgpnn_lw_solver_1rescl_gpt(*common, _p(gu), _p(gd)), "lw_solver_1rescl_gpt")
+            common = (ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux), _p(op.tau), _p(op.ssa), _p(op.g),
+                      _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source), _p(up), _p(dn))
+            if gpt:
+                check(L.rrtmgpnn_lw_solver_2stream_gpt(*common, _p(gu), _p(gd)), "lw_solver_2stream_gpt")
+            else:
+                check(L.rrtmgpnn_lw_solver_2stream(*common), "lw_solver_2stream")
+        elif is2:  # rescaled no-scattering solution (:372-387)
+            if check_values:
+                e = op.validate()
+                if e:
+                    return e
+            common = (ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu, float_array(GAUSS_DS[nmu]),
+                      float_array(GAUSS_WTS[nmu]), _p(inc_flux), _p(op.tau), _p(op.ssa), _p(op.g),
+                      _p(sources.lay_source), _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source), _p(up),
+                      _p(dn))
+            if gpt:
+                check(L.rrtmgpnn_lw_solver_1rescl_gpt(*common, _p(gu), _p(gd)), "lw_solver_1rescl_gpt")
+            else:
+                check(L.rrtmgpnn_lw_solver_1rescl(*common), "lw_solver_1rescl")
+        elif gpt or lw_Ds is not None:  # ty_fluxes_flexible g-point outputs / column-dependent secants (:329-341)
+            ds = _f32dev(lw_Ds, emis.device) if lw_Ds is not None else None
+            check(L.rrtmgpnn_lw_solver_noscat_gpt(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu,
+                                                  float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]), _p(ds),
+                                                  _p(inc_flux), _p(op.tau), _p(sources.lay_source),
+                                                  _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source),
+                                                  _p(up), _p(dn), _p(gu), _p(gd)), "lw_solver_noscat_gpt")
         else:
-            check(L.rrtmgpnn_lw_solver_1rescl(*common), "lw_solver_1rescl")
-    elif gpt or lw_Ds is not None:  # ty_fluxes_flexible g-point outputs / column-dependent secants (:329-341)
-        ds = _f32dev(lw_Ds, emis.device) if lw_Ds is not None else None
-        check(L.rrtmgpnn_lw_solver_noscat_gpt(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu,
-                                              float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]), _p(ds),
-                                              _p(inc_flux), _p(op.tau), _p(sources.lay_source),
-                                              _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source), _p(up),
-                                              _p(dn), _p(gu), _p(gd)), "lw_solver_noscat_gpt")
+            check(L.rrtmgpnn_lw_solver_noscat(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu,
+                                              float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]), _p(inc_flux),
+                                              _p(op.tau), _p(sources.lay_source), _p(sources.lev_source),
+                                              _p(emis_gpt), _p(sources.sfc_source), _p(up), _p(dn)),
+                  "lw_solver_noscat")
+        return ""
+
+    if not bb:
+        e = solve(gpt, gu, gd)
+        if e:
+            return e
     else:
-        check(L.rrtmgpnn_lw_solver_noscat(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu,
-                                          float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]), _p(inc_flux),
-                                          _p(op.tau), _p(sources.lay_source), _p(sources.lev_source),
-                                          _p(emis_gpt), _p(sources.sfc_source), _p(up), _p(dn)), "lw_solver_noscat")
+        # ty_fluxes_byband: the band sums are formed inside the solver.  Together with g-point outputs the g-point
+        # call runs first and its arrays are reduced (sum_byband) -- except with one angle of the no-scattering /
+        # rescaled solution, whose g-point arrays hold radiances (quirk B-5): there the solver runs a second time
+        # with the by-band request (same broadband fluxes).
+        one_angle = nmu == 1 and not (is2 and use_2stream)
+        if gpt:
+            e = solve(True, gu, gd)
+            if e:
+                return e
+        if gpt and not one_angle:
+            _sum_byband(ctx, op, gu, fluxes.bnd_flux_up)
+            _sum_byband(ctx, op, gd, fluxes.bnd_flux_dn)
+        else:
+            _byband_arm(ctx, op, fluxes.bnd_flux_up, fluxes.bnd_flux_dn, None)
+            e = solve(False, None, None)
+            if e:
+                _byband_disarm(ctx)
+                return e
+        if fluxes.bnd_flux_net is not None:
+            torch.sub(fluxes.bnd_flux_dn, fluxes.bnd_flux_up, out=fluxes.bnd_flux_net)
     if fluxes.flux_net is not None:
         torch.sub(dn, up, out=fluxes.flux_net)
     return ""
@@ -871,6 +969,11 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
         return "rte_sw: inc_flux_dif inconsistently sized"
     ctx = context(atmos.tau.device.index)
     dev = atmos.tau.device
+    bb = isinstance(fluxes, FluxesByBand) and fluxes.are_desired_byband()
+    if bb:
+        e = _byband_checks(fluxes, ncol, nlay + 1, atmos.get_nband(), have_beam=True)
+        if e:
+            return e
     if isinstance(atmos, OpticalProps1scl):
         # direct beam only (:213-222): apply_BC_factor + sw_solver_noscat; as in the reference only the direct flux
         # is written (flux_up / flux_dn / flux_net are left as they are)
@@ -883,7 +986,11 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
             check(_lib.lib().rrtmgpnn_sw_solver_noscat_gpt(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux),
                                                            _p(atmos.tau), _p(mu0), _p(fluxes.flux_dn_dir), _p(gdir)),
                   "sw_solver_noscat_gpt")
+            if bb:
+                _sum_byband(ctx, atmos, gdir, fluxes.bnd_flux_dn_dir)
         else:
+            if bb and fluxes.bnd_flux_dn_dir is not None:  # only the direct beam is computed here
+                _byband_arm(ctx, atmos, None, None, fluxes.bnd_flux_dn_dir)
             check(_lib.lib().rrtmgpnn_sw_solver_noscat(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux),
                                                        _p(atmos.tau), _p(mu0), _p(fluxes.flux_dn_dir)),
                   "sw_solver_noscat")
@@ -901,11 +1008,18 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
                                                         _p(inc_flux_dif), _p(atmos.tau), _p(atmos.ssa), _p(atmos.g),
                                                         _p(mu0), _p(sfc_alb_dir_gpt), _p(sfc_alb_dif_gpt), _p(up),
                                                         _p(dn), _p(dr), *[_p(a) for a in g3]), "sw_solver_2stream_gpt")
+        if bb:  # the g-point arrays hold what rte_sw saves (up, total down, direct): reduce them
+            for a, b in zip(g3, (fluxes.bnd_flux_up, fluxes.bnd_flux_dn, fluxes.bnd_flux_dn_dir)):
+                _sum_byband(ctx, atmos, a, b)
     else:
+        if bb:
+            _byband_arm(ctx, atmos, fluxes.bnd_flux_up, fluxes.bnd_flux_dn, fluxes.bnd_flux_dn_dir)
         check(_lib.lib().rrtmgpnn_sw_solver_2stream(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux),
                                                     _p(inc_flux_dif), _p(atmos.tau), _p(atmos.ssa), _p(atmos.g),
                                                     _p(mu0), _p(sfc_alb_dir_gpt), _p(sfc_alb_dif_gpt), _p(up),
                                                     _p(dn), _p(dr)), "sw_solver_2stream")
+    if bb and fluxes.bnd_flux_net is not None:
+        torch.sub(fluxes.bnd_flux_dn, fluxes.bnd_flux_up, out=fluxes.bnd_flux_net)
     if fluxes.flux_net is not None:
         torch.sub(dn, up, out=fluxes.flux_net)
     return ""

@@ -39,12 +39,14 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
-            "sw_solver"}
+            "sw_byband", "sw_solver"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
-FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "predict_nn_lw", "lw_solver",
-               "nn_inputs_sw", "cloud_optics_sw", "delta_scale_sw", "predict_nn_sw", "sw_solver"]
+# (lw_byband / sw_byband: a byband step's by-band requests, host-only calls issued right before their solver)
+FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "predict_nn_lw",
+               "lw_byband", "lw_solver", "nn_inputs_sw", "cloud_optics_sw", "delta_scale_sw", "predict_nn_sw",
+               "sw_byband", "sw_solver"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -73,8 +75,11 @@ def _t(a, dev):
 class ClearSkyStep:
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
-                 sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0):
+                 sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False):
         # sw=False: the LW half alone (config C2, rrtmgp_rfmip_lw.F90): gas optics LW + Planck + rte_lw
+        # byband: the step also owns by-band fluxes (ty_fluxes_byband; lw_bnd_up / lw_bnd_dn, sw_bnd_up / sw_bnd_dn /
+        # sw_bnd_dir, (ncol, nlay+1, nband)) and arms rrtmgpnn_solver_request_byband before each solver call, so the
+        # solvers' by-band instances run and a captured graph carries the arrays; False: today's call list
         # lw_after: the SW-chain call the LW chain starts after on two streams (None: the default gate in _finish;
         # "": the chains start together)
         self.dev = torch.device("cuda", device)
@@ -145,6 +150,12 @@ class ClearSkyStep:
         if not sw:
             for t in (self.sw_up, self.sw_dn, self.sw_dir):
                 t.zero_()
+        self.byband = bool(byband)
+        if self.byband:
+            self.lw_bnd_up, self.lw_bnd_dn = f(ncol, nlay + 1, self.nb_lw), f(ncol, nlay + 1, self.nb_lw)
+            if sw:
+                nbs = self.kd_sw["nband"]
+                self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (f(ncol, nlay + 1, nbs) for _ in range(3))
 
         # ---- prepared ctypes argument lists ----
         def gas_args(names):
@@ -221,6 +232,10 @@ class ClearSkyStep:
                      (c, ncol, nlay, self.ng_lw, self.nb_lw, self._lims_lw, p(self.tau_lw), None, None,
                       p(self.cld_tau_lw), None, None)),
                 ]
+        if self.byband:  # armed right before the solver call that consumes it
+            lw_calls.insert(len(lw_calls) - 1,
+                            ("lw_byband", L.rrtmgpnn_solver_request_byband,
+                             (c, self.nb_lw, self._lims_lw, p(self.lw_bnd_up), p(self.lw_bnd_dn), None)))
         self.calls += lw_calls
         if not sw:
             self.calls = [c for c in self.calls if c[0] != "cloud_optics_sw"]
@@ -267,6 +282,12 @@ class ClearSkyStep:
                      (c, ncol, nlay, self.ng_sw, self.nb_sw, self._lims_sw, p(self.tau_sw), p(self.ssa_sw), g_sw,
                       p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw))),
                 ]
+        if self.byband:
+            self._lims_sw_bnd = int_array(self.kd_sw["band_lims_gpt"].ravel())
+            self.calls += [
+                ("sw_byband", L.rrtmgpnn_solver_request_byband,
+                 (c, self.kd_sw["nband"], self._lims_sw_bnd, p(self.sw_bnd_up), p(self.sw_bnd_dn), p(self.sw_bnd_dir))),
+            ]
         if fused:
             # the boundary conditions and (all sky) clouds%increment(atmos) fused into the solver
             # (rrtmgpnn_sw_solver_2stream_rfmip; same bits as sw_boundary_rfmip + sw_solver_2stream[_inc])
@@ -578,6 +599,11 @@ class ClearSkyStep:
         if self.allsky:
             ins += [self.lwp, self.iwp, self.rel, self.rei]
         return ins, [self.lw_up, self.lw_dn, self.sw_up, self.sw_dn, self.sw_dir]
+
+    def byband_fluxes(self):
+        """Host copies of a byband step's by-band fluxes, (ncol, nlay+1, nband) each."""
+        names = ("lw_bnd_up", "lw_bnd_dn") + (("sw_bnd_up", "sw_bnd_dn", "sw_bnd_dir") if self.sw else ())
+        return {k: getattr(self, k).cpu().numpy() for k in names}
 
     def fluxes(self):
         """Host copies of the broadband fluxes, with SW zeroed where sza >= 90 is applied by the caller."""
