@@ -202,6 +202,14 @@ int rrtmgpnn_compute_planck_source_nn(rrtmgpnn_context *ctx, int ncol, int nlay,
 /* ---- RTE solvers ---------------------------------------------------------------------------- */
 /* lw_solver_noscat_GaussQuad (rte/kernels/mo_rte_solver_kernels.F90:332-415) without rescaling or
  * Jacobians.  Ds, weights: HOST arrays of nmus (<= 4) entries.  inc_flux may be NULL (zero). */
+/* OPERAND BOUND of every rrtmgpnn_lw_solver_noscat* entry (plain, _planck, _planck_inc, _gpt, _planck_gpt): the fluxes
+ * are the reference's bit for bit for tau * D <= 2^126 (8.5e37) in every layer, g-point and secant D (Gauss or lw_Ds;
+ * with _planck_inc, tau is the incremented optical depth).  Beyond it the layer source's (1 - T) / (tau * D) is
+ * taken as 0 where the reference has ~3e-39, and a tau * D that overflows to inf makes the column's fluxes nan where
+ * the reference's are finite.  The shortened division that causes this saves 1.2 - 2.3 % of the solver's time
+ * (DESIGN.md section 3); tests/test_gpu_solver_edges.py holds both sides of the bound.  The SW solvers have no such
+ * bound: tau, ssa, g and mu0 over their whole float range (tau up to 2e38, ssa down to 1e-45, mu0 down to FLT_MIN) were
+ * bitwise. */
 int rrtmgpnn_lw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
                               const float *Ds, const float *weights, const float *inc_flux,
                               const float *tau, const float *lay_source, const float *lev_source,

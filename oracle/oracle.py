@@ -318,9 +318,9 @@ class Oracle:
         up, dn = self.lw_solver(tau, go["lay_source"], go["lev_source"], emis, go["sfc_source"], prob["top_at_1"], nmus)
         return up, dn, dict(go, tau=tau, clouds=cld)
 
-    def all_sky_sw(self, prob, models, kd_sw, co, clouds, icergh=2, lut=True):
+    def all_sky_sw(self, prob, models, kd_sw, co, clouds, icergh=2, lut=True, zero_unused=True):
         """rrtmgp_allsky.F90:405-446: cloud_optics (2str) -> gas_optics -> clouds%delta_scale() ->
-        clouds%increment(atmos) -> rte_sw."""
+        clouds%increment(atmos) -> rte_sw.  zero_unused: as clear_sky_sw."""
         go = self.sw_gas_optics(prob, models)
         cld = self.delta_scale(*self.cloud_optics(co, *clouds, nstr=2, lut=lut, icergh=icergh))
         tau, ssa, g = self.increment_bybnd(kd_sw["band_lims_gpt"], (go["tau"], go["ssa"], go["g"]), cld)
@@ -328,20 +328,25 @@ class Oracle:
         toa = data.toa_flux(prob, kd_sw)
         alb = np.repeat(f32(prob["sfc_alb"])[:, None], ngpt, axis=1)
         up, dn, dr = self.sw_solver(tau, ssa, g, prob["mu0"], toa, alb, alb, prob["top_at_1"])
-        m = ~prob["usecol"]
-        up[m] = 0.0
-        dn[m] = 0.0
+        if zero_unused:
+            m = ~prob["usecol"]
+            up[m] = 0.0
+            dn[m] = 0.0
         return up, dn, dr, dict(go, tau=tau, ssa=ssa, g=g, clouds=cld)
 
-    def clear_sky_sw(self, prob, models, kd_sw):
+    def clear_sky_sw(self, prob, models, kd_sw, zero_unused=True):
+        """gas_optics -> rte_sw.  zero_unused: the up and down fluxes of the columns with usecol false (night columns,
+        solved with mu0 = 1) are set to zero afterwards, as the RFMIP program's output step does; False returns
+        rte_sw's raw output on every column."""
         go = self.sw_gas_optics(prob, models)
         ngpt = go["tau"].shape[-1]
         toa = data.toa_flux(prob, kd_sw)
         alb = np.repeat(f32(prob["sfc_alb"])[:, None], ngpt, axis=1)
         up, dn, dr = self.sw_solver(go["tau"], go["ssa"], go["g"], prob["mu0"], toa, alb, alb, prob["top_at_1"])
-        m = ~prob["usecol"]
-        up[m] = 0.0
-        dn[m] = 0.0
+        if zero_unused:
+            m = ~prob["usecol"]
+            up[m] = 0.0
+            dn[m] = 0.0
         return up, dn, dr, go
 
 

@@ -7,7 +7,10 @@
 // ~1e-3 W/m2 in the broadband fluxes.  These functions evaluate the same algorithm with the same
 // constants in double precision (gfx950 FP64 FMA is exact IEEE), so the GPU rounds every call exactly
 // as the reference does.  Verified bit-for-bit against glibc 2.35 expf on every 7th float in
-// (-110, 89) and logf on every 3rd positive finite float (tools/check_libm_ref.c).
+// (-110, 89) and logf on every 3rd positive finite float on the host (tools/check_libm_ref_*.c), and on the device
+// against the host's libm in the same program (tools/exhaustive_ops.hip): ref_expf_neg and ref_expf_neg_batch<4> with
+// the LDS table on every float of [-105, -0], ref_logf_nb / ref_logf on every positive finite float, ref_cosf on every
+// float of [0, pi].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -122,7 +125,8 @@ __device__ __forceinline__ float ref_expf_nb(float x, const uint64_t *tab)
 
 // Correctly rounded sqrtf for normal positive x (the solvers call it on max(., 1e-4)): the hardware
 // estimate corrected by one ulp either way, the same steps the compiler emits for sqrtf minus the
-// denormal pre-scaling and the zero/inf class test, which never fire in that range.
+// denormal pre-scaling and the zero/inf class test, which never fire in that range.  Equal to sqrtf on every float of
+// [2^-20, 2^20], this function and x2::sqrt2 on both lanes (tools/exhaustive_ops.hip, through the headers).
 __device__ __forceinline__ float sqrt_rn_normal(float x)
 {
   const float s = __builtin_amdgcn_sqrtf(x);
@@ -136,7 +140,9 @@ __device__ __forceinline__ float sqrt_rn_normal(float x)
 // 1 - R_dif*albedo): v_rcp_f32, one Newton step and one residual correction -- the compiler's IEEE division
 // sequence minus v_div_scale / v_div_fixup (which leave the operands and the result untouched in that range) and
 // minus its second correction.  Equal to 1.0f / b on every float of [2^-60, 2^60], checked on the GPU
-// (tools/exhaustive_ops.hip; the sequence with both corrections too).
+// (tools/exhaustive_ops.hip calls this function and x2::rcp2, both lanes, through the headers; the sequence with
+// both corrections too).  The solvers' denominators stay inside that range at every operand edge tried (ssa = 1 with
+// albedo 1, tau from 0 to 2e38, mu0 down to FLT_MIN: tests/test_gpu_solver_edges.py, bitwise).
 __device__ __forceinline__ float rcp_rn_normal(float b)
 {
   float r = __builtin_amdgcn_rcpf(b);
@@ -148,6 +154,13 @@ __device__ __forceinline__ float rcp_rn_normal(float b)
 // [2^-126, 2^126]; a == 0 also gives the IEEE result): the compiler's division sequence -- reciprocal, one Newton
 // step, quotient, two residual corrections -- without v_div_scale and v_div_fixup, which leave operands and
 // result untouched in that range, so the bits are those of a / b (3 of 11 instructions fewer).
+// Established on the GPU (tools/exhaustive_ops.hip calls this function and x2::div2 through the headers;
+// tests/test_gpu_solver_edges.py drives the solvers): equal to a / b for every b of [eps, 1] and [-4, -eps] under
+// numerators from 0 and 2^-100 to 100, and for (1 - exp(-t)) / t on every t of (sqrt(FLT_EPSILON), 2^126].  Below the
+// numerator bound the SW solvers still matched the reference bit for bit (ssa of 1e-45, 1e-38, 2^-101).  For
+// b > 2^126 the result is WRONG for every b: v_rcp_f32 returns 0 where 1/b is subnormal (quotient 0), and b = inf gives
+// nan (inf * 0 in the Newton step).  The LW solvers reach that with tau * D > 2^126 only; closing it (v_div_fixup: +1.2 %,
+// a branch into the IEEE division: +2.3 % of the C3 LW solver) was measured and rejected.
 __device__ __forceinline__ float div_rn_normal(float a, float b)
 {
   float r = __builtin_amdgcn_rcpf(b);

@@ -24,6 +24,10 @@ static constexpr int kExpTabOff = 0, kExpTabFloats = 64;  // exp table (32 x u64
 
 // The solvers' divisions whose operands stay in the normal range use div_rn_normal, and their exps of non-positive
 // arguments ref_expf_neg (libm_ref.hpp): the bits of a / b and of glibc's expf, in fewer instructions.
+// Two uses: sw_two_stream's (w0 * RT) / dd, bitwise against the reference at every operand edge tried, numerators
+// below div_rn_normal's stated 2^-100 included; and the LW source's (1 - T) / t, t = tau * D, bitwise up to
+// t = 2^126 and wrong beyond (0 for finite t, nan for t = inf): the LW entry points state tau * D <= 2^126
+// (include/rrtmgpnn.h; tests/test_gpu_solver_edges.py).
 __device__ __forceinline__ float solver_div(float a, float b) { return div_rn_normal(a, b); }
 // RRTMGPNN_FAST_LIBM (opt-in tolerance build, librrtmgpnn_fastlibm.so; never the default): the solvers' exps of
 // non-positive arguments use the hardware exponential (v_exp_f32, a few ulp) instead of glibc's algorithm

@@ -28,9 +28,13 @@ def _sample(ncol, n):
     return idx
 
 
-def _check(got, idx, prob_s, lw, sw):
+def _check(got, idx, prob_s, lw, sw_raw):
+    """sw_raw: the oracle's raw SW output (zero_unused=False), night columns included"""
     lu, ld = lw
-    su, sd, sr = sw
+    ru, rd, sr = sw_raw
+    su, sd = ru.copy(), rd.copy()
+    su[~prob_s["usecol"]] = 0.0  # what zero_unused=True returns (tests/test_night_columns_host.py)
+    sd[~prob_s["usecol"]] = 0.0
     np.testing.assert_array_equal(got["lw_up"][idx], lu)
     np.testing.assert_array_equal(got["lw_dn"][idx], ld)
     use = prob_s["usecol"]
@@ -39,6 +43,10 @@ def _check(got, idx, prob_s, lw, sw):
         g[~use] = 0.0
         np.testing.assert_array_equal(g, r, err_msg=k)
     np.testing.assert_array_equal(got["sw_dir"][idx][use], sr[use])
+    # the night columns too (mu0 = 1): the step's raw SW output against rte_sw's raw output on every sampled column
+    assert not use.all()
+    for k, r in (("sw_up", ru), ("sw_dn", rd), ("sw_dir", sr)):
+        np.testing.assert_array_equal(got[k][idx], r, err_msg=k + " (raw, night columns included)")
 
 
 def test_c4_full_size_allsky_step_sampled_vs_oracle(dev, orc):
@@ -59,7 +67,7 @@ def test_c4_full_size_allsky_step_sampled_vs_oracle(dev, orc):
     cs = tuple(c[idx] for c in clouds)
     m = {k: data.load_model(k) for k in ("lw_abs", "lw_pfrac", "sw_abs", "sw_ray")}
     lu, ld, _ = orc.all_sky_lw(ps, [m["lw_abs"], m["lw_pfrac"]], data.load_kdist("lw"), co_lw, cs)
-    su, sd, sr, _ = orc.all_sky_sw(ps, [m["sw_abs"], m["sw_ray"]], data.load_kdist("sw"), co_sw, cs)
+    su, sd, sr, _ = orc.all_sky_sw(ps, [m["sw_abs"], m["sw_ray"]], data.load_kdist("sw"), co_sw, cs, zero_unused=False)
     _check(got, idx, ps, (lu, ld), (su, sd, sr))
 
 
@@ -81,7 +89,7 @@ def test_c5_shard_full_size_step_sampled_vs_oracle(dev, orc):
     ps = subset(prob, idx)
     m = {k: data.load_model(k) for k in ("lw_abs", "lw_pfrac", "sw_abs", "sw_ray")}
     lu, ld, _ = orc.clear_sky_lw(ps, [m["lw_abs"], m["lw_pfrac"]], data.load_kdist("lw"))
-    su, sd, sr, _ = orc.clear_sky_sw(ps, [m["sw_abs"], m["sw_ray"]], data.load_kdist("sw"))
+    su, sd, sr, _ = orc.clear_sky_sw(ps, [m["sw_abs"], m["sw_ray"]], data.load_kdist("sw"), zero_unused=False)
     _check(got, idx, ps, (lu, ld), (su, sd, sr))
 
 
@@ -121,7 +129,7 @@ def test_c5_global_rank_chunked_full_size_sampled_vs_oracle(dev, orc):
     ps = _concat(parts)
     m = {k: data.load_model(k) for k in ("lw_abs", "lw_pfrac", "sw_abs", "sw_ray")}
     lu, ld, _ = orc.clear_sky_lw(ps, [m["lw_abs"], m["lw_pfrac"]], data.load_kdist("lw"))
-    su, sd, sr, _ = orc.clear_sky_sw(ps, [m["sw_abs"], m["sw_ray"]], data.load_kdist("sw"))
+    su, sd, sr, _ = orc.clear_sky_sw(ps, [m["sw_abs"], m["sw_ray"]], data.load_kdist("sw"), zero_unused=False)
     _check(got, idx, ps, (lu, ld), (su, sd, sr))
 
 

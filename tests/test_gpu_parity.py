@@ -203,8 +203,14 @@ def test_sw_solver_with_scattering_and_diffuse_inc(dev, orc, sw_kernel):
 def _oracle_fluxes(orc, prob, models):
     from rrtmgpnn import data
     lu, ld, _ = orc.clear_sky_lw(prob, [models["lw_abs"], models["lw_pfrac"]], data.load_kdist("lw"))
-    su, sd, sr, _ = orc.clear_sky_sw(prob, [models["sw_abs"], models["sw_ray"]], data.load_kdist("sw"))
-    return {"lw_up": lu, "lw_dn": ld, "sw_up": su, "sw_dn": sd, "sw_dir": sr}
+    # rte_sw's raw output on every column, and the same with the night columns' up and down fluxes zeroed (what
+    # zero_unused=True returns: tests/test_night_columns_host.py)
+    ru, rd, sr, _ = orc.clear_sky_sw(prob, [models["sw_abs"], models["sw_ray"]], data.load_kdist("sw"),
+                                     zero_unused=False)
+    su, sd = ru.copy(), rd.copy()
+    su[~prob["usecol"]] = 0.0
+    sd[~prob["usecol"]] = 0.0
+    return {"lw_up": lu, "lw_dn": ld, "sw_up": su, "sw_dn": sd, "sw_dir": sr, "sw_up_raw": ru, "sw_dn_raw": rd}
 
 
 def _check_pipeline(got, ref, usecol):
@@ -217,6 +223,10 @@ def _check_pipeline(got, ref, usecol):
         if k == "sw_dir":
             g, r = g[~m], r[~m]
         assert_flux(g, r, k)
+    # the night columns too (solved with mu0 = 1 from the TSI's incident flux): the step's raw SW output against
+    # rte_sw's raw output, on all columns
+    for k, r in (("sw_up", ref["sw_up_raw"]), ("sw_dn", ref["sw_dn_raw"]), ("sw_dir", ref["sw_dir"])):
+        assert_flux(got[k], r, k + " (raw, night columns included)")
 
 
 def test_full_rfmip_clear_sky_lw_sw(dev, orc, rfmip, models, sw_kernel, mlp_kernel):
