@@ -57,6 +57,12 @@ int rrtmgpnn_context_set_stream(rrtmgpnn_context *ctx, void *hip_stream);
  * checkpointed passes (beam / adding state stored every 3 levels instead of per level).  2 and 3 need even ngpt.
  * All kernels give bit-identical fluxes.  ctx == NULL sets the default of every context not set itself. */
 int rrtmgpnn_context_set_sw_kernel(rrtmgpnn_context *ctx, int mode);
+/* MI355X tuning, no reference counterpart: how rrtmgpnn_lw_solver_noscat_planck_clr_all produces its two flux sets.
+ * 0 (default): mode 1, measured 21 % faster than mode 2 at 10 000 x 60 columns.  1: the dual kernel, one launch that reads tau,
+ * pfrac and tau_bnd once and carries a clear and an all-sky radiance per lane (one angle; several angles take mode 2).
+ * 2: rrtmgpnn_lw_solver_noscat_planck followed by rrtmgpnn_lw_solver_noscat_planck_inc.
+ * Bit-identical fluxes either way.  ctx == NULL sets the default of every context not set itself. */
+int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode);
 /* MI355X tuning, no reference counterpart: the MFMA tiling of the gas-optics networks (rrtmgpnn_predict_nn_lw/_sw,
  * rrtmgpnn_gas_optics_lw_nn/_sw_nn).  0 (default): v_mfma_f32_32x32x2_f32 tiles where an instance exists for the
  * networks (the shipped LW g256 pair, LW g128 single model and SW g224 pair, softsign/softsign/linear), 16x16x4
@@ -202,9 +208,10 @@ int rrtmgpnn_compute_planck_source_nn(rrtmgpnn_context *ctx, int ncol, int nlay,
 /* ---- RTE solvers ---------------------------------------------------------------------------- */
 /* lw_solver_noscat_GaussQuad (rte/kernels/mo_rte_solver_kernels.F90:332-415) without rescaling or
  * Jacobians.  Ds, weights: HOST arrays of nmus (<= 4) entries.  inc_flux may be NULL (zero). */
-/* OPERAND BOUND of every rrtmgpnn_lw_solver_noscat* entry (plain, _planck, _planck_inc, _gpt, _planck_gpt): the fluxes
+/* OPERAND BOUND of every rrtmgpnn_lw_solver_noscat* entry (plain, _planck, _planck_inc, _planck_clr_all, _gpt,
+ * _planck_gpt): the fluxes
  * are the reference's bit for bit for tau * D <= 2^126 (8.5e37) in every layer, g-point and secant D (Gauss or lw_Ds;
- * with _planck_inc, tau is the incremented optical depth).  Beyond it the layer source's (1 - T) / (tau * D) is
+ * with _planck_inc and _planck_clr_all, tau is the incremented optical depth).  Beyond it the layer source's (1 - T) / (tau * D) is
  * taken as 0 where the reference has ~3e-39, and a tau * D that overflows to inf makes the column's fluxes nan where
  * the reference's are finite.  The shortened division that causes this saves 1.2 - 2.3 % of the solver's time
  * (DESIGN.md section 3); tests/test_gpu_solver_edges.py holds both sides of the bound.  The SW solvers have no such
@@ -238,6 +245,21 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          int sfc_lay, const int *band_lims_gpt, float temp_ref_min,
                                          float totplnk_delta, const float *totplnk, int emis_by_band,
                                          const float *sfc_emis, float *flux_up, float *flux_dn);
+/* rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 on the fused-Planck path: the clear-sky fluxes of tau into
+ * flux_up_clr / flux_dn_clr and the all-sky fluxes of tau + tau_bnd(band) into flux_up / flux_dn ((nlay+1, ncol) each),
+ * i.e. what rrtmgpnn_lw_solver_noscat_planck and rrtmgpnn_lw_solver_noscat_planck_inc give on the same arguments, bit
+ * for bit; tau and pfrac are only read.  With one angle (nmus == 1) a dual kernel reads the inputs once and solves
+ * both in one launch; nmus 2..4 issue the two existing kernels back to back on the context's stream
+ * (rrtmgpnn_context_set_lw_clr_all selects).  A by-band request armed on the context
+ * (rrtmgpnn_solver_request_byband) is refused with RRTMGPNN_ERR_ARGUMENT, and cleared as every solver entry clears it. */
+int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                             int nmus, const float *Ds, const float *weights, const float *inc_flux,
+                                             const float *tau, const float *tau_bnd, const float *pfrac, int nbnd,
+                                             int nPlanckTemp, const float *tlay, const float *tlev,
+                                             const float *tsfc, int sfc_lay, const int *band_lims_gpt,
+                                             float temp_ref_min, float totplnk_delta, const float *totplnk,
+                                             int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn,
+                                             float *flux_up_clr, float *flux_dn_clr);
 /* rte_lw on two-stream optical properties, default branch (rte/mo_rte_lw.F90:372-387): lw_solver_noscat_GaussQuad
  * with do_rescaling -- tau scaled by (1 - ssa + ssa(1-g)/2), a no-scattering pass down, then
  * lw_transport_1rescl up and down again with the adjustment terms (rte/kernels/mo_rte_solver_kernels.F90:209-233,

@@ -18,6 +18,7 @@ namespace rrtmgpnn {
 static thread_local std::string g_last_error;
 int g_sw_kernel_default = 0;
 int g_mlp_kernel_default = 0;
+int g_lw_clr_all_default = 0;
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -220,6 +221,18 @@ int rrtmgpnn_context_set_sw_kernel(rrtmgpnn_context *ctx, int mode)
   }
   if (int rc = check_ctx(ctx)) return rc;
   ctx->sw_kernel = mode;
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode)
+{
+  if (mode < 0 || mode > 2) return fail(RRTMGPNN_ERR_ARGUMENT, "lw clr_all mode must be 0, 1 or 2");
+  if (!ctx) {
+    rrtmgpnn::g_lw_clr_all_default = mode;
+    return RRTMGPNN_OK;
+  }
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->lw_clr_all = mode;
   return RRTMGPNN_OK;
 }
 
@@ -725,6 +738,40 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
   return launch_lw_noscat_planck(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, pfrac,
                                  nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min, totplnk_delta, totplnk,
                                  emis_by_band != 0, sfc_emis, tau_bnd, flux_up, flux_dn);
+}
+
+// mode 0 of rrtmgpnn_context_set_lw_clr_all: what the measurement of DESIGN.md section 3 chose
+static constexpr int kLwClrAllDefaultMode = 1;
+
+int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                             int nmus, const float *Ds, const float *weights, const float *inc_flux,
+                                             const float *tau, const float *tau_bnd, const float *pfrac, int nbnd,
+                                             int nPlanckTemp, const float *tlay, const float *tlev,
+                                             const float *tsfc, int sfc_lay, const int *band_lims_gpt,
+                                             float temp_ref_min, float totplnk_delta, const float *totplnk,
+                                             int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn,
+                                             float *flux_up_clr, float *flux_dn_clr)
+{
+  // an armed by-band request is taken (and so cleared) like in every solver entry, then refused: this entry has no
+  // by-band instance
+  ::rrtmgpnn::BybandScope byband_(ctx, ngpt);
+  if (byband_.owner)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all: by-band outputs are not available from this "
+                                       "entry (the _planck and _planck_inc entries have them)");
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
+      !flux_up || !flux_dn || !flux_up_clr || !flux_dn_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 ||
+      sfc_lay < 1 || sfc_lay > nlay || !(totplnk_delta > 0.0f))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all: bad argument");
+  BandArgs b;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_cover(b, ngpt)) return rc;
+  int mode = ctx->lw_clr_all >= 0 ? ctx->lw_clr_all : g_lw_clr_all_default;
+  if (mode == 0) mode = kLwClrAllDefaultMode;
+  return launch_lw_noscat_planck_clr_all(ctx, mode == 1, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau,
+                                         pfrac, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min,
+                                         totplnk_delta, totplnk, emis_by_band != 0, sfc_emis, tau_bnd, flux_up,
+                                         flux_dn, flux_up_clr, flux_dn_clr);
 }
 
 int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,

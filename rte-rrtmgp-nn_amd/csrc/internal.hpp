@@ -36,6 +36,7 @@ constexpr int kMaxInputs = 32;  // NN input features
 constexpr int kMaxBands = 64;
 extern int g_sw_kernel_default;  // rrtmgpnn_context_set_sw_kernel(NULL, mode)
 extern int g_mlp_kernel_default;  // rrtmgpnn_context_set_mlp_kernel(NULL, mode)
+extern int g_lw_clr_all_default;  // rrtmgpnn_context_set_lw_clr_all(NULL, mode)
 // Raise a kernel's dynamic-LDS limit to 160 KiB on the current device, once per (kernel, device): a function
 // attribute is per device, so a second GPU of the same process gets its own call.  Thread-safe; after the first
 // call for a (kernel, device) pair it makes no HIP call (hipGraph captures stay attribute-free).
@@ -62,6 +63,7 @@ struct rrtmgpnn_context {
   int sw_kernel = -1;  // SW two-stream kernel: 0 by ngpt, 1 / 2 g-points per lane, -1 the library default
   int mlp_max_cus = 0;  // rrtmgpnn_context_set_mlp_max_cus: CUs' worth of network blocks, 0 = all
   int mlp_kernel = -1;  // LW network tiling: 0 32x32x2 where instantiated, 1 16x16x4, -1 the library default
+  int lw_clr_all = -1;  // clear + all-sky LW entry: 0 default, 1 the dual kernel, 2 two launches, -1 the library default
   // Per-call solver extras, set by the *_gpt entry points for the duration of one call (rte_lw's lw_Ds and
   // ty_fluxes_flexible's g-point outputs, (ngpt, nlay+1, ncol) each); the other entries leave them null.
   struct SolverExtras {
@@ -227,6 +229,15 @@ int launch_lw_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
                             int sfc_lay, const BandArgs &bands, float temp_ref_min, float totplnk_delta,
                             const float *totplnk, bool emis_by_band, const float *sfc_emis, const float *tau_bnd,
                             float *flux_up, float *flux_dn);
+// clear-sky fluxes (tau) and all-sky fluxes (tau + tau_bnd) of the same columns; dual: one launch of the dual instance
+// where it exists (one angle), else the two instances back to back
+int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, bool dual, int ngpt, int nlay, int ncol, int top_at_1,
+                                    int nmus, const float *Ds, const float *wts, const float *inc_flux,
+                                    const float *tau, const float *pfrac, int ntemp, const float *tlay,
+                                    const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
+                                    float temp_ref_min, float totplnk_delta, const float *totplnk, bool emis_by_band,
+                                    const float *sfc_emis, const float *tau_bnd, float *flux_up, float *flux_dn,
+                                    float *flux_up_clr, float *flux_dn_clr);
 // bands != nullptr: atmosphere incremented by the band-resolved 2str set (tau, ssa, g)_bnd in-kernel
 int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
                       const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,

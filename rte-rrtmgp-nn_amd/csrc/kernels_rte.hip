@@ -96,6 +96,14 @@ static constexpr int kLwPf = 4, kLwfPf = 2, kSwPf = 2;
 // ring_flush_lanes walks slot s's 4 partials with lanes 4s .. 4s+3: a flush of kRing slots needs 4 * kRing lanes, and
 // the smallest LW block (ngpt <= 64) has 64
 static_assert(4 * kRing <= 64, "the LW ring's lane-per-partial flush needs 4 lanes per slot within one wave");
+// the dual (clear + all-sky) LW instance's ring depth per quantity: two rings of 4 take the LDS of one ring of 8, so
+// the block keeps 8 waves per SIMD (two rings of 8: 28.6 KB per block at 256 g-points x 60 layers, 5 blocks per CU,
+// +1.9 % at C4; two of 2: twice the flushes again, +10 %)
+#ifndef RRTMGPNN_LW_DUAL_RING
+#define RRTMGPNN_LW_DUAL_RING 4
+#endif
+static constexpr int kRingDual = RRTMGPNN_LW_DUAL_RING;
+static_assert(8 * kRingDual <= 64, "the dual LW instance flushes two rings with 4 lanes per slot within one wave");
 // LW no-scattering flush: one lane per partial sum over ring rows padded by 4 floats when ngpt % 4 == 0 (the float4
 // walk of ring_flush over unpadded rows otherwise)
 __host__ __device__ constexpr int lw_ring_stride(int ngpt) { return (ngpt & 3) == 0 ? ngpt + 4 : ngpt; }
@@ -127,7 +135,15 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // angle the band sums are formed from the ring rows in the flush's barrier window (band_flush), i.e. over the float32
 // terms the broadband sum adds: fac * radiance, or the bare radiance when ngpt % 4 != 0 (quirk B-5); with several
 // angles from the per-g accumulators in a by-band variant of the final loop.
-template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false>
+//
+// kDual (with kFused && kInc, one angle, no by-band output): clear-sky and all-sky fluxes of the same columns from one
+// read of tau, pfrac and tau_bnd (rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172: solve, increment, solve
+// again).  Each lane carries a second radiance with t = tau * D beside the all-sky one with t = (tau + tau_bnd) * D;
+// the sources, the emissivity and the incident flux are shared.  The clear values are staged in a second ring
+// ([2][kRingDual][rs]: 0 = all-sky, 1 = clear) and both are reduced by one flush (part [2 dn][nlev][4], [2 up][nlev][4]).
+// The clear fluxes go to gup / gdn (flux_up_clr, flux_dn_clr; (nlay+1, ncol)), which the one-angle instances do not
+// otherwise use.  Each set is bit-identical to what the <kFused, false> and <kFused, true> instances give.
+template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
@@ -136,10 +152,12 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
                                            float *__restrict__ gdn, float *__restrict__ gup, long long gcs,
                                            float *__restrict__ flux_up, float *__restrict__ flux_dn, BandOut bo)
 {
-  static_assert(kRing % kPF == 0, "prefetch depth must divide the ring");
+  constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
+  static_assert(kR % kPF == 0, "prefetch depth must divide the ring");
   // the fused down pass takes lev(l+1)'s Planck fraction from the neighbouring prefetch slot, py[(r+1) % kPF]: with
   // one slot that would be the layer's own pfrac
   static_assert(!kFused || kPF >= 2, "the fused down pass needs at least two prefetch slots");
+  static_assert(!kDual || (kFused && kInc && !kMulti && !kBand), "the dual instance is the one-angle fused-Planck path");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
   const bool on = g < ngpt;
@@ -160,7 +178,8 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   // [kRing][rs]: rows of ngpt floats, padded by 4 when the flush walks one lane per partial (rows in different banks)
   const int rs = lw_ring_stride(ngpt);
   float *ring = btab + (kFused ? lw_btab_floats(bands.nbnd, nlay) : 0);
-  float *part = ring + (size_t)kRing * rs;                   // [2][nlev][4]: 0 = dn, 1 = up
+  // [2][nlev][4]: 0 = dn, 1 = up; kDual: [4][nlev][4]: dn, dn clear, up, up clear
+  float *part = ring + (size_t)(kDual ? 2 : 1) * kR * rs;
   load_exp_table(etab);
   const ColArr Ttau(tau, (size_t)ngpt * nlay * icol, row * nlay);
   const ColArr Tlay(lay, (size_t)ngpt * nlay * icol, row * nlay);  // lay_source, or pfrac when fused
@@ -250,9 +269,18 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
       ring[(size_t)r * rs + g] = v;
     }
   };
+  // kDual: the clear-sky value of the same level, into the second ring
+  auto put_clr = [&](float v, int r) {
+    if (on) ring[(size_t)(kR + r) * rs + g] = v;
+  };
   // bq: the by-band array of the quantity being flushed (kBand)
   auto flush = [&](float *pq, int n, int lev0, int dl, float *bq) {
-    if constexpr (!kMulti) {
+    if constexpr (kDual) {
+      if (rs != ngpt)
+        ring_flush_lanes2<kR>(ring, rs, pq, nlev, n, lev0, dl, ngpt);
+      else
+        ring_flush<kR>(ring, pq, 2, n, lev0, dl, ngpt, nlev, false);
+    } else if constexpr (!kMulti) {
       if constexpr (kBand) {
         if (rs != ngpt)
           ring_flush_lanes<true>(ring, rs, pq, n, lev0, dl, ngpt, 0, &bo.b, bq, nlev, icol);
@@ -271,7 +299,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   // layer source and the level source on the side given by `li` (lev index, 0..nlay)
   auto lay_src = [&](float y, int l) { return kFused ? y * bl[l] : y; };
   auto lev_src = [&](float v, int li) { return kFused ? v * bl[nlay + li] : v; };
-  float *pdn = part, *pup = part + (size_t)nlev * 4;
+  float *pdn = part, *pup = part + (size_t)(kDual ? 2 : 1) * nlev * 4;
   const int dl_dn = top_at_1 ? 1 : -1;  // level index step going down
 
   for (int imu = 0; imu < ang.nmus; imu++) {
@@ -282,7 +310,9 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     const float fac = (kMulti || (ngpt & 3) == 0) ? 2.0f * kPi * ang.w[imu] : 1.0f;
     const bool acc = imu > 0;
     float I = inc / (2.0f * kPi * ang.w[imu]);
+    float Ic = I;  // kDual: the clear-sky radiance
     put(fac * I, I, 0, 0, top, acc);
+    if constexpr (kDual) put_clr(fac * Ic, 0);
     flush(pdn, 1, top, 1, bdn);
     // downward: lw_transport_noscat_dn (:982-1009)
     {
@@ -312,6 +342,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         const float y_next = py[(r + 1) % kPF], y_own = py[p];
         const float v = kFused ? (top_at_1 ? y_next : (j == 0 ? y_own : py_prev)) : pv[p];
         const float t = tau_of(pt[p], pi[p]) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
+        const float tc = kDual ? pt[p] * D : 0.0f;
         py_prev = y_own;
         {
           const int ln = lay_dn(min(j + kPF, nlay - 1));
@@ -325,12 +356,19 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           const float S = (1.0f - T) * lvdn + 2.0f * fact * (ly - lvdn);
           I = T * I + S;
           put(fac * I, I, r, 0, top_at_1 ? l + 1 : l, acc);
+          if constexpr (kDual) {
+            const float Tc = solver_exp_neg(-tc, etab);
+            const float fc = (tc > tau_thresh) ? solver_div(1.0f - Tc, tc) - Tc : tc * (0.5f - 1.0f / 3.0f * tc);
+            const float Sc = (1.0f - Tc) * lvdn + 2.0f * fc * (ly - lvdn);
+            Ic = Tc * Ic + Sc;
+            put_clr(fac * Ic, r);
+          }
         }
       };
-      for (int j0 = 0; j0 < nlay; j0 += kRing) {
+      for (int j0 = 0; j0 < nlay; j0 += kR) {
 #pragma unroll
-        for (int r = 0; r < kRing; r++) step(j0 + r, r);
-        flush(pdn, min(kRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn, bdn);
+        for (int r = 0; r < kR; r++) step(j0 + r, r);
+        flush(pdn, min(kR, nlay - j0), top + dl_dn * (j0 + 1), dl_dn, bdn);
       }
     }
     // upward: lw_transport_noscat_up (:950-980); j-th layer from the surface is l = lay_up(j).  With one angle its first
@@ -348,7 +386,9 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     }
     // surface reflection and emission (:269)
     float U = I * (1.0f - e) + e * ss;
+    float Uc = Ic * (1.0f - e) + e * ss;
     put(fac * U, U, 0, 1, sfcl, acc);
+    if constexpr (kDual) put_clr(fac * Uc, 0);
     flush(pup, 1, sfcl, 1, bup);
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
@@ -367,6 +407,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         // fused: lev(l) = pfrac(l) * B(tlev(l)) (l < nlay), from the layer's own pfrac
         const float t = tau_of(pt[p], pi[p]) * D, ly = lay_src(py[p], l);
         const float lvup = lev_src(kFused ? py[p] : pv[p], l);
+        const float tc = kDual ? pt[p] * D : 0.0f;
         {
           const int ln = lay_up(min(j + kPF, nlay - 1));
           pt[p] = Ttau.ld(vg, row * ln); py[p] = Tlay.ld(vg, row * ln); pi[p] = ld_inc(ln);
@@ -378,12 +419,19 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           const float S = (1.0f - T) * lvup + 2.0f * fact * (ly - lvup);
           U = T * U + S;
           put(fac * U, U, r, 1, top_at_1 ? l : l + 1, acc);
+          if constexpr (kDual) {
+            const float Tc = solver_exp_neg(-tc, etab);
+            const float fc = (tc > tau_thresh) ? solver_div(1.0f - Tc, tc) - Tc : tc * (0.5f - 1.0f / 3.0f * tc);
+            const float Sc = (1.0f - Tc) * lvup + 2.0f * fc * (ly - lvup);
+            Uc = Tc * Uc + Sc;
+            put_clr(fac * Uc, r);
+          }
         }
       };
-      for (int j0 = 0; j0 < nlay; j0 += kRing) {
+      for (int j0 = 0; j0 < nlay; j0 += kR) {
 #pragma unroll
-        for (int r = 0; r < kRing; r++) step(j0 + r, r);
-        flush(pup, min(kRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn, bup);
+        for (int r = 0; r < kR; r++) step(j0 + r, r);
+        flush(pup, min(kR, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn, bup);
       }
     }
   }
@@ -421,15 +469,21 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   for (int l = g; l < nlev; l += blockDim.x) {
     flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
     flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
+    if constexpr (kDual) {
+      gdn[l + (size_t)nlev * icol] = combine4(pdn + 4 * (nlev + l));
+      gup[l + (size_t)nlev * icol] = combine4(pup + 4 * (nlev + l));
+    }
   }
 }
 
+// up_clr / dn_clr (both or neither; kFused && kInc, one angle, no extras): the dual instance, clear-sky fluxes beside
+// the all-sky ones
 template <bool kFused, bool kInc>
 static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
                           const float *Ds, const float *wts, const float *inc_flux, const float *tau,
                           const float *lay_or_pfrac, const float *lev_source, const float *sfc_emis,
                           const float *sfc_source, const LwPlanck &pl, const BandArgs &bands, const float *tau_bnd,
-                          float *flux_up, float *flux_dn)
+                          float *flux_up, float *flux_dn, float *up_clr = nullptr, float *dn_clr = nullptr)
 {
   if (ncol == 0) return RRTMGPNN_OK;
   if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
@@ -440,6 +494,9 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
   const bool gpt = ex.gpt_up != nullptr;
   const bool bb = ex.byband();
+  const bool dual = up_clr != nullptr;
+  if (dual && (!kFused || !kInc || nmus != 1 || gpt || bb || ex.lw_Ds || !dn_clr))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: the dual instance is the one-angle fused-Planck path without extras");
   if (bb && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
   if (bb && gpt)
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
@@ -450,7 +507,8 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
   a.rad = gpt && nmus == 1;
   for (int i = 0; i < nmus; i++) { a.D[i] = Ds[i]; a.w[i] = wts[i]; }
   int threads = (ngpt + 63) / 64 * 64;
-  size_t lds = sizeof(float) * (kExpTabFloats + (size_t)kRing * lw_ring_stride(ngpt) + (size_t)2 * (nlay + 1) * 4);
+  size_t lds = sizeof(float) * (kExpTabFloats + (size_t)(dual ? 2 * kRingDual : kRing) * lw_ring_stride(ngpt) +
+                                (size_t)(dual ? 4 : 2) * (nlay + 1) * 4);
   if (kFused) lds += sizeof(float) * lw_btab_floats(bands.nbnd, nlay);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: too many layers for LDS partials");
   // per-g accumulators: the caller's g-point arrays, or (several angles) the context workspace
@@ -473,6 +531,15 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
                        gup, gcs, flux_up, flux_dn, bo);
   };
   const bool multi = nmus > 1 || gpt;
+  if constexpr (kFused && kInc) {
+    if (dual) {
+      gdn = dn_clr;
+      gup = up_clr;
+      go(lw_noscat_kernel<kFused, kInc, PF, false, false, true>);
+      RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual)");
+      return RRTMGPNN_OK;
+    }
+  }
   if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true>);
   else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true>);
   else if (multi)  go(lw_noscat_kernel<kFused, kInc, PF, true>);
@@ -505,6 +572,29 @@ int launch_lw_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
                                       sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn);
   return launch_lw_impl<true, false>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
                                      sfc_emis, nullptr, pl, bands, nullptr, flux_up, flux_dn);
+}
+
+// rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 on the fused-Planck path: clear-sky fluxes from tau, all-sky
+// fluxes from tau + tau_bnd(band).  dual: one launch of the dual instance (one angle only); otherwise the clear and
+// the incremented instance back to back on the context's stream.  Identical bits either way.
+int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, bool dual, int ngpt, int nlay, int ncol, int top_at_1,
+                                    int nmus, const float *Ds, const float *wts, const float *inc_flux,
+                                    const float *tau, const float *pfrac, int ntemp, const float *tlay,
+                                    const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
+                                    float temp_ref_min, float totplnk_delta, const float *totplnk, bool emis_by_band,
+                                    const float *sfc_emis, const float *tau_bnd, float *flux_up, float *flux_dn,
+                                    float *flux_up_clr, float *flux_dn_clr)
+{
+  LwPlanck pl{tlay, tlev, tsfc, totplnk, ntemp, sfc_lay, emis_by_band ? 1 : 0, temp_ref_min, totplnk_delta};
+  if (dual && nmus == 1)
+    return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
+                                      sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn, flux_up_clr,
+                                      flux_dn_clr);
+  if (int rc = launch_lw_impl<true, false>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac,
+                                           nullptr, sfc_emis, nullptr, pl, bands, nullptr, flux_up_clr, flux_dn_clr))
+    return rc;
+  return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
+                                    sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -229,6 +229,27 @@ __device__ __forceinline__ void ring_flush_lanes(const float *ring, int stride, 
   __syncthreads();
 }
 
+// ring_flush_lanes for two quantities staged in rows [2][R][stride] (the dual LW instance: all-sky, clear): lane
+// (q, s, j) walks partial j of quantity q's slot s and stores it to part[q][lev][j] (part [2][nlev][4]) -- the same
+// partial sums in the same order, 8 lanes per level within one wave (8 * R <= 64)
+template <int R>
+__device__ __forceinline__ void ring_flush_lanes2(const float *ring, int stride, float *part, int nlev, int n, int lev0,
+                                                  int dl, int ngpt)
+{
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 8 * n) {
+    const int q = t >= 4 * n ? 1 : 0, u = t - 4 * n * q, sl = u >> 2, j = u & 3;
+    const float *r = ring + (size_t)(q * R + sl) * stride + j;
+    const int n4 = ngpt >> 2;
+    float sum = 0.0f;
+#pragma unroll 8
+    for (int m = 0; m < n4; m++) sum = sum + r[4 * m];
+    part[((size_t)q * nlev + lev0 + sl * dl) * 4 + j] = sum;
+  }
+  __syncthreads();
+}
+
 __device__ __forceinline__ float combine4(const float *p) { return ((p[0] + p[1]) + p[2]) + p[3]; }
 
 // The SW solvers' flush for blocks that hold `ncb` columns: ring [ncb][3][R][ngpt] (up, dif, dir of column c at

@@ -79,6 +79,10 @@ class Context:
         """0: the gas-optics networks on 32x32x2 MFMA tiles where instantiated (default); 1: 16x16x4 (bit-identical)."""
         check(_lib.lib().rrtmgpnn_context_set_mlp_kernel(self.h, int(mode)), "context_set_mlp_kernel")
 
+    def set_lw_clr_all(self, mode):
+        """0: the clear + all-sky LW entry as the library chooses; 1: the dual kernel; 2: two launches (bit-identical)."""
+        check(_lib.lib().rrtmgpnn_context_set_lw_clr_all(self.h, int(mode)), "context_set_lw_clr_all")
+
     def close(self):
         """Destroy the context now (its workspace and buffer pool); the handle is unusable afterwards."""
         h, self.h = getattr(self, "h", None), None
@@ -102,6 +106,12 @@ def set_sw_kernel_default(mode):
     """The SW two-stream kernel of every context not set itself: 0 by ngpt (the default), 1 / 2 one /
     two g-points per lane (bit-identical fluxes; tests force each)."""
     check(_lib.lib().rrtmgpnn_context_set_sw_kernel(None, int(mode)), "context_set_sw_kernel")
+
+
+def set_lw_clr_all_default(mode):
+    """How rrtmgpnn_lw_solver_noscat_planck_clr_all runs on every context not set itself: 0 the library's choice, 1 the
+    dual kernel, 2 the clear and the incremented kernel back to back (bit-identical fluxes; tests force each)."""
+    check(_lib.lib().rrtmgpnn_context_set_lw_clr_all(None, int(mode)), "context_set_lw_clr_all")
 
 
 def context(device=None):
@@ -593,7 +603,11 @@ class GasOpticsRRTMGP(OpticalProps):
         return (ctx, col_dry), ""
 
     def _gas_optics_int(self, play, plev, tlay, tsfc, gas_desc, optical_props, sources, col_dry=None, tlev=None,
-                        neural_nets=None):
+                        neural_nets=None, defer_planck=False):
+        # defer_planck (clr_all_sky.rte_lw's dual path): the Planck sources are left unformed -- lay_source holds
+        # the network's Planck fraction and sources.planck_deferred the (tlay, tlev, tsfc, sfc_lay) a fused-Planck
+        # solver entry forms them from
+        sources.planck_deferred = None
         if neural_nets is None:
             return "gas_optics(): the lookup-table branch is not available (k-distribution files missing); pass neural_nets"
         r, e = self._common(play, plev, tlay, gas_desc, optical_props, col_dry)
@@ -614,6 +628,9 @@ class GasOpticsRRTMGP(OpticalProps):
                                        len(neural_nets), _p(optical_props.tau), _p(sources.lay_source)),
               "predict_nn_lw")
         sfc_lay = 1 if float(play[0, 0]) > float(play[0, nlay - 1]) else nlay  # :402
+        if defer_planck:
+            sources.planck_deferred = (tlay, tlev, tsfc, sfc_lay)
+            return ""
         check(L.rrtmgpnn_compute_planck_source_nn(
             ctx.h, ncol, nlay, self.get_nband(), ngpt, self.get_nPlanckTemp(), _p(tlay), _p(tlev), _p(tsfc), sfc_lay,
             int_array(self.band_lims_gpt.ravel()), self.temp_ref_min, self.totplnk_delta, _p(self.totplnk),

@@ -1,0 +1,175 @@
+"""Clear-sky and all-sky fluxes from one call: extensions/mo_rrtmgp_clr_all_sky.F90's rte_lw and rte_sw over the class
+layer of api.py.
+
+Both follow the reference's sequence (:146-172 LW, :274-308 SW): gas optics once, the optional
+aer_props%increment(optical_props), the clear solve into clrsky_fluxes, cloud_props%increment(optical_props), the
+all-sky solve into allsky_fluxes.  k_dist is a GasOpticsRRTMGP (the reference takes the abstract ty_gas_optics), and
+the networks go in as neural_nets, as GasOpticsRRTMGP.gas_optics takes them.  Error messages are the reference's,
+typos included ('rrtmpg_lw: ...').
+
+rte_lw takes the library's dual entry (rrtmgpnn_lw_solver_noscat_planck_clr_all: tau, the Planck fraction and the
+band cloud optical depth read once, both flux sets from one kernel with one angle) when the cloud properties are
+1scl and defined by band on k_dist's bands and both flux objects want broadband up / down fluxes only; gas optics then
+leaves the Planck sources unformed and the kernel forms them.  Every other case -- 2str clouds (the rescaled solver),
+clouds on g-points, g-point or by-band outputs -- runs the two solves with api.rte_lw.  rte_sw always runs two solves.
+"""
+import torch
+
+from . import _lib, api
+from ._lib import check, float_array, int_array
+from .api import (GAUSS_DS, GAUSS_WTS, FluxesByBand, OpticalProps1scl, OpticalProps2str, SourceFuncLW, _f32dev, _p,
+                  context)
+
+
+def _shape(a):
+    return None if a is None else tuple(a.shape)
+
+
+def _aer_check(aer_props, ncol, nlay, ngpt, nband, msg):
+    """The reference's aerosol extent checks (:93-99, :225-231), as written there: the second one can only fire when
+    ngpt == nband."""
+    e = ""
+    if aer_props is not None:
+        if (aer_props.get_ncol(), aer_props.get_nlay()) != (ncol, nlay):
+            e = msg
+        if not (aer_props.get_ngpt() != ngpt or aer_props.get_ngpt() != nband):
+            e = msg
+    return e
+
+
+def _alloc_like(cloud_props, k_dist, ncol, nlay, device, which):
+    """optical_props of cloud_props' class on k_dist's spectral grid (:117-137)."""
+    if isinstance(cloud_props, OpticalProps2str):
+        op = OpticalProps2str()
+        alloc = op.alloc_2str
+    elif isinstance(cloud_props, OpticalProps1scl):
+        op = OpticalProps1scl()
+        alloc = op.alloc_1scl
+    else:
+        return None, which + "_solver(...ty_optical_props_nstr...) not yet implemented"
+    e = op.init(k_dist.get_band_lims_wavenumber(), k_dist.get_band_lims_gpoint()) or alloc(ncol, nlay, device=device)
+    return op, e
+
+
+def _broadband_only(fluxes):
+    """Does this flux object want exactly the broadband up and down fluxes (what the dual entry writes)?"""
+    if fluxes.flux_up is None or fluxes.flux_dn is None or fluxes.flux_net is not None:
+        return False
+    if fluxes.are_desired_gpt() or (isinstance(fluxes, FluxesByBand) and fluxes.are_desired_byband()):
+        return False
+    return True
+
+
+def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props, allsky_fluxes, clrsky_fluxes,
+           aer_props=None, col_dry=None, t_lev=None, inc_flux=None, n_gauss_angles=None, neural_nets=None):
+    """rte_lw (extensions/mo_rrtmgp_clr_all_sky.F90:46-175).  Tensors in this project's layout: p_lay, t_lay (ncol,
+    nlay); p_lev, t_lev (ncol, nlay+1); t_sfc (ncol); sfc_emis (ncol, nband); inc_flux (ncol, ngpt)."""
+    ncol, nlay = tuple(p_lay.shape)
+    ngpt, nband = k_dist.get_ngpt(), k_dist.get_nband()
+    e = _aer_check(aer_props, ncol, nlay, ngpt, nband, "rrtmpg_lw: aerosol properties inconsistently sized")
+    if t_lev is not None and _shape(t_lev) != (ncol, nlay + 1):
+        e = "rrtmpg_lw: t_lev inconsistently sized"
+    if inc_flux is not None and _shape(inc_flux) != (ncol, ngpt):
+        e = "rrtmpg_lw: incident flux inconsistently sized"
+    if e:
+        return e
+    top_at_1 = bool(p_lay[0, 0] < p_lay[0, nlay - 1])
+    dev = p_lay.device
+    optical_props, e = _alloc_like(cloud_props, k_dist, ncol, nlay, dev, "lw")
+    if e:
+        return e
+    sources = SourceFuncLW()
+    e = sources.alloc(ncol, nlay, spec=k_dist, device=dev)
+    if e:
+        return e
+    nmu = 1 if n_gauss_angles is None else int(n_gauss_angles)
+    dual = (isinstance(optical_props, OpticalProps1scl) and cloud_props.bands_are_equal(optical_props)
+            and not cloud_props.gpoints_are_equal(optical_props) and cloud_props.get_ngpt() == nband
+            and (cloud_props.get_ncol(), cloud_props.get_nlay()) == (ncol, nlay)
+            and _broadband_only(allsky_fluxes) and _broadband_only(clrsky_fluxes) and 1 <= nmu <= 4
+            and _shape(sfc_emis) == (ncol, nband))
+    e = k_dist.gas_optics(p_lay, p_lev, t_lay, t_sfc, gas_concs, optical_props, sources, col_dry=col_dry, tlev=t_lev,
+                          neural_nets=neural_nets, defer_planck=dual)
+    if e:
+        return e
+    if aer_props is not None:
+        e = aer_props.increment(optical_props)
+        if e:
+            return e
+    if dual and sources.planck_deferred is not None:
+        tlay_d, tlev_d, tsfc_d, sfc_lay = sources.planck_deferred
+        ctx = context(dev.index)
+        emis = _f32dev(sfc_emis, dev)
+        check(_lib.lib().rrtmgpnn_lw_solver_noscat_planck_clr_all(
+            ctx.h, ngpt, nlay, ncol, int(top_at_1), nmu, float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]),
+            _p(inc_flux), _p(optical_props.tau), _p(cloud_props.tau), _p(sources.lay_source), nband,
+            k_dist.get_nPlanckTemp(), _p(tlay_d), _p(tlev_d), _p(tsfc_d), sfc_lay,
+            int_array(k_dist.band_lims_gpt.ravel()), k_dist.temp_ref_min, k_dist.totplnk_delta, _p(k_dist.totplnk), 1,
+            _p(emis), _p(allsky_fluxes.flux_up), _p(allsky_fluxes.flux_dn), _p(clrsky_fluxes.flux_up),
+            _p(clrsky_fluxes.flux_dn)), "lw_solver_noscat_planck_clr_all")
+        return ""
+    e = api.rte_lw(optical_props, top_at_1, sources, sfc_emis, clrsky_fluxes, inc_flux=inc_flux,
+                   n_gauss_angles=n_gauss_angles)
+    if e:
+        return e
+    e = cloud_props.increment(optical_props)
+    if e:
+        return e
+    return api.rte_lw(optical_props, top_at_1, sources, sfc_emis, allsky_fluxes, inc_flux=inc_flux,
+                      n_gauss_angles=n_gauss_angles)
+
+
+def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif, cloud_props, allsky_fluxes,
+           clrsky_fluxes, aer_props=None, col_dry=None, inc_flux=None, tsi_scaling=None, neural_nets=None):
+    """rte_sw (extensions/mo_rrtmgp_clr_all_sky.F90:177-310).  sfc_alb_dir / sfc_alb_dif: (ncol, nband) as there
+    (expanded to g-points), or (ncol, ngpt) as api.rte_sw takes them; inc_flux (ncol, ngpt); tsi_scaling: the
+    reference's single multiply of the incident flux."""
+    ncol, nlay = tuple(p_lay.shape)
+    ngpt, nband = k_dist.get_ngpt(), k_dist.get_nband()
+    e = ""
+    if inc_flux is not None and tsi_scaling is not None:
+        e = "rrtmpg_sw: only one of inc_flux, tsi_scaling may be supplied."
+    e = _aer_check(aer_props, ncol, nlay, ngpt, nband, "rrtmpg_sw: aerosol properties inconsistently sized") or e
+    if tsi_scaling is not None and tsi_scaling <= 0:
+        e = "rrtmpg_sw: tsi_scaling is < 0"
+    if inc_flux is not None and _shape(inc_flux) != (ncol, ngpt):
+        e = "rrtmpg_sw: incident flux inconsistently sized"
+    if e:
+        return e
+    top_at_1 = bool(p_lay[0, 0] < p_lay[0, nlay - 1])
+    dev = p_lay.device
+    optical_props, e = _alloc_like(cloud_props, k_dist, ncol, nlay, dev, "sw")
+    if e:
+        return e
+    toa_flux = torch.empty((ncol, ngpt), dtype=torch.float32, device=dev)
+    e = k_dist.gas_optics(p_lay, p_lev, t_lay, gas_concs, optical_props, toa_flux, col_dry=col_dry,
+                          neural_nets=neural_nets)
+    if e:
+        return e
+    if inc_flux is not None:
+        toa_flux.copy_(_f32dev(inc_flux, dev))
+    if tsi_scaling is not None:
+        toa_flux.mul_(float(tsi_scaling))
+    if aer_props is not None:
+        e = aer_props.increment(optical_props)
+        if e:
+            return e
+    ctx = context(dev.index)
+    albs = []
+    for a in (sfc_alb_dir, sfc_alb_dif):
+        a = _f32dev(a, dev)
+        if tuple(a.shape) == (ncol, nband) and nband != ngpt:
+            g = torch.empty((ncol, ngpt), dtype=torch.float32, device=dev)
+            check(_lib.lib().rrtmgpnn_expand_band_to_gpt(ctx.h, nband, ngpt, ncol,
+                                                         int_array(k_dist.band_lims_gpt.ravel()), _p(a), _p(g)),
+                  "expand")
+            a = g
+        albs.append(a)
+    mu0 = _f32dev(mu0, dev)
+    e = api.rte_sw(optical_props, top_at_1, mu0, toa_flux, albs[0], albs[1], clrsky_fluxes)
+    if e:
+        return e
+    e = cloud_props.increment(optical_props)
+    if e:
+        return e
+    return api.rte_sw(optical_props, top_at_1, mu0, toa_flux, albs[0], albs[1], allsky_fluxes)

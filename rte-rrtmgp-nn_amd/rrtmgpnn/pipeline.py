@@ -27,6 +27,11 @@ clouds=(lwp, iwp, rel, rei) makes it the all-sky step of examples/all-sky/rrtmgp
 (config C4) with NN gas optics: cloud optics by band (LUT by default, ice roughness 2 as in the example,
 :219), added to the LW absorption optical depth by band (1scl increment), and for SW delta-scaled and
 added as a two-stream increment; the SW solver then sees a non-zero asymmetry parameter.
+
+clrsky=True (with clouds) also produces the clear-sky fluxes of the same columns, as rte_lw / rte_sw of
+extensions/mo_rrtmgp_clr_all_sky.F90 do: gas optics once, a clear solve, clouds%increment, the all-sky solve.  Fused,
+the LW pair comes from one call (rrtmgpnn_lw_solver_noscat_planck_clr_all) and the SW chain gets one more solver
+launch on the unincremented properties; unfused, the clear solvers run before the increment_* calls.
 """
 
 import numpy as np
@@ -39,7 +44,7 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
-            "sw_byband", "sw_solver"}
+            "sw_byband", "sw_solver", "sw_solver_clr"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
@@ -75,13 +80,22 @@ def _t(a, dev):
 class ClearSkyStep:
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
-                 sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False):
+                 sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
+                 clrsky=False):
         # sw=False: the LW half alone (config C2, rrtmgp_rfmip_lw.F90): gas optics LW + Planck + rte_lw
         # byband: the step also owns by-band fluxes (ty_fluxes_byband; lw_bnd_up / lw_bnd_dn, sw_bnd_up / sw_bnd_dn /
         # sw_bnd_dir, (ncol, nlay+1, nband)) and arms rrtmgpnn_solver_request_byband before each solver call, so the
         # solvers' by-band instances run and a captured graph carries the arrays; False: today's call list
+        # clrsky (all-sky steps): the step also owns clear-sky fluxes of the same columns (lw_up_clr, lw_dn_clr,
+        # sw_up_clr, sw_dn_clr, sw_dir_clr; clrsky_fluxes()); False: today's call list.  By-band clear-sky fluxes are
+        # out of scope: clrsky with byband is refused
         # lw_after: the SW-chain call the LW chain starts after on two streams (None: the default gate in _finish;
         # "": the chains start together)
+        self.clrsky = bool(clrsky)
+        if self.clrsky and clouds is None:
+            raise ValueError("clrsky=True: clear-sky fluxes beside the all-sky ones need clouds=(lwp, iwp, rel, rei)")
+        if self.clrsky and byband:
+            raise ValueError("clrsky=True with byband=True: by-band clear-sky fluxes are not supported")
         self.dev = torch.device("cuda", device)
         self.allsky = clouds is not None
         self.fused = fused
@@ -150,6 +164,12 @@ class ClearSkyStep:
         if not sw:
             for t in (self.sw_up, self.sw_dn, self.sw_dir):
                 t.zero_()
+        if self.clrsky:
+            self.lw_up_clr, self.lw_dn_clr = f(ncol, nlay + 1), f(ncol, nlay + 1)
+            self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr = (f(ncol, nlay + 1) for _ in range(3))
+            if not sw:
+                for t in (self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr):
+                    t.zero_()
         self.byband = bool(byband)
         if self.byband:
             self.lw_bnd_up, self.lw_bnd_dn = f(ncol, nlay + 1, self.nb_lw), f(ncol, nlay + 1, self.nb_lw)
@@ -206,6 +226,11 @@ class ClearSkyStep:
                 ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_inc if self.allsky else L.rrtmgpnn_lw_solver_noscat_planck,
                  (c, self.ng_lw, nlay, ncol, self.top_at_1, nmus, self._Ds, self._W, None) + tail),
             ]
+            if self.clrsky:  # both flux sets from one call: the dual entry in place of _planck_inc
+                lw_calls = [
+                    ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all,
+                     lw_calls[0][2] + (p(self.lw_up_clr), p(self.lw_dn_clr))),
+                ]
         else:
             lw_calls = [
                 ("planck_source", L.rrtmgpnn_compute_planck_source_nn,
@@ -232,6 +257,14 @@ class ClearSkyStep:
                      (c, ncol, nlay, self.ng_lw, self.nb_lw, self._lims_lw, p(self.tau_lw), None, None,
                       p(self.cld_tau_lw), None, None)),
                 ]
+        if self.clrsky and not fused:
+            # the clear solve before clouds%increment(atmos) (mo_rrtmgp_clr_all_sky.F90:161-172): the increment moves
+            # from ahead of the Planck sources to between the two solver calls
+            inc_lw = [x for x in self.calls if x[0] == "increment_lw"]
+            self.calls = [x for x in self.calls if x[0] != "increment_lw"]
+            lw_calls = lw_calls[:-1] + [
+                ("lw_solver_clr", L.rrtmgpnn_lw_solver_noscat,
+                 lw_calls[-1][2][:-2] + (p(self.lw_up_clr), p(self.lw_dn_clr)))] + inc_lw + lw_calls[-1:]
         if self.byband:  # armed right before the solver call that consumes it
             lw_calls.insert(len(lw_calls) - 1,
                             ("lw_byband", L.rrtmgpnn_solver_request_byband,
@@ -276,6 +309,13 @@ class ClearSkyStep:
                 ("delta_scale_sw", L.rrtmgpnn_delta_scale_2str,
                  (c, ncol * nlay * self.nb_sw, p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw), None)),
             ]
+            if self.clrsky and not fused:  # the clear solve before clouds%increment(atmos) (:246-259)
+                self.calls += [
+                    ("sw_solver_clr", L.rrtmgpnn_sw_solver_2stream,
+                     (c, self.ng_sw, nlay, ncol, self.top_at_1, p(self.toa), None, p(self.tau_sw), p(self.ssa_sw),
+                      g_sw, p(self.mu0), p(self.alb), p(self.alb), p(self.sw_up_clr), p(self.sw_dn_clr),
+                      p(self.sw_dir_clr))),
+                ]
             if not fused:
                 self.calls += [
                     ("increment_sw", L.rrtmgpnn_increment_bybnd,
@@ -299,6 +339,17 @@ class ClearSkyStep:
                   p(self.sza), p(self.tau_sw), p(self.ssa_sw), None) + bnd
                  + (p(self.toa), p(self.alb), p(self.mu0), p(self.sw_up), p(self.sw_dn), p(self.sw_dir))),
             ]
+            if self.clrsky:
+                # one more solver launch on the SW chain, on the gas optics' own properties (the fused solver leaves
+                # tau / ssa as they were).  Through the same entry without an increment: the checkpointed kernel forms
+                # the boundary conditions in its prologue and never stores them, so there is nothing in toa / alb /
+                # mu0 for a plain solver call to read
+                self.calls += [
+                    ("sw_solver_clr", L.rrtmgpnn_sw_solver_2stream_rfmip,
+                     (c, self.ng_sw, nlay, ncol, self.top_at_1, p(self.solar_source), p(self.tsi), p(self.sfc_alb),
+                      p(self.sza), p(self.tau_sw), p(self.ssa_sw), None, 0, None, None, None, None, p(self.toa),
+                      p(self.alb), p(self.mu0), p(self.sw_up_clr), p(self.sw_dn_clr), p(self.sw_dir_clr))),
+                ]
         else:
             self.calls += [
                 ("sw_solver", L.rrtmgpnn_sw_solver_2stream,
@@ -604,6 +655,13 @@ class ClearSkyStep:
         """Host copies of a byband step's by-band fluxes, (ncol, nlay+1, nband) each."""
         names = ("lw_bnd_up", "lw_bnd_dn") + (("sw_bnd_up", "sw_bnd_dn", "sw_bnd_dir") if self.sw else ())
         return {k: getattr(self, k).cpu().numpy() for k in names}
+
+    def clrsky_fluxes(self):
+        """Host copies of a clrsky step's clear-sky broadband fluxes, keyed like fluxes() with a _clr suffix."""
+        if not self.clrsky:
+            raise ValueError("clrsky_fluxes: the step was built without clrsky=True")
+        return {k: getattr(self, k).cpu().numpy()
+                for k in ("lw_up_clr", "lw_dn_clr", "sw_up_clr", "sw_dn_clr", "sw_dir_clr")}
 
     def fluxes(self):
         """Host copies of the broadband fluxes, with SW zeroed where sza >= 90 is applied by the caller."""
