@@ -454,6 +454,52 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      const int *band_lims_gpt, const float *tau_bnd, const float *ssa_bnd,
                                      const float *g_bnd, float *toa_flux, float *sfc_alb_gpt, float *mu0,
                                      float *flux_up, float *flux_dn, float *flux_dir);
+/* ---- McICA cloud sampling: extensions/cloud_optics/mo_cloud_sampling.F90 ---------------------------
+ * The extension predates this fork's layout (as mo_heating_rates does).  Here, first index fastest, DEVICE arrays:
+ *   randoms (ngpt, nlay, ncol), read only where cloud_frac > 0, as in the reference (:17-18);
+ *   cloud_frac (nlay, ncol); overlap_param (nlay-1, ncol), alpha(i) between layers i and i+1 (may be NULL for nlay 1);
+ *   cloud_mask (ngpt, nlay, ncol) bytes, 0 / 1: the logical mask of the class layer (draw_samples);
+ *   mask_bits  (nw, nlay, ncol) 32-bit words, nw = ceil(ngpt / 32): bit g % 32 of word g / 32 is the mask of
+ *     0-based g-point g, unused high bits zero: the form the solvers take (rrtmgpnn_solver_request_cloud_mask).
+ * Either output may be NULL, not both.  Random numbers are the caller's, as in the reference (no generator here).
+ * rrtmgpnn_sampled_mask_max_ran (sampled_mask_max_ran, :125-192), maximum-random overlap: a cloudy layer
+ *   (cloud_frac > 0) under a cloudy one reuses its random deviates, one under a clear layer takes new ones; the mask is
+ *   the strict float32 comparison local_rand > (1 - cloud_frac); clear layers, and so every layer outside the first ..
+ *   last cloudy ones, are false.
+ * rrtmgpnn_sampled_mask_exp_ran (sampled_mask_exp_ran, :200-285), exponential-random overlap: under a cloudy layer
+ *   the deviates are rho * (local - 0.5) + sqrt(1 - rho * rho) * (rand - 0.5) + 0.5 with rho = overlap_param of the
+ *   layer pair, evaluated left to right in float32 without fused multiply-adds, the root correctly rounded.
+ *   QUIRK: the reference never assigns the mask of a clear layer lying between cloudy ones (its
+ *   `if(cloud_mask_layer(ilay))` has no else, :261-279; the mask is intent(out)); here those elements are false, the
+ *   evident meaning and what max_ran does.
+ * Neither checks values: cloud_frac in [0, 1] and overlap_param in [-1, 1] are the class layer's checks (:151, :233-240),
+ * made there with the reference's messages.  Bit-identical masks (tests/test_gpu_mcica.py, tests/golden/mcica_masks.npz). */
+int rrtmgpnn_sampled_mask_max_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                  const float *cloud_frac, unsigned char *cloud_mask, unsigned int *mask_bits);
+int rrtmgpnn_sampled_mask_exp_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                  const float *cloud_frac, const float *overlap_param, unsigned char *cloud_mask,
+                                  unsigned int *mask_bits);
+/* draw_samples / apply_cloud_mask (:36-120, :291-307): per g-point the band value (nbnd, nlay, ncol) where cloud_mask is
+ * set, else 0, into (ngpt, nlay, ncol).  tau always; ssa and g when all of ssa_bnd, g_bnd, ssa, g are given (2str),
+ * none of them for 1scl.  band_lims_gpt HOST (2, nbnd), every g-point in a band. */
+int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int nbnd, const int *band_lims_gpt,
+                          const unsigned char *cloud_mask, const float *tau_bnd, const float *ssa_bnd,
+                          const float *g_bnd, float *tau, float *ssa, float *g);
+/* Arms the packed cloud mask mask_bits (layout above) for the NEXT solver call on this context; that call clears the
+ * request whether it succeeds or fails (mask_bits == NULL: nothing armed).  The fused increments then switch the band
+ * value on or off per g-point: where a bit is clear the band operands are 0 (tau_bnd; and ssa_bnd, g_bnd in the SW), and
+ * everything downstream is the _inc arithmetic, so the fluxes are bit for bit those of rrtmgpnn_draw_samples +
+ * rrtmgpnn_increment (same resolution; inc_2stream_by_2stream with a zero increment still rounds
+ * tau * ssa / max(eps, tau), and so does this) + the solver, without the g-point cloud arrays.  Honoured by
+ * rrtmgpnn_lw_solver_noscat_planck_inc (every nmus), rrtmgpnn_sw_solver_2stream_inc and
+ * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, the SW ones on the checkpointed kernel (the default of
+ * rrtmgpnn_context_set_sw_kernel: even ngpt; other modes, and odd ngpt, RRTMGPNN_ERR_UNSUPPORTED).  Extents other than
+ * the call's: RRTMGPNN_ERR_ARGUMENT; every other solver entry (the plain ones, _clr_all, the _gpt entries, the
+ * scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT; together with a by-band request:
+ * RRTMGPNN_ERR_UNSUPPORTED.  The pointer becomes a kernel argument and nothing is allocated, so an armed call can be
+ * captured in a hipGraph.  No reference counterpart (the reference samples into g-point arrays, draw_samples). */
+int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
+                                       const unsigned int *mask_bits);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */
 int rrtmgpnn_delta_scale_2str(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);

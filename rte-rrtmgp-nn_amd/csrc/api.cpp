@@ -112,14 +112,23 @@ static int bands_cover(const BandArgs &b, int ngpt)
 // A solver entry's hold on the context's by-band request (rrtmgpnn_solver_request_byband): the first entry of a call
 // takes the armed request into the per-call extras, validates it against the call's ngpt, and clears it when the
 // call returns, whatever the outcome; an entry reached from another (the _gpt entries call the plain ones) finds
-// nothing armed and leaves the extras alone.
+// nothing armed and leaves the extras alone.  The packed cloud mask (rrtmgpnn_solver_request_cloud_mask) is taken and
+// cleared the same way; what the entry does with it is the macros' part below.
 struct BybandScope {
   rrtmgpnn_context *c;
   bool owner = false;
   int rc = RRTMGPNN_OK;
+  bool mask_owner = false;
+  rrtmgpnn_context::CloudMaskRequest mask{};
   BybandScope(rrtmgpnn_context *ctx, int ngpt) : c(ctx)
   {
-    if (!c || !c->byband.armed) return;
+    if (!c) return;
+    if (c->cloud_mask.armed) {
+      mask_owner = true;
+      mask = c->cloud_mask;
+      c->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+    }
+    if (!c->byband.armed) return;
     owner = true;
     const auto rq = c->byband;
     c->byband = rrtmgpnn_context::BybandRequest{};
@@ -129,17 +138,42 @@ struct BybandScope {
     c->extras.bnd_dn = rq.dn;
     c->extras.bnd_dir = rq.dir;
   }
+  // the entries with masked instances: the mask against the call's extents, then into the per-call extras
+  int take_mask(const char *entry, int ngpt, int nlay, int ncol)
+  {
+    if (!mask_owner) return RRTMGPNN_OK;
+    if (owner)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a cloud mask together with by-band outputs");
+    if (mask.ngpt != ngpt || mask.nlay != nlay || mask.ncol != ncol)
+      return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
+                                                              "are not this call's");
+    c->extras.mask_bits = mask.bits;
+    return RRTMGPNN_OK;
+  }
+  int refuse_mask() const
+  {
+    if (!mask_owner) return RRTMGPNN_OK;
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_cloud_mask: this solver entry takes no cloud mask (the "
+                                       "_planck_inc, _2stream_inc and _2stream_rfmip entries do)");
+  }
   ~BybandScope()
   {
+    if (mask_owner) c->extras.mask_bits = nullptr;
     if (!owner) return;
     c->extras.bnd_up = c->extras.bnd_dn = c->extras.bnd_dir = nullptr;
     c->extras.bnd = BandArgs{};
   }
 };
-// first statement of every solver entry
+// first statement of every solver entry: the entries without masked instances refuse an armed cloud mask
 #define RRTMGPNN_BYBAND(ctx, ngpt)        \
   ::rrtmgpnn::BybandScope byband_((ctx), (ngpt)); \
-  if (byband_.rc) return byband_.rc
+  if (byband_.rc) return byband_.rc;      \
+  if (int mrc_ = byband_.refuse_mask()) return mrc_
+// ... and of the three that honour it
+#define RRTMGPNN_BYBAND_MASK(entry, ctx, ngpt, nlay, ncol) \
+  ::rrtmgpnn::BybandScope byband_((ctx), (ngpt));          \
+  if (byband_.rc) return byband_.rc;                       \
+  if (int mrc_ = byband_.take_mask((entry), (ngpt), (nlay), (ncol))) return mrc_
 
 }  // namespace rrtmgpnn
 
@@ -726,7 +760,7 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          float totplnk_delta, const float *totplnk, int emis_by_band,
                                          const float *sfc_emis, float *flux_up, float *flux_dn)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
+  RRTMGPNN_BYBAND_MASK("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol);
   if (int rc = check_ctx(ctx)) return rc;
   if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
       !flux_up || !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 || sfc_lay < 1 || sfc_lay > nlay ||
@@ -758,6 +792,7 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
   if (byband_.owner)
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all: by-band outputs are not available from this "
                                        "entry (the _planck and _planck_inc entries have them)");
+  if (int rc = byband_.refuse_mask()) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
       !flux_up || !flux_dn || !flux_up_clr || !flux_dn_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 ||
@@ -935,7 +970,7 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
                                    float *flux_dn, float *flux_dir)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
+  RRTMGPNN_BYBAND_MASK("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol);
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !tau_bnd || !ssa_bnd || !g_bnd || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt ||
       !flux_up || !flux_dn || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
@@ -966,6 +1001,69 @@ int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *b
   rq.nbnd = nbnd;
   std::memcpy(rq.lims, band_lims_gpt, sizeof(int) * 2 * nbnd);
   return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
+                                       const unsigned int *mask_bits)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+  if (!mask_bits) return RRTMGPNN_OK;  // nothing wanted: nothing armed
+  if (ngpt < 1 || nlay < 1 || ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_cloud_mask: bad extents");
+  auto &rq = ctx->cloud_mask;
+  rq.armed = true;
+  rq.ngpt = ngpt;
+  rq.nlay = nlay;
+  rq.ncol = ncol;
+  rq.bits = mask_bits;
+  return RRTMGPNN_OK;
+}
+
+// ---- McICA cloud sampling (extensions/cloud_optics/mo_cloud_sampling.F90) ----
+static int sampled_mask(rrtmgpnn_context *ctx, const char *who, bool exp_ran, int ngpt, int nlay, int ncol,
+                        const float *randoms, const float *cloud_frac, const float *overlap_param,
+                        unsigned char *cloud_mask, unsigned int *mask_bits)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!randoms || !cloud_frac || ngpt < 1 || nlay < 1 || ncol < 0 || (exp_ran && nlay > 1 && !overlap_param))
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": bad argument");
+  if (!cloud_mask && !mask_bits)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": neither cloud_mask nor mask_bits is wanted");
+  return launch_sampled_mask(ctx, exp_ran, ngpt, nlay, ncol, randoms, cloud_frac, overlap_param, cloud_mask, mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_max_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                  const float *cloud_frac, unsigned char *cloud_mask, unsigned int *mask_bits)
+{
+  return sampled_mask(ctx, "sampled_mask_max_ran", false, ngpt, nlay, ncol, randoms, cloud_frac, nullptr, cloud_mask,
+                      mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_exp_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                  const float *cloud_frac, const float *overlap_param, unsigned char *cloud_mask,
+                                  unsigned int *mask_bits)
+{
+  return sampled_mask(ctx, "sampled_mask_exp_ran", true, ngpt, nlay, ncol, randoms, cloud_frac, overlap_param,
+                      cloud_mask, mask_bits);
+}
+
+int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int nbnd, const int *band_lims_gpt,
+                          const unsigned char *cloud_mask, const float *tau_bnd, const float *ssa_bnd,
+                          const float *g_bnd, float *tau, float *ssa, float *g)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!cloud_mask || !tau_bnd || !tau || ngpt < 1 || nlay < 1 || ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "draw_samples: bad argument");
+  // 2str: all of ssa_bnd, g_bnd, ssa, g; 1scl: none of them
+  const int n2 = (ssa_bnd != nullptr) + (g_bnd != nullptr) + (ssa != nullptr) + (g != nullptr);
+  if (n2 != 0 && n2 != 4)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "draw_samples: by-band and sampled cloud properties need to be the same "
+                                       "variable type");
+  BandArgs b;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_cover(b, ngpt)) return rc;
+  return launch_draw_samples(ctx, ngpt, nlay, ncol, b, cloud_mask, tau_bnd, ssa_bnd, g_bnd, tau, ssa, g);
 }
 
 int rrtmgpnn_sum_byband(rrtmgpnn_context *ctx, int ngpt, int nlev, int ncol, int nbnd, const int *band_lims_gpt,
@@ -1236,7 +1334,9 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      const float *g_bnd, float *toa_flux, float *sfc_alb_gpt, float *mu0,
                                      float *flux_up, float *flux_dn, float *flux_dir)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
+  RRTMGPNN_BYBAND_MASK("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol);
+  if (ctx && ctx->extras.mask_bits && nbnd <= 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream_rfmip: a cloud mask needs the band increment (nbnd > 0)");
   if (int rc = check_ctx(ctx)) return rc;
   if (!solar_source || !tsi || !sfc_alb || !sza || !tau || !ssa || !toa_flux || !sfc_alb_gpt || !mu0 || !flux_up ||
       !flux_dn || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0 || nbnd < 0 ||

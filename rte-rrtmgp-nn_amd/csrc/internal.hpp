@@ -75,6 +75,10 @@ struct rrtmgpnn_context {
     float *bnd_up = nullptr, *bnd_dn = nullptr, *bnd_dir = nullptr;
     rrtmgpnn::BandArgs bnd{};
     bool byband() const { return bnd_up || bnd_dn || bnd_dir; }
+    // McICA: the packed cloud mask (nw, nlay, ncol), nw = ceil(ngpt / 32), of the fused band increment, set from
+    // `cloud_mask` by the solver entry that consumes the request (rrtmgpnn_solver_request_cloud_mask); only the
+    // _planck_inc, _2stream_inc and _2stream_rfmip entries have masked instances
+    const uint32_t *mask_bits = nullptr;
   } extras;
   // rrtmgpnn_solver_request_byband: armed for the next solver call on this context, which clears it
   struct BybandRequest {
@@ -83,6 +87,12 @@ struct rrtmgpnn_context {
     int nbnd = 0;
     int lims[2 * rrtmgpnn::kMaxBands] = {0};
   } byband;
+  // rrtmgpnn_solver_request_cloud_mask: armed for the next solver call on this context, which clears it
+  struct CloudMaskRequest {
+    bool armed = false;
+    int ngpt = 0, nlay = 0, ncol = 0;
+    const uint32_t *bits = nullptr;
+  } cloud_mask;
   void *ws = nullptr;
   size_t ws_bytes = 0;
   bool ws_pinned = false;
@@ -184,6 +194,13 @@ struct SwBcDev {
 SwBcDev sw_boundary_device(const SwBc *bc);
 constexpr int kSwBoundaryMaxG = 1024;
 int launch_delta_scale(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);
+// kernels_mcica.hip: sampled_mask_max_ran / _exp_ran (mask: bytes, bits: packed words; either may be null) and
+// apply_cloud_mask
+int launch_sampled_mask(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay, int ncol, const float *randoms,
+                        const float *cloud_frac, const float *overlap, unsigned char *mask, uint32_t *bits);
+int launch_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const BandArgs &bands,
+                        const unsigned char *mask, const float *tau_bnd, const float *ssa_bnd, const float *g_bnd,
+                        float *tau, float *ssa, float *g);
 // kernels_nn.hip
 struct GasArgs {
   const float *p[kMaxInputs];

@@ -143,16 +143,24 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // ([2][kRingDual][rs]: 0 = all-sky, 1 = clear) and both are reduced by one flush (part [2 dn][nlev][4], [2 up][nlev][4]).
 // The clear fluxes go to gup / gdn (flux_up_clr, flux_dn_clr; (nlay+1, ncol)), which the one-angle instances do not
 // otherwise use.  Each set is bit-identical to what the <kFused, false> and <kFused, true> instances give.
-template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false>
+//
+// kMask (with kInc): the band increment is a McICA-sampled cloud (rrtmgpnn_solver_request_cloud_mask): bit g % 32 of
+// word g / 32 of cmask (nw, nlay, ncol) switches tau_bnd on or off for g-point g, tau + (bit ? tau_bnd(band) : 0) --
+// draw_samples (extensions/cloud_optics/mo_cloud_sampling.F90:291-307) and increment_1scalar_by_1scalar
+// (rte/kernels/mo_optical_props_kernels.F90:109-121) in the one add of kInc.  One mask word per layer per lane joins that
+// layer's prefetch.  The instances that run without a request hold no trace of it.
+template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false, bool kMask = false>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
                                            const float *__restrict__ emis, const float *__restrict__ sfc,
                                            LwPlanck pl, BandArgs bands, const float *__restrict__ tau_bnd,
                                            float *__restrict__ gdn, float *__restrict__ gup, long long gcs,
-                                           float *__restrict__ flux_up, float *__restrict__ flux_dn, BandOut bo)
+                                           float *__restrict__ flux_up, float *__restrict__ flux_dn, BandOut bo,
+                                           const uint32_t *__restrict__ cmask)
 {
   constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
+  static_assert(!kMask || (kInc && !kDual && !kBand), "the cloud mask switches the fused band increment");
   static_assert(kR % kPF == 0, "prefetch depth must divide the ring");
   // the fused down pass takes lev(l+1)'s Planck fraction from the neighbouring prefetch slot, py[(r+1) % kPF]: with
   // one slot that would be the layer's own pfrac
@@ -189,7 +197,16 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   const uint32_t irow = 4u * (uint32_t)bands.nbnd, vb = kInc ? 4u * (uint32_t)band_of(bands, gc) : 0u;
   const ColArr Tinc(kInc ? tau_bnd : tau, kInc ? (size_t)bands.nbnd * nlay * icol : 0, irow * nlay);
   auto ld_inc = [&](int l) { return kInc ? Tinc.ld(vb, irow * (uint32_t)l) : 0.0f; };
-  auto tau_of = [&](float t, float ti) { return kInc ? t + ti : t; };
+  // kMask: this lane's mask word, one per layer at stride nw, and its g-point's bit
+  const uint32_t mrow = kMask ? 4u * (uint32_t)((ngpt + 31) / 32) : 0u, vm = 4u * (uint32_t)(gc >> 5);
+  const uint32_t mbit = 1u << (gc & 31);
+  const ColArr Tmsk(kMask ? (const float *)cmask : tau, kMask ? (size_t)((ngpt + 31) / 32) * nlay * icol : 0,
+                    mrow * nlay);
+  auto ld_msk = [&](int l) { return kMask ? __float_as_uint(Tmsk.ld(vm, mrow * (uint32_t)l)) : 0u; };
+  auto tau_of = [&](float t, float ti, uint32_t m) {
+    if constexpr (kMask) return t + ((m & mbit) ? ti : 0.0f);
+    else return kInc ? t + ti : t;
+  };
   // the value to load for lev index li: lev_source(li), or pfrac(min(li, nlay-1)) when fused
   auto lev_ld = [&](int li) {
     return kFused ? Tlay.ld(vg, row * (uint32_t)min(li, nlay - 1)) : Tlev.ld(vg, row * (uint32_t)li);
@@ -317,6 +334,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // downward: lw_transport_noscat_dn (:982-1009)
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
+      uint32_t pm[kPF];
       if (kEarly && imu == 0) {  // loaded ahead of the prologue
 #pragma unroll
         for (int p = 0; p < kPF; p++) {
@@ -328,6 +346,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           const int l = lay_dn(min(p, nlay - 1));
           pt[p] = Ttau.ld(vg, row * l); py[p] = Tlay.ld(vg, row * l); pi[p] = ld_inc(l);
           if constexpr (!kFused) pv[p] = lev_ld(l + 1);
+          if constexpr (kMask) pm[p] = ld_msk(l);
         }
       }
       // fused: lev(l+1)'s Planck fraction pfrac(min(l+1, nlay-1)) is a neighbour's in walk order, already loaded --
@@ -341,7 +360,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         const int p = r % kPF, l = lay_dn(min(j, nlay - 1));
         const float y_next = py[(r + 1) % kPF], y_own = py[p];
         const float v = kFused ? (top_at_1 ? y_next : (j == 0 ? y_own : py_prev)) : pv[p];
-        const float t = tau_of(pt[p], pi[p]) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
+        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : 0u) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
         const float tc = kDual ? pt[p] * D : 0.0f;
         py_prev = y_own;
         {
@@ -349,6 +368,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           pt[p] = Ttau.ld(vg, row * ln); py[p] = Tlay.ld(vg, row * ln);
           if constexpr (!kFused) pv[p] = lev_ld(ln + 1);
           pi[p] = ld_inc(ln);
+          if constexpr (kMask) pm[p] = ld_msk(ln);
         }
         if (j < nlay) {
           const float T = solver_exp_neg(-t, etab);
@@ -376,11 +396,13 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // several angles there is no flush, and the registers would spill)
     auto lay_up = [&](int j) { return top_at_1 ? nlay - 1 - j : j; };
     float ptu[kPF], pyu[kPF], pvu[kPF], piu[kPF];
+    uint32_t pmu[kPF];
     if constexpr (!kMulti) {
 #pragma unroll
       for (int p = 0; p < kPF; p++) {
         const int l = lay_up(min(p, nlay - 1));
         ptu[p] = Ttau.ld(vg, row * l); pyu[p] = Tlay.ld(vg, row * l); piu[p] = ld_inc(l);
+        if constexpr (kMask) pmu[p] = ld_msk(l);
         pvu[p] = kFused ? 0.0f : Tlev.ld(vg, row * l);
       }
     }
@@ -392,26 +414,30 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     flush(pup, 1, sfcl, 1, bup);
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
+      uint32_t pm[kPF];
 #pragma unroll
       for (int p = 0; p < kPF; p++) {
         if constexpr (!kMulti) {
           pt[p] = ptu[p]; py[p] = pyu[p]; pi[p] = piu[p]; pv[p] = pvu[p];
+          if constexpr (kMask) pm[p] = pmu[p];
         } else {
           const int l = lay_up(min(p, nlay - 1));
           pt[p] = Ttau.ld(vg, row * l); py[p] = Tlay.ld(vg, row * l); pi[p] = ld_inc(l);
           if constexpr (!kFused) pv[p] = Tlev.ld(vg, row * l);
+          if constexpr (kMask) pm[p] = ld_msk(l);
         }
       }
       auto step = [&](int j, int r) {
         const int p = r % kPF, l = lay_up(min(j, nlay - 1));
         // fused: lev(l) = pfrac(l) * B(tlev(l)) (l < nlay), from the layer's own pfrac
-        const float t = tau_of(pt[p], pi[p]) * D, ly = lay_src(py[p], l);
+        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : 0u) * D, ly = lay_src(py[p], l);
         const float lvup = lev_src(kFused ? py[p] : pv[p], l);
         const float tc = kDual ? pt[p] * D : 0.0f;
         {
           const int ln = lay_up(min(j + kPF, nlay - 1));
           pt[p] = Ttau.ld(vg, row * ln); py[p] = Tlay.ld(vg, row * ln); pi[p] = ld_inc(ln);
           if constexpr (!kFused) pv[p] = Tlev.ld(vg, row * ln);
+          if constexpr (kMask) pm[p] = ld_msk(ln);
         }
         if (j < nlay) {
           const float T = solver_exp_neg(-t, etab);
@@ -528,7 +554,7 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1, a, inc_flux, tau,
                        lay_or_pfrac, kFused ? lay_or_pfrac : lev_source, sfc_emis, sfc_source, pl, bands, tau_bnd, gdn,
-                       gup, gcs, flux_up, flux_dn, bo);
+                       gup, gcs, flux_up, flux_dn, bo, ex.mask_bits);
   };
   const bool multi = nmus > 1 || gpt;
   if constexpr (kFused && kInc) {
@@ -538,6 +564,19 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
       go(lw_noscat_kernel<kFused, kInc, PF, false, false, true>);
       RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual)");
       return RRTMGPNN_OK;
+    }
+  }
+  if (ex.mask_bits) {
+    // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask)
+    if constexpr (kFused && kInc) {
+      if (bb || gpt || ex.lw_Ds)
+        return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: a cloud mask with by-band or g-point outputs or lw_Ds");
+      if (multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true>);
+      else       go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true>);
+      RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (masked)");
+      return RRTMGPNN_OK;
+    } else {
+      return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: a cloud mask needs the fused band increment");
     }
   }
   if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true>);
@@ -936,6 +975,13 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
                                           "reduces g-point fluxes)");
   const bool ck = (ngpt % 2) == 0 && (mode == 3 || mode == 0 || gpt);
   const bool x2 = !ck && (ngpt % 2) == 0 && mode != 1;
+  // McICA (rrtmgpnn_solver_request_cloud_mask): only the checkpointed kernel has masked instances
+  if (ctx->extras.mask_bits && !inc)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
+  if (ctx->extras.mask_bits && (!ck || gpt || bb))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask is taken by the checkpointed kernel only (even ngpt, "
+                                          "rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band or g-point "
+                                          "outputs");
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
   // the other kernels read them from memory, formed there first by sw_boundary_kernel
   SwBcDev bcd{};

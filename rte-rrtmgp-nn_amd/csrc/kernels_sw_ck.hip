@@ -176,10 +176,17 @@ constexpr int kCkAheadSmall = 1;
 // V: f2 (two g-points per lane) or float (one per lane).  kBandPair (fused increment, two g-points per lane): every
 // band starts at an even g-point, so both g-points of a lane lie in one band and its band values are one load each
 // (the RRTMGP g-point sets: 16 per band).  Round 4, C4: SW solver -1.7 % alone, steps -0.8 % (3 alternating pairs)
+// kMask (with kInc, two g-points per lane): the band increment is a McICA-sampled cloud
+// (rrtmgpnn_solver_request_cloud_mask): bit g % 32 of word g / 32 of cmask (nw, nlay, ncol) switches (tau, ssa, g)_bnd
+// on or off for g-point g -- a clear bit makes all three 0, draw_samples
+// (extensions/cloud_optics/mo_cloud_sampling.F90:291-307) -- and ck_inc then increments by them as it does by any
+// other values (a zero increment still rounds tau * ssa / max(eps, tau)).  Both g-points of a lane are selected
+// separately (g is even, so they share the word), also in the band-pair form; the word is loaded with the layer's
+// band values.
 template <bool kHasG, bool kInc, int K, bool kGpt = false, int R = kCkRing,
           int WAVES = (!kHasG && !kInc && !kGpt) ? kCkWavesNN : kCkWaves, bool kTn = false,
           class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1,
-          bool kBand = false>
+          bool kBand = false, bool kMask = false>
 __global__ void __launch_bounds__(512, WAVES)
     sw_2stream_ck_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
@@ -188,9 +195,11 @@ __global__ void __launch_bounds__(512, WAVES)
                          const float *__restrict__ tau_bnd, const float *__restrict__ ssa_bnd,
                          const float *__restrict__ g_bnd, float *__restrict__ ws, float *__restrict__ flux_up,
                          float *__restrict__ flux_dn, float *__restrict__ flux_dir, float *__restrict__ gpt_up,
-                         float *__restrict__ gpt_dn, float *__restrict__ gpt_dir, SwBcDev bc, BandOut bo)
+                         float *__restrict__ gpt_dn, float *__restrict__ gpt_dir, SwBcDev bc, BandOut bo,
+                         const uint32_t *__restrict__ cmask)
 {
   static_assert(R % K == 0, "the flux ring must hold whole chunks");
+  static_assert(!kMask || (kInc && sizeof(V) == 8 && !kBand && !kGpt), "the cloud mask switches the fused band increment");
   constexpr bool kG0 = !kHasG && !kInc;  // g is the literal 0 (the NN path)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // `ncb` columns per block: lane t works on column c = t / (ngpt/NPL), g-points g .. g + NPL - 1
@@ -254,6 +263,23 @@ __global__ void __launch_bounds__(512, WAVES)
     } else if constexpr (NPL == 2) return (f2){a.ld1(vb0, brow * (uint32_t)l), a.ld1(vb1, brow * (uint32_t)l)};
     else return a.ld1(vb0, brow * (uint32_t)l);
   };
+  // kMask: the lane's mask word of layer l (its column's plane of (nw, nlay, ncol)) and the selection of a band value
+  // by the bits of its two g-points
+  const int nw = (ngpt + 31) / 32;
+  const uint32_t mrow = kMask ? 4u * (uint32_t)nw : 0u;
+  const uint32_t vm = 4u * (uint32_t)(gc >> 5) + (uint32_t)c * mrow * nlay, msh = (uint32_t)(gc & 31);
+  const ColArr2 Mk(kMask ? (const float *)cmask : tau, kMask ? (size_t)nw * nlay * icol0 : 0,
+                   kMask ? (uint32_t)nc * mrow * nlay : 0u);
+  auto ld_msk = [&](int l) -> uint32_t {
+    if constexpr (kMask) return __float_as_uint(Mk.ld1(vm, mrow * (uint32_t)l));
+    else return 0u;
+  };
+  auto sel = [&](V v, uint32_t m) -> V {
+    if constexpr (kMask && NPL == 2) {
+      const uint32_t b = m >> msh;
+      return (f2){(b & 1u) ? v[0] : 0.0f, (b & 2u) ? v[1] : 0.0f};
+    } else return v;
+  };
   // mu0 = merge(cos(sza * deg_to_rad), 1, usecol) (rrtmgp_rfmip_sw.F90:236-238, 421-427) or the caller's
   const float sza = bcf ? bc.sza[icol] : 0.0f;
   const float mu0 = bcf ? (sza < bc.sza_max ? ref_cosf(sza * bc.deg_to_rad) : 1.0f) : mu0p[icol];
@@ -278,7 +304,8 @@ __global__ void __launch_bounds__(512, WAVES)
     for (int p = 0; p < P1; p++) {
       const int l = lay(c1 * P1 + p);
       b.t[p] = Ttau.ldv(vL, row * (uint32_t)l);
-      if constexpr (kInc) b.t[p] += ld_bnd(Bt, l);
+      if constexpr (kMask) b.t[p] += sel(ld_bnd(Bt, l), ld_msk(l));
+      else if constexpr (kInc) b.t[p] += ld_bnd(Bt, l);
     }
   };
   if constexpr (kEarly) {
@@ -309,6 +336,7 @@ __global__ void __launch_bounds__(512, WAVES)
   // bottom (pass 3)
   struct Chunk {
     V t[K], w[K], g[K], qt[K], qw[K], qg[K], tn[K], em[K], fb, ae, se;
+    uint32_t qm[kMask ? K : 1];
   };
   // pass: 2 or 3
   auto load_chunk = [&](Chunk &ch, int ck, int pass) {
@@ -325,6 +353,7 @@ __global__ void __launch_bounds__(512, WAVES)
         ch.qt[p] = ld_bnd(Bt, l);
         ch.qw[p] = ld_bnd(Bw, l);
         ch.qg[p] = ld_bnd(Bg, l);
+        if constexpr (kMask) ch.qm[p] = ld_msk(l);
       } else {
         ch.qt[p] = ch.qw[p] = ch.qg[p] = (V)0.0f;
       }
@@ -342,7 +371,8 @@ __global__ void __launch_bounds__(512, WAVES)
     t = ch.t[p];
     w = ch.w[p];
     g0 = kHasG ? ch.g[p] : (V)0.0f;
-    if constexpr (kInc) ck_inc(t, w, g0, ch.qt[p], ch.qw[p], ch.qg[p]);
+    if constexpr (kMask) ck_inc(t, w, g0, sel(ch.qt[p], ch.qm[p]), sel(ch.qw[p], ch.qm[p]), sel(ch.qg[p], ch.qm[p]));
+    else if constexpr (kInc) ck_inc(t, w, g0, ch.qt[p], ch.qw[p], ch.qg[p]);
   };
   // Each pass walks its chunks two at a time through two register buffers: the loads of the next chunk go to the other
   // buffer while this one is computed, so no copy waits for them at the end of the step.  body(buf, ck, valid)
@@ -607,10 +637,44 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, top_at_1, ncb, inc_flux, inc_flux_dif,
                        tau, ssa, g, mu0, alb_dir, alb_dif, b, tb, sb, gb, (float *)ws, flux_up, flux_dn, flux_dir,
-                       ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo);
+                       ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
+  if (ex.mask_bits) {
+    // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask), as the instances below
+    if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
+    if (bb || ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask with by-band or g-point outputs");
+    bool pair = true;
+    for (int i = 0; i < b.nbnd; i++) pair = pair && ((b.lims[2 * i] - 1) % 2 == 0);
+    constexpr int W = kCkWaves, P = kCkP1;
+    constexpr bool T = kCkTnInc, E = kCkEmkInc;
+    if (!planes) {
+      if (pair && g)
+        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      if (pair)
+        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      if (g)
+        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, false, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, false, true>,
+                tau_bnd, ssa_bnd, g_bnd);
+    }
+    if (pair && g)
+      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (pair)
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (g)
+      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, true>, tau_bnd,
+              ssa_bnd, g_bnd);
+  }
   if (ex.gpt_up || ex.gpt_dn || ex.gpt_dir) {  // ty_fluxes_flexible g-point outputs
     if (!ex.gpt_up || !ex.gpt_dn || !ex.gpt_dir)
       return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: g-point outputs need gpt_flux_up, gpt_flux_dn and gpt_flux_dn_dir");

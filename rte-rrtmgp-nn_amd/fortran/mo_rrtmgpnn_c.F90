@@ -19,6 +19,9 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_lw_solver_noscat_gpt, c_rrtmgpnn_lw_solver_noscat_planck_gpt, c_rrtmgpnn_sw_solver_2stream_gpt
   public :: c_rrtmgpnn_lw_solver_1rescl_gpt, c_rrtmgpnn_lw_solver_2stream_gpt, c_rrtmgpnn_sw_solver_noscat_gpt
   public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
+  public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
+            c_rrtmgpnn_draw_samples
+  public :: c_rrtmgpnn_present, c_rrtmgpnn_present_update_host, c_rrtmgpnn_present_delete  ! masks (mo_cloud_sampling)
   public :: c_rrtmgpnn_network_load, c_rrtmgpnn_compute_nn_inputs, c_rrtmgpnn_get_col_dry, &
             c_rrtmgpnn_interpolate_tlev, c_rrtmgpnn_predict_nn_lw, c_rrtmgpnn_predict_nn_sw, &
             c_rrtmgpnn_compute_planck_source_nn, c_rrtmgpnn_lw_solver_noscat, c_rrtmgpnn_sw_solver_2stream, &
@@ -299,6 +302,31 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, bnd_flux_up, bnd_flux_dn, bnd_flux_dir
       integer(c_int), value :: nbnd
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
+    end function
+    integer(c_int) function c_rrtmgpnn_solver_request_cloud_mask(ctx, ngpt, nlay, ncol, mask_bits) &
+        bind(C, name="rrtmgpnn_solver_request_cloud_mask")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_max_ran(ctx, ngpt, nlay, ncol, randoms, cloud_frac, cloud_mask, &
+        mask_bits) bind(C, name="rrtmgpnn_sampled_mask_max_ran")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, randoms, cloud_frac, cloud_mask, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_exp_ran(ctx, ngpt, nlay, ncol, randoms, cloud_frac, overlap_param, &
+        cloud_mask, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_exp_ran")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, randoms, cloud_frac, overlap_param, cloud_mask, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_draw_samples(ctx, ngpt, nlay, ncol, nbnd, band_lims_gpt, cloud_mask, tau_bnd, &
+        ssa_bnd, g_bnd, tau, ssa, g) bind(C, name="rrtmgpnn_draw_samples")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, cloud_mask, tau_bnd, ssa_bnd, g_bnd, tau, ssa, g
+      integer(c_int), value :: ngpt, nlay, ncol, nbnd
       integer(c_int), dimension(*), intent(in) :: band_lims_gpt
     end function
     integer(c_int) function c_rrtmgpnn_sum_byband(ctx, ngpt, nlev, ncol, nbnd, band_lims_gpt, gpt_flux, bnd_flux) &

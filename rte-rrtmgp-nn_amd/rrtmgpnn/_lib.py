@@ -98,6 +98,11 @@ SIGNATURES = {
     "rrtmgpnn_lw_solver_2stream_gpt": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 11),
     "rrtmgpnn_sw_solver_noscat_gpt": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 5),
     "rrtmgpnn_solver_request_byband": (c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp]),
+    "rrtmgpnn_solver_request_cloud_mask": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
+    "rrtmgpnn_sampled_mask_max_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_sampled_mask_exp_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_draw_samples": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp]),
     "rrtmgpnn_sum_byband": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp]),
     "rrtmgpnn_expand_band_to_gpt": (c_int, [c_vp, c_int, c_int, c_int, P(c_int), c_vp, c_vp]),
     "rrtmgpnn_compute_heating_rate": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -28,6 +28,11 @@ clouds=(lwp, iwp, rel, rei) makes it the all-sky step of examples/all-sky/rrtmgp
 :219), added to the LW absorption optical depth by band (1scl increment), and for SW delta-scaled and
 added as a two-stream increment; the SW solver then sees a non-zero asymmetry parameter.
 
+mcica={...} (with clouds) samples the band clouds per g-point with McICA (extensions/cloud_optics/mo_cloud_sampling.F90)
+from a cloud fraction per layer and the caller's random numbers.  Fused, each chain runs the mask kernel into a packed
+mask and arms it (rrtmgpnn_solver_request_cloud_mask) for the fused solver call, which switches the band increment per
+g-point; unfused, the class layer's mask -> draw_samples -> increment sequence.
+
 clrsky=True (with clouds) also produces the clear-sky fluxes of the same columns, as rte_lw / rte_sw of
 extensions/mo_rrtmgp_clr_all_sky.F90 do: gas optics once, a clear solve, clouds%increment, the all-sky solve.  Fused,
 the LW pair comes from one call (rrtmgpnn_lw_solver_noscat_planck_clr_all) and the SW chain gets one more solver
@@ -44,14 +49,16 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
-            "sw_byband", "sw_solver", "sw_solver_clr"}
+            "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
-# (lw_byband / sw_byband: a byband step's by-band requests, host-only calls issued right before their solver)
-FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "predict_nn_lw",
-               "lw_byband", "lw_solver", "nn_inputs_sw", "cloud_optics_sw", "delta_scale_sw", "predict_nn_sw",
-               "sw_byband", "sw_solver"]
+# (lw_byband / sw_byband: a byband step's by-band requests, host-only calls issued right before their solver;
+# mcica_mask_*: a McICA step's mask kernels, which depend on no network; lw_mask / sw_mask: its cloud-mask requests,
+# host-only like the by-band ones)
+FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
+               "predict_nn_lw", "lw_byband", "lw_mask", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
+               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_solver"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -81,7 +88,7 @@ class ClearSkyStep:
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
-                 clrsky=False):
+                 clrsky=False, mcica=None):
         # sw=False: the LW half alone (config C2, rrtmgp_rfmip_lw.F90): gas optics LW + Planck + rte_lw
         # byband: the step also owns by-band fluxes (ty_fluxes_byband; lw_bnd_up / lw_bnd_dn, sw_bnd_up / sw_bnd_dn /
         # sw_bnd_dir, (ncol, nlay+1, nband)) and arms rrtmgpnn_solver_request_byband before each solver call, so the
@@ -91,6 +98,20 @@ class ClearSkyStep:
         # out of scope: clrsky with byband is refused
         # lw_after: the SW-chain call the LW chain starts after on two streams (None: the default gate in _finish;
         # "": the chains start together)
+        # mcica (all-sky steps): McICA-sampled clouds (extensions/cloud_optics/mo_cloud_sampling.F90) in place of overcast
+        # ones: {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, ngpt_lw), "randoms_sw": (ncol, nlay, ngpt_sw),
+        # "overlap_param": None (maximum-random overlap) or (ncol, nlay-1) (exponential-random)}.  (`overlap` is the
+        # stream-overlap flag.)  Fused: per chain the mask kernel (packed bits), rrtmgpnn_solver_request_cloud_mask and
+        # the fused solver call of the all-sky step; fused=False: the class layer's sequence, mask -> draw_samples ->
+        # increment at g-point resolution.  The randoms are step-owned device buffers (mcica_randoms()) the caller
+        # refills between steps or replays (set_mcica_randoms).  None: today's call list
+        self.mcica = mcica is not None
+        if self.mcica and clouds is None:
+            raise ValueError("mcica: sampled clouds need clouds=(lwp, iwp, rel, rei)")
+        if self.mcica and (clrsky or byband):
+            raise ValueError("mcica with clrsky=True or byband=True is not supported")
+        if self.mcica and not sw:
+            raise ValueError("mcica with sw=False is not supported")
         self.clrsky = bool(clrsky)
         if self.clrsky and clouds is None:
             raise ValueError("clrsky=True: clear-sky fluxes beside the all-sky ones need clouds=(lwp, iwp, rel, rei)")
@@ -159,6 +180,25 @@ class ClearSkyStep:
             self.cld_tau_lw = f(ncol, nlay, self.nb_lw)
             self.cld_tau_sw, self.cld_ssa_sw, self.cld_g_sw = (f(ncol, nlay, self.nb_sw) for _ in range(3))
             self.cloud_lw, self.cloud_sw = (self._cloud_optics(w, cloud_lut, icergh) for w in ("lw", "sw"))
+        if self.mcica:
+            self.cloud_frac = _t(mcica["cloud_frac"], dev)
+            ov = mcica.get("overlap_param")
+            self.overlap_param = None if ov is None else _t(ov, dev)
+            self.randoms_lw, self.randoms_sw = _t(mcica["randoms_lw"], dev), _t(mcica["randoms_sw"], dev)
+            want = {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, self.ng_lw),
+                    "randoms_sw": (ncol, nlay, self.ng_sw), "overlap_param": (ncol, nlay - 1)}
+            for k, t in (("cloud_frac", self.cloud_frac), ("randoms_lw", self.randoms_lw),
+                         ("randoms_sw", self.randoms_sw), ("overlap_param", self.overlap_param)):
+                if t is not None and tuple(t.shape) != want[k]:
+                    raise ValueError("mcica: %s has shape %s, expected %s" % (k, tuple(t.shape), want[k]))
+            if fused:  # the packed masks the solvers take
+                self.mask_bits_lw = torch.zeros((ncol, nlay, (self.ng_lw + 31) // 32), dtype=torch.int32, device=dev)
+                self.mask_bits_sw = torch.zeros((ncol, nlay, (self.ng_sw + 31) // 32), dtype=torch.int32, device=dev)
+            else:  # the class layer's logical masks and g-point cloud properties
+                self.mask_lw = torch.zeros((ncol, nlay, self.ng_lw), dtype=torch.uint8, device=dev)
+                self.mask_sw = torch.zeros((ncol, nlay, self.ng_sw), dtype=torch.uint8, device=dev)
+                self.smp_tau_lw = f(ncol, nlay, self.ng_lw)
+                self.smp_tau_sw, self.smp_ssa_sw, self.smp_g_sw = (f(ncol, nlay, self.ng_sw) for _ in range(3))
         self.lw_up, self.lw_dn = f(ncol, nlay + 1), f(ncol, nlay + 1)
         self.sw_up, self.sw_dn, self.sw_dir = f(ncol, nlay + 1), f(ncol, nlay + 1), f(ncol, nlay + 1)
         if not sw:
@@ -251,12 +291,28 @@ class ClearSkyStep:
                  (c, self.cloud_lw, ncol, nlay, p(self.lwp), p(self.iwp), p(self.rel), p(self.rei),
                   p(self.cld_tau_lw), None, None)),
             ]
-            if not fused:
+            if not fused and self.mcica:
+                # the class layer's McICA sequence: mask, draw_samples, increment at g-point resolution
+                self.calls += [
+                    self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, p(self.mask_lw), None),
+                    ("draw_samples_lw", L.rrtmgpnn_draw_samples,
+                     (c, self.ng_lw, nlay, ncol, self.nb_lw, self._lims_lw, p(self.mask_lw), p(self.cld_tau_lw), None,
+                      None, p(self.smp_tau_lw), None, None)),
+                    ("increment_lw", L.rrtmgpnn_increment,
+                     (c, ncol, nlay, self.ng_lw, p(self.tau_lw), None, None, p(self.smp_tau_lw), None, None)),
+                ]
+            elif not fused:
                 self.calls += [
                     ("increment_lw", L.rrtmgpnn_increment_bybnd,
                      (c, ncol, nlay, self.ng_lw, self.nb_lw, self._lims_lw, p(self.tau_lw), None, None,
                       p(self.cld_tau_lw), None, None)),
                 ]
+            elif self.mcica:
+                self.calls += [self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, None,
+                                               p(self.mask_bits_lw))]
+                lw_calls.insert(len(lw_calls) - 1,
+                                ("lw_mask", L.rrtmgpnn_solver_request_cloud_mask,
+                                 (c, self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
         if self.clrsky and not fused:
             # the clear solve before clouds%increment(atmos) (mo_rrtmgp_clr_all_sky.F90:161-172): the increment moves
             # from ahead of the Planck sources to between the two solver calls
@@ -316,11 +372,27 @@ class ClearSkyStep:
                       g_sw, p(self.mu0), p(self.alb), p(self.alb), p(self.sw_up_clr), p(self.sw_dn_clr),
                       p(self.sw_dir_clr))),
                 ]
-            if not fused:
+            if not fused and self.mcica:
+                self.calls += [
+                    self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, p(self.mask_sw), None),
+                    ("draw_samples_sw", L.rrtmgpnn_draw_samples,
+                     (c, self.ng_sw, nlay, ncol, self.nb_sw, self._lims_sw, p(self.mask_sw), p(self.cld_tau_sw),
+                      p(self.cld_ssa_sw), p(self.cld_g_sw), p(self.smp_tau_sw), p(self.smp_ssa_sw), p(self.smp_g_sw))),
+                    ("increment_sw", L.rrtmgpnn_increment,
+                     (c, ncol, nlay, self.ng_sw, p(self.tau_sw), p(self.ssa_sw), g_sw, p(self.smp_tau_sw),
+                      p(self.smp_ssa_sw), p(self.smp_g_sw))),
+                ]
+            elif not fused:
                 self.calls += [
                     ("increment_sw", L.rrtmgpnn_increment_bybnd,
                      (c, ncol, nlay, self.ng_sw, self.nb_sw, self._lims_sw, p(self.tau_sw), p(self.ssa_sw), g_sw,
                       p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw))),
+                ]
+            elif self.mcica:
+                self.calls += [
+                    self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, None, p(self.mask_bits_sw)),
+                    ("sw_mask", L.rrtmgpnn_solver_request_cloud_mask,
+                     (c, self.ng_sw, nlay, ncol, p(self.mask_bits_sw))),
                 ]
         if self.byband:
             self._lims_sw_bnd = int_array(self.kd_sw["band_lims_gpt"].ravel())
@@ -434,6 +506,28 @@ class ClearSkyStep:
             self.calls = [(n, f, ((self.ctx2.h,) + tuple(a[1:])) if n in SW_CHAIN else a) for n, f, a in self.calls]
             self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
         self.graph = None
+
+    def _mask_call(self, name, c, ngpt, randoms, mask, bits):
+        """The step's call of sampled_mask_max_ran, or _exp_ran when the step has an overlap parameter."""
+        head = (c, ngpt, self.nlay, self.ncol, randoms.data_ptr(), self.cloud_frac.data_ptr())
+        if self.overlap_param is None:
+            return (name, self.L.rrtmgpnn_sampled_mask_max_ran, head + (mask, bits))
+        return (name, self.L.rrtmgpnn_sampled_mask_exp_ran, head + (self.overlap_param.data_ptr(), mask, bits))
+
+    def mcica_randoms(self):
+        """The step-owned device buffers of a McICA step's random numbers, (randoms_lw, randoms_sw), (ncol, nlay, ngpt)
+        each: refill them (in place) between steps or graph replays."""
+        if not self.mcica:
+            raise ValueError("mcica_randoms: the step was built without mcica=")
+        return self.randoms_lw, self.randoms_sw
+
+    def set_mcica_randoms(self, randoms_lw=None, randoms_sw=None):
+        """Copy new random numbers into the step's buffers; complete on return."""
+        lw, sw = self.mcica_randoms()
+        for dst, src in ((lw, randoms_lw), (sw, randoms_sw)):
+            if src is not None:
+                dst.copy_(_t(src, self.dev) if not isinstance(src, torch.Tensor) else src)
+        torch.cuda.synchronize(self.dev)
 
     def _new_stream(self, priority=0):
         """A stream held by this step alone until close() (_lib.stream_acquire)."""
