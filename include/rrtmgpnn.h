@@ -461,7 +461,8 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
  *   cloud_mask (ngpt, nlay, ncol) bytes, 0 / 1: the logical mask of the class layer (draw_samples);
  *   mask_bits  (nw, nlay, ncol) 32-bit words, nw = ceil(ngpt / 32): bit g % 32 of word g / 32 is the mask of
  *     0-based g-point g, unused high bits zero: the form the solvers take (rrtmgpnn_solver_request_cloud_mask).
- * Either output may be NULL, not both.  Random numbers are the caller's, as in the reference (no generator here).
+ * Either output may be NULL, not both.  Random numbers are the caller's in these two entries, as in the reference; the
+ * _seeded entries further down draw them inside the kernel from a seed (Philox4x32-10) and read no randoms array.
  * rrtmgpnn_sampled_mask_max_ran (sampled_mask_max_ran, :125-192), maximum-random overlap: a cloudy layer
  *   (cloud_frac > 0) under a cloudy one reuses its random deviates, one under a clear layer takes new ones; the mask is
  *   the strict float32 comparison local_rand > (1 - cloud_frac); clear layers, and so every layer outside the first ..
@@ -479,6 +480,39 @@ int rrtmgpnn_sampled_mask_max_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int
 int rrtmgpnn_sampled_mask_exp_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
                                   const float *cloud_frac, const float *overlap_param, unsigned char *cloud_mask,
                                   unsigned int *mask_bits);
+/* ---- McICA with in-kernel random numbers (counter-based, seeded).  No reference counterpart: the reference leaves
+ * random numbers to the caller.
+ * Generator: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ * 0xBB67AE85, 10 rounds).  One call gives the four 32-bit words of 4 consecutive layers of one g-point of one column:
+ *   counter (g, l >> 2, (col0 + icol) mod 2^32, stream), key (seed & 0xffffffff, seed >> 32),
+ *   g the 0-based g-point, l the 0-based layer in array order, icol the 0-based column of the call; the random number
+ *   of layer l is word l & 3 as (float)(w >> 8) * 2^-24: exact in float32, in [0, 1 - 2^-24].
+ * So a column's numbers depend on (seed, stream, global column col0 + icol, layer, g-point) and on nothing else: the
+ * same clouds however the columns are split over ranks, chunks or blocks.  stream is a free word (LW / SW, time
+ * steps).  col0 + icol wraps modulo 2^32.
+ * rng: a caller-owned DEVICE array of 4 unsigned int, {seed low, seed high, stream, col0}.  The kernels read it on the
+ *   device, so a captured hipGraph replays with whatever the words hold at replay time.
+ * rrtmgpnn_mcica_rng_set fills rng on the context's stream and is complete on return.  It is a copy from the host:
+ *   do not capture it (rewrite the words between replays instead). */
+int rrtmgpnn_mcica_rng_set(rrtmgpnn_context *ctx, unsigned long long seed, unsigned int stream, unsigned int col0,
+                           unsigned int *rng);
+/* The generator's numbers as an array, randoms (ngpt, nlay, ncol) DEVICE: counter (g, l >> 2, (col0 + icol) mod 2^32,
+ * stream) as above, col0 + icol wrapping modulo 2^32; what the _seeded mask entries draw, for hosts that want the numbers
+ * themselves (rrtmgpnn_sampled_mask_* on this array give the _seeded entries' masks, bit for bit).  No reference
+ * counterpart.  ncol == 0 is OK. */
+int rrtmgpnn_mcica_randoms(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng, float *randoms);
+/* rrtmgpnn_sampled_mask_max_ran / _exp_ran with the random numbers drawn in the kernel: counter (g, l >> 2,
+ * (col0 + icol) mod 2^32, stream), key (seed low, seed high), word l & 3 (layout above); col0 + icol wraps modulo 2^32.
+ * No randoms array is read or allocated; only cloud_frac and overlap_param are streamed, and a group of 4 layers
+ * without a cloudy one draws nothing.  Everything after the deviate is the array entries' arithmetic, and their output
+ * rules hold: either output may be NULL, not both; overlap_param may be NULL for nlay 1.  No reference counterpart. */
+int rrtmgpnn_sampled_mask_max_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng,
+                                         const float *cloud_frac, unsigned char *cloud_mask, unsigned int *mask_bits);
+/* As above with exponential-random overlap: counter (g, l >> 2, (col0 + icol) mod 2^32, stream), col0 + icol wrapping
+ * modulo 2^32.  No reference counterpart. */
+int rrtmgpnn_sampled_mask_exp_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng,
+                                         const float *cloud_frac, const float *overlap_param,
+                                         unsigned char *cloud_mask, unsigned int *mask_bits);
 /* draw_samples / apply_cloud_mask (:36-120, :291-307): per g-point the band value (nbnd, nlay, ncol) where cloud_mask is
  * set, else 0, into (ngpt, nlay, ncol).  tau always; ssa and g when all of ssa_bnd, g_bnd, ssa, g are given (2str),
  * none of them for 1scl.  band_lims_gpt HOST (2, nbnd), every g-point in a band. */

@@ -1048,6 +1048,56 @@ int rrtmgpnn_sampled_mask_exp_ran(rrtmgpnn_context *ctx, int ngpt, int nlay, int
                       cloud_mask, mask_bits);
 }
 
+// the seeded route (no reference counterpart): the random numbers come from Philox4x32-10 inside the kernels
+int rrtmgpnn_mcica_rng_set(rrtmgpnn_context *ctx, unsigned long long seed, unsigned int stream, unsigned int col0,
+                           unsigned int *rng)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!rng) return fail(RRTMGPNN_ERR_ARGUMENT, "mcica_rng_set: rng is NULL");
+  const unsigned int words[4] = {(unsigned int)(seed & 0xffffffffull), (unsigned int)(seed >> 32), stream, col0};
+  // from this call's stack: complete on return
+  RRTMGPNN_HIP(hipMemcpyAsync(rng, words, sizeof(words), hipMemcpyHostToDevice, ctx->stream));
+  RRTMGPNN_HIP(hipStreamSynchronize(ctx->stream));
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_mcica_randoms(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng, float *randoms)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!rng) return fail(RRTMGPNN_ERR_ARGUMENT, "mcica_randoms: rng is NULL");
+  if (!randoms || ngpt < 1 || nlay < 1 || ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "mcica_randoms: bad argument");
+  return launch_mcica_randoms(ctx, ngpt, nlay, ncol, rng, randoms);
+}
+
+static int sampled_mask_seeded(rrtmgpnn_context *ctx, const char *who, bool exp_ran, int ngpt, int nlay, int ncol,
+                               const unsigned int *rng, const float *cloud_frac, const float *overlap_param,
+                               unsigned char *cloud_mask, unsigned int *mask_bits)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!rng) return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": rng is NULL");
+  if (!cloud_frac || ngpt < 1 || nlay < 1 || ncol < 0 || (exp_ran && nlay > 1 && !overlap_param))
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": bad argument");
+  if (!cloud_mask && !mask_bits)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": neither cloud_mask nor mask_bits is wanted");
+  return launch_sampled_mask_seeded(ctx, exp_ran, ngpt, nlay, ncol, rng, cloud_frac, overlap_param, cloud_mask,
+                                    mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_max_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng,
+                                         const float *cloud_frac, unsigned char *cloud_mask, unsigned int *mask_bits)
+{
+  return sampled_mask_seeded(ctx, "sampled_mask_max_ran_seeded", false, ngpt, nlay, ncol, rng, cloud_frac, nullptr,
+                             cloud_mask, mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_exp_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng,
+                                         const float *cloud_frac, const float *overlap_param,
+                                         unsigned char *cloud_mask, unsigned int *mask_bits)
+{
+  return sampled_mask_seeded(ctx, "sampled_mask_exp_ran_seeded", true, ngpt, nlay, ncol, rng, cloud_frac,
+                             overlap_param, cloud_mask, mask_bits);
+}
+
 int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int nbnd, const int *band_lims_gpt,
                           const unsigned char *cloud_mask, const float *tau_bnd, const float *ssa_bnd,
                           const float *g_bnd, float *tau, float *ssa, float *g)

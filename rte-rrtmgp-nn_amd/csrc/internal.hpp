@@ -198,6 +198,10 @@ int launch_delta_scale(rrtmgpnn_context *ctx, long long n, float *tau, float *ss
 // apply_cloud_mask
 int launch_sampled_mask(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay, int ncol, const float *randoms,
                         const float *cloud_frac, const float *overlap, unsigned char *mask, uint32_t *bits);
+// the seeded route: rng is the four device words {seed low, seed high, stream, col0} (rrtmgpnn_mcica_rng_set)
+int launch_sampled_mask_seeded(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay, int ncol, const uint32_t *rng,
+                               const float *cloud_frac, const float *overlap, unsigned char *mask, uint32_t *bits);
+int launch_mcica_randoms(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const uint32_t *rng, float *randoms);
 int launch_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const BandArgs &bands,
                         const unsigned char *mask, const float *tau_bnd, const float *ssa_bnd, const float *g_bnd,
                         float *tau, float *ssa, float *g);

@@ -4,14 +4,17 @@
 //                          every (g-point, layer, column) from the caller's random numbers, as a byte mask for the class
 //                          layer and / or a packed mask (one bit per g-point) for the solvers' fused increment
 //  * draw_samples_kernel : apply_cloud_mask (:291-307): the band value where the mask is set, else 0
+//  * the seeded route (no reference counterpart): sampled_mask_kernel<kExp, true> draws its random numbers itself, and
+//    mcica_randoms_kernel writes the same stream out as an array (the generator is described below)
 //
 // The extension predates this fork's layout (as mo_heating_rates does); here randoms and both masks are
 // (ngpt, nlay, ncol), cloud_frac (nlay, ncol) and overlap_param (nlay-1, ncol), first index fastest.
 //
 // Mask kernel: one block per column, lane = g-point (striding by the block when ngpt exceeds it).  The layers are
 // walked in array order as the reference walks them, the carried random deviate in a register; the only array
-// streamed is randoms, kMaskPf layers of it in flight per lane.  The reference's first / last cloudy layer bounds
-// need no search: a layer outside them is a clear layer, and a clear layer's mask is false either way.  That is also
+// streamed is randoms, kMaskPf layers of it in flight per lane (the seeded instances stream none).  The reference's
+// first / last cloudy layer bounds need no search: a layer outside them is a clear layer, and a clear layer's mask is
+// false either way.  That is also
 // where this kernel departs from the reference's exp_ran, which never assigns the mask of a clear layer lying between
 // cloudy ones (its `if` has no `else`, :261-279): here those elements are false, the evident meaning and what max_ran
 // does.  The file is compiled with -ffp-contract=off: the comparison is the reference's strict
@@ -20,40 +23,97 @@
 #include "internal.hpp"
 
 #include <cmath>
+#include <type_traits>
 
 namespace rrtmgpnn {
 
 static constexpr int kMaskPf = 4;      // layers of randoms in flight per lane
 static constexpr int kMaskMaxT = 256;  // lanes per column block
 
-template <bool kExp>
+// The seeded route's generator: Philox4x32-10 (Salmon et al., SC'11), a counter-based generator, so a number depends on
+// its counter and key alone and neither on the launch nor on which other numbers were drawn.  One call gives the four
+// words of kMaskPf = 4 consecutive layers of one g-point of one column:
+//   counter (g, l >> 2, (col0 + icol) mod 2^32, stream), key (seed low, seed high); layer l takes word l & 3.
+// Each round is two 32 x 32 -> 64 bit products, written as 64-bit products so that both halves come from one
+// v_mad_u64_u32 (DESIGN.md §3 has what the compiler chose), and three exclusive-ors per pair.
+static_assert(kMaskPf == 4, "one Philox4x32 call per group of kMaskPf layers");
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&w)[4])
+{
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    if (r > 0) {  // the key is bumped before rounds 2..10
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+  }
+  w[0] = c0;
+  w[1] = c1;
+  w[2] = c2;
+  w[3] = c3;
+}
+
+// 24 random bits -> [0, 1 - 2^-24]: both the conversion and the product are exact in float32
+__device__ __forceinline__ float philox_unit(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }
+
+// kSeeded: `src` is rng, the four device words {seed low, seed high, stream, col0}, instead of randoms; the kMaskPf
+// layers of prefetched randoms become one Philox call per lane per group of kMaskPf layers, skipped by the whole block
+// where none of the group's layers is cloudy (cloud_frac is uniform over the block and a deviate is consumed only at a
+// cloudy layer, so the skip is exact).  Everything after the deviate is the same statements.
+template <bool kExp, bool kSeeded = false>
 __global__ void __launch_bounds__(kMaskMaxT)
-    sampled_mask_kernel(int ngpt, int nlay, const float *__restrict__ randoms, const float *__restrict__ cloud_frac,
-                        const float *__restrict__ overlap, unsigned char *__restrict__ mask,
-                        uint32_t *__restrict__ bits)
+    sampled_mask_kernel(int ngpt, int nlay, const std::conditional_t<kSeeded, uint32_t, float> *__restrict__ src,
+                        const float *__restrict__ cloud_frac, const float *__restrict__ overlap,
+                        unsigned char *__restrict__ mask, uint32_t *__restrict__ bits)
 {
   const int icol = blockIdx.x, nw = (ngpt + 31) / 32;
   const float *cf = cloud_frac + (size_t)nlay * icol;
   const float *ov = kExp ? overlap + (size_t)(nlay - 1) * icol : nullptr;
   const size_t col = (size_t)nlay * icol;  // this column's first (layer, column) row
+  uint32_t k0 = 0, k1 = 0, stream = 0, gcol = 0;  // seeded: rng, read once per block (block-uniform loads)
+  if constexpr (kSeeded) {
+    k0 = src[0];
+    k1 = src[1];
+    stream = src[2];
+    gcol = src[3] + (uint32_t)icol;  // the global column, modulo 2^32
+  }
   for (int g0 = 0; g0 < ngpt; g0 += blockDim.x) {
     const int g = g0 + (int)threadIdx.x;
     // a wave wholly past the last g-point has nothing to do (wave-uniform: the ballot below sees whole waves)
     if ((g & ~63) >= ngpt) continue;
     const bool on = g < ngpt;
     const int gc = on ? g : ngpt - 1;  // clamped g-point for unconditional loads
-    const float *rc = randoms + (size_t)ngpt * col + gc;
+    const float *rc = nullptr;
     float pr[kMaskPf];
+    if constexpr (!kSeeded) {
+      rc = src + (size_t)ngpt * col + gc;
 #pragma unroll
-    for (int p = 0; p < kMaskPf; p++) pr[p] = rc[(size_t)ngpt * min(p, nlay - 1)];
+      for (int p = 0; p < kMaskPf; p++) pr[p] = rc[(size_t)ngpt * min(p, nlay - 1)];
+    }
     float local = 0.0f;  // local_rands(igpt)
     bool prev = false;   // cloud_mask_layer(ilay-1)
     for (int l0 = 0; l0 < nlay; l0 += kMaskPf) {
+      if constexpr (kSeeded) {
+        bool any = false;  // block-uniform
+#pragma unroll
+        for (int p = 0; p < kMaskPf; p++) any = any || cf[min(l0 + p, nlay - 1)] > 0.0f;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if (any) philox4x32_10((uint32_t)g, (uint32_t)(l0 >> 2), gcol, stream, k0, k1, w);
+#pragma unroll
+        for (int p = 0; p < kMaskPf; p++) pr[p] = philox_unit(w[p]);
+      }
 #pragma unroll
       for (int p = 0; p < kMaskPf; p++) {
         const int l = l0 + p;
         const float r = pr[p];
-        pr[p] = rc[(size_t)ngpt * min(l + kMaskPf, nlay - 1)];
+        if constexpr (!kSeeded) pr[p] = rc[(size_t)ngpt * min(l + kMaskPf, nlay - 1)];
         // the last chunk's steps past nlay only issued their (clamped) load
         if (l < nlay) {
           const float frac = cf[l];
@@ -99,6 +159,56 @@ int launch_sampled_mask(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay,
     hipLaunchKernelGGL(sampled_mask_kernel<false>, dim3(ncol), dim3(threads), 0, ctx->stream, ngpt, nlay, randoms,
                        cloud_frac, overlap, mask, bits);
   RRTMGPNN_LAUNCH_CHECK("sampled_mask_kernel");
+  return RRTMGPNN_OK;
+}
+
+int launch_sampled_mask_seeded(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay, int ncol, const uint32_t *rng,
+                               const float *cloud_frac, const float *overlap, unsigned char *mask, uint32_t *bits)
+{
+  if (ncol == 0) return RRTMGPNN_OK;
+  const int threads = std::min((ngpt + 63) / 64 * 64, kMaskMaxT);
+  if (exp_ran)
+    hipLaunchKernelGGL((sampled_mask_kernel<true, true>), dim3(ncol), dim3(threads), 0, ctx->stream, ngpt, nlay, rng,
+                       cloud_frac, overlap, mask, bits);
+  else
+    hipLaunchKernelGGL((sampled_mask_kernel<false, true>), dim3(ncol), dim3(threads), 0, ctx->stream, ngpt, nlay, rng,
+                       cloud_frac, overlap, mask, bits);
+  RRTMGPNN_LAUNCH_CHECK("sampled_mask_kernel (seeded)");
+  return RRTMGPNN_OK;
+}
+
+// The seeded route's numbers as an array (ngpt, nlay, ncol): blocks stride over (layer group, column) pairs, lane =
+// g-point (striding by the block above kMaskMaxT g-points), one Philox call per lane and group, each of its up to
+// kMaskPf rows a contiguous store of ngpt values.
+__global__ void __launch_bounds__(kMaskMaxT)
+    mcica_randoms_kernel(int ngpt, int nlay, long long nblk, const uint32_t *__restrict__ rng,
+                         float *__restrict__ randoms)
+{
+  const int ngrp = (nlay + kMaskPf - 1) / kMaskPf;
+  const uint32_t k0 = rng[0], k1 = rng[1], stream = rng[2], col0 = rng[3];
+  for (long long b = blockIdx.x; b < nblk; b += gridDim.x) {
+    const long long icol = b / ngrp;
+    const int l0 = (int)(b - icol * ngrp) * kMaskPf;
+    float *out = randoms + (size_t)ngpt * ((size_t)nlay * icol + l0);
+    for (int g = threadIdx.x; g < ngpt; g += blockDim.x) {
+      uint32_t w[4];
+      philox4x32_10((uint32_t)g, (uint32_t)(l0 >> 2), col0 + (uint32_t)icol, stream, k0, k1, w);
+#pragma unroll
+      for (int p = 0; p < kMaskPf; p++)
+        if (l0 + p < nlay) out[(size_t)ngpt * p + g] = philox_unit(w[p]);
+    }
+  }
+}
+
+int launch_mcica_randoms(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const uint32_t *rng, float *randoms)
+{
+  const long long nblk = (long long)((nlay + kMaskPf - 1) / kMaskPf) * ncol;
+  if (nblk == 0) return RRTMGPNN_OK;
+  const int threads = std::min((ngpt + 63) / 64 * 64, kMaskMaxT);
+  const long long cap = (long long)ctx->num_cus * (2048 / threads);
+  hipLaunchKernelGGL(mcica_randoms_kernel, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(threads), 0, ctx->stream,
+                     ngpt, nlay, nblk, rng, randoms);
+  RRTMGPNN_LAUNCH_CHECK("mcica_randoms_kernel");
   return RRTMGPNN_OK;
 }
 

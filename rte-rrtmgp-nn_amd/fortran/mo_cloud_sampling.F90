@@ -12,10 +12,16 @@
 ! randoms, cloud_frac and overlap_param are copied to the device by every call (a host program refills them).
 ! The value checks follow check_values (rte_config_checks) as the other value checks of this layer do, with the
 ! reference's messages -- exp_ran's carry max_ran's prefix there too.
+! No reference counterpart: mcica_randoms, sampled_mask_max_ran_seeded and sampled_mask_exp_ran_seeded take
+! (seed, stream, col0) in place of randoms and draw the numbers on the device (Philox4x32-10; include/rrtmgpnn.h has the
+! counter layout): a column's numbers depend on the seed, the stream, its global index col0 + icol (0-based, modulo
+! 2**32), the layer and the g-point alone.  seed is integer(int64) (its bit pattern is the 64-bit seed); stream and col0
+! are integer(int64) holding 32-bit words (taken modulo 2**32).
 ! Quirk (SURVEY.md App. B, B-13): the reference's exp_ran never assigns the mask of a clear layer lying between cloudy
 ! ones; here those elements are .false., the evident meaning and what max_ran does.
 module mo_cloud_sampling
   use, intrinsic :: iso_c_binding
+  use, intrinsic :: iso_fortran_env, only: int64
   use mo_rte_kind,          only: wp, wl
   use mo_rte_rrtmgp_config, only: check_values
   use mo_optical_props,     only: ty_optical_props_arry, ty_optical_props_1scl, ty_optical_props_2str
@@ -23,6 +29,7 @@ module mo_cloud_sampling
   implicit none
   private
   public :: draw_samples, sampled_mask_max_ran, sampled_mask_exp_ran, cloud_mask_update_host, cloud_mask_delete
+  public :: mcica_randoms, sampled_mask_max_ran_seeded, sampled_mask_exp_ran_seeded
 contains
   ! the device copy of a logical(wl) mask of n elements (one byte each) in the context's data environment
   function mask_present(m, n, mode) result(d)
@@ -135,6 +142,126 @@ contains
                                c_null_ptr), "sampled_mask_exp_ran")
     call dev_release(d_r); call dev_release(d_cf); call dev_release(d_ov)
   end function sampled_mask_exp_ran
+
+  ! the low 32 bits of v as a C unsigned int's bit pattern
+  pure function u32(v) result(w)
+    integer(int64), intent(in) :: v
+    integer(c_int) :: w
+    integer(int64) :: m
+    m = iand(v, 4294967295_int64)
+    if (m >= 2147483648_int64) m = m - 4294967296_int64
+    w = int(m, c_int)
+  end function u32
+
+  ! a pool buffer holding the four rng words {seed low, seed high, stream, col0}
+  function rng_stage(seed, stream, col0, error_msg) result(d)
+    integer(int64), intent(in) :: seed, stream, col0
+    character(len=128), intent(out) :: error_msg
+    type(c_ptr) :: d
+    d = dev_scratch(4_c_long_long)
+    error_msg = rrtmgpnn_check(c_rrtmgpnn_mcica_rng_set(rrtmgpnn_ctx(), int(seed, c_long_long), u32(stream), u32(col0), &
+                               d), "mcica_rng_set")
+  end function rng_stage
+
+  function mcica_randoms(seed, stream, col0, randoms) result(error_msg)
+    integer(int64),                intent(in ) :: seed, stream, col0
+    real(wp), dimension(:,:,:),    intent(out) :: randoms ! ngpt, nlay, ncol
+    character(len=128) :: error_msg
+    integer :: ncol, nlay, ngpt
+    integer(c_long_long) :: n
+    type(c_ptr) :: d_rng, d_r
+
+    error_msg = ""
+    ngpt = size(randoms, 1); nlay = size(randoms, 2); ncol = size(randoms, 3)
+    n = int(ngpt, c_long_long) * nlay * ncol
+    if (n == 0) return
+    d_rng = rng_stage(seed, stream, col0, error_msg)
+    if (error_msg == "") then
+      d_r = dev_scratch(n)
+      error_msg = rrtmgpnn_check(c_rrtmgpnn_mcica_randoms(rrtmgpnn_ctx(), ngpt, nlay, ncol, d_rng, d_r), "mcica_randoms")
+      if (error_msg == "") call dev_copy_out(randoms, d_r, n)
+      call rrtmgpnn_sync(error_msg, "mcica_randoms")
+      call dev_release(d_r)
+    end if
+    call dev_release(d_rng)
+  end function mcica_randoms
+
+  function sampled_mask_max_ran_seeded(seed, stream, col0, cloud_frac, cloud_mask) result(error_msg)
+    integer(int64),                intent(in ) :: seed, stream, col0
+    real(wp),    dimension(:,:),   intent(in ) :: cloud_frac ! nlay, ncol
+    logical(wl), dimension(:,:,:), intent(out) :: cloud_mask ! ngpt, nlay, ncol
+    character(len=128) :: error_msg
+    integer :: ncol, nlay, ngpt
+    integer(c_long_long) :: n
+    type(c_ptr) :: d_rng, d_cf, d_m
+
+    error_msg = ""
+    ngpt = size(cloud_mask, 1); nlay = size(cloud_frac, 1); ncol = size(cloud_frac, 2)
+    if (any([nlay, ncol] /= [size(cloud_mask, 2), size(cloud_mask, 3)])) then
+      error_msg = "sampled_mask_max_ran: sizes of randoms(ngpt,nlay,ncol) and cloud_mask(ncol,nlay,ngpt) are inconsistent"
+      return
+    end if
+    if (check_values) then
+      if (any(cloud_frac > 1._wp) .or. any(cloud_frac < 0._wp)) then
+        error_msg = "sampled_mask_max_ran: cloud fraction values out of range [0,1]"
+        return
+      end if
+    end if
+    n = int(ngpt, c_long_long) * nlay * ncol
+    d_rng = rng_stage(seed, stream, col0, error_msg)
+    if (error_msg == "") then
+      d_cf = dev_stage(cloud_frac, int(nlay, c_long_long) * ncol)
+      d_m  = mask_present(cloud_mask, n, PRESENT_WRITE)
+      error_msg = rrtmgpnn_check(c_rrtmgpnn_sampled_mask_max_ran_seeded(rrtmgpnn_ctx(), ngpt, nlay, ncol, d_rng, d_cf, &
+                                 d_m, c_null_ptr), "sampled_mask_max_ran_seeded")
+      call dev_release(d_cf)
+    end if
+    call dev_release(d_rng)
+  end function sampled_mask_max_ran_seeded
+
+  function sampled_mask_exp_ran_seeded(seed, stream, col0, cloud_frac, overlap_param, cloud_mask) result(error_msg)
+    integer(int64),                intent(in ) :: seed, stream, col0
+    real(wp),    dimension(:,:),   intent(in ) :: cloud_frac    ! nlay, ncol
+    real(wp),    dimension(:,:),   intent(in ) :: overlap_param ! nlay-1, ncol
+    logical(wl), dimension(:,:,:), intent(out) :: cloud_mask    ! ngpt, nlay, ncol
+    character(len=128) :: error_msg
+    integer :: ncol, nlay, ngpt
+    integer(c_long_long) :: n
+    type(c_ptr) :: d_rng, d_cf, d_ov, d_m
+
+    error_msg = ""
+    ngpt = size(cloud_mask, 1); nlay = size(cloud_frac, 1); ncol = size(cloud_frac, 2)
+    if (any([nlay - 1, ncol] /= [size(overlap_param, 1), size(overlap_param, 2)])) then
+      error_msg = "sampled_mask_max_ran: sizes of randoms(ngpt,nlay,ncol) and overlap_param(ncol,nlay-1) are inconsistent"
+      return
+    end if
+    if (any([nlay, ncol] /= [size(cloud_mask, 2), size(cloud_mask, 3)])) then
+      error_msg = "sampled_mask_max_ran: sizes of randoms(ngpt,nlay,ncol) and cloud_mask(ncol,nlay,ngpt) are inconsistent"
+      return
+    end if
+    if (check_values) then
+      if (any(cloud_frac > 1._wp) .or. any(cloud_frac < 0._wp)) then
+        error_msg = "sampled_mask_max_ran: cloud fraction values out of range [0,1]"
+        return
+      end if
+      if (any(overlap_param > 1._wp) .or. any(overlap_param < -1._wp)) then
+        error_msg = "sampled_mask_max_ran: overlap_param values out of range [-1,1]"
+        return
+      end if
+    end if
+    n = int(ngpt, c_long_long) * nlay * ncol
+    d_rng = rng_stage(seed, stream, col0, error_msg)
+    if (error_msg == "") then
+      d_cf = dev_stage(cloud_frac, int(nlay, c_long_long) * ncol)
+      d_ov = c_null_ptr
+      if (nlay > 1) d_ov = dev_stage(overlap_param, int(nlay - 1, c_long_long) * ncol)
+      d_m  = mask_present(cloud_mask, n, PRESENT_WRITE)
+      error_msg = rrtmgpnn_check(c_rrtmgpnn_sampled_mask_exp_ran_seeded(rrtmgpnn_ctx(), ngpt, nlay, ncol, d_rng, d_cf, &
+                                 d_ov, d_m, c_null_ptr), "sampled_mask_exp_ran_seeded")
+      call dev_release(d_cf); call dev_release(d_ov)
+    end if
+    call dev_release(d_rng)
+  end function sampled_mask_exp_ran_seeded
 
   function draw_samples(cloud_mask, clouds, clouds_sampled) result(error_msg)
     logical(wl), dimension(:,:,:), intent(in   ) :: cloud_mask     ! ngpt, nlay, ncol

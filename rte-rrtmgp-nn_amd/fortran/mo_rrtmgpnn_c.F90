@@ -21,6 +21,8 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
   public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
             c_rrtmgpnn_draw_samples
+  public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
+            c_rrtmgpnn_sampled_mask_exp_ran_seeded
   public :: c_rrtmgpnn_present, c_rrtmgpnn_present_update_host, c_rrtmgpnn_present_delete  ! masks (mo_cloud_sampling)
   public :: c_rrtmgpnn_network_load, c_rrtmgpnn_compute_nn_inputs, c_rrtmgpnn_get_col_dry, &
             c_rrtmgpnn_interpolate_tlev, c_rrtmgpnn_predict_nn_lw, c_rrtmgpnn_predict_nn_sw, &
@@ -320,6 +322,32 @@ module mo_rrtmgpnn_c
         cloud_mask, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_exp_ran")
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, randoms, cloud_frac, overlap_param, cloud_mask, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    ! McICA with in-kernel random numbers: rng is 4 device words {seed low, seed high, stream, col0}; seed, stream and
+    ! col0 are unsigned in C (the bit patterns are passed)
+    integer(c_int) function c_rrtmgpnn_mcica_rng_set(ctx, seed, stream, col0, rng) bind(C, name="rrtmgpnn_mcica_rng_set")
+      import :: c_int, c_long_long, c_ptr
+      type(c_ptr), value :: ctx, rng
+      integer(c_long_long), value :: seed
+      integer(c_int), value :: stream, col0
+    end function
+    integer(c_int) function c_rrtmgpnn_mcica_randoms(ctx, ngpt, nlay, ncol, rng, randoms) &
+        bind(C, name="rrtmgpnn_mcica_randoms")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rng, randoms
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_max_ran_seeded(ctx, ngpt, nlay, ncol, rng, cloud_frac, cloud_mask, &
+        mask_bits) bind(C, name="rrtmgpnn_sampled_mask_max_ran_seeded")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rng, cloud_frac, cloud_mask, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_exp_ran_seeded(ctx, ngpt, nlay, ncol, rng, cloud_frac, &
+        overlap_param, cloud_mask, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_exp_ran_seeded")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rng, cloud_frac, overlap_param, cloud_mask, mask_bits
       integer(c_int), value :: ngpt, nlay, ncol
     end function
     integer(c_int) function c_rrtmgpnn_draw_samples(ctx, ngpt, nlay, ncol, nbnd, band_lims_gpt, cloud_mask, tau_bnd, &

@@ -101,6 +101,10 @@ SIGNATURES = {
     "rrtmgpnn_solver_request_cloud_mask": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
     "rrtmgpnn_sampled_mask_max_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_sampled_mask_exp_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_mcica_rng_set": (c_int, [c_vp, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, c_vp]),
+    "rrtmgpnn_mcica_randoms": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "rrtmgpnn_sampled_mask_max_ran_seeded": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_sampled_mask_exp_ran_seeded": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_draw_samples": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp]),
     "rrtmgpnn_sum_byband": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp]),

@@ -9,7 +9,10 @@ Functions RETURN the reference's error message ('' on success).  The extension p
 as torch tensors in C order, randoms and cloud_mask are (ncol, nlay, ngpt), cloud_frac (ncol, nlay) and overlap_param
 (ncol, nlay-1).  cloud_mask is a uint8 (or bool) tensor of 0 / 1; mask_bits, an int32 tensor (ncol, nlay,
 ceil(ngpt / 32)), is the packed form the solvers take (rrtmgpnn_solver_request_cloud_mask): bit g % 32 of word g / 32.
-Random numbers are the caller's, as in the reference.  The value checks (cloud_frac in [0, 1], overlap_param in
+Random numbers are the caller's, as in the reference; the *_seeded functions and mcica_randoms (no reference
+counterpart) draw them on the device from (seed, stream, col0) with Philox4x32-10 (include/rrtmgpnn.h has the counter
+layout): a column's numbers depend on the seed, the stream, its global index col0 + icol, the layer and the g-point
+alone.  The value checks (cloud_frac in [0, 1], overlap_param in
 [-1, 1]) follow api.check_values (rte_config_checks), as the other value checks of this layer do; extents are always
 checked.  Quirk: a clear layer between cloudy ones is false in both masks; the reference's exp_ran
 leaves it unassigned.
@@ -81,6 +84,96 @@ def sampled_mask_exp_ran(randoms, cloud_frac, overlap_param, cloud_mask=None, ma
                                                    _p(overlap_param) if nlay > 1 else None, _p(cloud_mask),
                                                    _p(mask_bits)), "sampled_mask_exp_ran")
     return ""
+
+
+def _rng(ctx, seed, stream, col0):
+    """The context's 4-word device buffer {seed low, seed high, stream, col0}, refilled (rrtmgpnn_mcica_rng_set: on the
+    context's stream, after the work already issued there, and complete on return)."""
+    import torch
+    buf = getattr(ctx, "_mcica_rng", None)
+    if buf is None:
+        buf = ctx._mcica_rng = torch.zeros(4, dtype=torch.int32, device=torch.device("cuda", ctx.device))
+    check(_lib.lib().rrtmgpnn_mcica_rng_set(ctx.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF,
+                                            int(col0) & 0xFFFFFFFF, _p(buf)), "mcica_rng_set")
+    return buf
+
+
+def mcica_randoms(seed, stream, col0, randoms):
+    """Fill randoms (ncol, nlay, ngpt) float32 with the numbers the *_seeded mask functions draw for the columns
+    col0 .. col0 + ncol - 1 (modulo 2^32)."""
+    if randoms.dim() != 3 or randoms.element_size() != 4 or not randoms.is_floating_point():
+        return "mcica_randoms: randoms is not a float32 (ncol, nlay, ngpt) array"
+    if not randoms.is_contiguous():
+        return "mcica_randoms: arrays must be contiguous"
+    ncol, nlay, ngpt = randoms.shape
+    ctx = context(randoms.device.index)
+    check(_lib.lib().rrtmgpnn_mcica_randoms(ctx.h, ngpt, nlay, ncol, _p(_rng(ctx, seed, stream, col0)), _p(randoms)),
+          "mcica_randoms")
+    return ""
+
+
+def _seeded_extents(who, cloud_frac, cloud_mask, mask_bits, ngpt):
+    """_mask_args without randoms, with the reference's messages: (message, (ncol, nlay, ngpt)).  ngpt is cloud_mask's
+    last extent; with mask_bits alone it must be given (the words round it up)."""
+    pre = "sampled_mask_max_ran: sizes of randoms(ngpt,nlay,ncol) and "
+    if cloud_mask is None and mask_bits is None:
+        return "%s: neither cloud_mask nor mask_bits given" % who, None
+    if cloud_frac.dim() != 2:
+        return pre + "cloud_frac(ncol,nlay) are inconsistent", None
+    ncol, nlay = cloud_frac.shape
+    if cloud_mask is not None:
+        if cloud_mask.dim() != 3 or tuple(cloud_mask.shape[:2]) != (ncol, nlay) or cloud_mask.element_size() != 1 \
+                or (ngpt is not None and int(ngpt) != cloud_mask.shape[2]):
+            return pre + "cloud_mask(ncol,nlay,ngpt) are inconsistent", None
+        ngpt = cloud_mask.shape[2]
+    elif ngpt is None:
+        return "%s: ngpt is needed with mask_bits alone" % who, None
+    ngpt = int(ngpt)
+    if mask_bits is not None and (tuple(mask_bits.shape) != (ncol, nlay, (ngpt + 31) // 32)
+                                  or mask_bits.element_size() != 4):
+        return "%s: mask_bits is not (ncol, nlay, ceil(ngpt/32)) 32-bit words" % who, None
+    return "", (ncol, nlay, ngpt)
+
+
+def _seeded(who, exp_ran, seed, stream, col0, cloud_frac, overlap_param, cloud_mask, mask_bits, ngpt):
+    e, ext = _seeded_extents(who, cloud_frac, cloud_mask, mask_bits, ngpt)
+    if e:
+        return e
+    ncol, nlay, ngpt = ext
+    if exp_ran and (overlap_param.dim() != 2 or tuple(overlap_param.shape) != (ncol, nlay - 1)):
+        return "sampled_mask_max_ran: sizes of randoms(ngpt,nlay,ncol) and overlap_param(ncol,nlay-1) are inconsistent"
+    e = _frac_check(cloud_frac)
+    if e:
+        return e
+    if exp_ran and api.check_values and (bool((overlap_param > 1).any()) or bool((overlap_param < -1).any())):
+        return "sampled_mask_max_ran: overlap_param values out of range [-1,1]"
+    if not _contig(cloud_frac, overlap_param, cloud_mask, mask_bits):
+        return "%s: arrays must be contiguous" % who
+    ctx = context(cloud_frac.device.index)
+    rng = _rng(ctx, seed, stream, col0)
+    L = _lib.lib()
+    if exp_ran:
+        check(L.rrtmgpnn_sampled_mask_exp_ran_seeded(ctx.h, ngpt, nlay, ncol, _p(rng), _p(cloud_frac),
+                                                     _p(overlap_param) if nlay > 1 else None, _p(cloud_mask),
+                                                     _p(mask_bits)), who)
+    else:
+        check(L.rrtmgpnn_sampled_mask_max_ran_seeded(ctx.h, ngpt, nlay, ncol, _p(rng), _p(cloud_frac), _p(cloud_mask),
+                                                     _p(mask_bits)), who)
+    return ""
+
+
+def sampled_mask_max_ran_seeded(seed, stream, col0, cloud_frac, cloud_mask=None, mask_bits=None, ngpt=None):
+    """sampled_mask_max_ran with the random numbers drawn in the kernel from (seed, stream, col0); ngpt: the g-point
+    count when only mask_bits is given."""
+    return _seeded("sampled_mask_max_ran_seeded", False, seed, stream, col0, cloud_frac, None, cloud_mask, mask_bits,
+                   ngpt)
+
+
+def sampled_mask_exp_ran_seeded(seed, stream, col0, cloud_frac, overlap_param, cloud_mask=None, mask_bits=None,
+                                ngpt=None):
+    """sampled_mask_exp_ran with the random numbers drawn in the kernel from (seed, stream, col0)."""
+    return _seeded("sampled_mask_exp_ran_seeded", True, seed, stream, col0, cloud_frac, overlap_param, cloud_mask,
+                   mask_bits, ngpt)
 
 
 def draw_samples(cloud_mask, clouds, clouds_sampled):

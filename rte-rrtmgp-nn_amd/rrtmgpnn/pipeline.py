@@ -31,7 +31,10 @@ added as a two-stream increment; the SW solver then sees a non-zero asymmetry pa
 mcica={...} (with clouds) samples the band clouds per g-point with McICA (extensions/cloud_optics/mo_cloud_sampling.F90)
 from a cloud fraction per layer and the caller's random numbers.  Fused, each chain runs the mask kernel into a packed
 mask and arms it (rrtmgpnn_solver_request_cloud_mask) for the fused solver call, which switches the band increment per
-g-point; unfused, the class layer's mask -> draw_samples -> increment sequence.
+g-point; unfused, the class layer's mask -> draw_samples -> increment sequence.  With "seed" in place of the
+"randoms_*" arrays the mask kernels draw the numbers themselves (Philox4x32-10, include/rrtmgpnn.h): the step then holds
+no randoms arrays, only two 4-word device buffers {seed low, seed high, stream, col0} (set_mcica_seed), and a column's
+clouds depend on (seed, stream, col0 + its index) alone, however the columns are split over steps.
 
 clrsky=True (with clouds) also produces the clear-sky fluxes of the same columns, as rte_lw / rte_sw of
 extensions/mo_rrtmgp_clr_all_sky.F90 do: gas optics once, a clear solve, clouds%increment, the all-sky solve.  Fused,
@@ -49,7 +52,8 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
-            "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask"}
+            "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask",
+            "mcica_randoms_sw"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
@@ -104,8 +108,13 @@ class ClearSkyStep:
         # stream-overlap flag.)  Fused: per chain the mask kernel (packed bits), rrtmgpnn_solver_request_cloud_mask and
         # the fused solver call of the all-sky step; fused=False: the class layer's sequence, mask -> draw_samples ->
         # increment at g-point resolution.  The randoms are step-owned device buffers (mcica_randoms()) the caller
-        # refills between steps or replays (set_mcica_randoms).  None: today's call list
+        # refills between steps or replays (set_mcica_randoms).  With "seed": int (and optionally "stream_lw": 0,
+        # "stream_sw": 1, "col0": 0) in place of "randoms_lw" / "randoms_sw" the numbers are drawn in the mask kernels
+        # (the _seeded entries) from two step-owned 4-word device buffers, which set_mcica_seed rewrites between steps
+        # or replays; fused=False then fills scratch arrays with rrtmgpnn_mcica_randoms ahead of the same sequence.
+        # None: today's call list
         self.mcica = mcica is not None
+        self.seeded = False
         if self.mcica and clouds is None:
             raise ValueError("mcica: sampled clouds need clouds=(lwp, iwp, rel, rei)")
         if self.mcica and (clrsky or byband):
@@ -184,7 +193,19 @@ class ClearSkyStep:
             self.cloud_frac = _t(mcica["cloud_frac"], dev)
             ov = mcica.get("overlap_param")
             self.overlap_param = None if ov is None else _t(ov, dev)
-            self.randoms_lw, self.randoms_sw = _t(mcica["randoms_lw"], dev), _t(mcica["randoms_sw"], dev)
+            self.seeded = mcica.get("seed") is not None
+            if self.seeded:
+                if mcica.get("randoms_lw") is not None or mcica.get("randoms_sw") is not None:
+                    raise ValueError("mcica: seed together with randoms_lw / randoms_sw")
+                self._seed = {"seed": int(mcica["seed"]), "stream_lw": int(mcica.get("stream_lw", 0)),
+                              "stream_sw": int(mcica.get("stream_sw", 1)), "col0": int(mcica.get("col0", 0))}
+                self.rng_lw, self.rng_sw = (torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(2))
+                self.set_mcica_seed()
+                # unfused: scratch arrays rrtmgpnn_mcica_randoms fills every step
+                self.randoms_lw = None if fused else f(ncol, nlay, self.ng_lw)
+                self.randoms_sw = None if fused else f(ncol, nlay, self.ng_sw)
+            else:
+                self.randoms_lw, self.randoms_sw = _t(mcica["randoms_lw"], dev), _t(mcica["randoms_sw"], dev)
             want = {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, self.ng_lw),
                     "randoms_sw": (ncol, nlay, self.ng_sw), "overlap_param": (ncol, nlay - 1)}
             for k, t in (("cloud_frac", self.cloud_frac), ("randoms_lw", self.randoms_lw),
@@ -293,7 +314,7 @@ class ClearSkyStep:
             ]
             if not fused and self.mcica:
                 # the class layer's McICA sequence: mask, draw_samples, increment at g-point resolution
-                self.calls += [
+                self.calls += self._randoms_call("lw", c) + [
                     self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, p(self.mask_lw), None),
                     ("draw_samples_lw", L.rrtmgpnn_draw_samples,
                      (c, self.ng_lw, nlay, ncol, self.nb_lw, self._lims_lw, p(self.mask_lw), p(self.cld_tau_lw), None,
@@ -373,7 +394,7 @@ class ClearSkyStep:
                       p(self.sw_dir_clr))),
                 ]
             if not fused and self.mcica:
-                self.calls += [
+                self.calls += self._randoms_call("sw", c) + [
                     self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, p(self.mask_sw), None),
                     ("draw_samples_sw", L.rrtmgpnn_draw_samples,
                      (c, self.ng_sw, nlay, ncol, self.nb_sw, self._lims_sw, p(self.mask_sw), p(self.cld_tau_sw),
@@ -508,17 +529,47 @@ class ClearSkyStep:
         self.graph = None
 
     def _mask_call(self, name, c, ngpt, randoms, mask, bits):
-        """The step's call of sampled_mask_max_ran, or _exp_ran when the step has an overlap parameter."""
+        """The step's call of sampled_mask_max_ran, or _exp_ran when the step has an overlap parameter; a seeded fused
+        step's call is the _seeded entry on its 4-word buffer (randoms None)."""
+        L, sfx = self.L, ""
+        if randoms is None:
+            randoms, sfx = (self.rng_lw if name.endswith("_lw") else self.rng_sw), "_seeded"
         head = (c, ngpt, self.nlay, self.ncol, randoms.data_ptr(), self.cloud_frac.data_ptr())
         if self.overlap_param is None:
-            return (name, self.L.rrtmgpnn_sampled_mask_max_ran, head + (mask, bits))
-        return (name, self.L.rrtmgpnn_sampled_mask_exp_ran, head + (self.overlap_param.data_ptr(), mask, bits))
+            return (name, getattr(L, "rrtmgpnn_sampled_mask_max_ran" + sfx), head + (mask, bits))
+        return (name, getattr(L, "rrtmgpnn_sampled_mask_exp_ran" + sfx),
+                head + (self.overlap_param.data_ptr(), mask, bits))
+
+    def _randoms_call(self, which, c):
+        """A seeded unfused step's fill of its scratch randoms ([] on the array route)."""
+        if not self.seeded:
+            return []
+        ng, rng, r = (self.ng_lw, self.rng_lw, self.randoms_lw) if which == "lw" else \
+            (self.ng_sw, self.rng_sw, self.randoms_sw)
+        return [("mcica_randoms_" + which, self.L.rrtmgpnn_mcica_randoms,
+                 (c, ng, self.nlay, self.ncol, rng.data_ptr(), r.data_ptr()))]
+
+    def set_mcica_seed(self, seed=None, stream_lw=None, stream_sw=None, col0=None):
+        """Rewrite a seeded step's two 4-word buffers (None keeps a value) between steps or graph replays; complete on
+        return."""
+        if not (self.mcica and self.seeded):
+            raise ValueError("set_mcica_seed: the step was built without mcica={'seed': ...}")
+        for k, v in (("seed", seed), ("stream_lw", stream_lw), ("stream_sw", stream_sw), ("col0", col0)):
+            if v is not None:
+                self._seed[k] = int(v)
+        torch.cuda.synchronize(self.dev)  # nothing in flight reads the words
+        sd = self._seed
+        for buf, stream in ((self.rng_lw, sd["stream_lw"]), (self.rng_sw, sd["stream_sw"])):
+            check(self.L.rrtmgpnn_mcica_rng_set(self.ctx.h, sd["seed"] & 0xFFFFFFFFFFFFFFFF, stream & 0xFFFFFFFF,
+                                                sd["col0"] & 0xFFFFFFFF, buf.data_ptr()), "mcica_rng_set")
 
     def mcica_randoms(self):
         """The step-owned device buffers of a McICA step's random numbers, (randoms_lw, randoms_sw), (ncol, nlay, ngpt)
         each: refill them (in place) between steps or graph replays."""
         if not self.mcica:
             raise ValueError("mcica_randoms: the step was built without mcica=")
+        if self.seeded:
+            raise ValueError("mcica_randoms: a seeded step holds no caller-filled random numbers (set_mcica_seed)")
         return self.randoms_lw, self.randoms_sw
 
     def set_mcica_randoms(self, randoms_lw=None, randoms_sw=None):
