@@ -61,7 +61,9 @@ int rrtmgpnn_context_set_sw_kernel(rrtmgpnn_context *ctx, int mode);
  * 0 (default): mode 1, measured 21 % faster than mode 2 at 10 000 x 60 columns.  1: the dual kernel, one launch that reads tau,
  * pfrac and tau_bnd once and carries a clear and an all-sky radiance per lane (one angle; several angles take mode 2).
  * 2: rrtmgpnn_lw_solver_noscat_planck followed by rrtmgpnn_lw_solver_noscat_planck_inc.
- * Bit-identical fluxes either way.  ctx == NULL sets the default of every context not set itself. */
+ * Bit-identical fluxes either way.  rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica follows the same setting with its
+ * masked twins: 0 is mode 1 there too, measured 21 % faster than mode 2 at 10 000 x 60 columns.
+ * ctx == NULL sets the default of every context not set itself. */
 int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode);
 /* MI355X tuning, no reference counterpart: the MFMA tiling of the gas-optics networks (rrtmgpnn_predict_nn_lw/_sw,
  * rrtmgpnn_gas_optics_lw_nn/_sw_nn).  0 (default): v_mfma_f32_32x32x2_f32 tiles where an instance exists for the
@@ -208,8 +210,8 @@ int rrtmgpnn_compute_planck_source_nn(rrtmgpnn_context *ctx, int ncol, int nlay,
 /* ---- RTE solvers ---------------------------------------------------------------------------- */
 /* lw_solver_noscat_GaussQuad (rte/kernels/mo_rte_solver_kernels.F90:332-415) without rescaling or
  * Jacobians.  Ds, weights: HOST arrays of nmus (<= 4) entries.  inc_flux may be NULL (zero). */
-/* OPERAND BOUND of every rrtmgpnn_lw_solver_noscat* entry (plain, _planck, _planck_inc, _planck_clr_all, _gpt,
- * _planck_gpt): the fluxes
+/* OPERAND BOUND of every rrtmgpnn_lw_solver_noscat* entry (plain, _planck, _planck_inc, _planck_clr_all,
+ * _planck_clr_all_mcica, _gpt, _planck_gpt): the fluxes
  * are the reference's bit for bit for tau * D <= 2^126 (8.5e37) in every layer, g-point and secant D (Gauss or lw_Ds;
  * with _planck_inc and _planck_clr_all, tau is the incremented optical depth).  Beyond it the layer source's (1 - T) / (tau * D) is
  * taken as 0 where the reference has ~3e-39, and a tau * D that overflows to inf makes the column's fluxes nan where
@@ -260,6 +262,28 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
                                              float temp_ref_min, float totplnk_delta, const float *totplnk,
                                              int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn,
                                              float *flux_up_clr, float *flux_dn_clr);
+/* rrtmgpnn_lw_solver_noscat_planck_clr_all with the all-sky increment switched per g-point by a McICA mask: mask_bits
+ * (ceil(ngpt/32), nlay, ncol) DEVICE, bit g % 32 of word g / 32, the layout the mask kernels write
+ * (rrtmgpnn_sampled_mask_*).  flux_up_clr / flux_dn_clr are what rrtmgpnn_lw_solver_noscat_planck gives on the same
+ * arguments and flux_up / flux_dn what rrtmgpnn_lw_solver_noscat_planck_inc gives with that mask armed
+ * (rrtmgpnn_solver_request_cloud_mask), bit for bit.  nmus == 1: one launch of the masked dual kernel, which reads tau,
+ * pfrac, tau_bnd and the mask once (ngpt % 64 == 0 and mask_bits 8-byte aligned: each wave's two mask words from one
+ * scalar load per layer; otherwise one word per lane).  nmus 2..4, or mode 2 of rrtmgpnn_context_set_lw_clr_all: those
+ * two launches back to back on the context's stream, the mask armed internally.  Mode 0 is mode 1 for this entry:
+ * at 10 000 x 60 columns the masked dual kernel measured 0.204 ms (21 %) below the two launches, four times their sample
+ * spread.  The mask is an argument, not a request: mask_bits == NULL,
+ * a cloud-mask request armed on the context and an armed by-band request are each refused with RRTMGPNN_ERR_ARGUMENT
+ * (the requests are cleared, as every solver entry clears them).  The pointer is a kernel argument and nothing is
+ * allocated with one angle, so the call can be captured in a hipGraph.  No reference counterpart. */
+int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                                   int nmus, const float *Ds, const float *weights,
+                                                   const float *inc_flux, const float *tau, const float *tau_bnd,
+                                                   const float *pfrac, int nbnd, int nPlanckTemp, const float *tlay,
+                                                   const float *tlev, const float *tsfc, int sfc_lay,
+                                                   const int *band_lims_gpt, float temp_ref_min, float totplnk_delta,
+                                                   const float *totplnk, int emis_by_band, const float *sfc_emis,
+                                                   float *flux_up, float *flux_dn, float *flux_up_clr,
+                                                   float *flux_dn_clr, const unsigned int *mask_bits);
 /* rte_lw on two-stream optical properties, default branch (rte/mo_rte_lw.F90:372-387): lw_solver_noscat_GaussQuad
  * with do_rescaling -- tau scaled by (1 - ssa + ssa(1-g)/2), a no-scattering pass down, then
  * lw_transport_1rescl up and down again with the adjustment terms (rte/kernels/mo_rte_solver_kernels.F90:209-233,
@@ -528,7 +552,8 @@ int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
  * rrtmgpnn_lw_solver_noscat_planck_inc (every nmus), rrtmgpnn_sw_solver_2stream_inc and
  * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, the SW ones on the checkpointed kernel (the default of
  * rrtmgpnn_context_set_sw_kernel: even ngpt; other modes, and odd ngpt, RRTMGPNN_ERR_UNSUPPORTED).  Extents other than
- * the call's: RRTMGPNN_ERR_ARGUMENT; every other solver entry (the plain ones, _clr_all, the _gpt entries, the
+ * the call's: RRTMGPNN_ERR_ARGUMENT; every other solver entry (the plain ones, _clr_all, _clr_all_mcica, which takes
+ * its mask as an argument, the _gpt entries, the
  * scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT; together with a by-band request:
  * RRTMGPNN_ERR_UNSUPPORTED.  The pointer becomes a kernel argument and nothing is allocated, so an armed call can be
  * captured in a hipGraph.  No reference counterpart (the reference samples into g-point arrays, draw_samples). */

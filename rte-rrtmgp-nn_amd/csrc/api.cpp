@@ -809,6 +809,45 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
                                          flux_dn, flux_up_clr, flux_dn_clr);
 }
 
+// mode 0 of rrtmgpnn_context_set_lw_clr_all for the McICA entry: the masked dual kernel
+static constexpr int kLwClrAllMcicaDefaultMode = 1;
+
+int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                                   int nmus, const float *Ds, const float *weights,
+                                                   const float *inc_flux, const float *tau, const float *tau_bnd,
+                                                   const float *pfrac, int nbnd, int nPlanckTemp, const float *tlay,
+                                                   const float *tlev, const float *tsfc, int sfc_lay,
+                                                   const int *band_lims_gpt, float temp_ref_min, float totplnk_delta,
+                                                   const float *totplnk, int emis_by_band, const float *sfc_emis,
+                                                   float *flux_up, float *flux_dn, float *flux_up_clr,
+                                                   float *flux_dn_clr, const unsigned int *mask_bits)
+{
+  // armed requests are taken (and so cleared) like in every solver entry, then refused: the mask is this entry's own
+  // argument, and it has no by-band instance
+  ::rrtmgpnn::BybandScope byband_(ctx, ngpt);
+  if (byband_.owner)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: by-band outputs are not available "
+                                       "from this entry (the _planck and _planck_inc entries have them)");
+  if (byband_.mask_owner)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: the cloud mask is this entry's "
+                                       "mask_bits argument, not a solver_request_cloud_mask request");
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!mask_bits) return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: mask_bits is null");
+  if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
+      !flux_up || !flux_dn || !flux_up_clr || !flux_dn_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 ||
+      sfc_lay < 1 || sfc_lay > nlay || !(totplnk_delta > 0.0f))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: bad argument");
+  BandArgs b;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_cover(b, ngpt)) return rc;
+  int mode = ctx->lw_clr_all >= 0 ? ctx->lw_clr_all : g_lw_clr_all_default;
+  if (mode == 0) mode = kLwClrAllMcicaDefaultMode;
+  return launch_lw_noscat_planck_clr_all(ctx, mode == 1, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau,
+                                         pfrac, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min,
+                                         totplnk_delta, totplnk, emis_by_band != 0, sfc_emis, tau_bnd, flux_up,
+                                         flux_dn, flux_up_clr, flux_dn_clr, mask_bits);
+}
+
 int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
                               const float *Ds, const float *weights, const float *inc_flux, const float *tau,
                               const float *ssa, const float *g, const float *lay_source, const float *lev_source,

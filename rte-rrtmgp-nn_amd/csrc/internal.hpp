@@ -251,14 +251,15 @@ int launch_lw_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
                             const float *totplnk, bool emis_by_band, const float *sfc_emis, const float *tau_bnd,
                             float *flux_up, float *flux_dn);
 // clear-sky fluxes (tau) and all-sky fluxes (tau + tau_bnd) of the same columns; dual: one launch of the dual instance
-// where it exists (one angle), else the two instances back to back
+// where it exists (one angle), else the two instances back to back.  mask_bits (nw, nlay, ncol), or null: the all-sky
+// set's increment is switched per g-point by a McICA mask (the masked dual instance, or the masked single one)
 int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, bool dual, int ngpt, int nlay, int ncol, int top_at_1,
                                     int nmus, const float *Ds, const float *wts, const float *inc_flux,
                                     const float *tau, const float *pfrac, int ntemp, const float *tlay,
                                     const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
                                     float temp_ref_min, float totplnk_delta, const float *totplnk, bool emis_by_band,
                                     const float *sfc_emis, const float *tau_bnd, float *flux_up, float *flux_dn,
-                                    float *flux_up_clr, float *flux_dn_clr);
+                                    float *flux_up_clr, float *flux_dn_clr, const uint32_t *mask_bits = nullptr);
 // bands != nullptr: atmosphere incremented by the band-resolved 2str set (tau, ssa, g)_bnd in-kernel
 int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
                       const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,

@@ -14,6 +14,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace rrtmgpnn {
 
@@ -149,7 +150,14 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // draw_samples (extensions/cloud_optics/mo_cloud_sampling.F90:291-307) and increment_1scalar_by_1scalar
 // (rte/kernels/mo_optical_props_kernels.F90:109-121) in the one add of kInc.  One mask word per layer per lane joins that
 // layer's prefetch.  The instances that run without a request hold no trace of it.
-template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false, bool kMask = false>
+//
+// kMask with kDual (rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica): the all-sky radiance takes the masked increment,
+// the clear one the bare tau; rings, flush and outputs are the dual instance's.  kMaskS (ngpt % 64 == 0, cmask 8-byte
+// aligned): a wave's 64 g-points are two consecutive mask words, the same pair for every lane, so the pair is read by
+// a scalar load into two SGPRs per prefetched layer and taken by the select as the lane mask (bit i = lane i = g-point
+// 64 * wave + i); no VGPR holds mask or bit.  Other ngpt keep the per-lane word.
+template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false, bool kMask = false,
+          bool kMaskS = false>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
@@ -160,7 +168,9 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
                                            const uint32_t *__restrict__ cmask)
 {
   constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
-  static_assert(!kMask || (kInc && !kDual && !kBand), "the cloud mask switches the fused band increment");
+  static_assert(!kMask || (kInc && !kBand), "the cloud mask switches the fused band increment");
+  static_assert(!kMaskS || (kMask && kDual), "the wave-uniform mask pair is the dual masked instance's");
+  using mask_t = std::conditional_t<kMaskS, uint64_t, uint32_t>;  // one layer's mask: the wave's pair, or the lane's word
   static_assert(kR % kPF == 0, "prefetch depth must divide the ring");
   // the fused down pass takes lev(l+1)'s Planck fraction from the neighbouring prefetch slot, py[(r+1) % kPF]: with
   // one slot that would be the layer's own pfrac
@@ -200,11 +210,19 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   // kMask: this lane's mask word, one per layer at stride nw, and its g-point's bit
   const uint32_t mrow = kMask ? 4u * (uint32_t)((ngpt + 31) / 32) : 0u, vm = 4u * (uint32_t)(gc >> 5);
   const uint32_t mbit = 1u << (gc & 31);
-  const ColArr Tmsk(kMask ? (const float *)cmask : tau, kMask ? (size_t)((ngpt + 31) / 32) * nlay * icol : 0,
-                    mrow * nlay);
-  auto ld_msk = [&](int l) { return kMask ? __float_as_uint(Tmsk.ld(vm, mrow * (uint32_t)l)) : 0u; };
-  auto tau_of = [&](float t, float ti, uint32_t m) {
-    if constexpr (kMask) return t + ((m & mbit) ? ti : 0.0f);
+  const ColArr Tmsk((kMask && !kMaskS) ? (const float *)cmask : tau,
+                    (kMask && !kMaskS) ? (size_t)((ngpt + 31) / 32) * nlay * icol : 0, mrow * nlay);
+  // kMaskS: this wave's pair of words, one per layer at stride nw / 2 (ngpt % 64 == 0: nw is even)
+  const uint64_t *mw = nullptr;
+  if constexpr (kMaskS)
+    mw = (const uint64_t *)cmask + (size_t)(ngpt >> 6) * nlay * icol + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  auto ld_msk = [&](int l) -> mask_t {
+    if constexpr (kMaskS) return mw[(size_t)(ngpt >> 6) * l];
+    else return kMask ? __float_as_uint(Tmsk.ld(vm, mrow * (uint32_t)l)) : 0u;
+  };
+  auto tau_of = [&](float t, float ti, mask_t m) {
+    if constexpr (kMaskS) return t + (__builtin_amdgcn_inverse_ballot_w64(m) ? ti : 0.0f);
+    else if constexpr (kMask) return t + ((m & mbit) ? ti : 0.0f);
     else return kInc ? t + ti : t;
   };
   // the value to load for lev index li: lev_source(li), or pfrac(min(li, nlay-1)) when fused
@@ -334,7 +352,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // downward: lw_transport_noscat_dn (:982-1009)
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
-      uint32_t pm[kPF];
+      mask_t pm[kPF];
       if (kEarly && imu == 0) {  // loaded ahead of the prologue
 #pragma unroll
         for (int p = 0; p < kPF; p++) {
@@ -360,7 +378,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         const int p = r % kPF, l = lay_dn(min(j, nlay - 1));
         const float y_next = py[(r + 1) % kPF], y_own = py[p];
         const float v = kFused ? (top_at_1 ? y_next : (j == 0 ? y_own : py_prev)) : pv[p];
-        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : 0u) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
+        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : mask_t(0)) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
         const float tc = kDual ? pt[p] * D : 0.0f;
         py_prev = y_own;
         {
@@ -396,7 +414,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // several angles there is no flush, and the registers would spill)
     auto lay_up = [&](int j) { return top_at_1 ? nlay - 1 - j : j; };
     float ptu[kPF], pyu[kPF], pvu[kPF], piu[kPF];
-    uint32_t pmu[kPF];
+    mask_t pmu[kPF];
     if constexpr (!kMulti) {
 #pragma unroll
       for (int p = 0; p < kPF; p++) {
@@ -414,7 +432,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     flush(pup, 1, sfcl, 1, bup);
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
-      uint32_t pm[kPF];
+      mask_t pm[kPF];
 #pragma unroll
       for (int p = 0; p < kPF; p++) {
         if constexpr (!kMulti) {
@@ -430,7 +448,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
       auto step = [&](int j, int r) {
         const int p = r % kPF, l = lay_up(min(j, nlay - 1));
         // fused: lev(l) = pfrac(l) * B(tlev(l)) (l < nlay), from the layer's own pfrac
-        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : 0u) * D, ly = lay_src(py[p], l);
+        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : mask_t(0)) * D, ly = lay_src(py[p], l);
         const float lvup = lev_src(kFused ? py[p] : pv[p], l);
         const float tc = kDual ? pt[p] * D : 0.0f;
         {
@@ -561,6 +579,16 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
     if (dual) {
       gdn = dn_clr;
       gup = up_clr;
+      if (ex.mask_bits) {
+        // McICA beside clear-sky: the wave-uniform pair where every wave is full and the pair can be read as one
+        // 8-byte scalar, the per-lane word otherwise
+        if (ngpt % 64 == 0 && (reinterpret_cast<uintptr_t>(ex.mask_bits) & 7u) == 0)
+          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, true>);
+        else
+          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, false>);
+        RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual, masked)");
+        return RRTMGPNN_OK;
+      }
       go(lw_noscat_kernel<kFused, kInc, PF, false, false, true>);
       RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual)");
       return RRTMGPNN_OK;
@@ -615,23 +643,34 @@ int launch_lw_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
 
 // rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 on the fused-Planck path: clear-sky fluxes from tau, all-sky
 // fluxes from tau + tau_bnd(band).  dual: one launch of the dual instance (one angle only); otherwise the clear and
-// the incremented instance back to back on the context's stream.  Identical bits either way.
+// the incremented instance back to back on the context's stream.  Identical bits either way.  mask_bits (the
+// _clr_all_mcica entry): the increment is a McICA-sampled cloud, in the dual launch or in the second of the two.
 int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, bool dual, int ngpt, int nlay, int ncol, int top_at_1,
                                     int nmus, const float *Ds, const float *wts, const float *inc_flux,
                                     const float *tau, const float *pfrac, int ntemp, const float *tlay,
                                     const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
                                     float temp_ref_min, float totplnk_delta, const float *totplnk, bool emis_by_band,
                                     const float *sfc_emis, const float *tau_bnd, float *flux_up, float *flux_dn,
-                                    float *flux_up_clr, float *flux_dn_clr)
+                                    float *flux_up_clr, float *flux_dn_clr, const uint32_t *mask_bits)
 {
   LwPlanck pl{tlay, tlev, tsfc, totplnk, ntemp, sfc_lay, emis_by_band ? 1 : 0, temp_ref_min, totplnk_delta};
-  if (dual && nmus == 1)
+  // mask_bits (the _clr_all_mcica entry): armed in the per-call extras for the launches that increment, and for
+  // those alone -- the clear launch of the pair carries no increment to switch
+  struct MaskArm {
+    rrtmgpnn_context *c;
+    MaskArm(rrtmgpnn_context *ctx, const uint32_t *m) : c(ctx) { c->extras.mask_bits = m; }
+    ~MaskArm() { c->extras.mask_bits = nullptr; }
+  };
+  if (dual && nmus == 1) {
+    MaskArm arm(ctx, mask_bits);
     return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
                                       sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn, flux_up_clr,
                                       flux_dn_clr);
+  }
   if (int rc = launch_lw_impl<true, false>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac,
                                            nullptr, sfc_emis, nullptr, pl, bands, nullptr, flux_up_clr, flux_dn_clr))
     return rc;
+  MaskArm arm(ctx, mask_bits);
   return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
                                     sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn);
 }

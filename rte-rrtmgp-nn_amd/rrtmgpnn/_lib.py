@@ -77,6 +77,10 @@ SIGNATURES = {
                                                          P(c_float), c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
                                                          c_vp, c_vp, c_int, P(c_int), c_float, c_float, c_vp, c_int,
                                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, P(c_float),
+                                                               P(c_float), c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
+                                                               c_vp, c_vp, c_int, P(c_int), c_float, c_float, c_vp,
+                                                               c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_context_set_lw_clr_all": (c_int, [c_vp, c_int]),
     "rrtmgpnn_sw_solver_2stream_inc": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_int, P(c_int), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

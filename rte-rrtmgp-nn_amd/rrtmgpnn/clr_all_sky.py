@@ -12,10 +12,16 @@ band cloud optical depth read once, both flux sets from one kernel with one angl
 1scl and defined by band on k_dist's bands and both flux objects want broadband up / down fluxes only; gas optics then
 leaves the Planck sources unformed and the kernel forms them.  Every other case -- 2str clouds (the rescaled solver),
 clouds on g-points, g-point or by-band outputs -- runs the two solves with api.rte_lw.  rte_sw always runs two solves.
+
+mask_bits= / cloud_mask= (both functions; not in the reference's interface) make the all-sky solve a McICA one: the band
+cloud is sampled per g-point by a mask from cloud_sampling.sampled_mask_*.  Where rte_lw would take the dual entry it
+takes its masked twin (rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica) on the packed mask, and rte_sw's all-sky solve is
+the library's masked fused solve; the cases that fall back run draw_samples on the byte mask ahead of the reference's
+sequence.
 """
 import torch
 
-from . import _lib, api
+from . import _lib, api, cloud_sampling
 from ._lib import check, float_array, int_array
 from .api import (GAUSS_DS, GAUSS_WTS, FluxesByBand, OpticalProps1scl, OpticalProps2str, SourceFuncLW, _f32dev, _p,
                   context)
@@ -60,10 +66,43 @@ def _broadband_only(fluxes):
     return True
 
 
+def _mask_check(who, mask_bits, cloud_mask, ncol, nlay, ngpt):
+    """Extents of the McICA masks rte_lw / rte_sw take, in the style of cloud_sampling._mask_args."""
+    if mask_bits is not None and (_shape(mask_bits) != (ncol, nlay, (ngpt + 31) // 32)
+                                  or mask_bits.element_size() != 4):
+        return "%s: mask_bits is not (ncol, nlay, ceil(ngpt/32)) 32-bit words" % who
+    if cloud_mask is not None and (_shape(cloud_mask) != (ncol, nlay, ngpt) or cloud_mask.element_size() != 1):
+        return "%s: cloud_mask is not (ncol, nlay, ngpt) bytes" % who
+    if not all(m is None or m.is_contiguous() for m in (mask_bits, cloud_mask)):
+        return "%s: arrays must be contiguous" % who
+    return ""
+
+
+def _sampled(who, cloud_mask, cloud_props, optical_props, k_dist):
+    """cloud_props (by band) sampled onto optical_props' g-points with the byte mask (draw_samples): (clouds, message)."""
+    if cloud_mask is None:
+        return None, ("%s: this case runs the sampled sequence (draw_samples, increment), which needs cloud_mask "
+                      "(ncol, nlay, ngpt); mask_bits alone serves the fused solver entries" % who)
+    smp = OpticalProps2str() if isinstance(cloud_props, OpticalProps2str) else OpticalProps1scl()
+    e = smp.init(k_dist.get_band_lims_wavenumber(), k_dist.get_band_lims_gpoint())
+    e = e or (smp.alloc_2str if isinstance(smp, OpticalProps2str) else smp.alloc_1scl)(
+        optical_props.get_ncol(), optical_props.get_nlay(), device=optical_props.tau.device)
+    e = e or cloud_sampling.draw_samples(cloud_mask, cloud_props, smp)
+    return smp, e
+
+
 def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props, allsky_fluxes, clrsky_fluxes,
-           aer_props=None, col_dry=None, t_lev=None, inc_flux=None, n_gauss_angles=None, neural_nets=None):
+           aer_props=None, col_dry=None, t_lev=None, inc_flux=None, n_gauss_angles=None, neural_nets=None,
+           mask_bits=None, cloud_mask=None):
     """rte_lw (extensions/mo_rrtmgp_clr_all_sky.F90:46-175).  Tensors in this project's layout: p_lay, t_lay (ncol,
-    nlay); p_lev, t_lev (ncol, nlay+1); t_sfc (ncol); sfc_emis (ncol, nband); inc_flux (ncol, ngpt)."""
+    nlay); p_lev, t_lev (ncol, nlay+1); t_sfc (ncol); sfc_emis (ncol, nband); inc_flux (ncol, ngpt).
+
+    mask_bits / cloud_mask (an extension of the reference's interface, which has no sampling here): the all-sky solve
+    sees cloud_props (by band) sampled per g-point with a McICA mask (cloud_sampling.sampled_mask_*), the clear solve
+    is unchanged.  mask_bits, int32 (ncol, nlay, ceil(ngpt/32)), serves the library's masked dual entry
+    (rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica) in the case the unmasked dual entry serves; every other case runs
+    the reference's sequence with the cloud sampled first (draw_samples), which needs the byte mask cloud_mask, uint8
+    (ncol, nlay, ngpt).  Given both, they must describe the same mask."""
     ncol, nlay = tuple(p_lay.shape)
     ngpt, nband = k_dist.get_ngpt(), k_dist.get_nband()
     e = _aer_check(aer_props, ncol, nlay, ngpt, nband, "rrtmpg_lw: aerosol properties inconsistently sized")
@@ -71,8 +110,10 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
         e = "rrtmpg_lw: t_lev inconsistently sized"
     if inc_flux is not None and _shape(inc_flux) != (ncol, ngpt):
         e = "rrtmpg_lw: incident flux inconsistently sized"
+    e = e or _mask_check("rte_lw", mask_bits, cloud_mask, ncol, nlay, ngpt)
     if e:
         return e
+    masked = mask_bits is not None or cloud_mask is not None
     top_at_1 = bool(p_lay[0, 0] < p_lay[0, nlay - 1])
     dev = p_lay.device
     optical_props, e = _alloc_like(cloud_props, k_dist, ncol, nlay, dev, "lw")
@@ -87,7 +128,7 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
             and not cloud_props.gpoints_are_equal(optical_props) and cloud_props.get_ngpt() == nband
             and (cloud_props.get_ncol(), cloud_props.get_nlay()) == (ncol, nlay)
             and _broadband_only(allsky_fluxes) and _broadband_only(clrsky_fluxes) and 1 <= nmu <= 4
-            and _shape(sfc_emis) == (ncol, nband))
+            and _shape(sfc_emis) == (ncol, nband) and (not masked or mask_bits is not None))
     e = k_dist.gas_optics(p_lay, p_lev, t_lay, t_sfc, gas_concs, optical_props, sources, col_dry=col_dry, tlev=t_lev,
                           neural_nets=neural_nets, defer_planck=dual)
     if e:
@@ -100,14 +141,22 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
         tlay_d, tlev_d, tsfc_d, sfc_lay = sources.planck_deferred
         ctx = context(dev.index)
         emis = _f32dev(sfc_emis, dev)
-        check(_lib.lib().rrtmgpnn_lw_solver_noscat_planck_clr_all(
-            ctx.h, ngpt, nlay, ncol, int(top_at_1), nmu, float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]),
-            _p(inc_flux), _p(optical_props.tau), _p(cloud_props.tau), _p(sources.lay_source), nband,
-            k_dist.get_nPlanckTemp(), _p(tlay_d), _p(tlev_d), _p(tsfc_d), sfc_lay,
-            int_array(k_dist.band_lims_gpt.ravel()), k_dist.temp_ref_min, k_dist.totplnk_delta, _p(k_dist.totplnk), 1,
-            _p(emis), _p(allsky_fluxes.flux_up), _p(allsky_fluxes.flux_dn), _p(clrsky_fluxes.flux_up),
-            _p(clrsky_fluxes.flux_dn)), "lw_solver_noscat_planck_clr_all")
+        args = (ctx.h, ngpt, nlay, ncol, int(top_at_1), nmu, float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]),
+                _p(inc_flux), _p(optical_props.tau), _p(cloud_props.tau), _p(sources.lay_source), nband,
+                k_dist.get_nPlanckTemp(), _p(tlay_d), _p(tlev_d), _p(tsfc_d), sfc_lay,
+                int_array(k_dist.band_lims_gpt.ravel()), k_dist.temp_ref_min, k_dist.totplnk_delta, _p(k_dist.totplnk),
+                1, _p(emis), _p(allsky_fluxes.flux_up), _p(allsky_fluxes.flux_dn), _p(clrsky_fluxes.flux_up),
+                _p(clrsky_fluxes.flux_dn))
+        if masked:
+            check(_lib.lib().rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(*args, _p(mask_bits)),
+                  "lw_solver_noscat_planck_clr_all_mcica")
+        else:
+            check(_lib.lib().rrtmgpnn_lw_solver_noscat_planck_clr_all(*args), "lw_solver_noscat_planck_clr_all")
         return ""
+    if masked:  # the reference's sequence on the sampled cloud
+        cloud_props, e = _sampled("rte_lw", cloud_mask, cloud_props, optical_props, k_dist)
+        if e:
+            return e
     e = api.rte_lw(optical_props, top_at_1, sources, sfc_emis, clrsky_fluxes, inc_flux=inc_flux,
                    n_gauss_angles=n_gauss_angles)
     if e:
@@ -120,10 +169,17 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
 
 
 def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif, cloud_props, allsky_fluxes,
-           clrsky_fluxes, aer_props=None, col_dry=None, inc_flux=None, tsi_scaling=None, neural_nets=None):
+           clrsky_fluxes, aer_props=None, col_dry=None, inc_flux=None, tsi_scaling=None, neural_nets=None,
+           mask_bits=None, cloud_mask=None):
     """rte_sw (extensions/mo_rrtmgp_clr_all_sky.F90:177-310).  sfc_alb_dir / sfc_alb_dif: (ncol, nband) as there
     (expanded to g-points), or (ncol, ngpt) as api.rte_sw takes them; inc_flux (ncol, ngpt); tsi_scaling: the
-    reference's single multiply of the incident flux."""
+    reference's single multiply of the incident flux.
+
+    mask_bits / cloud_mask (an extension of the reference's interface, as in rte_lw): the clear solve as without them,
+    then the all-sky solve on cloud_props (by band) sampled per g-point.  With mask_bits, 2str clouds on k_dist's
+    bands, even ngpt and broadband-only all-sky fluxes that is the library's masked fused solve
+    (rrtmgpnn_solver_request_cloud_mask + rrtmgpnn_sw_solver_2stream_inc: the increment switched per g-point as the
+    properties are read); every other case runs draw_samples and increment first, which needs cloud_mask."""
     ncol, nlay = tuple(p_lay.shape)
     ngpt, nband = k_dist.get_ngpt(), k_dist.get_nband()
     e = ""
@@ -134,8 +190,10 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
         e = "rrtmpg_sw: tsi_scaling is < 0"
     if inc_flux is not None and _shape(inc_flux) != (ncol, ngpt):
         e = "rrtmpg_sw: incident flux inconsistently sized"
+    e = e or _mask_check("rte_sw", mask_bits, cloud_mask, ncol, nlay, ngpt)
     if e:
         return e
+    masked = mask_bits is not None or cloud_mask is not None
     top_at_1 = bool(p_lay[0, 0] < p_lay[0, nlay - 1])
     dev = p_lay.device
     optical_props, e = _alloc_like(cloud_props, k_dist, ncol, nlay, dev, "sw")
@@ -169,6 +227,30 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
     e = api.rte_sw(optical_props, top_at_1, mu0, toa_flux, albs[0], albs[1], clrsky_fluxes)
     if e:
         return e
+    if masked:
+        fused = (mask_bits is not None and isinstance(optical_props, OpticalProps2str) and ngpt % 2 == 0
+                 and cloud_props.bands_are_equal(optical_props) and not cloud_props.gpoints_are_equal(optical_props)
+                 and cloud_props.get_ngpt() == nband
+                 and (cloud_props.get_ncol(), cloud_props.get_nlay()) == (ncol, nlay)
+                 and not allsky_fluxes.are_desired_gpt()
+                 and not (isinstance(allsky_fluxes, FluxesByBand) and allsky_fluxes.are_desired_byband())
+                 and allsky_fluxes.are_desired()
+                 and all(_shape(a) == (ncol, ngpt) for a in albs))
+        if fused:
+            f = lambda t: t if t is not None else torch.empty((ncol, nlay + 1), dtype=torch.float32, device=dev)  # noqa: E731
+            up, dn, dr = f(allsky_fluxes.flux_up), f(allsky_fluxes.flux_dn), f(allsky_fluxes.flux_dn_dir)
+            cloud_sampling.arm_cloud_mask(ctx, ngpt, mask_bits)
+            check(_lib.lib().rrtmgpnn_sw_solver_2stream_inc(
+                ctx.h, ngpt, nlay, ncol, int(top_at_1), _p(toa_flux), None, _p(optical_props.tau),
+                _p(optical_props.ssa), _p(optical_props.g), nband, int_array(k_dist.band_lims_gpt.ravel()),
+                _p(cloud_props.tau), _p(cloud_props.ssa), _p(cloud_props.g), _p(mu0), _p(albs[0]), _p(albs[1]),
+                _p(up), _p(dn), _p(dr)), "sw_solver_2stream_inc")
+            if allsky_fluxes.flux_net is not None:
+                torch.sub(dn, up, out=allsky_fluxes.flux_net)
+            return ""
+        cloud_props, e = _sampled("rte_sw", cloud_mask, cloud_props, optical_props, k_dist)
+        if e:
+            return e
     e = cloud_props.increment(optical_props)
     if e:
         return e

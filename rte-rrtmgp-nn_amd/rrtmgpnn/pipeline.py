@@ -40,6 +40,11 @@ clrsky=True (with clouds) also produces the clear-sky fluxes of the same columns
 extensions/mo_rrtmgp_clr_all_sky.F90 do: gas optics once, a clear solve, clouds%increment, the all-sky solve.  Fused,
 the LW pair comes from one call (rrtmgpnn_lw_solver_noscat_planck_clr_all) and the SW chain gets one more solver
 launch on the unincremented properties; unfused, the clear solvers run before the increment_* calls.
+
+mcica={..., "clrsky": True} is the two together: McICA all-sky fluxes and the clear-sky fluxes of the same columns
+(cloud radiative effect).  Fused, the LW pair comes from rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica, which takes the
+packed mask as an argument (one launch of the masked dual kernel with one angle), and the SW chain is the McICA one
+plus the clear solver launch; unfused, the clear solve, then mask -> draw_samples -> increment, then the all-sky solve.
 """
 
 import numpy as np
@@ -118,10 +123,13 @@ class ClearSkyStep:
         if self.mcica and clouds is None:
             raise ValueError("mcica: sampled clouds need clouds=(lwp, iwp, rel, rei)")
         if self.mcica and (clrsky or byband):
-            raise ValueError("mcica with clrsky=True or byband=True is not supported")
+            raise ValueError("mcica with clrsky=True or byband=True is not supported (clear-sky fluxes beside the "
+                             "sampled ones: the key mcica={..., 'clrsky': True})")
         if self.mcica and not sw:
             raise ValueError("mcica with sw=False is not supported")
-        self.clrsky = bool(clrsky)
+        # mcica={..., "clrsky": True}: the clear-sky fluxes of the same columns beside the McICA all-sky ones (fused: the
+        # LW pair from rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica, the SW chain as with clrsky=True)
+        self.clrsky = bool(clrsky) or bool(self.mcica and mcica.get("clrsky"))
         if self.clrsky and clouds is None:
             raise ValueError("clrsky=True: clear-sky fluxes beside the all-sky ones need clouds=(lwp, iwp, rel, rei)")
         if self.clrsky and byband:
@@ -292,6 +300,11 @@ class ClearSkyStep:
                     ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all,
                      lw_calls[0][2] + (p(self.lw_up_clr), p(self.lw_dn_clr))),
                 ]
+                if self.mcica:  # the McICA twin: the packed mask is the entry's last argument, not a request
+                    lw_calls = [
+                        ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica,
+                         lw_calls[0][2] + (p(self.mask_bits_lw),)),
+                    ]
         else:
             lw_calls = [
                 ("planck_source", L.rrtmgpnn_compute_planck_source_nn,
@@ -331,14 +344,17 @@ class ClearSkyStep:
             elif self.mcica:
                 self.calls += [self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, None,
                                                p(self.mask_bits_lw))]
-                lw_calls.insert(len(lw_calls) - 1,
-                                ("lw_mask", L.rrtmgpnn_solver_request_cloud_mask,
-                                 (c, self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
+                if not self.clrsky:  # (the clear + all-sky entry takes the mask as an argument)
+                    lw_calls.insert(len(lw_calls) - 1,
+                                    ("lw_mask", L.rrtmgpnn_solver_request_cloud_mask,
+                                     (c, self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
         if self.clrsky and not fused:
-            # the clear solve before clouds%increment(atmos) (mo_rrtmgp_clr_all_sky.F90:161-172): the increment moves
-            # from ahead of the Planck sources to between the two solver calls
-            inc_lw = [x for x in self.calls if x[0] == "increment_lw"]
-            self.calls = [x for x in self.calls if x[0] != "increment_lw"]
+            # the clear solve before clouds%increment(atmos) (mo_rrtmgp_clr_all_sky.F90:161-172): the increment (McICA:
+            # with the mask and draw_samples ahead of it) moves from ahead of the Planck sources to between the two
+            # solver calls
+            moved = ("mcica_randoms_lw", "mcica_mask_lw", "draw_samples_lw", "increment_lw")
+            inc_lw = [x for x in self.calls if x[0] in moved]
+            self.calls = [x for x in self.calls if x[0] not in moved]
             lw_calls = lw_calls[:-1] + [
                 ("lw_solver_clr", L.rrtmgpnn_lw_solver_noscat,
                  lw_calls[-1][2][:-2] + (p(self.lw_up_clr), p(self.lw_dn_clr)))] + inc_lw + lw_calls[-1:]
