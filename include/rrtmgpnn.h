@@ -37,6 +37,8 @@ extern "C" {
 #define RRTMGPNN_ACT_RELU         2
 #define RRTMGPNN_ACT_SIGMOID      3
 #define RRTMGPNN_ACT_HARD_SIGMOID 4
+#define RRTMGPNN_ACT_TANH         5
+#define RRTMGPNN_ACT_GAUSSIAN     6
 
 typedef struct rrtmgpnn_context rrtmgpnn_context;
 typedef struct rrtmgpnn_network rrtmgpnn_network;
@@ -67,10 +69,28 @@ int rrtmgpnn_context_set_sw_kernel(rrtmgpnn_context *ctx, int mode);
 int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode);
 /* MI355X tuning, no reference counterpart: the MFMA tiling of the gas-optics networks (rrtmgpnn_predict_nn_lw/_sw,
  * rrtmgpnn_gas_optics_lw_nn/_sw_nn).  0 (default): v_mfma_f32_32x32x2_f32 tiles where an instance exists for the
- * networks (the shipped LW g256 pair, LW g128 single model and SW g224 pair, softsign/softsign/linear), 16x16x4
- * otherwise.  1: 16x16x4 tiles.
- * Bit-identical outputs either way.  ctx == NULL sets the default of every context not set itself. */
+ * networks (the shipped LW g256 pair, LW g128 single model and SW g224 pair, softsign/softsign/linear, ngpt a
+ * multiple of 32, 16-byte aligned outputs), 16x16x4 otherwise.  1: 16x16x4 tiles.
+ * Bit-identical outputs either way.  ctx == NULL sets the default of every context not set itself.
+ * The 16x16x4 kernel is compiled for 3-layer networks [nx, h1, h2, ny] of these shapes, written (K1S, H1T, H2T) =
+ * (ceil(nx/4), ceil(h1/16), ceil(h2/16)): (2,1,1), (2,2,2), (5,1,1), (5,2,2), (5,3,3), (5,4,4), (5,5,5), (5,8,8) --
+ * nx in 5..8 or 17..20, equal hidden tile counts -- each for any activations (softsign/softsign/linear inlined, any
+ * other set by runtime code) and any ny, as long as the packed weights fit 160 KiB of LDS.  A single model
+ * (rrtmgpnn_network_forward, rrtmgpnn_predict_nn_lw with nnets == 1, rrtmgpnn_predict_nn_sw with ssa == NULL) may
+ * have any of them; the pairs compiled are LW (5,4,4)+(5,1,1), (5,5,5)+(5,2,2), (5,4,4)+(5,2,2) and SW (2,1,1)+(2,1,1),
+ * (2,2,2)+(2,1,1), (2,2,2)+(2,2,2).  rrtmgpnn_predict_nn_lw/_sw return RRTMGPNN_ERR_UNSUPPORTED for anything else;
+ * rrtmgpnn_network_forward runs anything else on the generic kernel. */
 int rrtmgpnn_context_set_mlp_kernel(rrtmgpnn_context *ctx, int mode);
+/* Which kernel served this context's last network launch (rrtmgpnn_network_forward, rrtmgpnn_predict_nn_lw/_sw,
+ * rrtmgpnn_gas_optics_lw_nn/_sw_nn), for tests of the dispatch: path[0] one of RRTMGPNN_MLP_PATH_* (NONE before the
+ * first launch); for MFMA16 path[1..3] = the first network's (K1S, H1T, H2T), path[4..6] the second's (0 without one);
+ * path[7] flag bits: 1 softsign/softsign/linear inlined, 2 output tile count compiled in, 4 inputs formed in-kernel,
+ * 8 16-byte output stores. */
+#define RRTMGPNN_MLP_PATH_NONE    0
+#define RRTMGPNN_MLP_PATH_GENERIC 1
+#define RRTMGPNN_MLP_PATH_MFMA32  2
+#define RRTMGPNN_MLP_PATH_MFMA16  3
+int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8]);
 /* MI355X tuning, no reference counterpart: the gas-optics networks launched on this context use at most `cus` CUs'
  * worth of resident blocks (0, the default: every CU).  For a host that runs the LW and SW chains side by side on two
  * streams: an LW network confined to part of the chip leaves the other CUs to the SW solver from its start (each LW
@@ -168,7 +188,11 @@ int rrtmgpnn_interpolate_tlev(rrtmgpnn_context *ctx, int ncol, int nlay, const f
                               const float *tlay, float *tlev);
 /* predict_nn_lw_blas (rrtmgp/kernels/mo_gas_optics_kernels.F90:690-774).  nnets == 2: nets[0] =
  * absorption (tau = (std*y+mean)^8 * col_dry), nets[1] = Planck fraction (pfrac = y^2);
- * nnets == 1: single "both" model with 2*ngpt outputs (:744-772). */
+ * nnets == 1: single "both" model with 2*ngpt outputs (:744-772).
+ * The networks' last layer is taken as linear, whatever its activation code (output_sgemm_tau / _lw add the bias and
+ * scale: "linear layer, no activation"); the same holds for rrtmgpnn_predict_nn_sw and the fused entries.  Compiled
+ * shapes and pairs: rrtmgpnn_context_set_mlp_kernel (RRTMGPNN_ERR_UNSUPPORTED otherwise); operand domain of softsign:
+ * rrtmgpnn_network_forward. */
 int rrtmgpnn_predict_nn_lw(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs,
                            const float *nn_inputs, const float *col_dry,
                            const rrtmgpnn_network *const *nets, int nnets, float *tau, float *pfrac);
@@ -195,7 +219,17 @@ int rrtmgpnn_gas_optics_sw_nn(rrtmgpnn_context *ctx, int ncol, int nlay, int ngp
                               const float *const *gas_conc, const int *gas_ndims,
                               const rrtmgpnn_network *const *nets, float *tau, float *ssa, float *g);
 /* Generic MLP forward (network_type%output_sgemm_flat, neural/mod_network.F90:273-354):
- * out(ny, nbatch) = net(x(nx, nbatch)), last-layer activation applied, no post-processing. */
+ * out(ny, nbatch) = net(x(nx, nbatch)), last-layer activation applied, no post-processing.  Any network
+ * rrtmgpnn_network_create accepts with hidden widths <= 256 (RRTMGPNN_ERR_UNSUPPORTED beyond): the 16x16x4 MFMA
+ * kernel where an instance is compiled for its shape (rrtmgpnn_context_set_mlp_kernel lists them), the one-thread-
+ * per-sample generic kernel otherwise; the same bits either way (every dot product an fmaf chain in ascending k).
+ * OPERAND DOMAIN of softsign in the MFMA kernels (this entry, rrtmgpnn_predict_nn_lw/_sw, rrtmgpnn_gas_optics_*_nn):
+ * in a softsign, softsign, linear network (the inlined activation set) a hidden pre-activation must not exceed 2^126
+ * (8.5e37) in magnitude: libm_ref.hpp div_softsign takes the hardware reciprocal of |x| + 1, which is 0 beyond, so the
+ * unit gives +-0 where x / (|x| + 1) is +-1.  Up to 2^126, subnormals and +-0 included, and for +-inf and nan (nan
+ * either way) the outputs are the reference's bit for bit (tests/test_gpu_mlp_shapes.py::test_mlp_operand_edges).
+ * Networks with any other activation set divide plainly and have no such bound.  The reference's networks see inputs
+ * scaled to about [0, 1] and pre-activations of order 1 to 10. */
 int rrtmgpnn_network_forward(rrtmgpnn_context *ctx, const rrtmgpnn_network *net, long long nbatch,
                              const float *x, float *out);
 /* compute_Planck_source_nn (rrtmgp/kernels/mo_gas_optics_kernels.F90:615-683).  sfc_lay 1-based.

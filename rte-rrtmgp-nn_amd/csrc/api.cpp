@@ -298,6 +298,14 @@ int rrtmgpnn_context_get_mlp_max_cus(rrtmgpnn_context *ctx, int *cus)
   return RRTMGPNN_OK;
 }
 
+int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8])
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!path) return fail(RRTMGPNN_ERR_ARGUMENT, "null path");
+  for (int i = 0; i < 8; i++) path[i] = ctx->mlp_path[i];
+  return RRTMGPNN_OK;
+}
+
 int rrtmgpnn_context_set_stream(rrtmgpnn_context *ctx, void *hip_stream)
 {
   if (int rc = check_ctx(ctx)) return rc;
@@ -696,7 +704,11 @@ int rrtmgpnn_network_forward(rrtmgpnn_context *ctx, const rrtmgpnn_network *net,
 {
   if (int rc = check_ctx(ctx)) return rc;
   if (!net || !x || !out || nbatch < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "network_forward: bad argument");
-  if (net->d_packed) return launch_mlp(ctx, MLP_PLAIN, net, nullptr, nbatch, net->dims[net->nlayers], x, nullptr, out, nullptr, nullptr);
+  // the MFMA kernel where an instance is compiled for the shape and its image fits the LDS; every other network (any
+  // depth, nx of 1..4 / 9..16 / 21..32, unequal or uncompiled hidden tile counts, images over 160 KiB) on the generic
+  // kernel -- decided here, so that no refusal's error string is left behind
+  if (mlp_plain_instance(net))
+    return launch_mlp(ctx, MLP_PLAIN, net, nullptr, nbatch, net->dims[net->nlayers], x, nullptr, out, nullptr, nullptr);
   return launch_mlp_generic(ctx, net, nbatch, x, out);
 }
 

@@ -64,6 +64,14 @@ struct rrtmgpnn_context {
   int mlp_max_cus = 0;  // rrtmgpnn_context_set_mlp_max_cus: CUs' worth of network blocks, 0 = all
   int mlp_kernel = -1;  // LW network tiling: 0 32x32x2 where instantiated, 1 16x16x4, -1 the library default
   int lw_clr_all = -1;  // clear + all-sky LW entry: 0 default, 1 the dual kernel, 2 two launches, -1 the library default
+  // rrtmgpnn_context_get_mlp_path: the kernel of this context's last network launch (kind, A's and B's (K1S, H1T, H2T),
+  // flags), written by the launchers
+  int mlp_path[8] = {0};
+  void set_mlp_path(int kind, int ak = 0, int ah1 = 0, int ah2 = 0, int bk = 0, int bh1 = 0, int bh2 = 0, int flags = 0)
+  {
+    const int p[8] = {kind, ak, ah1, ah2, bk, bh1, bh2, flags};
+    for (int i = 0; i < 8; i++) mlp_path[i] = p[i];
+  }
   // Per-call solver extras, set by the *_gpt entry points for the duration of one call (rte_lw's lw_Ds and
   // ty_fluxes_flexible's g-point outputs, (ngpt, nlay+1, ncol) each); the other entries leave them null.
   struct SolverExtras {
@@ -228,6 +236,8 @@ int launch_mlp(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A, c
                float *out2, const MlpInputs *in = nullptr);
 int launch_mlp_generic(rrtmgpnn_context *ctx, const rrtmgpnn_network *net, long long nbatch, const float *x,
                        float *out);
+// launch_mlp(MLP_PLAIN) has a 16x16x4 instance for the network: a packed image of a compiled shape within 160 KiB of LDS
+bool mlp_plain_instance(const rrtmgpnn_network *net);
 int pack_network(rrtmgpnn_network *net);
 // kernels_nn32.hip: the LW pair, LW both and SW pair modes on v_mfma_f32_32x32x2_f32; RRTMGPNN_ERR_UNSUPPORTED (no error set) when no instance
 // exists for the networks (launch_mlp then runs the 16x16x4 kernel)

@@ -152,7 +152,7 @@ __device__ __forceinline__ float activate(int act, float x)
   case RRTMGPNN_ACT_RELU: return fmaxf(0.0f, x);
   case RRTMGPNN_ACT_SIGMOID: return 1.0f / (1.0f + ref_expf(-x));
   case RRTMGPNN_ACT_HARD_SIGMOID: return fmaxf(0.0f, fminf(1.0f, 0.2f * x + 0.5f));
-  case 5: return tanhf(x);
+  case 5: return ref_tanhf(x);  // glibc's, as the oracle's (the device libm rounds differently)
   case 6: return ref_expf(-x * x);
   default: return x;
   }
@@ -577,6 +577,9 @@ static int launch_mlp_acts(rrtmgpnn_context *ctx, MlpArgs &a)
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, ctx->stream, a);
   RRTMGPNN_LAUNCH_CHECK("mlp_pair_kernel");
+  constexpr bool pair = MODE == MLP_LW_PAIR || MODE == MLP_SW_PAIR;
+  ctx->set_mlp_path(RRTMGPNN_MLP_PATH_MFMA16, AK, AH1, AH2, pair ? BK : 0, pair ? BH1 : 0, pair ? BH2 : 0,
+                    ACTS | (NGTC > 0 ? 2 : 0) | (XIN ? 4 : 0) | (a.vec4 ? 8 : 0));
   return RRTMGPNN_OK;
 }
 
@@ -623,6 +626,16 @@ static int launch_mlp_t(rrtmgpnn_context *ctx, MlpArgs &a)
 static bool shape_is(const rrtmgpnn_network *n, int k, int h1, int h2)
 {
   return n && n->d_packed && n->k1s == k && n->h1t == h1 && n->h2t == h2;
+}
+
+bool mlp_plain_instance(const rrtmgpnn_network *net)
+{
+  if (!net || !net->d_packed || sizeof(float) * (size_t)net->packed_floats > 160 * 1024) return false;
+#define X(K, H1, H2) \
+  if (shape_is(net, K, H1, H2)) return true;
+  RRTMGPNN_MLP_SHAPES(X)
+#undef X
+  return false;
 }
 
 int launch_mlp(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A, const rrtmgpnn_network *B,
@@ -749,6 +762,7 @@ int launch_mlp_generic(rrtmgpnn_context *ctx, const rrtmgpnn_network *net, long 
   hipLaunchKernelGGL(mlp_generic_kernel, dim3((unsigned)((nbatch + 127) / 128)), dim3(128), 0, ctx->stream, g, nbatch,
                      x, out);
   RRTMGPNN_LAUNCH_CHECK("mlp_generic_kernel");
+  ctx->set_mlp_path(RRTMGPNN_MLP_PATH_GENERIC);
   return RRTMGPNN_OK;
 }
 

@@ -538,6 +538,7 @@ static int launch32(rrtmgpnn_context *ctx, Mlp32Args &a)
   const long long grid = std::max<long long>(1, std::min<long long>(want, (long long)cus * per_cu));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, ctx->stream, a);
   RRTMGPNN_LAUNCH_CHECK("mlp32_kernel");
+  ctx->set_mlp_path(RRTMGPNN_MLP_PATH_MFMA32, 0, 0, 0, 0, 0, 0, 1 | 2 | (XIN ? 4 : 0) | 8);
   return RRTMGPNN_OK;
 }
 

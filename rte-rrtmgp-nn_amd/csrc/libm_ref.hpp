@@ -10,7 +10,8 @@
 // (-110, 89) and logf on every 3rd positive finite float on the host (tools/check_libm_ref_*.c), and on the device
 // against the host's libm in the same program (tools/exhaustive_ops.hip): ref_expf_neg and ref_expf_neg_batch<4> with
 // the LDS table on every float of [-105, -0], ref_logf_nb / ref_logf on every positive finite float, ref_cosf on every
-// float of [0, pi].
+// float of [0, pi], ref_tanhf (glibc's float tanhf on expm1f, in float arithmetic: the MLPs' tanh activation) on every float
+// of [-10, 10].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -314,6 +315,96 @@ __device__ __forceinline__ float ref_logf_nb(float x)
                    : ((ix0 & 0x80000000u) || ix0 * 2 >= 0xff000000u) ? __int_as_float(0x7fc00000)
                                                                       : res;
   return special && !subn ? sp : res;
+}
+
+// glibc 2.35 expm1f (sysdeps/ieee754/flt-32/s_expm1f.c): float arithmetic throughout, so it needs the library's
+// -ffp-contract=off (a contracted product would round differently) and hipcc's correctly rounded f32 division.
+__device__ __forceinline__ float ref_expm1f(float x)
+{
+  const float o_threshold = 8.8721679688e+01f, ln2_hi = 6.9313812256e-01f, ln2_lo = 9.0580006145e-06f,
+              invln2 = 1.4426950216e+00f, Q1 = -3.3333335072e-02f, Q2 = 1.5873016091e-03f, Q3 = -7.9365076090e-05f,
+              Q4 = 4.0082177293e-06f, Q5 = -2.0109921195e-07f;
+  float y, hi, lo, c = 0.0f, t, e;
+  int k;
+  uint32_t hx = __float_as_uint(x);
+  const uint32_t xsb = hx & 0x80000000u;
+  hx &= 0x7fffffffu;
+  if (hx >= 0x4195b844u) {  // |x| >= 27 ln2
+    if (hx >= 0x42b17218u) {
+      if (hx > 0x7f800000u) return x + x;
+      if (hx == 0x7f800000u) return xsb == 0 ? x : -1.0f;
+      if (x > o_threshold) return __int_as_float(0x7f800000);
+    }
+    if (xsb != 0) return -1.0f;
+  }
+  if (hx > 0x3eb17218u) {    // |x| > 0.5 ln2
+    if (hx < 0x3F851592u) {  // |x| < 1.5 ln2
+      if (xsb == 0) { hi = x - ln2_hi; lo = ln2_lo; k = 1; }
+      else { hi = x + ln2_hi; lo = -ln2_lo; k = -1; }
+    } else {
+      k = (int)(invln2 * x + (xsb == 0 ? 0.5f : -0.5f));
+      t = (float)k;
+      hi = x - t * ln2_hi;
+      lo = t * ln2_lo;
+    }
+    x = hi - lo;
+    c = (hi - x) - lo;
+  } else if (hx < 0x33000000u) {  // |x| < 2^-25
+    return x;
+  } else {
+    k = 0;
+  }
+  const float hfx = 0.5f * x, hxs = x * hfx;
+  const float r1 = 1.0f + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
+  t = 3.0f - r1 * hfx;
+  e = hxs * ((r1 - t) / (6.0f - x * t));
+  if (k == 0) return x - (x * e - hxs);
+  e = (x * (e - c) - c);
+  e -= hxs;
+  if (k == -1) return 0.5f * (x - e) - 0.5f;
+  if (k == 1) {
+    if (x < -0.25f) return -2.0f * (e - (x + 0.5f));
+    return 1.0f + 2.0f * (x - e);
+  }
+  if (k <= -2 || k > 56) {
+    y = 1.0f - (e - x);
+    y = __uint_as_float(__float_as_uint(y) + ((uint32_t)k << 23));
+    return y - 1.0f;
+  }
+  if (k < 23) {
+    t = __uint_as_float(0x3f800000u - (0x1000000u >> k));  // 1 - 2^-k
+    y = t - (e - x);
+  } else {
+    t = __uint_as_float((uint32_t)(0x7f - k) << 23);  // 2^-k
+    y = x - (e + t);
+    y += 1.0f;
+  }
+  return __uint_as_float(__float_as_uint(y) + ((uint32_t)k << 23));
+}
+
+// glibc 2.35 tanhf (sysdeps/ieee754/flt-32/s_tanhf.c) on ref_expm1f: the MLPs' tanh activation (mod_activation.F90's
+// tanh; the oracle calls the host's tanhf).  The C copy in tools/check_libm_ref_tanhf.c equals the host's tanhf on
+// every float of [-22.5, 22.5], a strided sample beyond, +-inf and nan; this function is checked on the device against
+// the host's tanhf on every float of [-10, 10] (tools/exhaustive_ops.hip).
+__device__ __forceinline__ float ref_tanhf(float x)
+{
+  const uint32_t jx = __float_as_uint(x), ix = jx & 0x7fffffffu;
+  float z;
+  if (ix >= 0x7f800000u) return (jx >> 31) ? 1.0f / x - 1.0f : 1.0f / x + 1.0f;
+  if (ix < 0x41b00000u) {  // |x| < 22
+    if (ix == 0) return x;
+    if (ix < 0x24000000u) return x * (1.0f + x);  // |x| < 2^-55
+    if (ix >= 0x3f800000u) {
+      const float t = ref_expm1f(2.0f * fabsf(x));
+      z = 1.0f - 2.0f / (t + 2.0f);
+    } else {
+      const float t = ref_expm1f(-2.0f * fabsf(x));
+      z = -t / (t + 2.0f);
+    }
+  } else {
+    z = 1.0f - 1.0e-30f;
+  }
+  return (jx >> 31) ? -z : z;
 }
 
 }  // namespace rrtmgpnn

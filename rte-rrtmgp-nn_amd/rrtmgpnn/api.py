@@ -192,6 +192,61 @@ class RrtmgpNetwork:
 
     load = load_netcdf
 
+    def from_arrays(self, model):
+        """The network of a model dict (the RBIN model's keys, what the oracle takes) through rrtmgpnn_network_create:
+        dims, activation (codes), w1..wn (dims[n-1], dims[n]) C order, b1..bn, input_min, input_max; optionally
+        output_mean and output_std (both or neither), input_names (an (nx, 32) character array, rbin.chars, or a list
+        of strings).  Fills the attributes load_netcdf fills."""
+        dims = [int(v) for v in np.asarray(model["dims"]).ravel()]
+        acts = [int(v) for v in np.asarray(model["activation"]).ravel()]
+        nl = len(dims) - 1
+        if nl < 1 or len(acts) != nl:
+            raise ValueError("from_arrays: dims and activation do not describe the same layers")
+        m = {"dims": np.array(dims, np.int32), "activation": np.array(acts, np.int32)}
+        for n in range(1, nl + 1):
+            w = np.ascontiguousarray(model["w%d" % n], np.float32)
+            b = np.ascontiguousarray(model["b%d" % n], np.float32).ravel()
+            if w.size != dims[n - 1] * dims[n] or (w.ndim == 2 and w.shape != (dims[n - 1], dims[n])) or \
+                    b.size != dims[n]:
+                raise ValueError("from_arrays: layer %d does not have the extents of dims" % n)
+            m["w%d" % n], m["b%d" % n] = w.reshape(dims[n - 1], dims[n]), b
+        for k in ("input_min", "input_max"):
+            m[k] = np.ascontiguousarray(model[k], np.float32).ravel()
+            if m[k].size != dims[0]:
+                raise ValueError("from_arrays: %s does not have dims[0] entries" % k)
+        has_out = model.get("output_mean") is not None and model.get("output_std") is not None
+        if has_out:
+            for k in ("output_mean", "output_std"):
+                m[k] = np.ascontiguousarray(model[k], np.float32).ravel()
+                if m[k].size != dims[-1]:
+                    raise ValueError("from_arrays: %s does not have dims[-1] entries" % k)
+        names = model.get("input_names")
+        if names is not None:
+            if len(names) and isinstance(names[0], str):
+                names = rbin.chars(list(names))
+            names = np.ascontiguousarray(names, np.uint8)
+            if names.shape != (dims[0], 32):
+                raise ValueError("from_arrays: input_names must be (dims[0], 32) characters")
+            m["input_names"] = names
+        self.dims, self.activation = dims, acts
+        self.input_names = rbin.unchars(names) if names is not None else [""] * dims[0]
+        self.coeffs_input_min, self.coeffs_input_max = m["input_min"], m["input_max"]
+        self.coeffs_output_mean = m["output_mean"] if has_out else None
+        self.coeffs_output_std = m["output_std"] if has_out else None
+        self.model = m
+        vp = lambda a: a.ctypes.data_as(_lib.c_vp)  # noqa: E731
+        h = _lib.c_vp()
+        check(_lib.lib().rrtmgpnn_network_create(
+            context(self.device).h, nl, int_array(dims), int_array(acts),
+            ptr_array([m["w%d" % n].ctypes.data for n in range(1, nl + 1)]),
+            ptr_array([m["b%d" % n].ctypes.data for n in range(1, nl + 1)]), vp(m["input_min"]), vp(m["input_max"]),
+            vp(m["output_mean"]) if has_out else None, vp(m["output_std"]) if has_out else None,
+            names.tobytes() if names is not None else None, h), "network_create")
+        if self.h:
+            _lib.lib().rrtmgpnn_network_destroy(self.h)
+        self.h = h
+        return self
+
     @property
     def nlayers(self):
         return len(self.dims) - 1

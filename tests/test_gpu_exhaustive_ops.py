@@ -1,7 +1,7 @@
 """GPU: the shortened correctly-rounded sequences the kernels use (libm_ref.hpp rcp_rn_normal, sqrt_rn_normal,
 div_rn_normal as solver_div, div_softsign; x2_device.hpp rcp2, sqrt2, div2 on both lanes)
 equal the IEEE results on EVERY float of their domains, and the libm restatements (ref_expf_neg, ref_expf_neg_batch<4>,
-ref_logf_nb, ref_cosf) equal the host's libm, checked on the device itself (v_rcp_f32 is a hardware approximation no
+ref_logf_nb, ref_cosf, ref_tanhf) equal the host's libm, checked on the device itself (v_rcp_f32 is a hardware approximation no
 host can emulate bit for bit): tools/exhaustive_ops.hip, built by __graft_entry__.build() against the product's own
 headers -- the "shipped:" rows call the functions the kernels call, not copies of them.  The reference column (the
 compiler's IEEE sequence) is cross-checked against a double-precision evaluation rounded once.
@@ -51,7 +51,9 @@ def test_shortened_division_sequences_are_exact_on_their_domains():
         by_header += [("divsw%s%d" % (s, i), "shipped:" + v) for s in "+-"
                       for v in ("solver_div", "div2.x", "div2.y", "div2(scalar)")]
     by_header += [("exp", "shipped:ref_expf_neg"), ("exp", "shipped:ref_expf_neg_batch4"),
-                  ("log", "shipped:ref_logf_nb"), ("log", "shipped:ref_logf"), ("cos", "shipped:ref_cosf")]
+                  ("log", "shipped:ref_logf_nb"), ("log", "shipped:ref_logf"), ("cos", "shipped:ref_cosf"),
+                  # the MLPs' tanh activation: glibc's tanhf on every float of [-10, 10]
+                  ("tanh+", "shipped:ref_tanhf"), ("tanh-", "shipped:ref_tanhf")]
     for key in by_header:
         n, bad = res[key]
         assert n > 100_000_000 and bad == 0, (key, n, bad)

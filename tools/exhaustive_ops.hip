@@ -16,6 +16,7 @@
 //            that, and -inf, against the host's expf evaluated in this program
 //   log    : ref_logf_nb (and ref_logf) on every positive finite float against the host's logf
 //   cos    : ref_cosf on every float of [0, pi] against the host's cosf
+//   tanh   : ref_tanhf (the MLPs' tanh activation) on every float of [-10, 10] against the host's tanhf
 //
 // reference of the divisions and roots: the compiler's IEEE sequences (default flags: correctly rounded f32 division
 // and sqrt), cross-checked with double-precision evaluations rounded once (innocuous double rounding for / and sqrt).
@@ -107,7 +108,7 @@ __device__ __forceinline__ float div_b(float a, float b)
 }
 
 constexpr int kVar = 10;
-enum Op { RCP = 0, SQRT, SOFT, DIVLW, DIVSW, EXP, LOG, COS };
+enum Op { RCP = 0, SQRT, SOFT, DIVLW, DIVSW, EXP, LOG, COS, TANH };
 
 struct Acc {
   unsigned long long c[kVar] = {};
@@ -123,7 +124,7 @@ struct Acc {
 
 // Element k of a run is the float with bits lo + k*stride.  One thread per `per` consecutive elements of the chunk
 // [k0, k0 + nchunk) of a run of n; per-thread mismatch counts and first bad input, stored with vector stores.  ref:
-// the host's results for the chunk (EXP, LOG, COS); num: the numerator (DIVSW).
+// the host's results for the chunk (EXP, LOG, COS, TANH); num: the numerator (DIVSW).
 template <int OP>
 __global__ void check(uint32_t lo, uint32_t stride, uint64_t n, uint64_t k0, uint64_t nchunk, uint32_t per,
                       const float *__restrict__ ref, float num, unsigned long long *cnt, uint32_t *first)
@@ -190,6 +191,8 @@ __global__ void check(uint32_t lo, uint32_t stride, uint64_t n, uint64_t k0, uin
         acc.cmp(0, ref_logf_nb(x), ref[k - k0], u); acc.cmp(1, ref_logf(x), ref[k - k0], u);
       } else if constexpr (OP == COS) {
         acc.cmp(0, ref_cosf(x), ref[k - k0], u);
+      } else if constexpr (OP == TANH) {
+        acc.cmp(0, ref_tanhf(x), ref[k - k0], u);
       }
     }
   }
@@ -327,5 +330,8 @@ int main()
   run<LOG>("log", 0x00000001u, 0x7f7fffffu, gv, 1, logf);
   const char *cv[kVar] = {"shipped:ref_cosf"};
   run<COS>("cos", 0x00000000u, 0x40490fdbu /* pi */, cv, 1, cosf);
+  const char *tv[kVar] = {"shipped:ref_tanhf"};
+  run<TANH>("tanh+", 0x00000000u, 0x41200000u /* 10 */, tv, 1, tanhf);
+  run<TANH>("tanh-", 0x80000000u, 0xc1200000u /* -10 */, tv, 1, tanhf);
   return 0;
 }
