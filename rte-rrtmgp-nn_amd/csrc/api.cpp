@@ -109,71 +109,192 @@ static int bands_cover(const BandArgs &b, int ngpt)
   return RRTMGPNN_OK;
 }
 
-// A solver entry's hold on the context's by-band request (rrtmgpnn_solver_request_byband): the first entry of a call
-// takes the armed request into the per-call extras, validates it against the call's ngpt, and clears it when the
-// call returns, whatever the outcome; an entry reached from another (the _gpt entries call the plain ones) finds
-// nothing armed and leaves the extras alone.  The packed cloud mask (rrtmgpnn_solver_request_cloud_mask) is taken and
-// cleared the same way; what the entry does with it is the macros' part below.
-struct BybandScope {
-  rrtmgpnn_context *c;
-  bool owner = false;
-  int rc = RRTMGPNN_OK;
-  bool mask_owner = false;
+// The requests armed on a context (rrtmgpnn_solver_request_byband / _cloud_mask) belong to its next solver call.
+// Every solver entry starts by taking them: they are copied out and cleared, whatever the entry then returns, so the
+// call after it never sees them.  The by-band request is validated against the call's ngpt into the call's
+// SolverExtras; what an entry does with the cloud mask, and whether it has by-band instances at all, is the entry's
+// part (the three functions below, or an `if` of its own).  A null context has nothing armed (check_ctx reports it).
+struct Requests {
+  bool byband = false;  // a by-band request was armed ...
+  int byband_rc = RRTMGPNN_OK;  // ... and its band limits against ngpt: ex's by-band part is filled when OK
   rrtmgpnn_context::CloudMaskRequest mask{};
-  BybandScope(rrtmgpnn_context *ctx, int ngpt) : c(ctx)
-  {
-    if (!c) return;
-    if (c->cloud_mask.armed) {
-      mask_owner = true;
-      mask = c->cloud_mask;
-      c->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
-    }
-    if (!c->byband.armed) return;
-    owner = true;
-    const auto rq = c->byband;
-    c->byband = rrtmgpnn_context::BybandRequest{};
-    rc = band_args(rq.nbnd, rq.lims, ngpt, c->extras.bnd);
-    if (rc) return;
-    c->extras.bnd_up = rq.up;
-    c->extras.bnd_dn = rq.dn;
-    c->extras.bnd_dir = rq.dir;
-  }
-  // the entries with masked instances: the mask against the call's extents, then into the per-call extras
-  int take_mask(const char *entry, int ngpt, int nlay, int ncol)
-  {
-    if (!mask_owner) return RRTMGPNN_OK;
-    if (owner)
-      return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a cloud mask together with by-band outputs");
-    if (mask.ngpt != ngpt || mask.nlay != nlay || mask.ncol != ncol)
-      return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
-                                                              "are not this call's");
-    c->extras.mask_bits = mask.bits;
-    return RRTMGPNN_OK;
-  }
-  int refuse_mask() const
-  {
-    if (!mask_owner) return RRTMGPNN_OK;
-    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_cloud_mask: this solver entry takes no cloud mask (the "
-                                       "_planck_inc, _2stream_inc and _2stream_rfmip entries do)");
-  }
-  ~BybandScope()
-  {
-    if (mask_owner) c->extras.mask_bits = nullptr;
-    if (!owner) return;
-    c->extras.bnd_up = c->extras.bnd_dn = c->extras.bnd_dir = nullptr;
-    c->extras.bnd = BandArgs{};
-  }
 };
-// first statement of every solver entry: the entries without masked instances refuse an armed cloud mask
-#define RRTMGPNN_BYBAND(ctx, ngpt)        \
-  ::rrtmgpnn::BybandScope byband_((ctx), (ngpt)); \
-  if (byband_.rc) return byband_.rc;      \
-  if (int mrc_ = byband_.refuse_mask()) return mrc_
-// ... and of the three that honour it
-#define RRTMGPNN_BYBAND_MASK(entry, ctx, ngpt, nlay, ncol) \
-  ::rrtmgpnn::BybandScope byband_((ctx), (ngpt));          \
-  if (byband_.rc) return byband_.rc;                       \
-  if (int mrc_ = byband_.take_mask((entry), (ngpt), (nlay), (ncol))) return mrc_
+
+static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
+{
+  Requests rq;
+  if (!ctx) return rq;
+  rq.mask = ctx->cloud_mask;
+  ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+  if (!ctx->byband.armed) return rq;
+  const auto bb = ctx->byband;
+  ctx->byband = rrtmgpnn_context::BybandRequest{};
+  rq.byband = true;
+  rq.byband_rc = band_args(bb.nbnd, bb.lims, ngpt, ex.bnd);
+  if (rq.byband_rc) return rq;
+  ex.bnd_up = bb.up;
+  ex.bnd_dn = bb.dn;
+  ex.bnd_dir = bb.dir;
+  return rq;
+}
+
+// the entries without masked instances refuse an armed cloud mask
+static const char kNoMaskMsg[] = "solver_request_cloud_mask: this solver entry takes no cloud mask (the _planck_inc, "
+                                 "_2stream_inc and _2stream_rfmip entries do)";
+static int take_byband(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
+{
+  const Requests rq = take_requests(ctx, ngpt, ex);
+  if (rq.byband_rc) return rq.byband_rc;
+  if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, kNoMaskMsg);
+  return RRTMGPNN_OK;
+}
+
+// the three that honour it: the mask against the call's extents, then into the call's extras
+static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex)
+{
+  const Requests rq = take_requests(ctx, ngpt, ex);
+  if (rq.byband_rc) return rq.byband_rc;
+  if (!rq.mask.armed) return RRTMGPNN_OK;
+  if (rq.byband)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a cloud mask together with by-band outputs");
+  if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
+                                                            "are not this call's");
+  ex.mask_bits = rq.mask.bits;
+  return RRTMGPNN_OK;
+}
+
+// the two _clr_all entries have neither by-band nor request-masked instances: `mask_msg` is the entry's refusal
+static int refuse_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, const char *mask_msg)
+{
+  SolverExtras ex;
+  const Requests rq = take_requests(ctx, ngpt, ex);
+  if (rq.byband)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": by-band outputs are not available from this entry (the "
+                                                            "_planck and _planck_inc entries have them)");
+  if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, mask_msg);
+  return RRTMGPNN_OK;
+}
+
+static int lw_ds_check(int nmus, const float *lw_Ds)
+{
+  if (lw_Ds && nmus != 1)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "rte_lw: providing lw_Ds incompatible with specifying n_gauss_angles");
+  return RRTMGPNN_OK;
+}
+
+// The solver entries and their *_gpt twins (rte_lw's lw_Ds and ty_fluxes_flexible's g-point outputs, null from the
+// plain entry) are wrappers of one function each: requests, context, lw_Ds, arguments, launch -- in that order.
+static int lw_noscat(rrtmgpnn_context *ctx, const LwNoscat &p, const float *lay_source, const float *lev_source,
+                     const float *sfc_source, const float *lw_Ds, float *gpt_up, float *gpt_dn)
+{
+  SolverExtras ex;
+  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (int rc = lw_ds_check(p.nmus, lw_Ds)) return rc;
+  if (!p.Ds || !p.wts || !p.tau || !lay_source || !lev_source || !p.sfc_emis || !sfc_source || !p.flux_up ||
+      !p.flux_dn || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat: bad argument");
+  ex.lw_Ds = lw_Ds;
+  ex.gpt_up = gpt_up;
+  ex.gpt_dn = gpt_dn;
+  return launch_lw_noscat(ctx, ex, p, lay_source, lev_source, sfc_source);
+}
+
+// the fused-Planck entries' arguments: `inc` needs tau_bnd, `more` is what else the entry needs; then the bands into
+// `in`, which cover every g-point where each g-point's band is looked up (the increment, by-band emissivity)
+static int planck_args(const char *entry, const LwNoscat &p, LwPlanckIn &in, int nbnd, const int *band_lims_gpt,
+                       bool inc, bool more = true)
+{
+  const LwPlanck &pl = in.pl;
+  if (!p.Ds || !p.wts || !p.tau || (inc && !in.tau_bnd) || !in.pfrac || !pl.tlay || !pl.tlev || !pl.tsfc ||
+      !pl.totplnk || !p.sfc_emis || !p.flux_up || !p.flux_dn || !more || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0 ||
+      pl.ntemp < 2 || pl.sfc_lay < 1 || pl.sfc_lay > p.nlay || !(pl.tdelta > 0.0f))
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": bad argument");
+  if (int rc = band_args(nbnd, band_lims_gpt, p.ngpt, in.bands)) return rc;
+  if (inc || pl.emis_by_band) return bands_cover(in.bands, p.ngpt);
+  return RRTMGPNN_OK;
+}
+
+static int lw_noscat_planck(rrtmgpnn_context *ctx, const LwNoscat &p, LwPlanckIn &in, int nbnd,
+                            const int *band_lims_gpt, const float *lw_Ds, float *gpt_up, float *gpt_dn)
+{
+  SolverExtras ex;
+  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (int rc = lw_ds_check(p.nmus, lw_Ds)) return rc;
+  if (int rc = planck_args("lw_solver_noscat_planck", p, in, nbnd, band_lims_gpt, false)) return rc;
+  ex.lw_Ds = lw_Ds;
+  ex.gpt_up = gpt_up;
+  ex.gpt_dn = gpt_dn;
+  return launch_lw_noscat_planck(ctx, ex, p, in);
+}
+
+static int lw_1rescl(rrtmgpnn_context *ctx, const LwNoscat &p, const float *ssa, const float *g,
+                     const float *lay_source, const float *lev_source, const float *sfc_source, float *gpt_up,
+                     float *gpt_dn)
+{
+  SolverExtras ex;
+  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!p.Ds || !p.wts || !p.tau || !ssa || !g || !lay_source || !lev_source || !p.sfc_emis || !sfc_source ||
+      !p.flux_up || !p.flux_dn || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_1rescl: bad argument");
+  ex.gpt_up = gpt_up;
+  ex.gpt_dn = gpt_dn;
+  return launch_lw_rescl(ctx, ex, p, ssa, g, lay_source, lev_source, sfc_source);
+}
+
+static int lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
+                      const float *tau, const float *ssa, const float *g, const float *lev_source,
+                      const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn,
+                      float *gpt_up, float *gpt_dn)
+{
+  SolverExtras ex;
+  if (int rc = take_byband(ctx, ngpt, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!tau || !ssa || !g || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn || ngpt < 1 ||
+      nlay < 1 || ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_2stream: bad argument");
+  ex.gpt_up = gpt_up;
+  ex.gpt_dn = gpt_dn;
+  return launch_lw_2stream(ctx, ex, ngpt, nlay, ncol, top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis_gpt,
+                           sfc_source, flux_up, flux_dn);
+}
+
+static int sw_2stream(rrtmgpnn_context *ctx, const Sw2Stream &p, float *gpt_up, float *gpt_dn, float *gpt_dir)
+{
+  SolverExtras ex;
+  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!p.inc_flux || !p.tau || !p.ssa || !p.mu0 || !p.alb_dir || !p.alb_dif || !p.flux_up || !p.flux_dn ||
+      !p.flux_dir || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream: bad argument");
+  ex.gpt_up = gpt_up;
+  ex.gpt_dn = gpt_dn;
+  ex.gpt_dir = gpt_dir;
+  return launch_sw_2stream(ctx, ex, p);
+}
+
+static int sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
+                     const float *tau, const float *mu0, float *flux_dir, float *gpt_dir)
+{
+  SolverExtras ex;
+  if (int rc = take_byband(ctx, ngpt, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!inc_flux || !tau || !mu0 || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: bad argument");
+  ex.gpt_dir = gpt_dir;
+  return launch_sw_noscat(ctx, ex, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir);
+}
+
+// rrtmgpnn_lw_solver_noscat_planck_clr_all(_mcica): the context's mode, 0 being `mode0` -- what the measurements of
+// DESIGN.md section 3 chose, the dual kernel and the masked dual kernel
+static bool lw_clr_all_dual(const rrtmgpnn_context *ctx, int mode0)
+{
+  const int mode = ctx->lw_clr_all >= 0 ? ctx->lw_clr_all : g_lw_clr_all_default;
+  return (mode == 0 ? mode0 : mode) == 1;
+}
 
 }  // namespace rrtmgpnn
 
@@ -733,13 +854,18 @@ int rrtmgpnn_lw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int nco
                               const float *lay_source, const float *lev_source, const float *sfc_emis_gpt,
                               const float *sfc_source, float *flux_up, float *flux_dn)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (!Ds || !weights || !tau || !lay_source || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn ||
-      ngpt < 1 || nlay < 1 || ncol < 0)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat: bad argument");
-  return launch_lw_noscat(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, lay_source, lev_source,
-                          sfc_emis_gpt, sfc_source, flux_up, flux_dn);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis_gpt, flux_up, flux_dn};
+  return lw_noscat(ctx, p, lay_source, lev_source, sfc_source, nullptr, nullptr, nullptr);
+}
+
+int rrtmgpnn_lw_solver_noscat_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
+                                  const float *Ds, const float *weights, const float *lw_Ds, const float *inc_flux,
+                                  const float *tau, const float *lay_source, const float *lev_source,
+                                  const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn,
+                                  float *gpt_flux_up, float *gpt_flux_dn)
+{
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis_gpt, flux_up, flux_dn};
+  return lw_noscat(ctx, p, lay_source, lev_source, sfc_source, lw_Ds, gpt_flux_up, gpt_flux_dn);
 }
 
 int rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
@@ -749,19 +875,25 @@ int rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      float temp_ref_min, float totplnk_delta, const float *totplnk,
                                      int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (!Ds || !weights || !tau || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis || !flux_up ||
-      !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 || sfc_lay < 1 || sfc_lay > nlay ||
-      !(totplnk_delta > 0.0f))
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck: bad argument");
-  BandArgs b;
-  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
-  if (emis_by_band)
-    if (int rc = bands_cover(b, ngpt)) return rc;
-  return launch_lw_noscat_planck(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, pfrac,
-                                 nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min, totplnk_delta, totplnk,
-                                 emis_by_band != 0, sfc_emis, nullptr, flux_up, flux_dn);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
+  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+                pfrac, {}, nullptr};
+  return lw_noscat_planck(ctx, p, in, nbnd, band_lims_gpt, nullptr, nullptr, nullptr);
+}
+
+int rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
+                                         const float *Ds, const float *weights, const float *lw_Ds,
+                                         const float *inc_flux, const float *tau, const float *pfrac, int nbnd,
+                                         int nPlanckTemp, const float *tlay, const float *tlev, const float *tsfc,
+                                         int sfc_lay, const int *band_lims_gpt, float temp_ref_min,
+                                         float totplnk_delta, const float *totplnk, int emis_by_band,
+                                         const float *sfc_emis, float *flux_up, float *flux_dn, float *gpt_flux_up,
+                                         float *gpt_flux_dn)
+{
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
+  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+                pfrac, {}, nullptr};
+  return lw_noscat_planck(ctx, p, in, nbnd, band_lims_gpt, lw_Ds, gpt_flux_up, gpt_flux_dn);
 }
 
 int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
@@ -772,18 +904,14 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          float totplnk_delta, const float *totplnk, int emis_by_band,
                                          const float *sfc_emis, float *flux_up, float *flux_dn)
 {
-  RRTMGPNN_BYBAND_MASK("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol);
+  SolverExtras ex;
+  if (int rc = take_byband_or_mask("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol, ex)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
-  if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
-      !flux_up || !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 || sfc_lay < 1 || sfc_lay > nlay ||
-      !(totplnk_delta > 0.0f))
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_inc: bad argument");
-  BandArgs b;
-  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
-  if (int rc = bands_cover(b, ngpt)) return rc;
-  return launch_lw_noscat_planck(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, pfrac,
-                                 nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min, totplnk_delta, totplnk,
-                                 emis_by_band != 0, sfc_emis, tau_bnd, flux_up, flux_dn);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
+  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+                pfrac, {}, tau_bnd};
+  if (int rc = planck_args("lw_solver_noscat_planck_inc", p, in, nbnd, band_lims_gpt, true)) return rc;
+  return launch_lw_noscat_planck(ctx, ex, p, in);
 }
 
 // mode 0 of rrtmgpnn_context_set_lw_clr_all: what the measurement of DESIGN.md section 3 chose
@@ -798,27 +926,16 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
                                              int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn,
                                              float *flux_up_clr, float *flux_dn_clr)
 {
-  // an armed by-band request is taken (and so cleared) like in every solver entry, then refused: this entry has no
-  // by-band instance
-  ::rrtmgpnn::BybandScope byband_(ctx, ngpt);
-  if (byband_.owner)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all: by-band outputs are not available from this "
-                                       "entry (the _planck and _planck_inc entries have them)");
-  if (int rc = byband_.refuse_mask()) return rc;
+  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all", ctx, ngpt, kNoMaskMsg)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
-  if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
-      !flux_up || !flux_dn || !flux_up_clr || !flux_dn_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 ||
-      sfc_lay < 1 || sfc_lay > nlay || !(totplnk_delta > 0.0f))
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all: bad argument");
-  BandArgs b;
-  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
-  if (int rc = bands_cover(b, ngpt)) return rc;
-  int mode = ctx->lw_clr_all >= 0 ? ctx->lw_clr_all : g_lw_clr_all_default;
-  if (mode == 0) mode = kLwClrAllDefaultMode;
-  return launch_lw_noscat_planck_clr_all(ctx, mode == 1, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau,
-                                         pfrac, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min,
-                                         totplnk_delta, totplnk, emis_by_band != 0, sfc_emis, tau_bnd, flux_up,
-                                         flux_dn, flux_up_clr, flux_dn_clr);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
+  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+                pfrac, {}, tau_bnd};
+  if (int rc = planck_args("lw_solver_noscat_planck_clr_all", p, in, nbnd, band_lims_gpt, true,
+                           flux_up_clr && flux_dn_clr))
+    return rc;
+  return launch_lw_noscat_planck_clr_all(ctx, SolverExtras{}, lw_clr_all_dual(ctx, kLwClrAllDefaultMode), p, in,
+                                         flux_up_clr, flux_dn_clr);
 }
 
 // mode 0 of rrtmgpnn_context_set_lw_clr_all for the McICA entry: the masked dual kernel
@@ -834,30 +951,22 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ng
                                                    float *flux_up, float *flux_dn, float *flux_up_clr,
                                                    float *flux_dn_clr, const unsigned int *mask_bits)
 {
-  // armed requests are taken (and so cleared) like in every solver entry, then refused: the mask is this entry's own
-  // argument, and it has no by-band instance
-  ::rrtmgpnn::BybandScope byband_(ctx, ngpt);
-  if (byband_.owner)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: by-band outputs are not available "
-                                       "from this entry (the _planck and _planck_inc entries have them)");
-  if (byband_.mask_owner)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: the cloud mask is this entry's "
-                                       "mask_bits argument, not a solver_request_cloud_mask request");
+  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all_mcica", ctx, ngpt,
+                               "lw_solver_noscat_planck_clr_all_mcica: the cloud mask is this entry's mask_bits "
+                               "argument, not a solver_request_cloud_mask request"))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!mask_bits) return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: mask_bits is null");
-  if (!Ds || !weights || !tau || !tau_bnd || !pfrac || !tlay || !tlev || !tsfc || !totplnk || !sfc_emis ||
-      !flux_up || !flux_dn || !flux_up_clr || !flux_dn_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nPlanckTemp < 2 ||
-      sfc_lay < 1 || sfc_lay > nlay || !(totplnk_delta > 0.0f))
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: bad argument");
-  BandArgs b;
-  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
-  if (int rc = bands_cover(b, ngpt)) return rc;
-  int mode = ctx->lw_clr_all >= 0 ? ctx->lw_clr_all : g_lw_clr_all_default;
-  if (mode == 0) mode = kLwClrAllMcicaDefaultMode;
-  return launch_lw_noscat_planck_clr_all(ctx, mode == 1, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau,
-                                         pfrac, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min,
-                                         totplnk_delta, totplnk, emis_by_band != 0, sfc_emis, tau_bnd, flux_up,
-                                         flux_dn, flux_up_clr, flux_dn_clr, mask_bits);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
+  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+                pfrac, {}, tau_bnd};
+  if (int rc = planck_args("lw_solver_noscat_planck_clr_all_mcica", p, in, nbnd, band_lims_gpt, true,
+                           flux_up_clr && flux_dn_clr))
+    return rc;
+  SolverExtras ex;
+  ex.mask_bits = mask_bits;
+  return launch_lw_noscat_planck_clr_all(ctx, ex, lw_clr_all_dual(ctx, kLwClrAllMcicaDefaultMode), p, in, flux_up_clr,
+                                         flux_dn_clr);
 }
 
 int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
@@ -865,118 +974,8 @@ int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int nco
                               const float *ssa, const float *g, const float *lay_source, const float *lev_source,
                               const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (!Ds || !weights || !tau || !ssa || !g || !lay_source || !lev_source || !sfc_emis_gpt || !sfc_source ||
-      !flux_up || !flux_dn || ngpt < 1 || nlay < 1 || ncol < 0)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_1rescl: bad argument");
-  return launch_lw_rescl(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, ssa, g, lay_source,
-                         lev_source, sfc_emis_gpt, sfc_source, flux_up, flux_dn);
-}
-
-int rrtmgpnn_lw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
-                               const float *inc_flux, const float *tau, const float *ssa, const float *g,
-                               const float *lev_source, const float *sfc_emis_gpt, const float *sfc_source,
-                               float *flux_up, float *flux_dn)
-{
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (!tau || !ssa || !g || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn || ngpt < 1 ||
-      nlay < 1 || ncol < 0)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_2stream: bad argument");
-  return launch_lw_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis_gpt,
-                           sfc_source, flux_up, flux_dn);
-}
-
-int rrtmgpnn_sw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
-                               const float *inc_flux, const float *inc_flux_dif, const float *tau, const float *ssa,
-                               const float *g, const float *mu0, const float *sfc_alb_dir_gpt,
-                               const float *sfc_alb_dif_gpt, float *flux_up, float *flux_dn, float *flux_dir)
-{
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (!inc_flux || !tau || !ssa || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt || !flux_up || !flux_dn ||
-      !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream: bad argument");
-  return launch_sw_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
-                           sfc_alb_dif_gpt, nullptr, nullptr, nullptr, nullptr, flux_up, flux_dn, flux_dir);
-}
-
-// ---- the *_gpt entries: the call above with rte_lw's lw_Ds and ty_fluxes_flexible's g-point outputs, handed to the
-// launch through the context for this one call ----
-namespace {
-struct ExtrasScope {
-  rrtmgpnn_context *c;
-  ExtrasScope(rrtmgpnn_context *ctx, const float *ds, float *up, float *dn, float *dir) : c(ctx)
-  {
-    c->extras.lw_Ds = ds;
-    c->extras.gpt_up = up;
-    c->extras.gpt_dn = dn;
-    c->extras.gpt_dir = dir;
-  }
-  ~ExtrasScope() { c->extras = rrtmgpnn_context::SolverExtras{}; }
-};
-int lw_ds_check(int nmus, const float *lw_Ds)
-{
-  if (lw_Ds && nmus != 1)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "rte_lw: providing lw_Ds incompatible with specifying n_gauss_angles");
-  return RRTMGPNN_OK;
-}
-}  // namespace
-
-int rrtmgpnn_lw_solver_noscat_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
-                                  const float *Ds, const float *weights, const float *lw_Ds, const float *inc_flux,
-                                  const float *tau, const float *lay_source, const float *lev_source,
-                                  const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn,
-                                  float *gpt_flux_up, float *gpt_flux_dn)
-{
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (int rc = lw_ds_check(nmus, lw_Ds)) return rc;
-  ExtrasScope x(ctx, lw_Ds, gpt_flux_up, gpt_flux_dn, nullptr);
-  return rrtmgpnn_lw_solver_noscat(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, lay_source,
-                                   lev_source, sfc_emis_gpt, sfc_source, flux_up, flux_dn);
-}
-
-int rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
-                                         const float *Ds, const float *weights, const float *lw_Ds,
-                                         const float *inc_flux, const float *tau, const float *pfrac, int nbnd,
-                                         int nPlanckTemp, const float *tlay, const float *tlev, const float *tsfc,
-                                         int sfc_lay, const int *band_lims_gpt, float temp_ref_min,
-                                         float totplnk_delta, const float *totplnk, int emis_by_band,
-                                         const float *sfc_emis, float *flux_up, float *flux_dn, float *gpt_flux_up,
-                                         float *gpt_flux_dn)
-{
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (int rc = lw_ds_check(nmus, lw_Ds)) return rc;
-  ExtrasScope x(ctx, lw_Ds, gpt_flux_up, gpt_flux_dn, nullptr);
-  return rrtmgpnn_lw_solver_noscat_planck(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, pfrac,
-                                          nbnd, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, band_lims_gpt, temp_ref_min,
-                                          totplnk_delta, totplnk, emis_by_band, sfc_emis, flux_up, flux_dn);
-}
-
-int rrtmgpnn_sw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
-                                   const float *inc_flux, const float *inc_flux_dif, const float *tau,
-                                   const float *ssa, const float *g, const float *mu0, const float *sfc_alb_dir_gpt,
-                                   const float *sfc_alb_dif_gpt, float *flux_up, float *flux_dn, float *flux_dir,
-                                   float *gpt_flux_up, float *gpt_flux_dn, float *gpt_flux_dir)
-{
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  ExtrasScope x(ctx, nullptr, gpt_flux_up, gpt_flux_dn, gpt_flux_dir);
-  return rrtmgpnn_sw_solver_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0,
-                                    sfc_alb_dir_gpt, sfc_alb_dif_gpt, flux_up, flux_dn, flux_dir);
-}
-
-int rrtmgpnn_sw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                              const float *tau, const float *mu0, float *flux_dir)
-{
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  if (!inc_flux || !tau || !mu0 || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
-    return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: bad argument");
-  return launch_sw_noscat(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis_gpt, flux_up, flux_dn};
+  return lw_1rescl(ctx, p, ssa, g, lay_source, lev_source, sfc_source, nullptr, nullptr);
 }
 
 int rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
@@ -985,11 +984,17 @@ int rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int
                                   const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn,
                                   float *gpt_flux_up, float *gpt_flux_dn)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  ExtrasScope x(ctx, nullptr, gpt_flux_up, gpt_flux_dn, nullptr);
-  return rrtmgpnn_lw_solver_1rescl(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, ssa, g,
-                                   lay_source, lev_source, sfc_emis_gpt, sfc_source, flux_up, flux_dn);
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis_gpt, flux_up, flux_dn};
+  return lw_1rescl(ctx, p, ssa, g, lay_source, lev_source, sfc_source, gpt_flux_up, gpt_flux_dn);
+}
+
+int rrtmgpnn_lw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                               const float *inc_flux, const float *tau, const float *ssa, const float *g,
+                               const float *lev_source, const float *sfc_emis_gpt, const float *sfc_source,
+                               float *flux_up, float *flux_dn)
+{
+  return lw_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis_gpt, sfc_source,
+                    flux_up, flux_dn, nullptr, nullptr);
 }
 
 int rrtmgpnn_lw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
@@ -997,21 +1002,42 @@ int rrtmgpnn_lw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *lev_source, const float *sfc_emis_gpt, const float *sfc_source,
                                    float *flux_up, float *flux_dn, float *gpt_flux_up, float *gpt_flux_dn)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  ExtrasScope x(ctx, nullptr, gpt_flux_up, gpt_flux_dn, nullptr);
-  return rrtmgpnn_lw_solver_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis_gpt,
-                                    sfc_source, flux_up, flux_dn);
+  return lw_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis_gpt, sfc_source,
+                    flux_up, flux_dn, gpt_flux_up, gpt_flux_dn);
+}
+
+int rrtmgpnn_sw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                               const float *inc_flux, const float *inc_flux_dif, const float *tau, const float *ssa,
+                               const float *g, const float *mu0, const float *sfc_alb_dir_gpt,
+                               const float *sfc_alb_dif_gpt, float *flux_up, float *flux_dn, float *flux_dir)
+{
+  const Sw2Stream p{ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
+                    sfc_alb_dif_gpt, nullptr, nullptr, nullptr, nullptr, flux_up, flux_dn, flux_dir};
+  return sw_2stream(ctx, p, nullptr, nullptr, nullptr);
+}
+
+int rrtmgpnn_sw_solver_2stream_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                   const float *inc_flux, const float *inc_flux_dif, const float *tau,
+                                   const float *ssa, const float *g, const float *mu0, const float *sfc_alb_dir_gpt,
+                                   const float *sfc_alb_dif_gpt, float *flux_up, float *flux_dn, float *flux_dir,
+                                   float *gpt_flux_up, float *gpt_flux_dn, float *gpt_flux_dir)
+{
+  const Sw2Stream p{ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
+                    sfc_alb_dif_gpt, nullptr, nullptr, nullptr, nullptr, flux_up, flux_dn, flux_dir};
+  return sw_2stream(ctx, p, gpt_flux_up, gpt_flux_dn, gpt_flux_dir);
+}
+
+int rrtmgpnn_sw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
+                              const float *tau, const float *mu0, float *flux_dir)
+{
+  return sw_noscat(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir, nullptr);
 }
 
 int rrtmgpnn_sw_solver_noscat_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
                                   const float *inc_flux, const float *tau, const float *mu0, float *flux_dir,
                                   float *gpt_flux_dir)
 {
-  RRTMGPNN_BYBAND(ctx, ngpt);
-  if (int rc = check_ctx(ctx)) return rc;
-  ExtrasScope x(ctx, nullptr, nullptr, nullptr, gpt_flux_dir);
-  return rrtmgpnn_sw_solver_noscat(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir);
+  return sw_noscat(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir, gpt_flux_dir);
 }
 
 int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
@@ -1021,7 +1047,8 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
                                    float *flux_dn, float *flux_dir)
 {
-  RRTMGPNN_BYBAND_MASK("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol);
+  SolverExtras ex;
+  if (int rc = take_byband_or_mask("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol, ex)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !tau_bnd || !ssa_bnd || !g_bnd || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt ||
       !flux_up || !flux_dn || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
@@ -1029,8 +1056,9 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
   BandArgs b;
   if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
   if (int rc = bands_cover(b, ngpt)) return rc;
-  return launch_sw_2stream(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
-                           sfc_alb_dif_gpt, &b, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir);
+  const Sw2Stream p{ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
+                    sfc_alb_dif_gpt, &b, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir};
+  return launch_sw_2stream(ctx, ex, p);
 }
 
 int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
@@ -1435,8 +1463,9 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      const float *g_bnd, float *toa_flux, float *sfc_alb_gpt, float *mu0,
                                      float *flux_up, float *flux_dn, float *flux_dir)
 {
-  RRTMGPNN_BYBAND_MASK("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol);
-  if (ctx && ctx->extras.mask_bits && nbnd <= 0)
+  SolverExtras ex;
+  if (int rc = take_byband_or_mask("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol, ex)) return rc;
+  if (ex.mask_bits && nbnd <= 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream_rfmip: a cloud mask needs the band increment (nbnd > 0)");
   if (int rc = check_ctx(ctx)) return rc;
   if (!solar_source || !tsi || !sfc_alb || !sza || !tau || !ssa || !toa_flux || !sfc_alb_gpt || !mu0 || !flux_up ||
@@ -1451,9 +1480,9 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
     if (int rc = bands_cover(b, ngpt)) return rc;
   }
   // inc_flux / mu0 / albedos: the scratch arrays, which the solver reads only when it does not form them itself
-  return launch_sw_2stream(ctx, ngpt, nlay, ncol, top_at_1, toa_flux, nullptr, tau, ssa, g, mu0, sfc_alb_gpt,
-                           sfc_alb_gpt, nbnd > 0 ? &b : nullptr, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir,
-                           &bc);
+  const Sw2Stream p{ngpt, nlay, ncol, top_at_1, toa_flux, nullptr, tau, ssa, g, mu0, sfc_alb_gpt, sfc_alb_gpt,
+                    nbnd > 0 ? &b : nullptr, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir};
+  return launch_sw_2stream(ctx, ex, p, &bc);
 }
 
 // ---- data files: RBIN, classic netCDF, netCDF-4 (datafile.cpp) ----

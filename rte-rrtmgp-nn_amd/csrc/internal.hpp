@@ -48,6 +48,56 @@ struct BandArgs {
   int nbnd;
 };
 
+// A solver call's options, beyond the problem itself.  The entry (api.cpp) builds one on its stack -- the by-band part
+// from the context's armed request (take_requests), the rest from its own arguments -- and hands it to the launchers,
+// which read it and nothing else: a launcher's signature says that it honours options, its body which.
+struct SolverExtras {
+  // rte_lw's lw_Ds and ty_fluxes_flexible's g-point outputs, (ngpt, nlay+1, ncol) each (the *_gpt entries)
+  const float *lw_Ds = nullptr;
+  float *gpt_up = nullptr, *gpt_dn = nullptr, *gpt_dir = nullptr;
+  // ty_fluxes_byband's by-band outputs, (nbnd, nlay+1, ncol) each, and their band limits
+  // (rrtmgpnn_solver_request_byband); every solver launch has by-band instances
+  float *bnd_up = nullptr, *bnd_dn = nullptr, *bnd_dir = nullptr;
+  BandArgs bnd{};
+  bool byband() const { return bnd_up || bnd_dn || bnd_dir; }
+  // McICA: the packed cloud mask (nw, nlay, ncol), nw = ceil(ngpt / 32), of the fused band increment
+  // (rrtmgpnn_solver_request_cloud_mask, or the _clr_all_mcica entry's argument); only the _planck_inc, _clr_all_mcica,
+  // _2stream_inc and _2stream_rfmip entries have masked instances
+  const uint32_t *mask_bits = nullptr;
+};
+
+// Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction (a kernel argument)
+struct LwPlanck {
+  const float *tlay, *tlev, *tsfc, *totplnk;
+  int ntemp, sfc_lay;
+  int emis_by_band;  // sfc_emis is (nbnd, ncol) and expanded in-kernel (rte_lw's expand)
+  float tmin, tdelta;
+};
+
+// The launchers' problem descriptions: plain aggregates, brace-initialised by the entries.
+// LW without scattering; sfc_emis is per g-point, or per band on the fused-Planck path with pl.emis_by_band
+struct LwNoscat {
+  int ngpt, nlay, ncol, top_at_1, nmus;
+  const float *Ds, *wts, *inc_flux, *tau, *sfc_emis;
+  float *flux_up, *flux_dn;
+};
+// ... its sources on the fused-Planck path; tau_bnd (nbnd, nlay, ncol), or null: the band increment of tau
+struct LwPlanckIn {
+  LwPlanck pl;
+  const float *pfrac;
+  BandArgs bands;
+  const float *tau_bnd;
+};
+// SW two-stream; bands != nullptr: the atmosphere is incremented by the band-resolved 2str set (tau, ssa, g)_bnd
+// in-kernel
+struct Sw2Stream {
+  int ngpt, nlay, ncol, top_at_1;
+  const float *inc_flux, *inc_flux_dif, *tau, *ssa, *g, *mu0, *alb_dir, *alb_dif;
+  const BandArgs *bands;
+  const float *tau_bnd, *ssa_bnd, *g_bnd;
+  float *flux_up, *flux_dn, *flux_dir;
+};
+
 }  // namespace rrtmgpnn
 
 // Device workspace owned by a context: grown on demand, never shrunk, so steady-state calls
@@ -72,22 +122,6 @@ struct rrtmgpnn_context {
     const int p[8] = {kind, ak, ah1, ah2, bk, bh1, bh2, flags};
     for (int i = 0; i < 8; i++) mlp_path[i] = p[i];
   }
-  // Per-call solver extras, set by the *_gpt entry points for the duration of one call (rte_lw's lw_Ds and
-  // ty_fluxes_flexible's g-point outputs, (ngpt, nlay+1, ncol) each); the other entries leave them null.
-  struct SolverExtras {
-    const float *lw_Ds = nullptr;
-    float *gpt_up = nullptr, *gpt_dn = nullptr, *gpt_dir = nullptr;
-    // ty_fluxes_byband's by-band outputs, (nbnd, nlay+1, ncol) each, and their band limits: set from `byband` by the
-    // solver entry that consumes the request (rrtmgpnn_solver_request_byband); every solver launch has by-band
-    // instances
-    float *bnd_up = nullptr, *bnd_dn = nullptr, *bnd_dir = nullptr;
-    rrtmgpnn::BandArgs bnd{};
-    bool byband() const { return bnd_up || bnd_dn || bnd_dir; }
-    // McICA: the packed cloud mask (nw, nlay, ncol), nw = ceil(ngpt / 32), of the fused band increment, set from
-    // `cloud_mask` by the solver entry that consumes the request (rrtmgpnn_solver_request_cloud_mask); only the
-    // _planck_inc, _2stream_inc and _2stream_rfmip entries have masked instances
-    const uint32_t *mask_bits = nullptr;
-  } extras;
   // rrtmgpnn_solver_request_byband: armed for the next solver call on this context, which clears it
   struct BybandRequest {
     bool armed = false;
@@ -250,59 +284,35 @@ int launch_planck_source(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, in
                          const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
                          float temp_ref_min, float totplnk_delta, const float *totplnk, float *sfc_source,
                          float *sfc_source_Jac, float *pfrac, float *lev_source);
-int launch_lw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus, const float *Ds,
-                     const float *wts, const float *inc_flux, const float *tau, const float *lay_source,
-                     const float *lev_source, const float *sfc_emis, const float *sfc_source, float *flux_up,
-                     float *flux_dn);
-int launch_lw_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
-                            const float *Ds, const float *wts, const float *inc_flux, const float *tau,
-                            const float *pfrac, int ntemp, const float *tlay, const float *tlev, const float *tsfc,
-                            int sfc_lay, const BandArgs &bands, float temp_ref_min, float totplnk_delta,
-                            const float *totplnk, bool emis_by_band, const float *sfc_emis, const float *tau_bnd,
-                            float *flux_up, float *flux_dn);
+int launch_lw_noscat(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *lay_source,
+                     const float *lev_source, const float *sfc_source);
+int launch_lw_noscat_planck(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in);
 // clear-sky fluxes (tau) and all-sky fluxes (tau + tau_bnd) of the same columns; dual: one launch of the dual instance
-// where it exists (one angle), else the two instances back to back.  mask_bits (nw, nlay, ncol), or null: the all-sky
-// set's increment is switched per g-point by a McICA mask (the masked dual instance, or the masked single one)
-int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, bool dual, int ngpt, int nlay, int ncol, int top_at_1,
-                                    int nmus, const float *Ds, const float *wts, const float *inc_flux,
-                                    const float *tau, const float *pfrac, int ntemp, const float *tlay,
-                                    const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
-                                    float temp_ref_min, float totplnk_delta, const float *totplnk, bool emis_by_band,
-                                    const float *sfc_emis, const float *tau_bnd, float *flux_up, float *flux_dn,
-                                    float *flux_up_clr, float *flux_dn_clr, const uint32_t *mask_bits = nullptr);
-// bands != nullptr: atmosphere incremented by the band-resolved 2str set (tau, ssa, g)_bnd in-kernel
-int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                      const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,
-                      const float *mu0, const float *alb_dir, const float *alb_dif, const BandArgs *bands,
-                      const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, float *flux_up,
-                      float *flux_dn, float *flux_dir, const SwBc *bc = nullptr);
+// where it exists (one angle), else the two instances back to back.  ex.mask_bits, or null: the all-sky set's
+// increment is switched per g-point by a McICA mask (the masked dual instance, or the masked single one)
+int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex, bool dual, const LwNoscat &p,
+                                    const LwPlanckIn &in, float *flux_up_clr, float *flux_dn_clr);
+// bc: the RFMIP boundary conditions, which overwrite p's inc_flux, mu0 and albedos
+int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p, const SwBc *bc = nullptr);
 // kernels_sw_x2.hip (called by launch_sw_2stream for even ngpt; ws sized by it)
 size_t sw_2stream_x2_layer_planes(bool inc);
-int launch_sw_2stream_x2(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                         const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,
-                         const float *mu0, const float *alb_dir, const float *alb_dif, const BandArgs *bands,
-                         const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, void *ws, float *flux_up,
-                         float *flux_dn, float *flux_dir);
-int launch_sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                     const float *tau, const float *mu0, float *flux_dir);
+int launch_sw_2stream_x2(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws);
+int launch_sw_noscat(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,
+                     const float *inc_flux, const float *tau, const float *mu0, float *flux_dir);
 // kernels_sw_ck.hip (checkpointed passes; called by launch_sw_2stream for even ngpt in mode 3)
 // the checkpointed SW kernel's small-grid instance applies (clear sky, g = 0, no g-point outputs, the grid in one round)
 bool sw_ck_small(const rrtmgpnn_context *ctx, int ngpt, int ncol, bool has_g, bool inc, bool gpt);
 // planes: the large-grid instances' workspace planes (kCkTnNN, kCkTnInc, ...); false after that allocation failed
 size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool inc, bool nn, bool planes = true);
-int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                         const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,
-                         const float *mu0, const float *alb_dir, const float *alb_dif, const BandArgs *bands,
-                         const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, void *ws, float *flux_up,
-                         float *flux_dn, float *flux_dir, bool planes = true, const SwBcDev *bc = nullptr);
+int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws,
+                         bool planes = true, const SwBcDev *bc = nullptr);
 // kernels_lw_scat.hip
-int launch_lw_rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus, const float *Ds,
-                    const float *wts, const float *inc_flux, const float *tau, const float *ssa, const float *g,
-                    const float *lay_source, const float *lev_source, const float *sfc_emis, const float *sfc_source,
-                    float *flux_up, float *flux_dn);
-int launch_lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                      const float *tau, const float *ssa, const float *g, const float *lev_source,
-                      const float *sfc_emis, const float *sfc_source, float *flux_up, float *flux_dn);
+int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *ssa, const float *g,
+                    const float *lay_source, const float *lev_source, const float *sfc_source);
+int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,
+                      const float *inc_flux, const float *tau, const float *ssa, const float *g,
+                      const float *lev_source, const float *sfc_emis, const float *sfc_source, float *flux_up,
+                      float *flux_dn);
 int launch_expand(rrtmgpnn_context *ctx, int nband, int ngpt, int ncol, const BandArgs &bands, const float *in,
                   float *out);
 // kernels_fluxes.hip: sum_byband of a g-point array (ngpt, nlev, ncol) into (nbnd, nlev, ncol)

@@ -314,23 +314,21 @@ __global__ void __launch_bounds__(256) lw_2stream_kernel(int ngpt, int nlay, int
   }
 }
 
-int launch_lw_rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus, const float *Ds,
-                    const float *wts, const float *inc_flux, const float *tau, const float *ssa, const float *g,
-                    const float *lay_source, const float *lev_source, const float *sfc_emis, const float *sfc_source,
-                    float *flux_up, float *flux_dn)
+int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *ssa, const float *g,
+                    const float *lay_source, const float *lev_source, const float *sfc_source)
 {
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol, nmus = p.nmus;
   if (ncol == 0) return RRTMGPNN_OK;
   if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
   if (ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
   LwAngles a{};
   a.nmus = nmus;
-  for (int i = 0; i < nmus; i++) { a.D[i] = Ds[i]; a.w[i] = wts[i]; }
+  for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
   const int threads = (ngpt + 63) / 64 * 64;
   const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)kScatRing * ngpt + (size_t)2 * (nlay + 1) * 4);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
   void *ws = nullptr;
   if (int rc = ctx->workspace(sizeof(float) * (nmus > 1 ? 4 : 2) * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
-  const auto &ex = ctx->extras;
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
   if (ex.byband() && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
@@ -338,20 +336,21 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
                                           "reduces g-point fluxes)");
   if (ex.byband())
-    hipLaunchKernelGGL(lw_rescl_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
-                       a, inc_flux, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up,
-                       flux_dn, ex.gpt_up, ex.gpt_dn, band_out(ctx));
+    hipLaunchKernelGGL(lw_rescl_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1,
+                       a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
+                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, band_out(ex));
   else
-    hipLaunchKernelGGL(lw_rescl_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
-                       a, inc_flux, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up,
-                       flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{});
+    hipLaunchKernelGGL(lw_rescl_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1,
+                       a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
+                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{});
   RRTMGPNN_LAUNCH_CHECK("lw_rescl_kernel");
   return RRTMGPNN_OK;
 }
 
-int launch_lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                      const float *tau, const float *ssa, const float *g, const float *lev_source,
-                      const float *sfc_emis, const float *sfc_source, float *flux_up, float *flux_dn)
+int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,
+                      const float *inc_flux, const float *tau, const float *ssa, const float *g,
+                      const float *lev_source, const float *sfc_emis, const float *sfc_source, float *flux_up,
+                      float *flux_dn)
 {
   if (ncol == 0) return RRTMGPNN_OK;
   if (ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw two-stream solver: more than 256 g-points");
@@ -360,7 +359,6 @@ int launch_lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw two-stream solver: too many layers for LDS partials");
   void *ws = nullptr;
   if (int rc = ctx->workspace(sizeof(float) * 2 * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
-  const auto &ex = ctx->extras;
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
   if (ex.byband() && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
@@ -370,7 +368,7 @@ int launch_lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
   if (ex.byband())
     hipLaunchKernelGGL(lw_2stream_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1,
                        inc_flux, tau, ssa, g, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up, flux_dn,
-                       ex.gpt_up, ex.gpt_dn, band_out(ctx));
+                       ex.gpt_up, ex.gpt_dn, band_out(ex));
   else
     hipLaunchKernelGGL(lw_2stream_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol,
                        top_at_1, inc_flux, tau, ssa, g, lev_source, sfc_emis, sfc_source, (float *)ws, flux_up, flux_dn,

@@ -520,19 +520,18 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   }
 }
 
-// up_clr / dn_clr (both or neither; kFused && kInc, one angle, no extras): the dual instance, clear-sky fluxes beside
-// the all-sky ones
+// lay_source / lev_source / sfc_source: the unfused path's sources (kFused: formed in-kernel from `in`).
+// up_clr / dn_clr (both or neither; kFused && kInc, one angle, no extras but the mask): the dual instance, clear-sky
+// fluxes beside the all-sky ones
 template <bool kFused, bool kInc>
-static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
-                          const float *Ds, const float *wts, const float *inc_flux, const float *tau,
-                          const float *lay_or_pfrac, const float *lev_source, const float *sfc_emis,
-                          const float *sfc_source, const LwPlanck &pl, const BandArgs &bands, const float *tau_bnd,
-                          float *flux_up, float *flux_dn, float *up_clr = nullptr, float *dn_clr = nullptr)
+static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *lay_source,
+                          const float *lev_source, const float *sfc_source, const LwPlanckIn &in,
+                          float *up_clr = nullptr, float *dn_clr = nullptr)
 {
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol, nmus = p.nmus;
   if (ncol == 0) return RRTMGPNN_OK;
   if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
   if (ngpt > kLwMaxG) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: too many g-points");
-  const auto &ex = ctx->extras;
   if (ex.lw_Ds && nmus != 1) return fail(RRTMGPNN_ERR_ARGUMENT, "rte_lw: providing lw_Ds incompatible with specifying n_gauss_angles");
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
@@ -549,11 +548,11 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
   a.nmus = nmus;
   a.Dg = ex.lw_Ds;
   a.rad = gpt && nmus == 1;
-  for (int i = 0; i < nmus; i++) { a.D[i] = Ds[i]; a.w[i] = wts[i]; }
+  for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
   int threads = (ngpt + 63) / 64 * 64;
   size_t lds = sizeof(float) * (kExpTabFloats + (size_t)(dual ? 2 * kRingDual : kRing) * lw_ring_stride(ngpt) +
                                 (size_t)(dual ? 4 : 2) * (nlay + 1) * 4);
-  if (kFused) lds += sizeof(float) * lw_btab_floats(bands.nbnd, nlay);
+  if (kFused) lds += sizeof(float) * lw_btab_floats(in.bands.nbnd, nlay);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: too many layers for LDS partials");
   // per-g accumulators: the caller's g-point arrays, or (several angles) the context workspace
   float *gdn = ex.gpt_dn, *gup = ex.gpt_up;
@@ -568,11 +567,12 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
     gcs = 2 * nv;
   }
   constexpr int PF = kFused ? kLwfPf : kLwPf;
-  const BandOut bo = bb ? band_out(ctx) : BandOut{};
+  const BandOut bo = bb ? band_out(ex) : BandOut{};
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, top_at_1, a, inc_flux, tau,
-                       lay_or_pfrac, kFused ? lay_or_pfrac : lev_source, sfc_emis, sfc_source, pl, bands, tau_bnd, gdn,
-                       gup, gcs, flux_up, flux_dn, bo, ex.mask_bits);
+    const float *src = kFused ? in.pfrac : lay_source;
+    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
+                       p.tau, src, kFused ? src : lev_source, p.sfc_emis, sfc_source, in.pl, in.bands,
+                       kInc ? in.tau_bnd : nullptr, gdn, gup, gcs, p.flux_up, p.flux_dn, bo, ex.mask_bits);
   };
   const bool multi = nmus > 1 || gpt;
   if constexpr (kFused && kInc) {
@@ -615,64 +615,35 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
   return RRTMGPNN_OK;
 }
 
-int launch_lw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus, const float *Ds,
-                     const float *wts, const float *inc_flux, const float *tau, const float *lay_source,
-                     const float *lev_source, const float *sfc_emis, const float *sfc_source, float *flux_up,
-                     float *flux_dn)
+int launch_lw_noscat(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *lay_source,
+                     const float *lev_source, const float *sfc_source)
 {
-  LwPlanck pl{};
-  BandArgs b{};
-  return launch_lw_impl<false, false>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, lay_source,
-                                      lev_source, sfc_emis, sfc_source, pl, b, nullptr, flux_up, flux_dn);
+  return launch_lw_impl<false, false>(ctx, ex, p, lay_source, lev_source, sfc_source, LwPlanckIn{});
 }
 
-int launch_lw_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
-                            const float *Ds, const float *wts, const float *inc_flux, const float *tau,
-                            const float *pfrac, int ntemp, const float *tlay, const float *tlev, const float *tsfc,
-                            int sfc_lay, const BandArgs &bands, float temp_ref_min, float totplnk_delta,
-                            const float *totplnk, bool emis_by_band, const float *sfc_emis, const float *tau_bnd,
-                            float *flux_up, float *flux_dn)
+int launch_lw_noscat_planck(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in)
 {
-  LwPlanck pl{tlay, tlev, tsfc, totplnk, ntemp, sfc_lay, emis_by_band ? 1 : 0, temp_ref_min, totplnk_delta};
-  if (tau_bnd)
-    return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
-                                      sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn);
-  return launch_lw_impl<true, false>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
-                                     sfc_emis, nullptr, pl, bands, nullptr, flux_up, flux_dn);
+  if (in.tau_bnd) return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
+  return launch_lw_impl<true, false>(ctx, ex, p, nullptr, nullptr, nullptr, in);
 }
 
 // rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 on the fused-Planck path: clear-sky fluxes from tau, all-sky
 // fluxes from tau + tau_bnd(band).  dual: one launch of the dual instance (one angle only); otherwise the clear and
-// the incremented instance back to back on the context's stream.  Identical bits either way.  mask_bits (the
-// _clr_all_mcica entry): the increment is a McICA-sampled cloud, in the dual launch or in the second of the two.
-int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, bool dual, int ngpt, int nlay, int ncol, int top_at_1,
-                                    int nmus, const float *Ds, const float *wts, const float *inc_flux,
-                                    const float *tau, const float *pfrac, int ntemp, const float *tlay,
-                                    const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
-                                    float temp_ref_min, float totplnk_delta, const float *totplnk, bool emis_by_band,
-                                    const float *sfc_emis, const float *tau_bnd, float *flux_up, float *flux_dn,
-                                    float *flux_up_clr, float *flux_dn_clr, const uint32_t *mask_bits)
+// the incremented instance back to back on the context's stream.  Identical bits either way.  ex.mask_bits (the
+// _clr_all_mcica entry): the increment is a McICA-sampled cloud, in the dual launch or in the second of the two -- the
+// clear launch of the pair carries no increment to switch, so it gets the extras without the mask.
+int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex, bool dual, const LwNoscat &p,
+                                    const LwPlanckIn &in, float *flux_up_clr, float *flux_dn_clr)
 {
-  LwPlanck pl{tlay, tlev, tsfc, totplnk, ntemp, sfc_lay, emis_by_band ? 1 : 0, temp_ref_min, totplnk_delta};
-  // mask_bits (the _clr_all_mcica entry): armed in the per-call extras for the launches that increment, and for
-  // those alone -- the clear launch of the pair carries no increment to switch
-  struct MaskArm {
-    rrtmgpnn_context *c;
-    MaskArm(rrtmgpnn_context *ctx, const uint32_t *m) : c(ctx) { c->extras.mask_bits = m; }
-    ~MaskArm() { c->extras.mask_bits = nullptr; }
-  };
-  if (dual && nmus == 1) {
-    MaskArm arm(ctx, mask_bits);
-    return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
-                                      sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn, flux_up_clr,
-                                      flux_dn_clr);
-  }
-  if (int rc = launch_lw_impl<true, false>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac,
-                                           nullptr, sfc_emis, nullptr, pl, bands, nullptr, flux_up_clr, flux_dn_clr))
-    return rc;
-  MaskArm arm(ctx, mask_bits);
-  return launch_lw_impl<true, true>(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, wts, inc_flux, tau, pfrac, nullptr,
-                                    sfc_emis, nullptr, pl, bands, tau_bnd, flux_up, flux_dn);
+  if (dual && p.nmus == 1)
+    return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in, flux_up_clr, flux_dn_clr);
+  SolverExtras clear_ex = ex;
+  clear_ex.mask_bits = nullptr;
+  LwNoscat clear = p;
+  clear.flux_up = flux_up_clr;
+  clear.flux_dn = flux_dn_clr;
+  if (int rc = launch_lw_impl<true, false>(ctx, clear_ex, clear, nullptr, nullptr, nullptr, in)) return rc;
+  return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -975,49 +946,33 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
   }
 }
 
-template <bool kHasG, bool kInc, bool kGpt = false, bool kBand = false>
-static void sw_launch(rrtmgpnn_context *ctx, size_t lds, int threads, int ngpt, int nlay, int ncol,
-                      int top_at_1, const float *inc_flux, const float *inc_flux_dif, const float *tau,
-                      const float *ssa, const float *g, const float *mu0, const float *alb_dir, const float *alb_dif,
-                      const BandArgs &bands, const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, void *ws,
-                      float *flux_up, float *flux_dn, float *flux_dir)
+int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p, const SwBc *bc)
 {
-  const auto &ex = ctx->extras;
-  hipLaunchKernelGGL((sw_2stream_kernel<kHasG, kInc, kSwPf, kGpt, kBand>), dim3(ncol), dim3(threads), lds,
-                     ctx->stream, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, alb_dir,
-                     alb_dif, bands, tau_bnd, ssa_bnd, g_bnd, (float *)ws, flux_up, flux_dn, flux_dir, ex.gpt_up,
-                     ex.gpt_dn, ex.gpt_dir, kBand ? band_out(ctx) : BandOut{});
-}
-
-int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                      const float *inc_flux_dif, const float *tau, const float *ssa, const float *g, const float *mu0,
-                      const float *alb_dir, const float *alb_dif, const BandArgs *bands, const float *tau_bnd,
-                      const float *ssa_bnd, const float *g_bnd, float *flux_up, float *flux_dn, float *flux_dir,
-                      const SwBc *bc)
-{
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
+  const float *const g = p.g;
   if (ncol == 0) return RRTMGPNN_OK;
   if (ngpt > kSwMaxG) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: too many g-points");
-  const bool inc = bands != nullptr;
+  const bool inc = p.bands != nullptr;
   // Even ngpt: two g-points per lane.  By default the checkpointed kernel (kernels_sw_ck.hip: 0.67 instead of 1.07 GB
   // per launch at C3, whole step C3 -3 %, C4 -1 % against kernels_sw_x2.hip, tools/gpu_ab.sh); mode 2 forces the
   // workspace-plane kernel, mode 1 one g-point per lane (also the odd-ngpt kernel).
   const int mode = ctx->sw_kernel >= 0 ? ctx->sw_kernel : g_sw_kernel_default;
   // g-point outputs (the *_gpt entries) are written by the checkpointed kernel for even ngpt, whatever the mode, and
   // by the one-per-lane kernel for odd ngpt
-  const bool gpt = ctx->extras.gpt_up || ctx->extras.gpt_dn || ctx->extras.gpt_dir;
-  if (gpt && (!ctx->extras.gpt_up || !ctx->extras.gpt_dn || !ctx->extras.gpt_dir))
+  const bool gpt = ex.gpt_up || ex.gpt_dn || ex.gpt_dir;
+  if (gpt && (!ex.gpt_up || !ex.gpt_dn || !ex.gpt_dir))
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: g-point outputs need gpt_flux_up, gpt_flux_dn and gpt_flux_dn_dir");
   if (gpt && inc) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: g-point outputs with a fused increment");
-  const bool bb = ctx->extras.byband();
+  const bool bb = ex.byband();
   if (bb && gpt)
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
                                           "reduces g-point fluxes)");
   const bool ck = (ngpt % 2) == 0 && (mode == 3 || mode == 0 || gpt);
   const bool x2 = !ck && (ngpt % 2) == 0 && mode != 1;
   // McICA (rrtmgpnn_solver_request_cloud_mask): only the checkpointed kernel has masked instances
-  if (ctx->extras.mask_bits && !inc)
+  if (ex.mask_bits && !inc)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
-  if (ctx->extras.mask_bits && (!ck || gpt || bb))
+  if (ex.mask_bits && (!ck || gpt || bb))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask is taken by the checkpointed kernel only (even ngpt, "
                                           "rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band or g-point "
                                           "outputs");
@@ -1030,9 +985,9 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
     if (int rc = launch_sw_boundary(ctx, ngpt, ncol, bc->solar_source, bc->tsi, bc->sfc_alb, bc->sza, bc->toa, bc->alb,
                                     bc->mu0))
       return rc;
-    inc_flux = bc->toa;
-    alb_dir = alb_dif = bc->alb;
-    mu0 = bc->mu0;
+    p.inc_flux = bc->toa;
+    p.alb_dir = p.alb_dif = bc->alb;
+    p.mu0 = bc->mu0;
   }
   void *ws = nullptr;
   const size_t nlp = x2 ? sw_2stream_x2_layer_planes(inc) : (inc ? 3 : 0);
@@ -1055,52 +1010,30 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
     rc = ctx->workspace(sizeof(float) * nws0, &ws);
   }
   if (rc) return rc;
-  if (ck)
-    return launch_sw_2stream_ck(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, alb_dir,
-                                alb_dif, bands, tau_bnd, ssa_bnd, g_bnd, ws, flux_up, flux_dn, flux_dir, planes,
-                                bc ? &bcd : nullptr);
-  if (x2)
-    return launch_sw_2stream_x2(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, alb_dir,
-                                alb_dif, bands, tau_bnd, ssa_bnd, g_bnd, ws, flux_up, flux_dn, flux_dir);
+  if (ck) return launch_sw_2stream_ck(ctx, ex, p, ws, planes, bc ? &bcd : nullptr);
+  if (x2) return launch_sw_2stream_x2(ctx, ex, p, ws);
   const int threads = (ngpt + 63) / 64 * 64;
   const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)3 * kRingSw * ngpt + (size_t)3 * (nlay + 1) * 4);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: too many layers for LDS partials");
   const BandArgs nob{};
-  const BandArgs &b = inc ? *bands : nob;
-  if (bb && inc && g)
-    sw_launch<true, true, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa,
-                                       g, mu0, alb_dir, alb_dif, b, tau_bnd, ssa_bnd, g_bnd, ws, flux_up, flux_dn,
-                                       flux_dir);
-  else if (bb && inc)
-    sw_launch<false, true, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau,
-                                        ssa, g, mu0, alb_dir, alb_dif, b, tau_bnd, ssa_bnd, g_bnd, ws, flux_up,
-                                        flux_dn, flux_dir);
-  else if (bb && g)
-    sw_launch<true, false, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau,
-                                        ssa, g, mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up,
-                                        flux_dn, flux_dir);
-  else if (bb)
-    sw_launch<false, false, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau,
-                                         ssa, g, mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up,
-                                         flux_dn, flux_dir);
-  else if (gpt && g)
-    sw_launch<true, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
-                                 mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up, flux_dn, flux_dir);
-  else if (gpt)
-    sw_launch<false, false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
-                                  mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up, flux_dn, flux_dir);
-  else if (inc && g)
-    sw_launch<true, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
-                          mu0, alb_dir, alb_dif, b, tau_bnd, ssa_bnd, g_bnd, ws, flux_up, flux_dn, flux_dir);
-  else if (inc)
-    sw_launch<false, true>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
-                           mu0, alb_dir, alb_dif, b, tau_bnd, ssa_bnd, g_bnd, ws, flux_up, flux_dn, flux_dir);
-  else if (g)
-    sw_launch<true, false>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
-                           mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up, flux_dn, flux_dir);
-  else
-    sw_launch<false, false>(ctx, lds, threads, ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g,
-                            mu0, alb_dir, alb_dif, b, nullptr, nullptr, nullptr, ws, flux_up, flux_dn, flux_dir);
+  const BandOut bo = bb ? band_out(ex) : BandOut{};
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, p.inc_flux,
+                       p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, inc ? *p.bands : nob,
+                       inc ? p.tau_bnd : nullptr, inc ? p.ssa_bnd : nullptr, inc ? p.g_bnd : nullptr, (float *)ws,
+                       p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bo);
+  };
+  // <kHasG, kInc, kPF, kGpt, kBand>
+  if (bb && inc && g) go(sw_2stream_kernel<true, true, kSwPf, false, true>);
+  else if (bb && inc) go(sw_2stream_kernel<false, true, kSwPf, false, true>);
+  else if (bb && g)   go(sw_2stream_kernel<true, false, kSwPf, false, true>);
+  else if (bb)        go(sw_2stream_kernel<false, false, kSwPf, false, true>);
+  else if (gpt && g)  go(sw_2stream_kernel<true, false, kSwPf, true>);
+  else if (gpt)       go(sw_2stream_kernel<false, false, kSwPf, true>);
+  else if (inc && g)  go(sw_2stream_kernel<true, true, kSwPf>);
+  else if (inc)       go(sw_2stream_kernel<false, true, kSwPf>);
+  else if (g)         go(sw_2stream_kernel<true, false, kSwPf>);
+  else                go(sw_2stream_kernel<false, false, kSwPf>);
   RRTMGPNN_LAUNCH_CHECK("sw_2stream_kernel");
   return RRTMGPNN_OK;
 }
@@ -1173,14 +1106,13 @@ __global__ void __launch_bounds__(1024) sw_noscat_kernel(int ngpt, int nlay, int
   }
 }
 
-int launch_sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                     const float *tau, const float *mu0, float *flux_dir)
+int launch_sw_noscat(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,
+                     const float *inc_flux, const float *tau, const float *mu0, float *flux_dir)
 {
   if (ncol == 0) return RRTMGPNN_OK;
   if (ngpt > 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw_solver_noscat: more than 1024 g-points");
   const int threads = (ngpt + 63) / 64 * 64;
   const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)kNsRing * ngpt);
-  const auto &ex = ctx->extras;
   if (ex.byband() && (ex.bnd_up || ex.bnd_dn))
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: only bnd_flux_dn_dir is an output of the direct-beam solver");
   if (ex.byband() && ex.gpt_dir)
@@ -1188,7 +1120,7 @@ int launch_sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int to
                                           "(rrtmgpnn_sum_byband reduces g-point fluxes)");
   if (ex.byband())
     hipLaunchKernelGGL(sw_noscat_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, top_at_1,
-                       inc_flux, tau, mu0, flux_dir, ex.gpt_dir, band_out(ctx));
+                       inc_flux, tau, mu0, flux_dir, ex.gpt_dir, band_out(ex));
   else
     hipLaunchKernelGGL(sw_noscat_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, top_at_1,
                        inc_flux, tau, mu0, flux_dir, ex.gpt_dir, BandOut{});

@@ -610,20 +610,19 @@ size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool in
 }
 
 // ngpt even and <= 256
-int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                         const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,
-                         const float *mu0, const float *alb_dir, const float *alb_dif, const BandArgs *bands,
-                         const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, void *ws, float *flux_up,
-                         float *flux_dn, float *flux_dir, bool planes, const SwBcDev *bc)
+int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws, bool planes,
+                         const SwBcDev *bc)
 {
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
+  const float *const g = p.g, *const tau_bnd = p.tau_bnd, *const ssa_bnd = p.ssa_bnd, *const g_bnd = p.g_bnd;
+  const BandArgs *const bands = p.bands;
   const int ncb2 = 2 * (ngpt / 2) <= 512 ? 2 : 1;  // two columns per block where 512 lanes hold them
   const BandArgs nob{};
   const BandArgs &b = bands ? *bands : nob;
   const SwBcDev nobc{};  // tsi == NULL: the caller's inc_flux, mu0 and albedos
   const SwBcDev &bcd = bc ? *bc : nobc;
-  const auto &ex = ctx->extras;
   const bool bb = ex.byband();
-  const BandOut bo = bb ? band_out(ctx) : BandOut{};
+  const BandOut bo = bb ? band_out(ex) : BandOut{};
   // npl g-points per lane, ncb columns per block
   auto go = [&](auto kern, const float *tb, const float *sb, const float *gb, int ring = kCkRing, int npl = 2) -> int {
     const int ncb = npl == 2 ? ncb2 : columns_per_block(ngpt);
@@ -635,9 +634,9 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
     if (lds > 160 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: LDS ring exceeds 160 KiB");
     if (lds > 64 * 1024)
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
-    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, top_at_1, ncb, inc_flux, inc_flux_dif,
-                       tau, ssa, g, mu0, alb_dir, alb_dif, b, tb, sb, gb, (float *)ws, flux_up, flux_dn, flux_dir,
-                       ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits);
+    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
+                       p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tb, sb, gb, (float *)ws,
+                       p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
@@ -675,9 +674,7 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
     return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, true>, tau_bnd,
               ssa_bnd, g_bnd);
   }
-  if (ex.gpt_up || ex.gpt_dn || ex.gpt_dir) {  // ty_fluxes_flexible g-point outputs
-    if (!ex.gpt_up || !ex.gpt_dn || !ex.gpt_dir)
-      return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: g-point outputs need gpt_flux_up, gpt_flux_dn and gpt_flux_dn_dir");
+  if (ex.gpt_up || ex.gpt_dn || ex.gpt_dir) {  // ty_fluxes_flexible g-point outputs: all three (launch_sw_2stream)
     if (bands) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: g-point outputs with a fused increment");
     if (g) return go(sw_2stream_ck_kernel<true, false, kCkK, true>, nullptr, nullptr, nullptr);
     return go(sw_2stream_ck_kernel<false, false, kCkK, true>, nullptr, nullptr, nullptr);

@@ -305,12 +305,11 @@ __global__ void __launch_bounds__(512, kSw2Waves)
 size_t sw_2stream_x2_layer_planes(bool) { return 0; }
 
 // ngpt even and <= 256; workspace: 4 level planes + sw_2stream_x2_layer_planes(inc) layer planes
-int launch_sw_2stream_x2(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, const float *inc_flux,
-                         const float *inc_flux_dif, const float *tau, const float *ssa, const float *g,
-                         const float *mu0, const float *alb_dir, const float *alb_dif, const BandArgs *bands,
-                         const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, void *ws, float *flux_up,
-                         float *flux_dn, float *flux_dir)
+int launch_sw_2stream_x2(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws)
 {
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
+  const float *const g = p.g, *const tau_bnd = p.tau_bnd, *const ssa_bnd = p.ssa_bnd, *const g_bnd = p.g_bnd;
+  const BandArgs *const bands = p.bands;
   // Columns per block: 2 (224 g-points: 224 lanes in 4 waves, 32 idle, a 32 KB ring).  Four columns fill 7 waves
   // exactly and were 5 % faster alone at C4, but in the overlapped step the smaller blocks share the CUs better with
   // the LW chain: whole step C3 -1.7 %, C4 -3.5 % (tools/ab_env.sh RRTMGPNN_LIB).
@@ -322,14 +321,15 @@ int launch_sw_2stream_x2(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, in
   const BandArgs &b = bands ? *bands : nob;
   const dim3 grid((ncol + ncb - 1) / ncb), block(threads);
   constexpr int PF = kSw2Pf, PFN = kSw2PfNoG, PFI = kSw2PfInc;
-  const bool bb = ctx->extras.byband();
-  const BandOut bo = bb ? band_out(ctx) : BandOut{};
+  const bool bb = ex.byband();
+  const BandOut bo = bb ? band_out(ex) : BandOut{};
   auto go = [&](auto kern, const float *tb, const float *sb, const float *gb) -> int {
     // rings past 64 KiB (4 columns of 224 g-points: 64.5 KiB) need the dynamic-LDS limit raised (per device)
     if (lds > 64 * 1024)
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
-    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, top_at_1, ncb, inc_flux, inc_flux_dif,
-                       tau, ssa, g, mu0, alb_dir, alb_dif, b, tb, sb, gb, (float *)ws, flux_up, flux_dn, flux_dir, bo);
+    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
+                       p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tb, sb, gb, (float *)ws,
+                       p.flux_up, p.flux_dn, p.flux_dir, bo);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_x2_kernel");
     return RRTMGPNN_OK;
   };

@@ -70,14 +70,6 @@ __device__ __forceinline__ float interp1d(float val, float offset, float delta, 
   return lo + frac * (hi - lo);
 }
 
-// Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction
-struct LwPlanck {
-  const float *tlay, *tlev, *tsfc, *totplnk;
-  int ntemp, sfc_lay;
-  int emis_by_band;  // sfc_emis is (nbnd, ncol) and expanded in-kernel (rte_lw's expand)
-  float tmin, tdelta;
-};
-
 // fused Planck table size in floats, padded so the ring that follows stays 16-byte aligned
 __host__ __device__ constexpr size_t lw_btab_floats(int nbnd, int nlay) { return ((size_t)nbnd * (2 * nlay + 2) + 3) & ~(size_t)3; }
 
@@ -101,10 +93,7 @@ struct BandOut {
   BandArgs b;
 };
 
-inline BandOut band_out(const rrtmgpnn_context *ctx)
-{
-  return BandOut{ctx->extras.bnd_up, ctx->extras.bnd_dn, ctx->extras.bnd_dir, ctx->extras.bnd};
-}
+inline BandOut band_out(const SolverExtras &ex) { return BandOut{ex.bnd_up, ex.bnd_dn, ex.bnd_dir, ex.bnd}; }
 
 // sum_byband over g-points [lo, hi) of one row; add2: the value is r[i] + r2[i], rounded once per g-point (the SW
 // total down flux from the diffuse and direct rows)
