@@ -587,12 +587,33 @@ int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
  * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, the SW ones on the checkpointed kernel (the default of
  * rrtmgpnn_context_set_sw_kernel: even ngpt; other modes, and odd ngpt, RRTMGPNN_ERR_UNSUPPORTED).  Extents other than
  * the call's: RRTMGPNN_ERR_ARGUMENT; every other solver entry (the plain ones, _clr_all, _clr_all_mcica, which takes
- * its mask as an argument, the _gpt entries, the
- * scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT; together with a by-band request:
- * RRTMGPNN_ERR_UNSUPPORTED.  The pointer becomes a kernel argument and nothing is allocated, so an armed call can be
- * captured in a hipGraph.  No reference counterpart (the reference samples into g-point arrays, draw_samples). */
+ * its mask as an argument, the _gpt entries, the scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT;
+ * together with a separate by-band request: RRTMGPNN_ERR_UNSUPPORTED (rrtmgpnn_solver_request_byband_mcica below
+ * requests the pair).  The pointer becomes a kernel argument and nothing is allocated, so an armed call can be captured
+ * in a hipGraph.  No reference counterpart (the reference samples into g-point arrays, draw_samples). */
 int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
                                        const unsigned int *mask_bits);
+/* By-band fluxes under a McICA-sampled cloud: arms the by-band outputs of rrtmgpnn_solver_request_byband (the same
+ * arrays, band limits and rules: any widths, any start parity, not necessarily every g-point; independent of the cloud
+ * bands of the increment) and the packed mask of rrtmgpnn_solver_request_cloud_mask TOGETHER, as a pair, for the NEXT
+ * solver call on this context; that call clears both whether it succeeds or fails.  The two separate requests beside
+ * each other stay refused (RRTMGPNN_ERR_UNSUPPORTED: a by-band request left from an earlier call beside a fresh mask
+ * is a mistake); this entry states the pair.  A later separate rrtmgpnn_solver_request_byband or
+ * rrtmgpnn_solver_request_cloud_mask replaces its half and drops the pairing.
+ * RRTMGPNN_ERR_ARGUMENT, with nothing armed and whatever was armed cleared: mask_bits NULL, all three outputs NULL,
+ * ngpt < 1, nlay < 1, ncol < 0, nbnd outside 1..64, band limits outside [1, ngpt] or first > last.
+ * Honoured by rrtmgpnn_lw_solver_noscat_planck_inc (every nmus; bnd_flux_dir must be NULL: RRTMGPNN_ERR_ARGUMENT),
+ * rrtmgpnn_sw_solver_2stream_inc and rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, the SW ones on the checkpointed
+ * kernel (other modes of rrtmgpnn_context_set_sw_kernel, odd ngpt: RRTMGPNN_ERR_UNSUPPORTED).  Mask extents other than
+ * the call's: RRTMGPNN_ERR_ARGUMENT.  Every entry that refuses a cloud mask refuses the pair and clears it.
+ * The by-band values are those of the _inc entries with a by-band request (one angle: the float32 terms the broadband
+ * sum adds; SW: up, total down, direct), on the sampled optical properties: bit for bit rrtmgpnn_draw_samples +
+ * rrtmgpnn_increment + the plain solver with rrtmgpnn_solver_request_byband.  The call's broadband fluxes are bit for
+ * bit those of the same masked call without by-band outputs.  Nothing is allocated and the pointers become kernel
+ * arguments, so an armed call can be captured in a hipGraph.  No reference counterpart. */
+int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
+                                         float *bnd_flux_dn, float *bnd_flux_dir, int ngpt, int nlay, int ncol,
+                                         const unsigned int *mask_bits);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */
 int rrtmgpnn_delta_scale_2str(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);

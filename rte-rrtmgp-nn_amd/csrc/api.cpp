@@ -149,14 +149,18 @@ static int take_byband(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
   return RRTMGPNN_OK;
 }
 
-// the three that honour it: the mask against the call's extents, then into the call's extras
+// the three that honour it, alone or paired with by-band outputs: the mask against the call's extents, then into the
+// call's extras
 static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
   if (rq.byband_rc) return rq.byband_rc;
   if (!rq.mask.armed) return RRTMGPNN_OK;
-  if (rq.byband)
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a cloud mask together with by-band outputs");
+  // both armed: only as the pair rrtmgpnn_solver_request_byband_mcica states (a by-band request left over from an
+  // earlier call beside a fresh mask is not one)
+  if (rq.byband && !rq.mask.paired)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a cloud mask together with by-band outputs, requested "
+                                                               "separately (solver_request_byband_mcica requests the pair)");
   if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
                                                             "are not this call's");
@@ -1066,6 +1070,7 @@ int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *b
 {
   if (int rc = check_ctx(ctx)) return rc;
   ctx->byband = rrtmgpnn_context::BybandRequest{};
+  ctx->cloud_mask.paired = false;  // a by-band half of its own: no longer the pair of solver_request_byband_mcica
   if (!bnd_flux_up && !bnd_flux_dn && !bnd_flux_dir) return RRTMGPNN_OK;  // nothing wanted: nothing armed
   if (nbnd < 1 || nbnd > kMaxBands || !band_lims_gpt)
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband: band limits: need 1..64 bands");
@@ -1092,6 +1097,38 @@ int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_cloud_mask: bad extents");
   auto &rq = ctx->cloud_mask;
   rq.armed = true;
+  rq.ngpt = ngpt;
+  rq.nlay = nlay;
+  rq.ncol = ncol;
+  rq.bits = mask_bits;
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
+                                         float *bnd_flux_dn, float *bnd_flux_dir, int ngpt, int nlay, int ncol,
+                                         const unsigned int *mask_bits)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->byband = rrtmgpnn_context::BybandRequest{};
+  ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+  if (!mask_bits) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: mask_bits is null");
+  if (!bnd_flux_up && !bnd_flux_dn && !bnd_flux_dir)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: no by-band output");
+  if (ngpt < 1 || nlay < 1 || ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: bad extents");
+  if (nbnd < 1 || nbnd > kMaxBands || !band_lims_gpt)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: band limits: need 1..64 bands");
+  for (int i = 0; i < nbnd; i++)
+    if (band_lims_gpt[2 * i] < 1 || band_lims_gpt[2 * i + 1] > ngpt || band_lims_gpt[2 * i] > band_lims_gpt[2 * i + 1])
+      return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: band limits out of range [1, ngpt]");
+  auto &bb = ctx->byband;
+  bb.armed = true;
+  bb.up = bnd_flux_up;
+  bb.dn = bnd_flux_dn;
+  bb.dir = bnd_flux_dir;
+  bb.nbnd = nbnd;
+  std::memcpy(bb.lims, band_lims_gpt, sizeof(int) * 2 * nbnd);
+  auto &rq = ctx->cloud_mask;
+  rq.armed = rq.paired = true;
   rq.ngpt = ngpt;
   rq.nlay = nlay;
   rq.ncol = ncol;

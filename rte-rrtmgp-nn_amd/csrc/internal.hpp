@@ -61,8 +61,9 @@ struct SolverExtras {
   BandArgs bnd{};
   bool byband() const { return bnd_up || bnd_dn || bnd_dir; }
   // McICA: the packed cloud mask (nw, nlay, ncol), nw = ceil(ngpt / 32), of the fused band increment
-  // (rrtmgpnn_solver_request_cloud_mask, or the _clr_all_mcica entry's argument); only the _planck_inc, _clr_all_mcica,
-  // _2stream_inc and _2stream_rfmip entries have masked instances
+  // (rrtmgpnn_solver_request_cloud_mask / _byband_mcica, or the _clr_all_mcica entry's argument); only the _planck_inc,
+  // _clr_all_mcica, _2stream_inc and _2stream_rfmip entries have masked instances, the three that take a request also
+  // with by-band outputs
   const uint32_t *mask_bits = nullptr;
 };
 
@@ -132,6 +133,9 @@ struct rrtmgpnn_context {
   // rrtmgpnn_solver_request_cloud_mask: armed for the next solver call on this context, which clears it
   struct CloudMaskRequest {
     bool armed = false;
+    // armed together with the by-band request by rrtmgpnn_solver_request_byband_mcica: the pair is meant.  A later
+    // separate request of either half drops it
+    bool paired = false;
     int ngpt = 0, nlay = 0, ncol = 0;
     const uint32_t *bits = nullptr;
   } cloud_mask;

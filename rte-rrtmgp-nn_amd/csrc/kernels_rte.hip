@@ -149,7 +149,9 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // word g / 32 of cmask (nw, nlay, ncol) switches tau_bnd on or off for g-point g, tau + (bit ? tau_bnd(band) : 0) --
 // draw_samples (extensions/cloud_optics/mo_cloud_sampling.F90:291-307) and increment_1scalar_by_1scalar
 // (rte/kernels/mo_optical_props_kernels.F90:109-121) in the one add of kInc.  One mask word per layer per lane joins that
-// layer's prefetch.  The instances that run without a request hold no trace of it.
+// layer's prefetch.  The instances that run without a request hold no trace of it.  With kBand
+// (rrtmgpnn_solver_request_byband_mcica) the by-band sums are those of the sampled columns: the mask acts where tau is
+// read, the band walk where the ring rows are flushed, and neither knows of the other.
 //
 // kMask with kDual (rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica): the all-sky radiance takes the masked increment,
 // the clear one the bare tau; rings, flush and outputs are the dual instance's.  kMaskS (ngpt % 64 == 0, cmask 8-byte
@@ -168,7 +170,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
                                            const uint32_t *__restrict__ cmask)
 {
   constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
-  static_assert(!kMask || (kInc && !kBand), "the cloud mask switches the fused band increment");
+  static_assert(!kMask || (kInc && (!kBand || !kDual)), "the cloud mask switches the fused band increment");
   static_assert(!kMaskS || (kMask && kDual), "the wave-uniform mask pair is the dual masked instance's");
   using mask_t = std::conditional_t<kMaskS, uint64_t, uint32_t>;  // one layer's mask: the wave's pair, or the lane's word
   static_assert(kR % kPF == 0, "prefetch depth must divide the ring");
@@ -337,7 +339,13 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   float *pdn = part, *pup = part + (size_t)(kDual ? 2 : 1) * nlev * 4;
   const int dl_dn = top_at_1 ? 1 : -1;  // level index step going down
 
-  for (int imu = 0; imu < ang.nmus; imu++) {
+  // The one-angle masked by-band instance states its trip count: as a loop over ang.nmus (always 1 in a !kMulti
+  // instance) the compiler hoists the two single-level flushes' LDS addresses out of it and, at the 64-VGPR bound,
+  // spills them across the layer loops (2 VGPRs, 12 bytes of scratch); with the count known they are formed in place.
+  // (Every !kMulti instance runs one angle; stating it for all of them is left as a change of its own, since it moves the
+  // other one-angle instances' register allocation: DESIGN.md section 8.)
+  const int nmus = (kMask && kBand && !kMulti) ? 1 : ang.nmus;
+  for (int imu = 0; imu < nmus; imu++) {
     // lw_Ds (rte/mo_rte_lw.F90:329-341): the kernel's D(igpt, icol), one angle
     const float D = ang.Dg ? ang.Dg[gc + (size_t)ngpt * icol] : ang.D[imu];
     // radiance -> flux factor inside the broadband sum; with nmus == 1 and ngpt % 4 != 0 the reference
@@ -597,10 +605,13 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   if (ex.mask_bits) {
     // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask)
     if constexpr (kFused && kInc) {
-      if (bb || gpt || ex.lw_Ds)
-        return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: a cloud mask with by-band or g-point outputs or lw_Ds");
-      if (multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true>);
-      else       go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true>);
+      if (gpt || ex.lw_Ds)
+        return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: a cloud mask with g-point outputs or lw_Ds");
+      // bb: the masked by-band twins (rrtmgpnn_solver_request_byband_mcica)
+      if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true, false, true>);
+      else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true, false, true>);
+      else if (multi)  go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true>);
+      else             go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true>);
       RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (masked)");
       return RRTMGPNN_OK;
     } else {
@@ -972,10 +983,9 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
   // McICA (rrtmgpnn_solver_request_cloud_mask): only the checkpointed kernel has masked instances
   if (ex.mask_bits && !inc)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
-  if (ex.mask_bits && (!ck || gpt || bb))
+  if (ex.mask_bits && (!ck || gpt))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask is taken by the checkpointed kernel only (even ngpt, "
-                                          "rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band or g-point "
-                                          "outputs");
+                                          "rrtmgpnn_context_set_sw_kernel mode 0 or 3), without g-point outputs");
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
   // the other kernels read them from memory, formed there first by sw_boundary_kernel
   SwBcDev bcd{};

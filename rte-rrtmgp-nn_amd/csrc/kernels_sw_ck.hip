@@ -182,7 +182,8 @@ constexpr int kCkAheadSmall = 1;
 // (extensions/cloud_optics/mo_cloud_sampling.F90:291-307) -- and ck_inc then increments by them as it does by any
 // other values (a zero increment still rounds tau * ssa / max(eps, tau)).  Both g-points of a lane are selected
 // separately (g is even, so they share the word), also in the band-pair form; the word is loaded with the layer's
-// band values.
+// band values.  With kBand (rrtmgpnn_solver_request_byband_mcica) the flush's band sums are those of the sampled
+// columns; the by-band limits are the request's, not the increment's.
 template <bool kHasG, bool kInc, int K, bool kGpt = false, int R = kCkRing,
           int WAVES = (!kHasG && !kInc && !kGpt) ? kCkWavesNN : kCkWaves, bool kTn = false,
           class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1,
@@ -199,7 +200,7 @@ __global__ void __launch_bounds__(512, WAVES)
                          const uint32_t *__restrict__ cmask)
 {
   static_assert(R % K == 0, "the flux ring must hold whole chunks");
-  static_assert(!kMask || (kInc && sizeof(V) == 8 && !kBand && !kGpt), "the cloud mask switches the fused band increment");
+  static_assert(!kMask || (kInc && sizeof(V) == 8 && !kGpt), "the cloud mask switches the fused band increment");
   constexpr bool kG0 = !kHasG && !kInc;  // g is the literal 0 (the NN path)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // `ncb` columns per block: lane t works on column c = t / (ngpt/NPL), g-points g .. g + NPL - 1
@@ -643,12 +644,27 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
   if (ex.mask_bits) {
     // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask), as the instances below
     if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
-    if (bb || ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
-      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask with by-band or g-point outputs");
+    if (ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask with g-point outputs");
     bool pair = true;
     for (int i = 0; i < b.nbnd; i++) pair = pair && ((b.lims[2 * i] - 1) % 2 == 0);
     constexpr int W = kCkWaves, P = kCkP1;
     constexpr bool T = kCkTnInc, E = kCkEmkInc;
+    if (bb) {
+      // by-band under the mask (rrtmgpnn_solver_request_byband_mcica): the masked twins of the by-band all-sky
+      // instances below, without workspace planes (the same bits as the others)
+      if (pair && g)
+        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      if (pair)
+        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      if (g)
+        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true, true>,
+                tau_bnd, ssa_bnd, g_bnd);
+    }
     if (!planes) {
       if (pair && g)
         return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true>,

@@ -20,6 +20,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_lw_solver_noscat_gpt, c_rrtmgpnn_lw_solver_noscat_planck_gpt, c_rrtmgpnn_sw_solver_2stream_gpt
   public :: c_rrtmgpnn_lw_solver_1rescl_gpt, c_rrtmgpnn_lw_solver_2stream_gpt, c_rrtmgpnn_sw_solver_noscat_gpt
   public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
+  public :: c_rrtmgpnn_solver_request_byband_mcica
   public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
             c_rrtmgpnn_draw_samples
   public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
@@ -325,6 +326,14 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, mask_bits
       integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    ! the two requests above as a pair: by-band outputs of the next solver call under its McICA mask
+    integer(c_int) function c_rrtmgpnn_solver_request_byband_mcica(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, &
+        bnd_flux_dir, ngpt, nlay, ncol, mask_bits) bind(C, name="rrtmgpnn_solver_request_byband_mcica")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, bnd_flux_up, bnd_flux_dn, bnd_flux_dir, mask_bits
+      integer(c_int), value :: nbnd, ngpt, nlay, ncol
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
     end function
     integer(c_int) function c_rrtmgpnn_sampled_mask_max_ran(ctx, ngpt, nlay, ncol, randoms, cloud_frac, cloud_mask, &
         mask_bits) bind(C, name="rrtmgpnn_sampled_mask_max_ran")

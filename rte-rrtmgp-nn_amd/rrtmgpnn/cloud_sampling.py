@@ -218,3 +218,15 @@ def arm_cloud_mask(ctx, ngpt, mask_bits):
     ncol, nlay, _ = mask_bits.shape
     check(_lib.lib().rrtmgpnn_solver_request_cloud_mask(ctx.h, int(ngpt), nlay, ncol, _p(mask_bits)),
           "solver_request_cloud_mask")
+
+
+def arm_cloud_mask_byband(ctx, ngpt, mask_bits, band_lims_gpt, bnd_up, bnd_dn, bnd_dir=None):
+    """Arm the packed mask mask_bits (ncol, nlay, ceil(ngpt / 32)) together with by-band outputs (ncol, nlay + 1, nbnd)
+    over band_lims_gpt (nbnd, 2; 1-based, inclusive) for the next solver call on ctx
+    (rrtmgpnn_solver_request_byband_mcica); that call clears the pair.  An output that is None is not written; bnd_dir
+    is a shortwave output."""
+    lims = [int(v) for pair in band_lims_gpt for v in pair]
+    ncol, nlay, _ = mask_bits.shape
+    check(_lib.lib().rrtmgpnn_solver_request_byband_mcica(
+        ctx.h, len(lims) // 2, int_array(lims), _p(bnd_up), _p(bnd_dn), _p(bnd_dir), int(ngpt), nlay, ncol,
+        _p(mask_bits)), "solver_request_byband_mcica")

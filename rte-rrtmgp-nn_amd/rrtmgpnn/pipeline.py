@@ -45,6 +45,11 @@ mcica={..., "clrsky": True} is the two together: McICA all-sky fluxes and the cl
 (cloud radiative effect).  Fused, the LW pair comes from rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica, which takes the
 packed mask as an argument (one launch of the masked dual kernel with one angle), and the SW chain is the McICA one
 plus the clear solver launch; unfused, the clear solve, then mask -> draw_samples -> increment, then the all-sky solve.
+
+mcica={..., "byband": True}: the by-band fluxes of a byband=True step under the sampled clouds (byband_fluxes()).  Fused,
+the paired request rrtmgpnn_solver_request_byband_mcica takes the place of each chain's cloud-mask request, so the
+masked by-band solver instances run; unfused, rrtmgpnn_solver_request_byband ahead of each plain solver call of the
+McICA sequence.  Not with "clrsky": the clear + all-sky kernel has no by-band form.
 """
 
 import numpy as np
@@ -58,16 +63,16 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
             "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask",
-            "mcica_randoms_sw"}
+            "mcica_randoms_sw", "sw_mask_byband"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
 # (lw_byband / sw_byband: a byband step's by-band requests, host-only calls issued right before their solver;
 # mcica_mask_*: a McICA step's mask kernels, which depend on no network; lw_mask / sw_mask: its cloud-mask requests,
-# host-only like the by-band ones)
+# host-only like the by-band ones; lw_mask_byband / sw_mask_byband: the two as one paired request, mcica={"byband": True})
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
-               "predict_nn_lw", "lw_byband", "lw_mask", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
-               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_solver"]
+               "predict_nn_lw", "lw_byband", "lw_mask", "lw_mask_byband", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
+               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_solver"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -117,7 +122,9 @@ class ClearSkyStep:
         # "stream_sw": 1, "col0": 0) in place of "randoms_lw" / "randoms_sw" the numbers are drawn in the mask kernels
         # (the _seeded entries) from two step-owned 4-word device buffers, which set_mcica_seed rewrites between steps
         # or replays; fused=False then fills scratch arrays with rrtmgpnn_mcica_randoms ahead of the same sequence.
-        # None: today's call list
+        # "byband": True: the step also owns the by-band fluxes of a byband=True step, under the sampled clouds (fused:
+        # rrtmgpnn_solver_request_byband_mcica in place of the cloud-mask requests; fused=False: a by-band request ahead
+        # of each plain solver call); not together with "clrsky".  None: today's call list
         self.mcica = mcica is not None
         self.seeded = False
         if self.mcica and clouds is None:
@@ -134,6 +141,9 @@ class ClearSkyStep:
             raise ValueError("clrsky=True: clear-sky fluxes beside the all-sky ones need clouds=(lwp, iwp, rel, rei)")
         if self.clrsky and byband:
             raise ValueError("clrsky=True with byband=True: by-band clear-sky fluxes are not supported")
+        mcica_byband = bool(self.mcica and mcica.get("byband"))
+        if mcica_byband and self.clrsky:
+            raise ValueError("mcica: 'byband' with 'clrsky': the clear + all-sky kernel has no by-band form")
         self.dev = torch.device("cuda", device)
         self.allsky = clouds is not None
         self.fused = fused
@@ -239,7 +249,9 @@ class ClearSkyStep:
             if not sw:
                 for t in (self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr):
                     t.zero_()
-        self.byband = bool(byband)
+        self.byband = bool(byband) or mcica_byband
+        # fused McICA by-band: each chain's mask and by-band requests are one paired request
+        paired = mcica_byband and fused
         if self.byband:
             self.lw_bnd_up, self.lw_bnd_dn = f(ncol, nlay + 1, self.nb_lw), f(ncol, nlay + 1, self.nb_lw)
             if sw:
@@ -344,7 +356,12 @@ class ClearSkyStep:
             elif self.mcica:
                 self.calls += [self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, None,
                                                p(self.mask_bits_lw))]
-                if not self.clrsky:  # (the clear + all-sky entry takes the mask as an argument)
+                if paired:  # the mask together with the by-band outputs
+                    lw_calls.insert(len(lw_calls) - 1,
+                                    ("lw_mask_byband", L.rrtmgpnn_solver_request_byband_mcica,
+                                     (c, self.nb_lw, self._lims_lw, p(self.lw_bnd_up), p(self.lw_bnd_dn), None,
+                                      self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
+                elif not self.clrsky:  # (the clear + all-sky entry takes the mask as an argument)
                     lw_calls.insert(len(lw_calls) - 1,
                                     ("lw_mask", L.rrtmgpnn_solver_request_cloud_mask,
                                      (c, self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
@@ -358,7 +375,7 @@ class ClearSkyStep:
             lw_calls = lw_calls[:-1] + [
                 ("lw_solver_clr", L.rrtmgpnn_lw_solver_noscat,
                  lw_calls[-1][2][:-2] + (p(self.lw_up_clr), p(self.lw_dn_clr)))] + inc_lw + lw_calls[-1:]
-        if self.byband:  # armed right before the solver call that consumes it
+        if self.byband and not paired:  # armed right before the solver call that consumes it
             lw_calls.insert(len(lw_calls) - 1,
                             ("lw_byband", L.rrtmgpnn_solver_request_byband,
                              (c, self.nb_lw, self._lims_lw, p(self.lw_bnd_up), p(self.lw_bnd_dn), None)))
@@ -427,11 +444,19 @@ class ClearSkyStep:
                 ]
             elif self.mcica:
                 self.calls += [
-                    self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, None, p(self.mask_bits_sw)),
-                    ("sw_mask", L.rrtmgpnn_solver_request_cloud_mask,
-                     (c, self.ng_sw, nlay, ncol, p(self.mask_bits_sw))),
-                ]
-        if self.byband:
+                    self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, None, p(self.mask_bits_sw))]
+                if paired:
+                    self.calls += [
+                        ("sw_mask_byband", L.rrtmgpnn_solver_request_byband_mcica,
+                         (c, self.nb_sw, self._lims_sw, p(self.sw_bnd_up), p(self.sw_bnd_dn), p(self.sw_bnd_dir),
+                          self.ng_sw, nlay, ncol, p(self.mask_bits_sw))),
+                    ]
+                else:
+                    self.calls += [
+                        ("sw_mask", L.rrtmgpnn_solver_request_cloud_mask,
+                         (c, self.ng_sw, nlay, ncol, p(self.mask_bits_sw))),
+                    ]
+        if self.byband and not paired:
             self._lims_sw_bnd = int_array(self.kd_sw["band_lims_gpt"].ravel())
             self.calls += [
                 ("sw_byband", L.rrtmgpnn_solver_request_byband,
