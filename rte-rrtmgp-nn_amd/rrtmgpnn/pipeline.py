@@ -52,6 +52,8 @@ masked by-band solver instances run; unfused, rrtmgpnn_solver_request_byband ahe
 McICA sequence.  Not with "clrsky": the clear + all-sky kernel has no by-band form.
 """
 
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -99,34 +101,49 @@ def _t(a, dev):
 
 
 class ClearSkyStep:
+    """One column block's step (module docstring).  `calls`, its launch list of (name, fn, args), is built chain by
+    chain: _lw_chain() and _sw_chain() write each chain's calls down in the order the unfused step issues them, from
+    one record per chain (_chain_record) and one method per sequence the two chains share (_cloud_optics_call,
+    _clouds_in, _request); _finish() applies the schedule.  tests/golden/step_plan.json pins the list, the buffers and
+    the schedule of every option set (tests/step_plan.py).
+
+    sw=False: the LW half alone (config C2, rrtmgp_rfmip_lw.F90): gas optics LW + Planck + rte_lw.
+    byband: the step also owns by-band fluxes (ty_fluxes_byband; lw_bnd_up / lw_bnd_dn, sw_bnd_up / sw_bnd_dn /
+    sw_bnd_dir, (ncol, nlay+1, nband)) and arms rrtmgpnn_solver_request_byband before each solver call, so the
+    solvers' by-band instances run and a captured graph carries the arrays.
+    clrsky (all-sky steps): the step also owns clear-sky fluxes of the same columns (lw_up_clr, lw_dn_clr, sw_up_clr,
+    sw_dn_clr, sw_dir_clr; clrsky_fluxes()).  By-band clear-sky fluxes are out of scope: clrsky with byband is refused.
+    lw_after: the SW-chain call the LW chain starts after on two streams (None: the default gate in _finish; "": the
+    chains start together).  (`overlap` is the stream-overlap flag.)
+    mcica (all-sky steps): McICA-sampled clouds (extensions/cloud_optics/mo_cloud_sampling.F90) in place of overcast
+    ones: {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, ngpt_lw), "randoms_sw": (ncol, nlay, ngpt_sw),
+    "overlap_param": None (maximum-random overlap) or (ncol, nlay-1) (exponential-random)}.  The randoms are step-owned
+    device buffers (mcica_randoms()) the caller refills between steps or replays (set_mcica_randoms).  With "seed": int
+    (and optionally "stream_lw": 0, "stream_sw": 1, "col0": 0) in place of "randoms_lw" / "randoms_sw" the numbers are
+    drawn in the mask kernels (the _seeded entries) from two step-owned 4-word device buffers, which set_mcica_seed
+    rewrites between steps or replays; fused=False then fills scratch arrays with rrtmgpnn_mcica_randoms ahead of the
+    class layer's sequence.  "clrsky": True / "byband": True: also the clear-sky fluxes of the same columns / the by-band
+    fluxes of a byband=True step under the sampled clouds, not the two together; the clrsky= and byband= arguments
+    themselves are refused with mcica."""
+
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
                  clrsky=False, mcica=None):
-        # sw=False: the LW half alone (config C2, rrtmgp_rfmip_lw.F90): gas optics LW + Planck + rte_lw
-        # byband: the step also owns by-band fluxes (ty_fluxes_byband; lw_bnd_up / lw_bnd_dn, sw_bnd_up / sw_bnd_dn /
-        # sw_bnd_dir, (ncol, nlay+1, nband)) and arms rrtmgpnn_solver_request_byband before each solver call, so the
-        # solvers' by-band instances run and a captured graph carries the arrays; False: today's call list
-        # clrsky (all-sky steps): the step also owns clear-sky fluxes of the same columns (lw_up_clr, lw_dn_clr,
-        # sw_up_clr, sw_dn_clr, sw_dir_clr; clrsky_fluxes()); False: today's call list.  By-band clear-sky fluxes are
-        # out of scope: clrsky with byband is refused
-        # lw_after: the SW-chain call the LW chain starts after on two streams (None: the default gate in _finish;
-        # "": the chains start together)
-        # mcica (all-sky steps): McICA-sampled clouds (extensions/cloud_optics/mo_cloud_sampling.F90) in place of overcast
-        # ones: {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, ngpt_lw), "randoms_sw": (ncol, nlay, ngpt_sw),
-        # "overlap_param": None (maximum-random overlap) or (ncol, nlay-1) (exponential-random)}.  (`overlap` is the
-        # stream-overlap flag.)  Fused: per chain the mask kernel (packed bits), rrtmgpnn_solver_request_cloud_mask and
-        # the fused solver call of the all-sky step; fused=False: the class layer's sequence, mask -> draw_samples ->
-        # increment at g-point resolution.  The randoms are step-owned device buffers (mcica_randoms()) the caller
-        # refills between steps or replays (set_mcica_randoms).  With "seed": int (and optionally "stream_lw": 0,
-        # "stream_sw": 1, "col0": 0) in place of "randoms_lw" / "randoms_sw" the numbers are drawn in the mask kernels
-        # (the _seeded entries) from two step-owned 4-word device buffers, which set_mcica_seed rewrites between steps
-        # or replays; fused=False then fills scratch arrays with rrtmgpnn_mcica_randoms ahead of the same sequence.
-        # "byband": True: the step also owns the by-band fluxes of a byband=True step, under the sampled clouds (fused:
-        # rrtmgpnn_solver_request_byband_mcica in place of the cloud-mask requests; fused=False: a by-band request ahead
-        # of each plain solver call); not together with "clrsky".  None: today's call list
+        self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica)
+        self._open_device(device, ctx, lw_models, sw_models, icergh, cloud_lut)
+        self._allocate(prob, clouds, mcica)
+        self._prepare_arguments(nmus)
+        # unfused, the SW boundary conditions follow get_col_dry, the call the SW stream forks after
+        self.calls = self._col_dry() + self._sw_boundary() + self._lw_chain() + (self._sw_chain() if sw else [])
+        if sw:
+            self._finish(overlap, lw_after, sw_after, lw_net_cus, sw_net_cus)
+        else:
+            self._finish(False)
+
+    def _resolve_options(self, fused, clouds, sw, sw_priority, byband, clrsky, mcica):
+        """Every option check, and the flags derived from the options, before any device object exists."""
         self.mcica = mcica is not None
-        self.seeded = False
         if self.mcica and clouds is None:
             raise ValueError("mcica: sampled clouds need clouds=(lwp, iwp, rel, rei)")
         if self.mcica and (clrsky or byband):
@@ -134,8 +151,6 @@ class ClearSkyStep:
                              "sampled ones: the key mcica={..., 'clrsky': True})")
         if self.mcica and not sw:
             raise ValueError("mcica with sw=False is not supported")
-        # mcica={..., "clrsky": True}: the clear-sky fluxes of the same columns beside the McICA all-sky ones (fused: the
-        # LW pair from rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica, the SW chain as with clrsky=True)
         self.clrsky = bool(clrsky) or bool(self.mcica and mcica.get("clrsky"))
         if self.clrsky and clouds is None:
             raise ValueError("clrsky=True: clear-sky fluxes beside the all-sky ones need clouds=(lwp, iwp, rel, rei)")
@@ -144,10 +159,22 @@ class ClearSkyStep:
         mcica_byband = bool(self.mcica and mcica.get("byband"))
         if mcica_byband and self.clrsky:
             raise ValueError("mcica: 'byband' with 'clrsky': the clear + all-sky kernel has no by-band form")
-        self.dev = torch.device("cuda", device)
+        self.seeded = bool(self.mcica and mcica.get("seed") is not None)
+        if self.seeded:
+            if mcica.get("randoms_lw") is not None or mcica.get("randoms_sw") is not None:
+                raise ValueError("mcica: seed together with randoms_lw / randoms_sw")
+            self._seed = {"seed": int(mcica["seed"]), "stream_lw": int(mcica.get("stream_lw", 0)),
+                          "stream_sw": int(mcica.get("stream_sw", 1)), "col0": int(mcica.get("col0", 0))}
         self.allsky = clouds is not None
-        self.fused = fused
-        self._own_ctx = ctx is None  # a caller's context keeps its settings (the LW network's CU cap below)
+        self.fused, self.sw, self.sw_priority = fused, sw, sw_priority
+        self.byband = bool(byband) or mcica_byband
+        # fused McICA by-band: each chain's mask and by-band requests are one paired request
+        self._paired = mcica_byband and fused
+
+    def _open_device(self, device, ctx, lw_models, sw_models, icergh, cloud_lut):
+        """The step's streams and context, and the model data: networks, k-distributions, cloud optics."""
+        self.dev = torch.device("cuda", device)
+        self._own_ctx = ctx is None  # a caller's context keeps its settings (the LW network's CU cap in _finish)
         # Streams: non-blocking HIP streams this step alone holds for its lifetime (_lib.stream_acquire), released by
         # close() after its graph and contexts -- never torch's pooled streams, which torch hands out round-robin to
         # every caller, nor the legacy null stream.  Captures run on these same streams and replays launch on the LW
@@ -156,9 +183,6 @@ class ClearSkyStep:
         self.ctx = ctx or Context(device, self._new_stream())
         L = self.L = _lib.lib()
         self.kd_lw, self.kd_sw = data.load_kdist("lw"), data.load_kdist("sw")
-        self.ncol, self.nlay = ncol, nlay = prob["ncol"], prob["nlay"]
-        self.top_at_1 = int(bool(prob["top_at_1"]))
-        dev = self.dev
 
         def net(name):
             h = _lib.c_vp()
@@ -172,8 +196,17 @@ class ClearSkyStep:
         self.nx_lw, self.nx_sw = len(self.lw_names), len(self.sw_names)
         self.ng_lw, self.ng_sw = self.kd_lw["ngpt"], self.kd_sw["ngpt"]
         self.nb_lw = self.kd_lw["nband"]
+        if self.allsky:
+            self.nb_sw = self.kd_sw["nband"]
+            self.cloud_lw, self.cloud_sw = (self._cloud_optics(w, cloud_lut, icergh) for w in ("lw", "sw"))
 
-        # ---- inputs (HBM resident) ----
+    def _allocate(self, prob, clouds, mcica):
+        """The step's HBM-resident tensors: inputs, intermediates, outputs, and what clrsky / byband / mcica add."""
+        self.ncol, self.nlay = ncol, nlay = prob["ncol"], prob["nlay"]
+        self.top_at_1 = int(bool(prob["top_at_1"]))
+        dev, sw, fused = self.dev, self.sw, self.fused
+
+        # ---- inputs ----
         self._gas_names = list(prob["gases"])
         ins = self._inputs(prob, clouds)
         self.play, self.plev, self.tlay, self.tlev, self.tsfc = ins[:5]
@@ -190,7 +223,6 @@ class ClearSkyStep:
         self.x_lw, self.x_sw = f(ncol, nlay, self.nx_lw), f(ncol, nlay, self.nx_sw)
         self.tau_lw, self.lay_src = f(ncol, nlay, self.ng_lw), f(ncol, nlay, self.ng_lw)
         self.emis_gpt = f(ncol, self.ng_lw)
-        self.sw = sw
         if sw:
             self.tau_sw, self.ssa_sw = f(ncol, nlay, self.ng_sw), f(ncol, nlay, self.ng_sw)
             # the SW boundary conditions, formed every step (unfused: rrtmgpnn_sw_boundary_rfmip; fused: in the SW
@@ -202,63 +234,58 @@ class ClearSkyStep:
         if not fused and sw:
             self.g_sw = f(ncol, nlay, self.ng_sw)
         if self.allsky:
-            self.nb_sw = self.kd_sw["nband"]
             self.lwp, self.iwp, self.rel, self.rei = ins[-4:]
             self.cld_tau_lw = f(ncol, nlay, self.nb_lw)
             self.cld_tau_sw, self.cld_ssa_sw, self.cld_g_sw = (f(ncol, nlay, self.nb_sw) for _ in range(3))
-            self.cloud_lw, self.cloud_sw = (self._cloud_optics(w, cloud_lut, icergh) for w in ("lw", "sw"))
         if self.mcica:
-            self.cloud_frac = _t(mcica["cloud_frac"], dev)
-            ov = mcica.get("overlap_param")
-            self.overlap_param = None if ov is None else _t(ov, dev)
-            self.seeded = mcica.get("seed") is not None
-            if self.seeded:
-                if mcica.get("randoms_lw") is not None or mcica.get("randoms_sw") is not None:
-                    raise ValueError("mcica: seed together with randoms_lw / randoms_sw")
-                self._seed = {"seed": int(mcica["seed"]), "stream_lw": int(mcica.get("stream_lw", 0)),
-                              "stream_sw": int(mcica.get("stream_sw", 1)), "col0": int(mcica.get("col0", 0))}
-                self.rng_lw, self.rng_sw = (torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(2))
-                self.set_mcica_seed()
-                # unfused: scratch arrays rrtmgpnn_mcica_randoms fills every step
-                self.randoms_lw = None if fused else f(ncol, nlay, self.ng_lw)
-                self.randoms_sw = None if fused else f(ncol, nlay, self.ng_sw)
-            else:
-                self.randoms_lw, self.randoms_sw = _t(mcica["randoms_lw"], dev), _t(mcica["randoms_sw"], dev)
-            want = {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, self.ng_lw),
-                    "randoms_sw": (ncol, nlay, self.ng_sw), "overlap_param": (ncol, nlay - 1)}
-            for k, t in (("cloud_frac", self.cloud_frac), ("randoms_lw", self.randoms_lw),
-                         ("randoms_sw", self.randoms_sw), ("overlap_param", self.overlap_param)):
-                if t is not None and tuple(t.shape) != want[k]:
-                    raise ValueError("mcica: %s has shape %s, expected %s" % (k, tuple(t.shape), want[k]))
-            if fused:  # the packed masks the solvers take
-                self.mask_bits_lw = torch.zeros((ncol, nlay, (self.ng_lw + 31) // 32), dtype=torch.int32, device=dev)
-                self.mask_bits_sw = torch.zeros((ncol, nlay, (self.ng_sw + 31) // 32), dtype=torch.int32, device=dev)
-            else:  # the class layer's logical masks and g-point cloud properties
-                self.mask_lw = torch.zeros((ncol, nlay, self.ng_lw), dtype=torch.uint8, device=dev)
-                self.mask_sw = torch.zeros((ncol, nlay, self.ng_sw), dtype=torch.uint8, device=dev)
-                self.smp_tau_lw = f(ncol, nlay, self.ng_lw)
-                self.smp_tau_sw, self.smp_ssa_sw, self.smp_g_sw = (f(ncol, nlay, self.ng_sw) for _ in range(3))
+            self._allocate_mcica(mcica, f)
+        f_sw = f if sw else (lambda *s: f(*s).zero_())  # an LW-only step's SW fluxes are zero
         self.lw_up, self.lw_dn = f(ncol, nlay + 1), f(ncol, nlay + 1)
-        self.sw_up, self.sw_dn, self.sw_dir = f(ncol, nlay + 1), f(ncol, nlay + 1), f(ncol, nlay + 1)
-        if not sw:
-            for t in (self.sw_up, self.sw_dn, self.sw_dir):
-                t.zero_()
+        self.sw_up, self.sw_dn, self.sw_dir = (f_sw(ncol, nlay + 1) for _ in range(3))
         if self.clrsky:
             self.lw_up_clr, self.lw_dn_clr = f(ncol, nlay + 1), f(ncol, nlay + 1)
-            self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr = (f(ncol, nlay + 1) for _ in range(3))
-            if not sw:
-                for t in (self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr):
-                    t.zero_()
-        self.byband = bool(byband) or mcica_byband
-        # fused McICA by-band: each chain's mask and by-band requests are one paired request
-        paired = mcica_byband and fused
+            self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr = (f_sw(ncol, nlay + 1) for _ in range(3))
         if self.byband:
             self.lw_bnd_up, self.lw_bnd_dn = f(ncol, nlay + 1, self.nb_lw), f(ncol, nlay + 1, self.nb_lw)
             if sw:
-                nbs = self.kd_sw["nband"]
-                self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (f(ncol, nlay + 1, nbs) for _ in range(3))
+                self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (
+                    f(ncol, nlay + 1, self.kd_sw["nband"]) for _ in range(3))
 
-        # ---- prepared ctypes argument lists ----
+    def _allocate_mcica(self, mcica, f):
+        """A McICA step's cloud fraction, overlap parameter, random numbers (or seed words) and masks."""
+        ncol, nlay, dev = self.ncol, self.nlay, self.dev
+        self.cloud_frac = _t(mcica["cloud_frac"], dev)
+        ov = mcica.get("overlap_param")
+        self.overlap_param = None if ov is None else _t(ov, dev)
+        if self.seeded:
+            self.rng_lw, self.rng_sw = (torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(2))
+            self.set_mcica_seed()
+            # unfused: scratch arrays rrtmgpnn_mcica_randoms fills every step
+            self.randoms_lw = None if self.fused else f(ncol, nlay, self.ng_lw)
+            self.randoms_sw = None if self.fused else f(ncol, nlay, self.ng_sw)
+        else:
+            self.randoms_lw, self.randoms_sw = _t(mcica["randoms_lw"], dev), _t(mcica["randoms_sw"], dev)
+        want = {"cloud_frac": (ncol, nlay), "randoms_lw": (ncol, nlay, self.ng_lw),
+                "randoms_sw": (ncol, nlay, self.ng_sw), "overlap_param": (ncol, nlay - 1)}
+        for k, t in (("cloud_frac", self.cloud_frac), ("randoms_lw", self.randoms_lw),
+                     ("randoms_sw", self.randoms_sw), ("overlap_param", self.overlap_param)):
+            if t is not None and tuple(t.shape) != want[k]:
+                raise ValueError("mcica: %s has shape %s, expected %s" % (k, tuple(t.shape), want[k]))
+        if self.fused:  # the packed masks the solvers take
+            self.mask_bits_lw = torch.zeros((ncol, nlay, (self.ng_lw + 31) // 32), dtype=torch.int32, device=dev)
+            self.mask_bits_sw = torch.zeros((ncol, nlay, (self.ng_sw + 31) // 32), dtype=torch.int32, device=dev)
+        else:  # the class layer's logical masks and g-point cloud properties
+            self.mask_lw = torch.zeros((ncol, nlay, self.ng_lw), dtype=torch.uint8, device=dev)
+            self.mask_sw = torch.zeros((ncol, nlay, self.ng_sw), dtype=torch.uint8, device=dev)
+            self.smp_tau_lw = f(ncol, nlay, self.ng_lw)
+            self.smp_tau_sw, self.smp_ssa_sw, self.smp_g_sw = (f(ncol, nlay, self.ng_sw) for _ in range(3))
+
+    def _p(self, *names):
+        """The device addresses of the step's tensors of these names (None where this mode holds no such tensor)."""
+        return tuple(None if t is None else t.data_ptr() for t in (getattr(self, n, None) for n in names))
+
+    def _prepare_arguments(self, nmus):
+        """The ctypes arrays the calls share, and the two chains' records."""
         def gas_args(names):
             ptrs, nds = [], []
             for k, n in enumerate(names):
@@ -267,231 +294,223 @@ class ClearSkyStep:
                 nds.append(2)
             return ptr_array(ptrs), int_array(nds)
 
-        p = lambda t: t.data_ptr()  # noqa: E731
         self._g_lw, self._nd_lw = gas_args(self.lw_names)
         self._g_sw, self._nd_sw = gas_args(self.sw_names)
         self._nets_lw = ptr_array([h.value for h in self.lw_nets])
         self._nets_sw = ptr_array([h.value for h in self.sw_nets])
         self._lims_lw = int_array(self.kd_lw["band_lims_gpt"].ravel())
+        self._lims_sw = int_array(self.kd_sw["band_lims_gpt"].ravel())
         self._Ds, self._W = float_array(GAUSS_DS[nmus]), float_array(GAUSS_WTS[nmus])
         self.nmus = nmus
-        c = self.ctx.h
-        if fused:
+        self._chain_lw = self._chain_record("lw", self.kd_lw, self._lims_lw)
+        self._chain_sw = self._chain_record("sw", self.kd_sw, self._lims_sw)
+
+    def _chain_record(self, w, kd, lims):
+        """What the cloud handling of the two chains differs in: the sizes and band limits, and the addresses (or None)
+        of the optical properties, the clouds by band, the sampled clouds, the masks, the random numbers and the
+        by-band outputs.  The LW chain carries tau alone, so the ssa and g slots of its triples are NULL; the SW
+        asymmetry parameter is NULL in the fused step (quirk B-6: identically zero in the NN path, which the SW kernels
+        take as a literal 0 instead of writing and re-reading a zero array; same fluxes, bit for bit)."""
+        p = self._p
+        triple = (lambda stem: p(stem + "tau_lw") + (None, None)) if w == "lw" else \
+            (lambda stem: p(stem + "tau_sw", stem + "ssa_sw", stem + "g_sw"))
+        mask, bits, randoms, rng = p("mask_" + w, "mask_bits_" + w, "randoms_" + w, "rng_" + w)
+        return SimpleNamespace(sfx=w, ngpt=kd["ngpt"], nband=kd["nband"], lims=lims, props=triple(""),
+                               cld=triple("cld_"), smp=triple("smp_"), mask=mask, bits=bits, randoms=randoms, rng=rng,
+                               bnd=p(w + "_bnd_up", w + "_bnd_dn") + (p("sw_bnd_dir") if w == "sw" else (None,)))
+
+    # ---- the sequences both chains issue, from a chain's record ----
+    def _cloud_optics_call(self, ch):
+        """Cloud optics by band (rrtmgp_allsky.F90:383, :420); none on a clear-sky step."""
+        if not self.allsky:
+            return []
+        return [("cloud_optics_" + ch.sfx, self.L.rrtmgpnn_cloud_optics_compute,
+                 (self.ctx.h, getattr(self, "cloud_" + ch.sfx), self.ncol, self.nlay)
+                 + self._p("lwp", "iwp", "rel", "rei") + ch.cld)]
+
+    def _clouds_in(self, ch):
+        """clouds%increment(atmos) of a chain (rrtmgp_allsky.F90:383-395, :420-433).  Fused, the solver adds the band
+        clouds itself, so only a McICA step issues something here: the mask kernel, into packed bits.  Unfused: the
+        increment by band, or the class layer's McICA sequence at g-point resolution, (randoms ->) mask -> draw_samples
+        -> increment."""
+        L, c, ncol, nlay = self.L, self.ctx.h, self.ncol, self.nlay
+        if not self.allsky:
+            return []
+        if self.fused:
+            return [self._mask_call(ch, None, ch.bits)] if self.mcica else []
+        if not self.mcica:
+            return [("increment_" + ch.sfx, L.rrtmgpnn_increment_bybnd,
+                     (c, ncol, nlay, ch.ngpt, ch.nband, ch.lims) + ch.props + ch.cld)]
+        return self._randoms_call(ch) + [
+            self._mask_call(ch, ch.mask, None),
+            ("draw_samples_" + ch.sfx, L.rrtmgpnn_draw_samples,
+             (c, ch.ngpt, nlay, ncol, ch.nband, ch.lims, ch.mask) + ch.cld + ch.smp),
+            ("increment_" + ch.sfx, L.rrtmgpnn_increment, (c, ncol, nlay, ch.ngpt) + ch.props + ch.smp),
+        ]
+
+    def _request(self, ch, mask=True):
+        """The host-only request armed right before the solver call that consumes it: the fused McICA step's cloud mask
+        (mask=False: that solver entry takes the mask as an argument), the by-band outputs, or the two as one paired
+        request."""
+        L, c = self.L, self.ctx.h
+        if self._paired:
+            return [(ch.sfx + "_mask_byband", L.rrtmgpnn_solver_request_byband_mcica,
+                     (c, ch.nband, ch.lims) + ch.bnd + (ch.ngpt, self.nlay, self.ncol, ch.bits))]
+        if self.mcica and self.fused:
+            return [(ch.sfx + "_mask", L.rrtmgpnn_solver_request_cloud_mask,
+                     (c, ch.ngpt, self.nlay, self.ncol, ch.bits))] if mask else []
+        if self.byband:
+            return [(ch.sfx + "_byband", L.rrtmgpnn_solver_request_byband, (c, ch.nband, ch.lims) + ch.bnd)]
+        return []
+
+    def _mask_call(self, ch, mask, bits):
+        """The chain's call of sampled_mask_max_ran, or _exp_ran when the step has an overlap parameter, into a logical
+        mask or packed bits; a seeded fused step, which holds no random numbers, calls the _seeded entry on its 4-word
+        buffer."""
+        src, sfx = (ch.rng, "_seeded") if ch.randoms is None else (ch.randoms, "")
+        head = (self.ctx.h, ch.ngpt, self.nlay, self.ncol, src) + self._p("cloud_frac")
+        if self.overlap_param is None:
+            return ("mcica_mask_" + ch.sfx, getattr(self.L, "rrtmgpnn_sampled_mask_max_ran" + sfx), head + (mask, bits))
+        return ("mcica_mask_" + ch.sfx, getattr(self.L, "rrtmgpnn_sampled_mask_exp_ran" + sfx),
+                head + self._p("overlap_param") + (mask, bits))
+
+    def _randoms_call(self, ch):
+        """A seeded unfused step's fill of its scratch randoms ([] on the array route)."""
+        if not self.seeded:
+            return []
+        return [("mcica_randoms_" + ch.sfx, self.L.rrtmgpnn_mcica_randoms,
+                 (self.ctx.h, ch.ngpt, self.nlay, self.ncol, ch.rng, ch.randoms))]
+
+    # ---- the call list ----
+    def _col_dry(self):
+        """Unfused: col_dry, computed once for both chains (the fused network kernels form it themselves)."""
+        if self.fused:
+            return []
+        return [("get_col_dry", self.L.rrtmgpnn_get_col_dry,
+                 (self.ctx.h, self.ncol, self.nlay, self.gases["h2o"].data_ptr()) + self._p("plev", "col_dry"))]
+
+    def _sw_boundary(self):
+        """The driver's SW boundary conditions.  Fused: formed in the SW solver's prologue
+        (rrtmgpnn_sw_solver_2stream_rfmip).  Round 6 before that: a kernel at the head of the SW chain (7.7 us at C3);
+        on the LW stream beside the SW network, with the SW solver waiting for it, the C3 step measured 0.497 ms against
+        0.43 (the extra edge into the SW solver let the LW network take the CUs first; profiles/r06/README.md).
+        Unfused (the class layer's calls): a kernel of its own."""
+        if self.fused or not self.sw:
+            return []
+        return [("sw_boundary", self.L.rrtmgpnn_sw_boundary_rfmip,
+                 (self.ctx.h, self.ng_sw, self.ncol)
+                 + self._p("solar_source", "tsi", "sfc_alb", "sza", "toa", "alb", "mu0"))]
+
+    def _lw_chain(self):
+        """The LW chain's calls in issue order (unfused: after get_col_dry)."""
+        L, c, ncol, nlay, p, ch = self.L, self.ctx.h, self.ncol, self.nlay, self._p, self._chain_lw
+        h2o = (self.gases["h2o"].data_ptr(),)
+        if self.fused:
             # compute_nn_inputs + get_col_dry + predict_nn_lw in one kernel (rrtmgpnn_gas_optics_lw_nn): the network
             # inputs and column amounts are formed in-kernel and never stored (same bits as the three calls)
-            self.calls = [
+            return [
                 ("predict_nn_lw", L.rrtmgpnn_gas_optics_lw_nn,
-                 (c, ncol, nlay, self.ng_lw, self.nx_lw, p(self.play), p(self.tlay), p(self.plev), p(self.gases["h2o"]),
-                  self._g_lw, self._nd_lw, self._nets_lw, len(self.lw_nets), p(self.tau_lw), p(self.lay_src))),
+                 (c, ncol, nlay, self.ng_lw, self.nx_lw) + p("play", "tlay", "plev") + h2o
+                 + (self._g_lw, self._nd_lw, self._nets_lw, len(self.lw_nets)) + p("tau_lw", "lay_src")),
+                *self._cloud_optics_call(ch),
+                *self._clouds_in(ch),
+                # (the clear + all-sky McICA entry takes the mask as an argument)
+                *self._request(ch, mask=not self.clrsky),
+                self._lw_solver_fused(),
             ]
-        else:
-            self.calls = [
-                ("get_col_dry", L.rrtmgpnn_get_col_dry,
-                 (c, ncol, nlay, p(self.gases["h2o"]), p(self.plev), p(self.col_dry))),
-                ("nn_inputs_lw", L.rrtmgpnn_compute_nn_inputs,
-                 (c, ncol, nlay, self.nx_lw, p(self.play), p(self.tlay), self._g_lw, self._nd_lw, self.lw_nets[0],
-                  p(self.x_lw))),
-                ("predict_nn_lw", L.rrtmgpnn_predict_nn_lw,
-                 (c, ncol, nlay, self.ng_lw, self.nx_lw, p(self.x_lw), p(self.col_dry), self._nets_lw,
-                  len(self.lw_nets), p(self.tau_lw), p(self.lay_src))),
-            ]
-        if fused:
-            # compute_Planck_source_nn fused into the LW solver (sources formed in-kernel from pfrac); all-sky:
-            # the cloud increment by band is added as tau is read (rrtmgpnn_lw_solver_noscat_planck_inc)
-            tail = (p(self.tau_lw),) + ((p(self.cld_tau_lw),) if self.allsky else ()) + (
-                p(self.lay_src), self.nb_lw, self.kd_lw["nPlanckTemp"], p(self.tlay), p(self.tlev), p(self.tsfc),
-                self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"]),
-                p(self.totplnk), 1, p(self.sfc_emis), p(self.lw_up), p(self.lw_dn))
-            # the surface emissivity goes in by band (as rte_lw takes it) and is expanded in-kernel
-            lw_calls = [
-                ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_inc if self.allsky else L.rrtmgpnn_lw_solver_noscat_planck,
-                 (c, self.ng_lw, nlay, ncol, self.top_at_1, nmus, self._Ds, self._W, None) + tail),
-            ]
-            if self.clrsky:  # both flux sets from one call: the dual entry in place of _planck_inc
-                lw_calls = [
-                    ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all,
-                     lw_calls[0][2] + (p(self.lw_up_clr), p(self.lw_dn_clr))),
-                ]
-                if self.mcica:  # the McICA twin: the packed mask is the entry's last argument, not a request
-                    lw_calls = [
-                        ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica,
-                         lw_calls[0][2] + (p(self.mask_bits_lw),)),
-                    ]
-        else:
-            lw_calls = [
-                ("planck_source", L.rrtmgpnn_compute_planck_source_nn,
-                 (c, ncol, nlay, self.nb_lw, self.ng_lw, self.kd_lw["nPlanckTemp"], p(self.tlay), p(self.tlev),
-                  p(self.tsfc), self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]),
-                  float(self.kd_lw["totplnk_delta"]), p(self.totplnk), p(self.sfc_src), p(self.sfc_jac),
-                  p(self.lay_src), p(self.lev_src))),
-                ("expand_emis", L.rrtmgpnn_expand_band_to_gpt,
-                 (c, self.nb_lw, self.ng_lw, ncol, self._lims_lw, p(self.sfc_emis), p(self.emis_gpt))),
-                ("lw_solver", L.rrtmgpnn_lw_solver_noscat,
-                 (c, self.ng_lw, nlay, ncol, self.top_at_1, nmus, self._Ds, self._W, None, p(self.tau_lw),
-                  p(self.lay_src), p(self.lev_src), p(self.emis_gpt), p(self.sfc_src), p(self.lw_up), p(self.lw_dn))),
-            ]
-        if self.allsky:  # clouds%increment(atmos) before rte_lw (rrtmgp_allsky.F90:383-395)
-            self._lims_sw = int_array(self.kd_sw["band_lims_gpt"].ravel())
-            self.calls += [
-                ("cloud_optics_lw", L.rrtmgpnn_cloud_optics_compute,
-                 (c, self.cloud_lw, ncol, nlay, p(self.lwp), p(self.iwp), p(self.rel), p(self.rei),
-                  p(self.cld_tau_lw), None, None)),
-            ]
-            if not fused and self.mcica:
-                # the class layer's McICA sequence: mask, draw_samples, increment at g-point resolution
-                self.calls += self._randoms_call("lw", c) + [
-                    self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, p(self.mask_lw), None),
-                    ("draw_samples_lw", L.rrtmgpnn_draw_samples,
-                     (c, self.ng_lw, nlay, ncol, self.nb_lw, self._lims_lw, p(self.mask_lw), p(self.cld_tau_lw), None,
-                      None, p(self.smp_tau_lw), None, None)),
-                    ("increment_lw", L.rrtmgpnn_increment,
-                     (c, ncol, nlay, self.ng_lw, p(self.tau_lw), None, None, p(self.smp_tau_lw), None, None)),
-                ]
-            elif not fused:
-                self.calls += [
-                    ("increment_lw", L.rrtmgpnn_increment_bybnd,
-                     (c, ncol, nlay, self.ng_lw, self.nb_lw, self._lims_lw, p(self.tau_lw), None, None,
-                      p(self.cld_tau_lw), None, None)),
-                ]
-            elif self.mcica:
-                self.calls += [self._mask_call("mcica_mask_lw", c, self.ng_lw, self.randoms_lw, None,
-                                               p(self.mask_bits_lw))]
-                if paired:  # the mask together with the by-band outputs
-                    lw_calls.insert(len(lw_calls) - 1,
-                                    ("lw_mask_byband", L.rrtmgpnn_solver_request_byband_mcica,
-                                     (c, self.nb_lw, self._lims_lw, p(self.lw_bnd_up), p(self.lw_bnd_dn), None,
-                                      self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
-                elif not self.clrsky:  # (the clear + all-sky entry takes the mask as an argument)
-                    lw_calls.insert(len(lw_calls) - 1,
-                                    ("lw_mask", L.rrtmgpnn_solver_request_cloud_mask,
-                                     (c, self.ng_lw, nlay, ncol, p(self.mask_bits_lw))))
-        if self.clrsky and not fused:
-            # the clear solve before clouds%increment(atmos) (mo_rrtmgp_clr_all_sky.F90:161-172): the increment (McICA:
-            # with the mask and draw_samples ahead of it) moves from ahead of the Planck sources to between the two
-            # solver calls
-            moved = ("mcica_randoms_lw", "mcica_mask_lw", "draw_samples_lw", "increment_lw")
-            inc_lw = [x for x in self.calls if x[0] in moved]
-            self.calls = [x for x in self.calls if x[0] not in moved]
-            lw_calls = lw_calls[:-1] + [
-                ("lw_solver_clr", L.rrtmgpnn_lw_solver_noscat,
-                 lw_calls[-1][2][:-2] + (p(self.lw_up_clr), p(self.lw_dn_clr)))] + inc_lw + lw_calls[-1:]
-        if self.byband and not paired:  # armed right before the solver call that consumes it
-            lw_calls.insert(len(lw_calls) - 1,
-                            ("lw_byband", L.rrtmgpnn_solver_request_byband,
-                             (c, self.nb_lw, self._lims_lw, p(self.lw_bnd_up), p(self.lw_bnd_dn), None)))
-        self.calls += lw_calls
-        if not sw:
-            self.calls = [c for c in self.calls if c[0] != "cloud_optics_sw"]
-            self._finish(False)
-            return
-        # the driver's SW boundary conditions.  Fused: formed in the SW solver's prologue
-        # (rrtmgpnn_sw_solver_2stream_rfmip).  Round 6 before that: a kernel at the head of the SW chain (7.7 us at C3);
-        # on the LW stream beside the SW network, with the SW solver waiting for it, the C3 step measured 0.497 ms against
-        # 0.43 (the extra edge into the SW solver let the LW network take the CUs first; profiles/r06/README.md).
-        # Unfused (the class layer's calls): the kernel after get_col_dry, the call the SW stream forks after
-        if not fused:
-            self.calls.insert(1, ("sw_boundary", L.rrtmgpnn_sw_boundary_rfmip,
-                                  (c, self.ng_sw, ncol, p(self.solar_source), p(self.tsi), p(self.sfc_alb),
-                                   p(self.sza), p(self.toa), p(self.alb), p(self.mu0))))
-        # g == NULL: the NN path's asymmetry parameter is identically zero (quirk B-6); the SW kernels take
-        # that as a literal 0 instead of writing and re-reading a zero array (same fluxes, bit for bit)
-        g_sw = None if fused else p(self.g_sw)
-        if fused:
-            self.calls += [
-                ("predict_nn_sw", L.rrtmgpnn_gas_optics_sw_nn,
-                 (c, ncol, nlay, self.ng_sw, self.nx_sw, p(self.play), p(self.tlay), p(self.plev), p(self.gases["h2o"]),
-                  self._g_sw, self._nd_sw, self._nets_sw, p(self.tau_sw), p(self.ssa_sw), g_sw)),
-            ]
-        else:
-            self.calls += [
-                ("nn_inputs_sw", L.rrtmgpnn_compute_nn_inputs,
-                 (c, ncol, nlay, self.nx_sw, p(self.play), p(self.tlay), self._g_sw, self._nd_sw, self.sw_nets[0],
-                  p(self.x_sw))),
-                ("predict_nn_sw", L.rrtmgpnn_predict_nn_sw,
-                 (c, ncol, nlay, self.ng_sw, self.nx_sw, p(self.x_sw), p(self.col_dry), self._nets_sw, p(self.tau_sw),
-                  p(self.ssa_sw), g_sw)),
-            ]
-        if self.allsky:  # clouds%delta_scale(); clouds%increment(atmos) before rte_sw (rrtmgp_allsky.F90:420-433)
-            self.calls += [
-                ("cloud_optics_sw", L.rrtmgpnn_cloud_optics_compute,
-                 (c, self.cloud_sw, ncol, nlay, p(self.lwp), p(self.iwp), p(self.rel), p(self.rei),
-                  p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw))),
-                ("delta_scale_sw", L.rrtmgpnn_delta_scale_2str,
-                 (c, ncol * nlay * self.nb_sw, p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw), None)),
-            ]
-            if self.clrsky and not fused:  # the clear solve before clouds%increment(atmos) (:246-259)
-                self.calls += [
-                    ("sw_solver_clr", L.rrtmgpnn_sw_solver_2stream,
-                     (c, self.ng_sw, nlay, ncol, self.top_at_1, p(self.toa), None, p(self.tau_sw), p(self.ssa_sw),
-                      g_sw, p(self.mu0), p(self.alb), p(self.alb), p(self.sw_up_clr), p(self.sw_dn_clr),
-                      p(self.sw_dir_clr))),
-                ]
-            if not fused and self.mcica:
-                self.calls += self._randoms_call("sw", c) + [
-                    self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, p(self.mask_sw), None),
-                    ("draw_samples_sw", L.rrtmgpnn_draw_samples,
-                     (c, self.ng_sw, nlay, ncol, self.nb_sw, self._lims_sw, p(self.mask_sw), p(self.cld_tau_sw),
-                      p(self.cld_ssa_sw), p(self.cld_g_sw), p(self.smp_tau_sw), p(self.smp_ssa_sw), p(self.smp_g_sw))),
-                    ("increment_sw", L.rrtmgpnn_increment,
-                     (c, ncol, nlay, self.ng_sw, p(self.tau_sw), p(self.ssa_sw), g_sw, p(self.smp_tau_sw),
-                      p(self.smp_ssa_sw), p(self.smp_g_sw))),
-                ]
-            elif not fused:
-                self.calls += [
-                    ("increment_sw", L.rrtmgpnn_increment_bybnd,
-                     (c, ncol, nlay, self.ng_sw, self.nb_sw, self._lims_sw, p(self.tau_sw), p(self.ssa_sw), g_sw,
-                      p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw))),
-                ]
-            elif self.mcica:
-                self.calls += [
-                    self._mask_call("mcica_mask_sw", c, self.ng_sw, self.randoms_sw, None, p(self.mask_bits_sw))]
-                if paired:
-                    self.calls += [
-                        ("sw_mask_byband", L.rrtmgpnn_solver_request_byband_mcica,
-                         (c, self.nb_sw, self._lims_sw, p(self.sw_bnd_up), p(self.sw_bnd_dn), p(self.sw_bnd_dir),
-                          self.ng_sw, nlay, ncol, p(self.mask_bits_sw))),
-                    ]
-                else:
-                    self.calls += [
-                        ("sw_mask", L.rrtmgpnn_solver_request_cloud_mask,
-                         (c, self.ng_sw, nlay, ncol, p(self.mask_bits_sw))),
-                    ]
-        if self.byband and not paired:
-            self._lims_sw_bnd = int_array(self.kd_sw["band_lims_gpt"].ravel())
-            self.calls += [
-                ("sw_byband", L.rrtmgpnn_solver_request_byband,
-                 (c, self.kd_sw["nband"], self._lims_sw_bnd, p(self.sw_bnd_up), p(self.sw_bnd_dn), p(self.sw_bnd_dir))),
-            ]
-        if fused:
+        planck = (self.nb_lw, self.ng_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") + (
+            self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"]))
+        solver = lambda name, up, dn: (  # noqa: E731
+            name, L.rrtmgpnn_lw_solver_noscat,
+            (c, self.ng_lw, nlay, ncol, self.top_at_1, self.nmus, self._Ds, self._W, None)
+            + p("tau_lw", "lay_src", "lev_src", "emis_gpt", "sfc_src", up, dn))
+        clouds = self._clouds_in(ch)
+        return [
+            ("nn_inputs_lw", L.rrtmgpnn_compute_nn_inputs,
+             (c, ncol, nlay, self.nx_lw) + p("play", "tlay") + (self._g_lw, self._nd_lw, self.lw_nets[0]) + p("x_lw")),
+            ("predict_nn_lw", L.rrtmgpnn_predict_nn_lw,
+             (c, ncol, nlay, self.ng_lw, self.nx_lw) + p("x_lw", "col_dry") + (self._nets_lw, len(self.lw_nets))
+             + p("tau_lw", "lay_src")),
+            *self._cloud_optics_call(ch),
+            # clouds%increment(atmos) before rte_lw (rrtmgp_allsky.F90:383-395) ...
+            *([] if self.clrsky else clouds),
+            ("planck_source", L.rrtmgpnn_compute_planck_source_nn,
+             (c, ncol, nlay) + planck + p("totplnk", "sfc_src", "sfc_jac", "lay_src", "lev_src")),
+            ("expand_emis", L.rrtmgpnn_expand_band_to_gpt,
+             (c, self.nb_lw, self.ng_lw, ncol, self._lims_lw) + p("sfc_emis", "emis_gpt")),
+            # ... or, with clear-sky fluxes, after the clear solve (mo_rrtmgp_clr_all_sky.F90:161-172)
+            *([solver("lw_solver_clr", "lw_up_clr", "lw_dn_clr")] + clouds if self.clrsky else []),
+            *self._request(ch),
+            solver("lw_solver", "lw_up", "lw_dn"),
+        ]
+
+    def _lw_solver_fused(self):
+        """The fused step's LW solver call: compute_Planck_source_nn fused into the solver (sources formed in-kernel
+        from pfrac; the surface emissivity goes in by band, as rte_lw takes it, and is expanded in-kernel).  All-sky,
+        the cloud increment by band is added as tau is read (_planck_inc); with clear-sky fluxes both flux sets come
+        from one call of the dual entry (_clr_all), whose McICA twin takes the packed mask as its last argument instead
+        of a request."""
+        L, p = self.L, self._p
+        args = (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W, None) \
+            + p("tau_lw") + (p("cld_tau_lw") if self.allsky else ()) + p("lay_src") \
+            + (self.nb_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") \
+            + (self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"])) \
+            + p("totplnk") + (1,) + p("sfc_emis", "lw_up", "lw_dn")
+        if self.clrsky and self.mcica:
+            return ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica,
+                    args + p("lw_up_clr", "lw_dn_clr", "mask_bits_lw"))
+        if self.clrsky:
+            return ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all, args + p("lw_up_clr", "lw_dn_clr"))
+        entry = L.rrtmgpnn_lw_solver_noscat_planck_inc if self.allsky else L.rrtmgpnn_lw_solver_noscat_planck
+        return ("lw_solver", entry, args)
+
+    def _sw_chain(self):
+        """The SW chain's calls in issue order (unfused: after sw_boundary)."""
+        L, c, ncol, nlay, p, ch = self.L, self.ctx.h, self.ncol, self.nlay, self._p, self._chain_sw
+        h2o = (self.gases["h2o"].data_ptr(),)
+        delta_scale = [("delta_scale_sw", L.rrtmgpnn_delta_scale_2str,
+                        (c, ncol * nlay * self.nb_sw) + ch.cld + (None,))] if self.allsky else []
+        if self.fused:
             # the boundary conditions and (all sky) clouds%increment(atmos) fused into the solver
             # (rrtmgpnn_sw_solver_2stream_rfmip; same bits as sw_boundary_rfmip + sw_solver_2stream[_inc])
-            bnd = (self.nb_sw, self._lims_sw, p(self.cld_tau_sw), p(self.cld_ssa_sw), p(self.cld_g_sw)) \
-                if self.allsky else (0, None, None, None, None)
-            self.calls += [
-                ("sw_solver", L.rrtmgpnn_sw_solver_2stream_rfmip,
-                 (c, self.ng_sw, nlay, ncol, self.top_at_1, p(self.solar_source), p(self.tsi), p(self.sfc_alb),
-                  p(self.sza), p(self.tau_sw), p(self.ssa_sw), None) + bnd
-                 + (p(self.toa), p(self.alb), p(self.mu0), p(self.sw_up), p(self.sw_dn), p(self.sw_dir))),
+            band_inc = (self.nb_sw, self._lims_sw) + ch.cld if self.allsky else (0, None, None, None, None)
+            solver = lambda name, inc, *out: (  # noqa: E731
+                name, L.rrtmgpnn_sw_solver_2stream_rfmip,
+                (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("solar_source", "tsi", "sfc_alb", "sza")
+                + p("tau_sw", "ssa_sw") + (None,) + inc + p("toa", "alb", "mu0", *out))
+            return [
+                ("predict_nn_sw", L.rrtmgpnn_gas_optics_sw_nn,
+                 (c, ncol, nlay, self.ng_sw, self.nx_sw) + p("play", "tlay", "plev") + h2o
+                 + (self._g_sw, self._nd_sw, self._nets_sw) + ch.props),
+                *self._cloud_optics_call(ch),
+                *delta_scale,
+                *self._clouds_in(ch),
+                *self._request(ch),
+                solver("sw_solver", band_inc, "sw_up", "sw_dn", "sw_dir"),
+                # clear-sky fluxes: one more solver launch on the SW chain, on the gas optics' own properties (the fused
+                # solver leaves tau / ssa as they were).  Through the same entry without an increment: the
+                # checkpointed kernel forms the boundary conditions in its prologue and never stores them, so there is
+                # nothing in toa / alb / mu0 for a plain solver call to read
+                *([solver("sw_solver_clr", (0, None, None, None, None), "sw_up_clr", "sw_dn_clr", "sw_dir_clr")]
+                  if self.clrsky else []),
             ]
-            if self.clrsky:
-                # one more solver launch on the SW chain, on the gas optics' own properties (the fused solver leaves
-                # tau / ssa as they were).  Through the same entry without an increment: the checkpointed kernel forms
-                # the boundary conditions in its prologue and never stores them, so there is nothing in toa / alb /
-                # mu0 for a plain solver call to read
-                self.calls += [
-                    ("sw_solver_clr", L.rrtmgpnn_sw_solver_2stream_rfmip,
-                     (c, self.ng_sw, nlay, ncol, self.top_at_1, p(self.solar_source), p(self.tsi), p(self.sfc_alb),
-                      p(self.sza), p(self.tau_sw), p(self.ssa_sw), None, 0, None, None, None, None, p(self.toa),
-                      p(self.alb), p(self.mu0), p(self.sw_up_clr), p(self.sw_dn_clr), p(self.sw_dir_clr))),
-                ]
-        else:
-            self.calls += [
-                ("sw_solver", L.rrtmgpnn_sw_solver_2stream,
-                 (c, self.ng_sw, nlay, ncol, self.top_at_1, p(self.toa), None, p(self.tau_sw), p(self.ssa_sw),
-                  g_sw, p(self.mu0), p(self.alb), p(self.alb), p(self.sw_up), p(self.sw_dn), p(self.sw_dir))),
-            ]
-        self.sw_priority = sw_priority
-        self._finish(overlap, lw_after, sw_after, lw_net_cus, sw_net_cus)
+        solver = lambda name, *out: (  # noqa: E731
+            name, L.rrtmgpnn_sw_solver_2stream,
+            (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("toa") + (None,) + ch.props + p("mu0", "alb", "alb", *out))
+        return [
+            ("nn_inputs_sw", L.rrtmgpnn_compute_nn_inputs,
+             (c, ncol, nlay, self.nx_sw) + p("play", "tlay") + (self._g_sw, self._nd_sw, self.sw_nets[0]) + p("x_sw")),
+            ("predict_nn_sw", L.rrtmgpnn_predict_nn_sw,
+             (c, ncol, nlay, self.ng_sw, self.nx_sw) + p("x_sw", "col_dry") + (self._nets_sw,) + ch.props),
+            # clouds%delta_scale(); clouds%increment(atmos) before rte_sw (rrtmgp_allsky.F90:420-433), and with clear-sky
+            # fluxes the clear solve before the increment (mo_rrtmgp_clr_all_sky.F90:246-259)
+            *self._cloud_optics_call(ch),
+            *delta_scale,
+            *([solver("sw_solver_clr", "sw_up_clr", "sw_dn_clr", "sw_dir_clr")] if self.clrsky else []),
+            *self._clouds_in(ch),
+            *self._request(ch),
+            solver("sw_solver", "sw_up", "sw_dn", "sw_dir"),
+        ]
 
     def _finish(self, overlap, lw_after=None, sw_after=None, lw_net_cus=None, sw_net_cus=0):
         # fused: the small kernels that do not depend on a network's output go first in their chain, ahead of the big
@@ -549,10 +568,9 @@ class ClearSkyStep:
         # sw_after: an LW-chain call the SW solver waits for (the two networks first, then the two solvers side by side)
         self.sw_after = sw_after if overlap else ""
         if self.sw_after:
-            names = [n for n, _, _ in self.calls]
+            names = [n for n, _, _ in self.calls]  # (as reordered for lw_after)
             if self.sw_after not in names or self.sw_after in SW_CHAIN or "sw_solver" not in names:
                 raise ValueError("sw_after: %r is not a call of this fused step's LW chain" % self.sw_after)
-            names = [n for n, _, _ in self.calls]
             if names.index(self.sw_after) > names.index("sw_solver"):
                 raise ValueError("sw_after: %r is issued after the SW solver" % self.sw_after)
             # the event is recorded on the LW stream right after that call is issued, and the SW stream waits for it
@@ -568,27 +586,6 @@ class ClearSkyStep:
             self.calls = [(n, f, ((self.ctx2.h,) + tuple(a[1:])) if n in SW_CHAIN else a) for n, f, a in self.calls]
             self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
         self.graph = None
-
-    def _mask_call(self, name, c, ngpt, randoms, mask, bits):
-        """The step's call of sampled_mask_max_ran, or _exp_ran when the step has an overlap parameter; a seeded fused
-        step's call is the _seeded entry on its 4-word buffer (randoms None)."""
-        L, sfx = self.L, ""
-        if randoms is None:
-            randoms, sfx = (self.rng_lw if name.endswith("_lw") else self.rng_sw), "_seeded"
-        head = (c, ngpt, self.nlay, self.ncol, randoms.data_ptr(), self.cloud_frac.data_ptr())
-        if self.overlap_param is None:
-            return (name, getattr(L, "rrtmgpnn_sampled_mask_max_ran" + sfx), head + (mask, bits))
-        return (name, getattr(L, "rrtmgpnn_sampled_mask_exp_ran" + sfx),
-                head + (self.overlap_param.data_ptr(), mask, bits))
-
-    def _randoms_call(self, which, c):
-        """A seeded unfused step's fill of its scratch randoms ([] on the array route)."""
-        if not self.seeded:
-            return []
-        ng, rng, r = (self.ng_lw, self.rng_lw, self.randoms_lw) if which == "lw" else \
-            (self.ng_sw, self.rng_sw, self.randoms_sw)
-        return [("mcica_randoms_" + which, self.L.rrtmgpnn_mcica_randoms,
-                 (c, ng, self.nlay, self.ncol, rng.data_ptr(), r.data_ptr()))]
 
     def set_mcica_seed(self, seed=None, stream_lw=None, stream_sw=None, col0=None):
         """Rewrite a seeded step's two 4-word buffers (None keeps a value) between steps or graph replays; complete on
@@ -632,7 +629,7 @@ class ClearSkyStep:
         # CU first and the chains stop overlapping (tools/ab_prio.sh)
         # sw_priority < 0: a higher-priority stream (the two-solvers-side-by-side schedule, so the SW solver's blocks are
         # dispatched ahead of the LW solver's when both are ready)
-        return self._new_stream(getattr(self, "sw_priority", 0))
+        return self._new_stream(self.sw_priority)
 
     def stream_for(self, name):
         """The torch stream a call of `self.calls` is issued on."""
