@@ -614,6 +614,29 @@ int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay
 int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
                                          float *bnd_flux_dn, float *bnd_flux_dir, int ngpt, int nlay, int ncol,
                                          const unsigned int *mask_bits);
+/* rte_lw's flux_up_Jac: the Jacobian of the upward LW flux with respect to the surface temperature, at every level,
+ * carried through the NEXT solver call on this context beside its upward radiance; that call clears the request whether
+ * it succeeds or fails (flux_up_Jac == NULL: nothing armed).  flux_up_Jac DEVICE (nlay+1, ncol); sfc_source_Jac DEVICE
+ * (ngpt, ncol), what rrtmgpnn_compute_planck_source_nn writes.  The reference's path
+ * (rte/kernels/mo_rte_solver_kernels.F90:270, 290, 319, 390-411, 967, 975, 1761, 1782) is compiled out by compute_Jac =
+ * .false. (rte/mo_rte_rrtmgp_config.F90:28); per column and g-point, in float32:
+ *   J = sfc_emis * sfc_source_Jac at the surface, J = T * J through each layer going up, T the transmittance that
+ *   multiplies the upward radiance there (of the incremented or masked tau; the rescaled one in lw_solver_1rescl),
+ * and flux_up_Jac sums J over g-points exactly as the call sums flux_up (one angle: fac * J in four partial sums, the
+ * bare J sequentially when ngpt % 4 != 0; several angles: fac * J accumulated per g-point in angle order, then summed
+ * sequentially).  So flux_up_Jac is bit for bit the flux_up the same entry returns on the same optical properties with
+ * zero layer and level sources, no incident flux and sfc_source_Jac as the surface source.  There is no downward
+ * Jacobian.  The call's flux_up and flux_dn are bit for bit those of the call without the request.
+ * Honoured by rrtmgpnn_lw_solver_noscat, rrtmgpnn_lw_solver_noscat_gpt without g-point outputs (lw_Ds is honoured) and
+ * rrtmgpnn_lw_solver_1rescl, which need sfc_source_Jac, and by rrtmgpnn_lw_solver_noscat_planck and
+ * rrtmgpnn_lw_solver_noscat_planck_inc (also beside a cloud-mask request), which form it in-kernel as
+ * pfrac(g, sfc_lay) * (B_b(tsfc + 1) - B_b(tsfc)) and for which sfc_source_Jac must be NULL.  RRTMGPNN_ERR_ARGUMENT or
+ * RRTMGPNN_ERR_UNSUPPORTED, with a message naming the entry: the NULL / non-NULL rule broken, extents other than the
+ * call's, any by-band request beside it, g-point outputs, the _clr_all entries, every SW entry, and
+ * rrtmgpnn_lw_solver_2stream ("rte_lw: can't provide Jacobian of fluxes w.r.t surface temperature with 2-stream").
+ * Nothing is allocated beyond the context workspace and the pointers become kernel arguments. */
+int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *sfc_source_Jac,
+                                     float *flux_up_Jac);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */
 int rrtmgpnn_delta_scale_2str(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);

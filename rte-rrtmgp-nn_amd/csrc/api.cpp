@@ -118,6 +118,7 @@ struct Requests {
   bool byband = false;  // a by-band request was armed ...
   int byband_rc = RRTMGPNN_OK;  // ... and its band limits against ngpt: ex's by-band part is filled when OK
   rrtmgpnn_context::CloudMaskRequest mask{};
+  rrtmgpnn_context::JacobianRequest jac{};
 };
 
 static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
@@ -126,6 +127,8 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
   if (!ctx) return rq;
   rq.mask = ctx->cloud_mask;
   ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+  rq.jac = ctx->jacobian;
+  ctx->jacobian = rrtmgpnn_context::JacobianRequest{};
   if (!ctx->byband.armed) return rq;
   const auto bb = ctx->byband;
   ctx->byband = rrtmgpnn_context::BybandRequest{};
@@ -141,20 +144,56 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
 // the entries without masked instances refuse an armed cloud mask
 static const char kNoMaskMsg[] = "solver_request_cloud_mask: this solver entry takes no cloud mask (the _planck_inc, "
                                  "_2stream_inc and _2stream_rfmip entries do)";
-static int take_byband(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
+// What an entry does with an armed Jacobian request (rrtmgpnn_solver_request_jacobian): the LW entries that read source
+// arrays need its sfc_source_Jac, the fused-Planck ones form it in-kernel and take none, every other entry refuses
+// (`refusal`, or a message naming the entry).  The extents are the call's; by-band outputs do not go with it.
+enum JacMode { kJacRefuse, kJacSources, kJacFused };
+static int take_jacobian(const char *entry, const Requests &rq, JacMode mode, int ngpt, int nlay, int ncol,
+                         SolverExtras &ex, const char *refusal = nullptr)
+{
+  if (!rq.jac.armed) return RRTMGPNN_OK;
+  const std::string e(entry);
+  if (mode == kJacRefuse)
+    return fail(RRTMGPNN_ERR_ARGUMENT,
+                refusal ? std::string(refusal)
+                        : e + ": no flux Jacobian from this entry (the lw_solver_noscat, _noscat_planck, "
+                              "_noscat_planck_inc and _1rescl entries have it)");
+  if (rq.byband) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": a flux Jacobian together with by-band outputs");
+  if (rq.jac.ngpt != ngpt || rq.jac.nlay != nlay || rq.jac.ncol != ncol)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested flux Jacobian's extents (ngpt, nlay, ncol) are not this call's");
+  if (mode == kJacSources && !rq.jac.sfc_jac)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the flux Jacobian needs sfc_source_Jac beside this entry's source arrays");
+  if (mode == kJacFused && rq.jac.sfc_jac)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": sfc_source_Jac must be null, this entry forms it from the Planck fraction");
+  ex.sfc_jac = rq.jac.sfc_jac;
+  ex.jac_up = rq.jac.flux_up;
+  return RRTMGPNN_OK;
+}
+// ... and with g-point outputs beside it
+static int jacobian_no_gpt(const char *entry, const SolverExtras &ex, const float *gpt_up, const float *gpt_dn)
+{
+  if (ex.jac_up && (gpt_up || gpt_dn))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a flux Jacobian together with g-point outputs");
+  return RRTMGPNN_OK;
+}
+
+static int take_byband(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
+                       JacMode jac = kJacRefuse, const char *jac_refusal = nullptr)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
   if (rq.byband_rc) return rq.byband_rc;
   if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, kNoMaskMsg);
-  return RRTMGPNN_OK;
+  return take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex, jac_refusal);
 }
 
 // the three that honour it, alone or paired with by-band outputs: the mask against the call's extents, then into the
 // call's extras
-static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex)
+static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
+                               JacMode jac = kJacRefuse)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
   if (rq.byband_rc) return rq.byband_rc;
+  if (int rc = take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex)) return rc;
   if (!rq.mask.armed) return RRTMGPNN_OK;
   // both armed: only as the pair rrtmgpnn_solver_request_byband_mcica states (a by-band request left over from an
   // earlier call beside a fresh mask is not one)
@@ -177,7 +216,7 @@ static int refuse_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, c
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": by-band outputs are not available from this entry (the "
                                                             "_planck and _planck_inc entries have them)");
   if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, mask_msg);
-  return RRTMGPNN_OK;
+  return take_jacobian(entry, rq, kJacRefuse, ngpt, 0, 0, ex);
 }
 
 static int lw_ds_check(int nmus, const float *lw_Ds)
@@ -193,7 +232,8 @@ static int lw_noscat(rrtmgpnn_context *ctx, const LwNoscat &p, const float *lay_
                      const float *sfc_source, const float *lw_Ds, float *gpt_up, float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = take_byband("lw_solver_noscat", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacSources)) return rc;
+  if (int rc = jacobian_no_gpt("lw_solver_noscat", ex, gpt_up, gpt_dn)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (int rc = lw_ds_check(p.nmus, lw_Ds)) return rc;
   if (!p.Ds || !p.wts || !p.tau || !lay_source || !lev_source || !p.sfc_emis || !sfc_source || !p.flux_up ||
@@ -224,7 +264,8 @@ static int lw_noscat_planck(rrtmgpnn_context *ctx, const LwNoscat &p, LwPlanckIn
                             const int *band_lims_gpt, const float *lw_Ds, float *gpt_up, float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = take_byband("lw_solver_noscat_planck", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacFused)) return rc;
+  if (int rc = jacobian_no_gpt("lw_solver_noscat_planck", ex, gpt_up, gpt_dn)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (int rc = lw_ds_check(p.nmus, lw_Ds)) return rc;
   if (int rc = planck_args("lw_solver_noscat_planck", p, in, nbnd, band_lims_gpt, false)) return rc;
@@ -239,7 +280,8 @@ static int lw_1rescl(rrtmgpnn_context *ctx, const LwNoscat &p, const float *ssa,
                      float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = take_byband("lw_solver_1rescl", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacSources)) return rc;
+  if (int rc = jacobian_no_gpt("lw_solver_1rescl", ex, gpt_up, gpt_dn)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!p.Ds || !p.wts || !p.tau || !ssa || !g || !lay_source || !lev_source || !p.sfc_emis || !sfc_source ||
       !p.flux_up || !p.flux_dn || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
@@ -255,7 +297,9 @@ static int lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
                       float *gpt_up, float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband(ctx, ngpt, ex)) return rc;
+  if (int rc = take_byband("lw_solver_2stream", ctx, ngpt, nlay, ncol, ex, kJacRefuse,
+                           "rte_lw: can't provide Jacobian of fluxes w.r.t surface temperature with 2-stream"))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!tau || !ssa || !g || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn || ngpt < 1 ||
       nlay < 1 || ncol < 0)
@@ -269,7 +313,7 @@ static int lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
 static int sw_2stream(rrtmgpnn_context *ctx, const Sw2Stream &p, float *gpt_up, float *gpt_dn, float *gpt_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband(ctx, p.ngpt, ex)) return rc;
+  if (int rc = take_byband("sw_solver_2stream", ctx, p.ngpt, p.nlay, p.ncol, ex)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!p.inc_flux || !p.tau || !p.ssa || !p.mu0 || !p.alb_dir || !p.alb_dif || !p.flux_up || !p.flux_dn ||
       !p.flux_dir || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
@@ -284,7 +328,7 @@ static int sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int to
                      const float *tau, const float *mu0, float *flux_dir, float *gpt_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband(ctx, ngpt, ex)) return rc;
+  if (int rc = take_byband("sw_solver_noscat", ctx, ngpt, nlay, ncol, ex)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !mu0 || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: bad argument");
@@ -909,7 +953,7 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          const float *sfc_emis, float *flux_up, float *flux_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol, ex)) return rc;
+  if (int rc = take_byband_or_mask("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol, ex, kJacFused)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
   LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
@@ -1101,6 +1145,23 @@ int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay
   rq.nlay = nlay;
   rq.ncol = ncol;
   rq.bits = mask_bits;
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *sfc_source_Jac,
+                                     float *flux_up_Jac)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->jacobian = rrtmgpnn_context::JacobianRequest{};
+  if (!flux_up_Jac) return RRTMGPNN_OK;  // nothing wanted: nothing armed
+  if (ngpt < 1 || nlay < 1 || ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_jacobian: bad extents");
+  auto &rq = ctx->jacobian;
+  rq.armed = true;
+  rq.ngpt = ngpt;
+  rq.nlay = nlay;
+  rq.ncol = ncol;
+  rq.sfc_jac = sfc_source_Jac;
+  rq.flux_up = flux_up_Jac;
   return RRTMGPNN_OK;
 }
 

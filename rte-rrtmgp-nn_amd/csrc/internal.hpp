@@ -65,6 +65,11 @@ struct SolverExtras {
   // _clr_all_mcica, _2stream_inc and _2stream_rfmip entries have masked instances, the three that take a request also
   // with by-band outputs
   const uint32_t *mask_bits = nullptr;
+  // rte_lw's flux_up_Jac (rrtmgpnn_solver_request_jacobian): d flux_up / d T_sfc, (nlay+1, ncol), carried beside the
+  // up pass from sfc_jac (ngpt, ncol) -- null on the fused-Planck path, which forms it in-kernel.  Only the LW
+  // no-scattering and rescaled launchers have Jacobian instances, without by-band or g-point outputs
+  const float *sfc_jac = nullptr;
+  float *jac_up = nullptr;
 };
 
 // Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction (a kernel argument)
@@ -139,6 +144,13 @@ struct rrtmgpnn_context {
     int ngpt = 0, nlay = 0, ncol = 0;
     const uint32_t *bits = nullptr;
   } cloud_mask;
+  // rrtmgpnn_solver_request_jacobian: armed for the next solver call on this context, which clears it
+  struct JacobianRequest {
+    bool armed = false;
+    int ngpt = 0, nlay = 0, ncol = 0;
+    const float *sfc_jac = nullptr;
+    float *flux_up = nullptr;
+  } jacobian;
   void *ws = nullptr;
   size_t ws_bytes = 0;
   bool ws_pinned = false;

@@ -45,7 +45,12 @@ __device__ __forceinline__ RsLayer rs_layer(float tau, float ssal, float g, floa
 // kBand: also the by-band fluxes bo.up / bo.dn (ty_fluxes_byband, (nbnd, nlay+1, ncol)): with one angle summed from the
 // ring rows in the flush's barrier window (the terms the broadband sum adds: fac * radiance, the bare radiance when
 // ngpt % 4 != 0), with several angles from the per-g accumulators
-template <bool kBand = false>
+//
+// kJac (without kBand and g-point outputs; rrtmgpnn_solver_request_jacobian): also flux_jac (nlay+1, ncol), the Jacobian of
+// the upward flux with respect to the surface temperature: J = e * sfc_jac at the surface, J = trans * J with the
+// rescaled transmittance in pass 2 (:1761, 1782), staged in a second ring beside the up values (or, several angles,
+// a third accumulator plane) and summed as flux_up is.  No downward Jacobian (:1743-1745).
+template <bool kBand = false, bool kJac = false>
 __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                                        const float *__restrict__ inc_flux,
                                                        const float *__restrict__ tau, const float *__restrict__ ssa,
@@ -54,8 +59,10 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
                                                        const float *__restrict__ sfc, float *__restrict__ ws,
                                                        float *__restrict__ flux_up, float *__restrict__ flux_dn,
                                                        float *__restrict__ gpt_up, float *__restrict__ gpt_dn,
-                                                       BandOut bo)
+                                                       BandOut bo, const float *__restrict__ sfc_jac,
+                                                       float *__restrict__ flux_jac)
 {
+  static_assert(!kJac || !kBand, "the Jacobian instance has no by-band outputs");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
   const bool on = g < ngpt;
@@ -66,19 +73,20 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
   const bool gpt = gpt_up != nullptr;
   float *gdn = gpt ? gpt_dn + (size_t)ngpt * nlev * icol : nullptr, *gup = gpt ? gpt_up + (size_t)ngpt * nlev * icol : nullptr;
   uint64_t *etab = (uint64_t *)(smem + kExpTabOff);
-  float *ring = smem + kExpTabFloats;                 // [kScatRing][ngpt]
-  float *part = ring + (size_t)kScatRing * ngpt;      // [2][nlev][4]: 0 = dn, 1 = up
+  float *ring = smem + kExpTabFloats;                 // [kScatRing][ngpt]; kJac: [2][kScatRing][ngpt]
+  float *part = ring + (size_t)(kJac ? 2 : 1) * kScatRing * ngpt;  // [2][nlev][4]: 0 = dn, 1 = up; kJac: 2 = Jacobian
   load_exp_table(etab);
   __syncthreads();
   const bool multi = ang.nmus > 1;
   // workspace per column: first-pass radn_dn and the radn_up of the up pass (nlev each), and with nmus > 1
-  // the per-g flux accumulators (dn, up)
-  float *wcol = ws + (size_t)(multi ? 4 : 2) * nlev * ngpt * icol;
+  // the per-g flux accumulators (dn, up; kJac: and the Jacobian's)
+  float *wcol = ws + (size_t)(multi ? (kJac ? 5 : 4) : 2) * nlev * ngpt * icol;
   float *WD = wcol, *WU = wcol + (size_t)nlev * ngpt, *acc_base = wcol + (size_t)2 * nlev * ngpt;
   const size_t cl = (size_t)ngpt * nlay * icol, cv = (size_t)ngpt * nlev * icol;
   auto X = [&](int l) { return (size_t)gc + (size_t)ngpt * l; };
   const float *tc = tau + cl, *wc = ssa + cl, *gcol = gg + cl, *yc = lay + cl, *vc = lev + cv;
   const float e = emis[gc + (size_t)ngpt * icol], ss = sfc[gc + (size_t)ngpt * icol];
+  const float sj = kJac ? sfc_jac[gc + (size_t)ngpt * icol] : 0.0f;
   const float inc = inc_flux ? inc_flux[gc + (size_t)ngpt * icol] : 0.0f;
   auto layer = [&](int l, float D) {
     return rs_layer(tc[X(l)], wc[X(l)], gcol[X(l)], D, yc[X(l)], vc[X(l)], vc[X(l + 1)], etab);
@@ -101,9 +109,23 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
         if (gpt) (q == 0 ? gdn : gup)[(size_t)level * ngpt + g] = rad;
       }
     };
+    // kJac: v = fac * J of an up-pass level
+    auto put_jac = [&](float v, int r, int level) {
+      if (!on) return;
+      if (multi) {
+        float *w = acc_base + ((size_t)2 * nlev + level) * ngpt + g;
+        *w = acc ? *w + v : v;
+      } else {
+        ring[((size_t)kScatRing + r) * ngpt + g] = v;
+      }
+    };
     auto flush = [&](float *pq, int n, int lev0, int dl) {
       if (multi) return;
-      if constexpr (kBand)
+      if constexpr (kJac) {
+        // the up pass flushes both rings: flux_up's partials to pup, the Jacobian's to the plane after it
+        if (pq == pup) ring_flush<kScatRing>(ring, pq, 2, n, lev0, dl, ngpt, nlev, false);
+        else           ring_flush<kScatRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
+      } else if constexpr (kBand)
         ring_flush<kScatRing, true>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false, false, 0, &bo.b,
                                     pq == pdn ? bo.dn : bo.up, nullptr, nullptr, icol);
       else
@@ -121,8 +143,10 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
     }
     // surface reflection and emission
     float U = I * (1.0f - e) + e * ss;
+    float J = e * sj;  // kJac (:270)
     if (on) WU[X(sfcl)] = U;
     put(fac * U, U, 0, 1, sfcl);
+    if constexpr (kJac) put_jac(fac * J, 0, sfcl);
     flush(pup, 1, sfcl, 1);
     // 2: up with the adjustment from the first-pass radiance at the layer top (lw_transport_1rescl)
     for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
@@ -136,6 +160,10 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
           U = r.trans * U + r.sup + adj;
           if (on) WU[X(ltop)] = U;
           put(fac * U, U, s, 1, ltop);
+          if constexpr (kJac) {
+            J = r.trans * J;
+            put_jac(fac * J, s, ltop);
+          }
         }
       }
       flush(pup, min(kScatRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
@@ -180,11 +208,20 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
       const int l = t % nlev;
       (t < nlev ? flux_dn : flux_up)[l + (size_t)nlev * icol] = s;
     }
+    if constexpr (kJac) {
+      for (int l = g; l < nlev; l += blockDim.x) {
+        const float *w = acc_base + ((size_t)2 * nlev + l) * ngpt;
+        float s = 0.0f;
+        for (int i = 0; i < ngpt; i++) s = s + w[i];  // sum_broadband
+        flux_jac[l + (size_t)nlev * icol] = s;
+      }
+    }
     return;
   }
   for (int l = g; l < nlev; l += blockDim.x) {
     flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
     flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
+    if constexpr (kJac) flux_jac[l + (size_t)nlev * icol] = combine4(pup + 4 * (nlev + l));
   }
 }
 
@@ -325,24 +362,34 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNosca
   a.nmus = nmus;
   for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
   const int threads = (ngpt + 63) / 64 * 64;
-  const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)kScatRing * ngpt + (size_t)2 * (nlay + 1) * 4);
+  const bool jac = ex.jac_up != nullptr;
+  if (jac && (ex.gpt_up || ex.gpt_dn || ex.byband()))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: the flux Jacobian comes without g-point or by-band outputs");
+  if (jac && !ex.sfc_jac) return fail(RRTMGPNN_ERR_ARGUMENT, "lw rescaled solver: the flux Jacobian needs sfc_source_Jac");
+  const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)(jac ? 2 : 1) * kScatRing * ngpt +
+                                      (size_t)(jac ? 3 : 2) * (nlay + 1) * 4);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
   void *ws = nullptr;
-  if (int rc = ctx->workspace(sizeof(float) * (nmus > 1 ? 4 : 2) * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
+  const int planes = nmus > 1 ? (jac ? 5 : 4) : 2;
+  if (int rc = ctx->workspace(sizeof(float) * planes * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
   if ((ex.gpt_up == nullptr) != (ex.gpt_dn == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: g-point outputs need both gpt_flux_up and gpt_flux_dn");
   if (ex.byband() && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
   if (ex.byband() && ex.gpt_up)
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
                                           "reduces g-point fluxes)");
-  if (ex.byband())
+  if (jac)
+    hipLaunchKernelGGL((lw_rescl_kernel<false, true>), dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol,
+                       p.top_at_1, a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source,
+                       (float *)ws, p.flux_up, p.flux_dn, nullptr, nullptr, BandOut{}, ex.sfc_jac, ex.jac_up);
+  else if (ex.byband())
     hipLaunchKernelGGL(lw_rescl_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1,
                        a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
-                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, band_out(ex));
+                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, band_out(ex), nullptr, nullptr);
   else
     hipLaunchKernelGGL(lw_rescl_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1,
                        a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
-                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{});
+                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{}, nullptr, nullptr);
   RRTMGPNN_LAUNCH_CHECK("lw_rescl_kernel");
   return RRTMGPNN_OK;
 }

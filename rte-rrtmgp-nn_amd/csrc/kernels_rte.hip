@@ -158,8 +158,18 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // aligned): a wave's 64 g-points are two consecutive mask words, the same pair for every lane, so the pair is read by
 // a scalar load into two SGPRs per prefetched layer and taken by the select as the lane mask (bit i = lane i = g-point
 // 64 * wave + i); no VGPR holds mask or bit.  Other ngpt keep the per-lane word.
+//
+// kJac (without kBand and kDual; rrtmgpnn_solver_request_jacobian): also flux_jac (nlay+1, ncol), the Jacobian of the
+// upward flux with respect to the surface temperature (rte/kernels/mo_rte_solver_kernels.F90:270, 290, 319, 390-411,
+// 967, 975; compiled out in the reference by compute_Jac = .false.).  The up pass carries J beside U: J = e * sfc_jac at
+// the surface (sfc_jac read, or formed from the Planck table's extra row B_b(tsfc + 1) when fused), J = T * J through each
+// layer with the T that multiplies U.  With one angle the values fac * J are staged beside fac * U in the up pass only:
+// that pass walks chunks of kRingDual with two rings in the single ring's LDS, flushed as the dual instance's are
+// (part gains the plane [nlev][4] after up); the down pass keeps chunks of kRing.  With several angles fac * J is
+// accumulated in a third per-g plane behind gup's and summed as flux_up is.  Summed with flux_up's convention at every
+// angle count: the bare J when ngpt % 4 != 0 at one angle.
 template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false, bool kMask = false,
-          bool kMaskS = false>
+          bool kMaskS = false, bool kJac = false>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
@@ -167,9 +177,16 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
                                            LwPlanck pl, BandArgs bands, const float *__restrict__ tau_bnd,
                                            float *__restrict__ gdn, float *__restrict__ gup, long long gcs,
                                            float *__restrict__ flux_up, float *__restrict__ flux_dn, BandOut bo,
-                                           const uint32_t *__restrict__ cmask)
+                                           const uint32_t *__restrict__ cmask, const float *__restrict__ sfc_jac,
+                                           float *__restrict__ flux_jac)
 {
   constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
+  // kJac with one angle: the down pass' chunk, the up pass' (two rings), and the ring's rows
+  constexpr bool kJac1 = kJac && !kMulti;
+  constexpr int kRd = kR, kRu = kJac1 ? kRingDual : kR;
+  constexpr int kRows = kDual ? 2 * kR : (kJac1 && 2 * kRu > kR ? 2 * kRu : kR);
+  static_assert(!kJac || (!kBand && !kDual && !kMaskS), "the Jacobian instances have no by-band or clear-sky outputs");
+  static_assert(kRu % kPF == 0, "prefetch depth must divide the up pass' ring");
   static_assert(!kMask || (kInc && (!kBand || !kDual)), "the cloud mask switches the fused band increment");
   static_assert(!kMaskS || (kMask && kDual), "the wave-uniform mask pair is the dual masked instance's");
   using mask_t = std::conditional_t<kMaskS, uint64_t, uint32_t>;  // one layer's mask: the wave's pair, or the lane's word
@@ -197,9 +214,10 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   const int brow = 2 * nlay + 1;
   // [kRing][rs]: rows of ngpt floats, padded by 4 when the flush walks one lane per partial (rows in different banks)
   const int rs = lw_ring_stride(ngpt);
-  float *ring = btab + (kFused ? lw_btab_floats(bands.nbnd, nlay) : 0);
+  float *ring = btab + (kFused ? lw_btab_floats(bands.nbnd, nlay, kJac) : 0);
   // [2][nlev][4]: 0 = dn, 1 = up; kDual: [4][nlev][4]: dn, dn clear, up, up clear
-  float *part = ring + (size_t)(kDual ? 2 : 1) * kR * rs;
+  // kJac, one angle: [3][nlev][4]: dn, up, Jacobian
+  float *part = ring + (size_t)kRows * rs;
   load_exp_table(etab);
   const ColArr Ttau(tau, (size_t)ngpt * nlay * icol, row * nlay);
   const ColArr Tlay(lay, (size_t)ngpt * nlay * icol, row * nlay);  // lay_source, or pfrac when fused
@@ -260,18 +278,26 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // kBtabU entries per thread per round, their loads issued together: the temperatures, then the table pairs (a
     // loop of one entry per round waits out two dependent load latencies per entry, ~16 per block at C3)
     constexpr int kBtabU = 8;
-    const int ntab = bands.nbnd * (brow + 1), nrow = bands.nbnd * brow;
+    // kJac: one more row, B_b(tsfc + 1), at [nbnd*(brow+1) + b]
+    const int ntab = bands.nbnd * (brow + (kJac ? 2 : 1)), nrow = bands.nbnd * brow;
     for (int i0 = threadIdx.x; i0 < ntab; i0 += kBtabU * (int)blockDim.x) {
       float T[kBtabU];
       int bb[kBtabU];
 #pragma unroll
       for (int u = 0; u < kBtabU; u++) {
         const int i = min(i0 + u * (int)blockDim.x, ntab - 1);  // clamped: past-the-end entries are not stored
-        const int b = i < nrow ? i / brow : i - nrow;
+        int b = i < nrow ? i / brow : i - nrow;
         const int k = i < nrow ? i - b * brow : -1;
+        bool plus1 = false;
+        if constexpr (kJac) {
+          plus1 = b >= bands.nbnd;
+          if (plus1) b -= bands.nbnd;
+        }
         bb[u] = b;
         const float *p = k < 0 ? pl.tsfc + icol : (k < nlay ? tl + k : tv + (k - nlay));  // one load, no branch
         T[u] = *p;
+        if constexpr (kJac)
+          if (plus1) T[u] = T[u] + 1.0f;
       }
       float v[kBtabU];
 #pragma unroll
@@ -310,6 +336,27 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   auto put_clr = [&](float v, int r) {
     if (on) ring[(size_t)(kR + r) * rs + g] = v;
   };
+  // kJac: v = fac * J of an up-pass level, into the up pass' second ring or (kMulti) the third accumulator plane
+  float *wjac = (kJac && kMulti) ? wup + (size_t)nlev * ngpt : nullptr;
+  auto put_jac = [&](float v, int r, int level, bool acc) {
+    if constexpr (kMulti) {
+      if (on) {
+        float *w = wjac + (size_t)level * ngpt + g;
+        *w = acc ? *w + v : v;
+      }
+    } else if (on) {
+      ring[(size_t)(kRu + r) * rs + g] = v;
+    }
+  };
+  // kJac, one angle: the up pass' flush of both rings, flux_up's partials to pq and the Jacobian's to the plane after
+  auto flush_jac = [&](float *pq, int n, int lev0, int dl) {
+    if constexpr (kJac1) {
+      if (rs != ngpt)
+        ring_flush_lanes2<kRu>(ring, rs, pq, nlev, n, lev0, dl, ngpt);
+      else
+        ring_flush<kRu>(ring, pq, 2, n, lev0, dl, ngpt, nlev, false);
+    }
+  };
   // bq: the by-band array of the quantity being flushed (kBand)
   auto flush = [&](float *pq, int n, int lev0, int dl, float *bq) {
     if constexpr (kDual) {
@@ -344,7 +391,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   // spills them across the layer loops (2 VGPRs, 12 bytes of scratch); with the count known they are formed in place.
   // (Every !kMulti instance runs one angle; stating it for all of them is left as a change of its own, since it moves the
   // other one-angle instances' register allocation: DESIGN.md section 8.)
-  const int nmus = (kMask && kBand && !kMulti) ? 1 : ang.nmus;
+  const int nmus = ((kMask && kBand && !kMulti) || kJac1) ? 1 : ang.nmus;  // kJac1: as stated, for the same reason
   for (int imu = 0; imu < nmus; imu++) {
     // lw_Ds (rte/mo_rte_lw.F90:329-341): the kernel's D(igpt, icol), one angle
     const float D = ang.Dg ? ang.Dg[gc + (size_t)ngpt * icol] : ang.D[imu];
@@ -411,10 +458,10 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           }
         }
       };
-      for (int j0 = 0; j0 < nlay; j0 += kR) {
+      for (int j0 = 0; j0 < nlay; j0 += kRd) {
 #pragma unroll
-        for (int r = 0; r < kR; r++) step(j0 + r, r);
-        flush(pdn, min(kR, nlay - j0), top + dl_dn * (j0 + 1), dl_dn, bdn);
+        for (int r = 0; r < kRd; r++) step(j0 + r, r);
+        flush(pdn, min(kRd, nlay - j0), top + dl_dn * (j0 + 1), dl_dn, bdn);
       }
     }
     // upward: lw_transport_noscat_up (:950-980); j-th layer from the surface is l = lay_up(j).  With one angle its first
@@ -435,9 +482,24 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // surface reflection and emission (:269)
     float U = I * (1.0f - e) + e * ss;
     float Uc = Ic * (1.0f - e) + e * ss;
+    // kJac: the surface level's Jacobian (:270), from sfc_source_Jac: read, or pfrac * (B_b(tsfc + 1) - B_b(tsfc)) as
+    // planck_source_kernel forms it.  Fetched here, not in the prologue, so that no register holds it down the column
+    float J = 0.0f;
+    if constexpr (kJac) {
+      float sj;
+      if constexpr (kFused) {
+        const float *bs = btab + (size_t)bands.nbnd * brow + band_of(bands, gc);
+        sj = Tlay.ld(vg, row * (uint32_t)(pl.sfc_lay - 1)) * (bs[bands.nbnd] - bs[0]);
+      } else {
+        sj = on ? sfc_jac[g + (size_t)ngpt * icol] : 0.0f;
+      }
+      J = e * sj;
+    }
     put(fac * U, U, 0, 1, sfcl, acc);
     if constexpr (kDual) put_clr(fac * Uc, 0);
-    flush(pup, 1, sfcl, 1, bup);
+    if constexpr (kJac) put_jac(fac * J, 0, sfcl, acc);
+    if constexpr (kJac1) flush_jac(pup, 1, sfcl, 1);
+    else flush(pup, 1, sfcl, 1, bup);
     {
       float pt[kPF], py[kPF], pv[kPF], pi[kPF];
       mask_t pm[kPF];
@@ -471,6 +533,10 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           const float S = (1.0f - T) * lvup + 2.0f * fact * (ly - lvup);
           U = T * U + S;
           put(fac * U, U, r, 1, top_at_1 ? l : l + 1, acc);
+          if constexpr (kJac) {
+            J = T * J;  // :967, 975
+            put_jac(fac * J, r, top_at_1 ? l : l + 1, acc);
+          }
           if constexpr (kDual) {
             const float Tc = solver_exp_neg(-tc, etab);
             const float fc = (tc > tau_thresh) ? solver_div(1.0f - Tc, tc) - Tc : tc * (0.5f - 1.0f / 3.0f * tc);
@@ -480,10 +546,11 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           }
         }
       };
-      for (int j0 = 0; j0 < nlay; j0 += kR) {
+      for (int j0 = 0; j0 < nlay; j0 += kRu) {
 #pragma unroll
-        for (int r = 0; r < kR; r++) step(j0 + r, r);
-        flush(pup, min(kR, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn, bup);
+        for (int r = 0; r < kRu; r++) step(j0 + r, r);
+        if constexpr (kJac1) flush_jac(pup, min(kRu, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
+        else flush(pup, min(kRu, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn, bup);
       }
     }
   }
@@ -516,11 +583,21 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
       }
       (t < nlev ? flux_dn : flux_up)[l + (size_t)nlev * icol] = s;
     }
+    if constexpr (kJac) {
+      // sum_broadband of the angle-summed g-point Jacobians (:406, 411)
+      for (int l = g; l < nlev; l += blockDim.x) {
+        const float *w = wjac + (size_t)l * ngpt;
+        float s = 0.0f;
+        for (int i = 0; i < ngpt; i++) s = s + w[i];
+        flux_jac[l + (size_t)nlev * icol] = s;
+      }
+    }
     return;
   }
   for (int l = g; l < nlev; l += blockDim.x) {
     flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
     flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
+    if constexpr (kJac) flux_jac[l + (size_t)nlev * icol] = combine4(pup + 4 * (nlev + l));
     if constexpr (kDual) {
       gdn[l + (size_t)nlev * icol] = combine4(pdn + 4 * (nlev + l));
       gup[l + (size_t)nlev * icol] = combine4(pup + 4 * (nlev + l));
@@ -552,15 +629,25 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   if (bb && gpt)
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
                                           "reduces g-point fluxes)");
+  // flux_up_Jac: sfc_source_Jac is read where the sources are read, and formed in-kernel where they are formed
+  const bool jac = ex.jac_up != nullptr;
+  if (jac && (gpt || bb || dual))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: the flux Jacobian comes without g-point, by-band or clear-sky outputs");
+  if (jac && (ex.sfc_jac == nullptr) != kFused)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: the flux Jacobian needs sfc_source_Jac with source arrays, and none "
+                                       "with the fused Planck sources");
+  const bool multi = nmus > 1 || gpt;
   LwAngles a{};
   a.nmus = nmus;
   a.Dg = ex.lw_Ds;
   a.rad = gpt && nmus == 1;
   for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
   int threads = (ngpt + 63) / 64 * 64;
-  size_t lds = sizeof(float) * (kExpTabFloats + (size_t)(dual ? 2 * kRingDual : kRing) * lw_ring_stride(ngpt) +
-                                (size_t)(dual ? 4 : 2) * (nlay + 1) * 4);
-  if (kFused) lds += sizeof(float) * lw_btab_floats(in.bands.nbnd, nlay);
+  // one-angle Jacobian: two rings of kRingDual in the up pass, one more plane of partials
+  const int ring_rows = dual ? 2 * kRingDual : ((jac && !multi) ? std::max(kRing, 2 * kRingDual) : kRing);
+  size_t lds = sizeof(float) * (kExpTabFloats + (size_t)ring_rows * lw_ring_stride(ngpt) +
+                                (size_t)(dual ? 4 : ((jac && !multi) ? 3 : 2)) * (nlay + 1) * 4);
+  if (kFused) lds += sizeof(float) * lw_btab_floats(in.bands.nbnd, nlay, jac);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: too many layers for LDS partials");
   // per-g accumulators: the caller's g-point arrays, or (several angles) the context workspace
   float *gdn = ex.gpt_dn, *gup = ex.gpt_up;
@@ -568,11 +655,12 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   long long gcs = nv;
   if (!gpt && nmus > 1) {
     void *ws = nullptr;
-    int rc = ctx->workspace(sizeof(float) * 2 * (size_t)nv * ncol, &ws);
+    const int planes = jac ? 3 : 2;  // dn, up and the Jacobian's accumulators
+    int rc = ctx->workspace(sizeof(float) * planes * (size_t)nv * ncol, &ws);
     if (rc) return rc;
     gdn = (float *)ws;
     gup = gdn + nv;
-    gcs = 2 * nv;
+    gcs = planes * nv;
   }
   constexpr int PF = kFused ? kLwfPf : kLwPf;
   const BandOut bo = bb ? band_out(ex) : BandOut{};
@@ -580,9 +668,9 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
     const float *src = kFused ? in.pfrac : lay_source;
     hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
                        p.tau, src, kFused ? src : lev_source, p.sfc_emis, sfc_source, in.pl, in.bands,
-                       kInc ? in.tau_bnd : nullptr, gdn, gup, gcs, p.flux_up, p.flux_dn, bo, ex.mask_bits);
+                       kInc ? in.tau_bnd : nullptr, gdn, gup, gcs, p.flux_up, p.flux_dn, bo, ex.mask_bits, ex.sfc_jac,
+                       ex.jac_up);
   };
-  const bool multi = nmus > 1 || gpt;
   if constexpr (kFused && kInc) {
     if (dual) {
       gdn = dn_clr;
@@ -607,6 +695,12 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
     if constexpr (kFused && kInc) {
       if (gpt || ex.lw_Ds)
         return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: a cloud mask with g-point outputs or lw_Ds");
+      if (jac) {
+        if (multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true, false, true>);
+        else       go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true, false, true>);
+        RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (masked, Jacobian)");
+        return RRTMGPNN_OK;
+      }
       // bb: the masked by-band twins (rrtmgpnn_solver_request_byband_mcica)
       if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true, false, true>);
       else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true, false, true>);
@@ -618,7 +712,9 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
       return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: a cloud mask needs the fused band increment");
     }
   }
-  if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true>);
+  if (jac && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, false, false, true>);
+  else if (jac)    go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, false, false, true>);
+  else if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true>);
   else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true>);
   else if (multi)  go(lw_noscat_kernel<kFused, kInc, PF, true>);
   else             go(lw_noscat_kernel<kFused, kInc, PF, false>);

@@ -70,8 +70,12 @@ __device__ __forceinline__ float interp1d(float val, float offset, float delta, 
   return lo + frac * (hi - lo);
 }
 
-// fused Planck table size in floats, padded so the ring that follows stays 16-byte aligned
-__host__ __device__ constexpr size_t lw_btab_floats(int nbnd, int nlay) { return ((size_t)nbnd * (2 * nlay + 2) + 3) & ~(size_t)3; }
+// fused Planck table size in floats, padded so the ring that follows stays 16-byte aligned; jac: with the row
+// B_b(tsfc + 1) of the Jacobian instances
+__host__ __device__ constexpr size_t lw_btab_floats(int nbnd, int nlay, bool jac = false)
+{
+  return ((size_t)nbnd * (2 * nlay + 2 + (jac ? 1 : 0)) + 3) & ~(size_t)3;
+}
 
 // Gauss-Jacobi quadrature of the LW no-scattering solvers (secants and weights, nmus <= 4)
 struct LwAngles {

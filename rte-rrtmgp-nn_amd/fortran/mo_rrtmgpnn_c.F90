@@ -21,6 +21,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_lw_solver_1rescl_gpt, c_rrtmgpnn_lw_solver_2stream_gpt, c_rrtmgpnn_sw_solver_noscat_gpt
   public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
   public :: c_rrtmgpnn_solver_request_byband_mcica
+  public :: c_rrtmgpnn_solver_request_jacobian
   public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
             c_rrtmgpnn_draw_samples
   public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
@@ -334,6 +335,14 @@ module mo_rrtmgpnn_c
       type(c_ptr), value :: ctx, bnd_flux_up, bnd_flux_dn, bnd_flux_dir, mask_bits
       integer(c_int), value :: nbnd, ngpt, nlay, ncol
       integer(c_int), dimension(*), intent(in) :: band_lims_gpt
+    end function
+    ! rte_lw's flux_up_Jac (nlay+1, ncol) from the next LW solver call; sfc_source_Jac (ngpt, ncol), or null on the
+    ! fused-Planck entries
+    integer(c_int) function c_rrtmgpnn_solver_request_jacobian(ctx, ngpt, nlay, ncol, sfc_source_Jac, flux_up_Jac) &
+        bind(C, name="rrtmgpnn_solver_request_jacobian")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, sfc_source_Jac, flux_up_Jac
+      integer(c_int), value :: ngpt, nlay, ncol
     end function
     integer(c_int) function c_rrtmgpnn_sampled_mask_max_ran(ctx, ngpt, nlay, ncol, randoms, cloud_frac, cloud_mask, &
         mask_bits) bind(C, name="rrtmgpnn_sampled_mask_max_ran")

@@ -1,5 +1,5 @@
 ! mo_rte_lw -- drop-in for rte/mo_rte_lw.F90 (rte_lw, :60-424) in the fork's configuration
-! (compute_Jac = .false., rte/mo_rte_rrtmgp_config.F90:28).
+! (compute_Jac = .false., rte/mo_rte_rrtmgp_config.F90:28; here a switch, rte_rrtmgp_config_jacobian).
 ! The optical properties and sources are read from their device copies (mo_optical_props, mo_source_functions);
 ! sources gas_optics left unformed are formed inside the no-scattering solver from the Planck fraction
 ! (rrtmgpnn_lw_solver_noscat_planck, emissivity expanded by band in-kernel); the broadband reduction is fused into
@@ -8,7 +8,10 @@
 ! (use_2stream).  ty_fluxes_flexible g-point fluxes through the *_gpt entries: no-scattering and rescaled solutions
 ! with one angle the g-point radiances (quirk B-5), with several the angle-summed fluxes; lw_solver_2stream the adding
 ! fluxes.  lw_Ds on 1scl properties; flux_up_Jac / flux_dn_Jac accepted and left untouched (compute_Jac = .false.),
-! an error string only with use_2stream, as the reference.
+! an error string only with use_2stream, as the reference.  With compute_Jac switched on (:160-163): flux_up_Jac is
+! required, (nlay+1, ncol), and returned by the no-scattering and rescaled solvers (rrtmgpnn_solver_request_jacobian,
+! from sources%sfc_source_Jac, or formed in-kernel with the deferred Planck sources); flux_dn_Jac stays untouched (there
+! is no downward Jacobian, rte/kernels/mo_rte_solver_kernels.F90:1743-1745); not with g-point or by-band outputs.
 ! ty_fluxes_byband (mo_fluxes_byband) is detected with select type: the solver forms the band sums itself
 ! (rrtmgpnn_solver_request_byband).  Together with g-point outputs the g-point arrays are reduced with
 ! rrtmgpnn_sum_byband -- except with one angle of the no-scattering / rescaled solution, whose g-point arrays hold
@@ -20,7 +23,7 @@ module mo_rte_lw
   use mo_source_functions, only: ty_source_func_lw
   use mo_fluxes,           only: ty_fluxes_flexible
   use mo_fluxes_byband,    only: ty_fluxes_byband
-  use mo_rte_rrtmgp_config, only: check_values
+  use mo_rte_rrtmgp_config, only: check_values, compute_Jac
   use mo_rrtmgpnn_c
   implicit none
   private
@@ -57,11 +60,11 @@ contains
     integer(c_long_long) :: ng, nv, nsfc, ngv
     integer(c_int), allocatable :: lims(:,:)
     type(c_ptr) :: d_tau, d_ssa, d_g, d_lay, d_lev, d_sfc, d_jac, d_emis, d_emis_gpt, d_inc, d_up, d_dn
-    type(c_ptr) :: d_ds, d_gup, d_gdn, d_bup, d_bdn
+    type(c_ptr) :: d_ds, d_gup, d_gdn, d_bup, d_bdn, d_upj
     integer(c_long_long) :: nbv
     integer(c_int) :: rc_drop
     logical :: two_str, use_2s, src_tmp, g_tmp, gpt, du, dd, bb, one_angle
-    real(wp), allocatable :: up(:,:), dn(:,:)
+    real(wp), allocatable :: up(:,:), dn(:,:), upj(:,:)
 
     ncol  = optical_props%get_ncol()
     nlay  = optical_props%get_nlay()
@@ -106,7 +109,15 @@ contains
     end if
     ! flux_up_Jac / flux_dn_Jac: accepted and left untouched, as in the reference, where compute_Jac is a .false.
     ! parameter (mo_rte_rrtmgp_config.F90:28): no extent check (:160-163), no write; rejected only with use_2stream
-    ! on 2str properties (:252-253, below).
+    ! on 2str properties (:252-253, below).  With compute_Jac switched on, (:160-163):
+    if (compute_Jac) then
+      if (.not. present(flux_up_Jac)) then
+        error_msg = "rte_lw: compute_Jac=true but Jacobian arrays not provided"; return
+      end if
+      if (any(shape(flux_up_Jac) /= [nlay + 1, ncol])) then
+        error_msg = "rte_lw: flux Jacobian inconsistently sized"; return
+      end if
+    end if
     if (associated(fluxes%gpt_flux_up)) then
       if (any(shape(fluxes%gpt_flux_up) /= [ngpt, nlay + 1, ncol])) then
         error_msg = "rte_lw: gpt_flux_up inconsistently sized"; return
@@ -124,6 +135,14 @@ contains
       if (bb) error_msg = fluxes%check_extents_bnd(nband, nlay + 1, ncol, .false.)
       if (error_msg /= '') return
     end select
+    if (compute_Jac) then
+      if (fluxes%are_desired_gpt()) then
+        error_msg = "rte_lw: flux Jacobian together with g-point fluxes is not supported"; return
+      end if
+      if (bb) then
+        error_msg = "rte_lw: flux Jacobian together with by-band fluxes is not supported"; return
+      end if
+    end if
     use_2s = .false.
     if (present(use_2stream)) use_2s = use_2stream
     two_str = .false.
@@ -182,6 +201,8 @@ contains
       d_gup = dev_scratch(ngv)
       d_gdn = dev_scratch(ngv)
     end if
+    d_upj = c_null_ptr
+    if (compute_Jac) d_upj = dev_scratch(nv)
     d_emis_gpt = c_null_ptr
     d_bup = c_null_ptr
     d_bdn = c_null_ptr
@@ -232,6 +253,10 @@ contains
       else
         call dev_copy_out(dn, d_dn, nv)
       end if
+      if (compute_Jac) then
+        allocate(upj(nlay + 1, ncol))
+        call dev_copy_out(upj, d_upj, nv)
+      end if
       if (gpt) then
         if (associated(fluxes%gpt_flux_up)) call dev_copy_out(fluxes%gpt_flux_up, d_gup, ngv)
         if (associated(fluxes%gpt_flux_dn)) call dev_copy_out(fluxes%gpt_flux_dn, d_gdn, ngv)
@@ -249,6 +274,7 @@ contains
       if (associated(fluxes%flux_up) .and. .not. du) fluxes%flux_up = up
       if (associated(fluxes%flux_dn) .and. .not. dd) fluxes%flux_dn = dn
       if (associated(fluxes%flux_net)) fluxes%flux_net = dn - up
+      if (compute_Jac) flux_up_Jac = upj
       if (bb) then
         select type (fluxes)
         class is (ty_fluxes_byband)  ! net_byband_precalc
@@ -259,9 +285,18 @@ contains
     call dev_release(d_emis); call dev_release(d_emis_gpt); call dev_release(d_inc)
     call dev_release(d_up); call dev_release(d_dn)
     call dev_release(d_ds); call dev_release(d_gup); call dev_release(d_gdn)
-    call dev_release(d_bup); call dev_release(d_bdn)
+    call dev_release(d_bup); call dev_release(d_bdn); call dev_release(d_upj)
 
   contains
+
+    ! compute_Jac: flux_up_Jac from the solver call that follows, which clears the request (sfc_jac: the device copy of
+    ! sources%sfc_source_Jac, or NULL where the solver forms it from the deferred Planck sources)
+    subroutine arm_jacobian(sfc_jac)
+      type(c_ptr), intent(in) :: sfc_jac
+      if (compute_Jac .and. error_msg == '') &
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_solver_request_jacobian(rrtmgpnn_ctx(), ngpt, nlay, ncol, sfc_jac, d_upj), &
+                                   "rte_lw: solver_request_jacobian")
+    end subroutine arm_jacobian
 
     ! the solver for these optical properties and sources, with g-point outputs gu / gd (NULL: none)
     subroutine run_solver(gu, gd)
@@ -269,6 +304,8 @@ contains
       if (.not. two_str .and. sources%planck_deferred) then
         ! lw_solver_noscat_GaussQuad (:326-353) with compute_Planck_source_nn (gas_optics, :398-404) and expand(sfc_emis)
         ! (:429-447) inside the solver
+        call arm_jacobian(c_null_ptr)
+        if (error_msg == '') &
         error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
                       merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_ds, &
                       d_inc, d_tau, dev_present(sources%lay_source, ng, PRESENT_READ), nband, sources%pk_ntemp, &
@@ -281,6 +318,9 @@ contains
         src_tmp = .false.
         g_tmp = .false.
         error_msg = sources%device_sources(d_lay, d_lev, d_sfc, d_jac, src_tmp)
+        ! (sources held on the host or the device as arrays: device_sources leaves sfc_source_Jac aside)
+        if (compute_Jac .and. error_msg == '' .and. .not. src_tmp) &
+          d_jac = dev_present(sources%sfc_source_Jac, nsfc, PRESENT_READ)
         if (error_msg == '') then
           d_emis_gpt = dev_scratch(nsfc)
           ! sfc_emis expanded to g-points (:429-447), then the solver (:326-387)
@@ -298,11 +338,15 @@ contains
                                        merge(1_c_int, 0_c_int, top_at_1), d_inc, d_tau, d_ssa, d_g, d_lev, d_emis_gpt, &
                                        d_sfc, d_up, d_dn, gu, gd), "rte_lw: lw_solver_2stream")
           else if (two_str) then
+            call arm_jacobian(d_jac)
+            if (error_msg == '') &
             error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
                                        merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), &
                                        gauss_wts(1:nmus, nmus), d_inc, d_tau, d_ssa, d_g, d_lay, d_lev, d_emis_gpt, &
                                        d_sfc, d_up, d_dn, gu, gd), "rte_lw: lw_solver_noscat (rescaled)")
           else
+            call arm_jacobian(d_jac)
+            if (error_msg == '') &
             error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_gpt(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
                                        merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), &
                                        gauss_wts(1:nmus, nmus), d_ds, d_inc, d_tau, d_lay, d_lev, d_emis_gpt, d_sfc, &

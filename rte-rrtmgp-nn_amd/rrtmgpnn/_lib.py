@@ -104,7 +104,8 @@ SIGNATURES = {
     "rrtmgpnn_sw_solver_noscat_gpt": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 5),
     "rrtmgpnn_solver_request_byband": (c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp]),
     "rrtmgpnn_solver_request_cloud_mask": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
-    "rrtmgpnn_solver_request_byband_mcica": (c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp, c_int, c_int, c_int,
+    "rrtmgpnn_solver_request_jacobian": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "rrtmgpnn_solver_request_byband_mcica":(c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                                      c_vp]),
     "rrtmgpnn_sampled_mask_max_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_sampled_mask_exp_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),

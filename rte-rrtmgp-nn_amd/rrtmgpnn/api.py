@@ -12,6 +12,7 @@ Names, argument meaning and error behaviour follow the reference:
   ty_cloud_optics                extensions/cloud_optics/mo_cloud_optics.F90 -> CloudOptics
   ty_optical_props_arry%increment / %delta_scale  rte/mo_optical_props.F90:882-1023, 565-604
   rte_config_checks              rte/mo_rte_rrtmgp_config.F90:45-61        -> rte_config_checks
+  compute_Jac                    rte/mo_rte_rrtmgp_config.F90:28           -> rte_config_jacobian (a switch here)
 Class-level functions RETURN an error message ('' on success), never raise for user errors, like the
 reference's `character(len=128) error_msg`; `stop_on_err` turns one into an exception.
 
@@ -36,6 +37,17 @@ def rte_config_checks(logical):
     """rte_config_checks (rte/mo_rte_rrtmgp_config.F90:56-61)."""
     global check_values
     check_values = bool(logical)
+
+
+# compute_Jac is a .false. parameter in the reference (rte/mo_rte_rrtmgp_config.F90:28); here a switch, off by default:
+# with it on, rte_lw follows rte/mo_rte_lw.F90:160-163 and returns flux_up_Jac
+compute_jac = False
+
+
+def rte_config_jacobian(logical):
+    """Switch rte_lw's flux_up_Jac on or off (off: the arrays are accepted and left untouched, as in the reference)."""
+    global compute_jac
+    compute_jac = bool(logical)
 
 
 class Context:
@@ -912,8 +924,22 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
         if e:
             return e
     # flux_up_Jac / flux_dn_Jac are otherwise accepted and left untouched: compute_Jac is a .false. parameter
-    # (rte/mo_rte_rrtmgp_config.F90:28), so the reference neither checks their extents (:160-163) nor writes them.
+    # (rte/mo_rte_rrtmgp_config.F90:28), so the reference neither checks their extents (:160-163) nor writes them --
+    # unless rte_config_jacobian(True) switched it on.  flux_dn_Jac stays untouched then too: there is no downward
+    # Jacobian (rte/kernels/mo_rte_solver_kernels.F90:1743-1745).
     ncol, nlay, ngpt = optical_props.tau.shape
+    jac = compute_jac
+    if jac:  # (:160-163); Fortran extents (nlay+1, ncol)
+        if flux_up_Jac is None:
+            return "rte_lw: compute_Jac=true but Jacobian arrays not provided"
+        if tuple(flux_up_Jac.shape) != (ncol, nlay + 1):
+            return "rte_lw: flux Jacobian inconsistently sized"
+        if is2 and use_2stream:
+            return "rte_lw: can't provide Jacobian of fluxes w.r.t surface temperature with 2-stream"
+        if fluxes.are_desired_gpt():
+            return "rte_lw: flux Jacobian together with g-point fluxes is not supported"
+        if isinstance(fluxes, FluxesByBand) and fluxes.are_desired_byband():
+            return "rte_lw: flux Jacobian together with by-band fluxes is not supported"
     if lw_Ds is not None:  # (:239-246); Fortran extents (ncol, ngpt) = this tensor layout's (ngpt, ncol)
         if tuple(lw_Ds.shape) != (ngpt, ncol):
             return "rte_lw: lw_Ds inconsistently sized"
@@ -952,6 +978,11 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
             torch.empty((ncol, nlay + 1, ngpt), device=emis.device)
         gd = fluxes.gpt_flux_dn if fluxes.gpt_flux_dn is not None else \
             torch.empty((ncol, nlay + 1, ngpt), device=emis.device)
+    def arm_jacobian():
+        if jac:  # armed for the solver call that follows, which clears it
+            check(L.rrtmgpnn_solver_request_jacobian(ctx.h, ngpt, nlay, ncol, _p(sources.sfc_source_Jac),
+                                                     _p(flux_up_Jac)), "solver_request_jacobian")
+
     def solve(gpt, gu, gd):
         if is2 and use_2stream:  # lw_solver_2stream (rte/mo_rte_lw.F90:357-371); validate() runs unconditionally
             e = op.validate()
@@ -972,18 +1003,21 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
                       float_array(GAUSS_WTS[nmu]), _p(inc_flux), _p(op.tau), _p(op.ssa), _p(op.g),
                       _p(sources.lay_source), _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source), _p(up),
                       _p(dn))
+            arm_jacobian()
             if gpt:
                 check(L.rrtmgpnn_lw_solver_1rescl_gpt(*common, _p(gu), _p(gd)), "lw_solver_1rescl_gpt")
             else:
                 check(L.rrtmgpnn_lw_solver_1rescl(*common), "lw_solver_1rescl")
         elif gpt or lw_Ds is not None:  # ty_fluxes_flexible g-point outputs / column-dependent secants (:329-341)
             ds = _f32dev(lw_Ds, emis.device) if lw_Ds is not None else None
+            arm_jacobian()
             check(L.rrtmgpnn_lw_solver_noscat_gpt(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu,
                                                   float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]), _p(ds),
                                                   _p(inc_flux), _p(op.tau), _p(sources.lay_source),
                                                   _p(sources.lev_source), _p(emis_gpt), _p(sources.sfc_source),
                                                   _p(up), _p(dn), _p(gu), _p(gd)), "lw_solver_noscat_gpt")
         else:
+            arm_jacobian()
             check(L.rrtmgpnn_lw_solver_noscat(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), nmu,
                                               float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]), _p(inc_flux),
                                               _p(op.tau), _p(sources.lay_source), _p(sources.lev_source),

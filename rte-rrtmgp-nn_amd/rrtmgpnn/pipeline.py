@@ -50,6 +50,12 @@ mcica={..., "byband": True}: the by-band fluxes of a byband=True step under the 
 the paired request rrtmgpnn_solver_request_byband_mcica takes the place of each chain's cloud-mask request, so the
 masked by-band solver instances run; unfused, rrtmgpnn_solver_request_byband ahead of each plain solver call of the
 McICA sequence.  Not with "clrsky": the clear + all-sky kernel has no by-band form.
+
+jacobian=True: the step also owns lw_up_jac (ncol, nlay+1), rte_lw's flux_up_Jac -- d flux_up / d T_sfc at every level,
+for a host model that updates its LW fluxes between radiation calls -- and arms rrtmgpnn_solver_request_jacobian right
+before the LW solver call, which then carries the Jacobian beside its upward radiance: fused, sfc_source_Jac is formed
+in-kernel; unfused, it is the array compute_planck_source_nn already writes.  Clear-sky, overcast or McICA clouds; not
+with by-band or clear-sky outputs, which have no Jacobian instances.
 """
 
 from types import SimpleNamespace
@@ -71,9 +77,10 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
 # (lw_byband / sw_byband: a byband step's by-band requests, host-only calls issued right before their solver;
 # mcica_mask_*: a McICA step's mask kernels, which depend on no network; lw_mask / sw_mask: its cloud-mask requests,
-# host-only like the by-band ones; lw_mask_byband / sw_mask_byband: the two as one paired request, mcica={"byband": True})
+# host-only like the by-band ones; lw_mask_byband / sw_mask_byband: the two as one paired request, mcica={"byband": True};
+# lw_jacobian: a jacobian=True step's request, host-only too)
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
-               "predict_nn_lw", "lw_byband", "lw_mask", "lw_mask_byband", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
+               "predict_nn_lw", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
                "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_solver"]
 
 
@@ -124,13 +131,20 @@ class ClearSkyStep:
     rewrites between steps or replays; fused=False then fills scratch arrays with rrtmgpnn_mcica_randoms ahead of the
     class layer's sequence.  "clrsky": True / "byband": True: also the clear-sky fluxes of the same columns / the by-band
     fluxes of a byband=True step under the sampled clouds, not the two together; the clrsky= and byband= arguments
-    themselves are refused with mcica."""
+    themselves are refused with mcica.
+    jacobian: the step also owns lw_up_jac (ncol, nlay+1), the Jacobian of lw_up with respect to the surface
+    temperature (rte_lw's flux_up_Jac), requested from the LW solver call; refused with byband, clrsky and their mcica
+    keys."""
 
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
-                 clrsky=False, mcica=None):
+                 clrsky=False, mcica=None, jacobian=False):
         self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica)
+        self.jacobian = bool(jacobian)
+        if self.jacobian and (self.byband or self.clrsky):
+            raise ValueError("jacobian=True with by-band or clear-sky outputs (byband, clrsky or the mcica keys) is not "
+                             "supported: the solvers' by-band and clear + all-sky instances carry no Jacobian")
         self._open_device(device, ctx, lw_models, sw_models, icergh, cloud_lut)
         self._allocate(prob, clouds, mcica)
         self._prepare_arguments(nmus)
@@ -242,6 +256,8 @@ class ClearSkyStep:
         f_sw = f if sw else (lambda *s: f(*s).zero_())  # an LW-only step's SW fluxes are zero
         self.lw_up, self.lw_dn = f(ncol, nlay + 1), f(ncol, nlay + 1)
         self.sw_up, self.sw_dn, self.sw_dir = (f_sw(ncol, nlay + 1) for _ in range(3))
+        if self.jacobian:
+            self.lw_up_jac = f(ncol, nlay + 1)
         if self.clrsky:
             self.lw_up_clr, self.lw_dn_clr = f(ncol, nlay + 1), f(ncol, nlay + 1)
             self.sw_up_clr, self.sw_dn_clr, self.sw_dir_clr = (f_sw(ncol, nlay + 1) for _ in range(3))
@@ -363,6 +379,16 @@ class ClearSkyStep:
             return [(ch.sfx + "_byband", L.rrtmgpnn_solver_request_byband, (c, ch.nband, ch.lims) + ch.bnd)]
         return []
 
+    def _jacobian_request(self):
+        """A jacobian=True step's request, armed right before the LW solver call (after the chain's other request, which
+        it may stand beside): flux_up_Jac into lw_up_jac.  Fused, the solver forms sfc_source_Jac itself and takes none;
+        unfused, the array planck_source wrote."""
+        if not self.jacobian:
+            return []
+        return [("lw_jacobian", self.L.rrtmgpnn_solver_request_jacobian,
+                 (self.ctx.h, self.ng_lw, self.nlay, self.ncol)
+                 + ((None,) if self.fused else self._p("sfc_jac")) + self._p("lw_up_jac"))]
+
     def _mask_call(self, ch, mask, bits):
         """The chain's call of sampled_mask_max_ran, or _exp_ran when the step has an overlap parameter, into a logical
         mask or packed bits; a seeded fused step, which holds no random numbers, calls the _seeded entry on its 4-word
@@ -416,6 +442,7 @@ class ClearSkyStep:
                 *self._clouds_in(ch),
                 # (the clear + all-sky McICA entry takes the mask as an argument)
                 *self._request(ch, mask=not self.clrsky),
+                *self._jacobian_request(),
                 self._lw_solver_fused(),
             ]
         planck = (self.nb_lw, self.ng_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") + (
@@ -441,6 +468,7 @@ class ClearSkyStep:
             # ... or, with clear-sky fluxes, after the clear solve (mo_rrtmgp_clr_all_sky.F90:161-172)
             *([solver("lw_solver_clr", "lw_up_clr", "lw_dn_clr")] + clouds if self.clrsky else []),
             *self._request(ch),
+            *self._jacobian_request(),
             solver("lw_solver", "lw_up", "lw_dn"),
         ]
 
@@ -845,6 +873,12 @@ class ClearSkyStep:
             raise ValueError("clrsky_fluxes: the step was built without clrsky=True")
         return {k: getattr(self, k).cpu().numpy()
                 for k in ("lw_up_clr", "lw_dn_clr", "sw_up_clr", "sw_dn_clr", "sw_dir_clr")}
+
+    def jacobian_flux(self):
+        """Host copy of a jacobian=True step's lw_up_jac, (ncol, nlay+1)."""
+        if not self.jacobian:
+            raise ValueError("jacobian_flux: the step was built without jacobian=True")
+        return self.lw_up_jac.cpu().numpy()
 
     def fluxes(self):
         """Host copies of the broadband fluxes, with SW zeroed where sza >= 90 is applied by the caller."""
