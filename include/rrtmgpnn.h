@@ -637,6 +637,37 @@ int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const 
  * Nothing is allocated beyond the context workspace and the pointers become kernel arguments. */
 int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *sfc_source_Jac,
                                      float *flux_up_Jac);
+/* Aerosols (aer_props of extensions/mo_rrtmgp_clr_all_sky.F90:155-157, 288-290): a second band increment applied by the
+ * NEXT solver call on this context in front of its fused band increment; that call clears the request whether it succeeds
+ * or fails (all three arrays NULL: nothing armed).  tau_aer DEVICE (nbnd, nlay, ncol) on the call's own bands; ssa_aer and
+ * g_aer both NULL for a 1scl (LW) aerosol, both set for a 2str (SW) one.  Per g-point, in float32, two separately
+ * rounded adds in the reference's order, aerosols then clouds:
+ *   ta = tau + tau_aer(band);  t = ta + tau_bnd(band), or ta + (bit ? tau_bnd(band) : 0) under a cloud mask,
+ * bit for bit rrtmgpnn_increment_bybnd by the aerosol, then the entry's own increment, then the plain solver.  The sum of
+ * the two increments or the other order gives other float32 values, so the two cannot be added on the host; a mask
+ * switches the cloud and never the aerosol.
+ * In the SW the properties are inc_2stream_by_2stream_bybnd (rte/kernels/mo_optical_props_kernels.F90:430-463) by the
+ * aerosol, then by the (mask-selected) cloud; the gas g may be NULL as in the entry without the request (the literal 0
+ * then goes into the first increment, so gas optics writes no g array).  A zero aerosol is still an increment (it
+ * rounds tau * ssa / max(eps, tau)), not the call without the request.
+ * Honoured, for a 1scl aerosol, by rrtmgpnn_lw_solver_noscat_planck_inc (nmus 1..4, also beside a cloud-mask request)
+ * and by rrtmgpnn_lw_solver_noscat_planck_clr_all and _clr_all_mcica, whose clear-sky outputs are then the fluxes of
+ * tau + tau_aer(band) (gases plus aerosols, as the reference defines clear sky) and whose all-sky outputs those of
+ * (tau + tau_aer(band)) + [bit ?] tau_bnd(band); with two launches (mode 2, or nmus > 1) the clear launch is the _planck_inc
+ * instance with the aerosol as its increment.  Honoured, for a 2str aerosol, by rrtmgpnn_sw_solver_2stream_inc and
+ * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, on the checkpointed kernel (even ngpt, rrtmgpnn_context_set_sw_kernel
+ * mode 0 or 3) with every band starting at an odd 1-based g-point, with or without a cloud-mask request; the
+ * transmittance plane of the all-sky instances is used when its workspace fits, the same bits without it.
+ * Clear sky with aerosols and no clouds needs no request and no kernel of its own: it is the existing
+ * rrtmgpnn_lw_solver_noscat_planck_inc, rrtmgpnn_sw_solver_2stream_inc or rrtmgpnn_sw_solver_2stream_rfmip (nbnd > 0)
+ * call with the aerosol arrays as its band increment.
+ * RRTMGPNN_ERR_ARGUMENT: nbnd, nlay or ncol other than the call's; a 2str aerosol for an LW entry or a 1scl one for an SW
+ * entry; every other solver entry, with a message naming the entries that take it.  RRTMGPNN_ERR_UNSUPPORTED: any by-band
+ * request or a flux-Jacobian request beside it; in the SW also the other kernel modes, odd ngpt and a band starting at
+ * an even 1-based g-point.
+ * Nothing is allocated and the pointers become kernel arguments, so an armed call can be captured in a hipGraph. */
+int rrtmgpnn_solver_request_aerosol(rrtmgpnn_context *ctx, int nbnd, int nlay, int ncol, const float *tau_aer,
+                                    const float *ssa_aer, const float *g_aer);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */
 int rrtmgpnn_delta_scale_2str(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);

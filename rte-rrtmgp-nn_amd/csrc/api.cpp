@@ -119,6 +119,7 @@ struct Requests {
   int byband_rc = RRTMGPNN_OK;  // ... and its band limits against ngpt: ex's by-band part is filled when OK
   rrtmgpnn_context::CloudMaskRequest mask{};
   rrtmgpnn_context::JacobianRequest jac{};
+  rrtmgpnn_context::AerosolRequest aer{};
 };
 
 static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
@@ -129,6 +130,8 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
   ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
   rq.jac = ctx->jacobian;
   ctx->jacobian = rrtmgpnn_context::JacobianRequest{};
+  rq.aer = ctx->aerosol;
+  ctx->aerosol = rrtmgpnn_context::AerosolRequest{};
   if (!ctx->byband.armed) return rq;
   const auto bb = ctx->byband;
   ctx->byband = rrtmgpnn_context::BybandRequest{};
@@ -169,6 +172,33 @@ static int take_jacobian(const char *entry, const Requests &rq, JacMode mode, in
   ex.jac_up = rq.jac.flux_up;
   return RRTMGPNN_OK;
 }
+// What an entry does with an armed aerosol request (rrtmgpnn_solver_request_aerosol): the entries with aerosol
+// instances take a set of their kind (LW: 1scl, SW: 2str) on the call's own bands and extents into the call's extras, every
+// other entry refuses.  By-band outputs and the flux Jacobian do not go with it (the class layers then use the
+// materialising increment).
+enum AerMode { kAerRefuse, kAerLw, kAerSw };
+static int take_aerosol(const char *entry, const Requests &rq, AerMode mode, int nbnd, int nlay, int ncol,
+                        SolverExtras &ex)
+{
+  if (!rq.aer.armed) return RRTMGPNN_OK;
+  const std::string e(entry);
+  if (mode == kAerRefuse)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": this solver entry takes no aerosol request (the lw_solver_noscat_planck_inc, "
+                                           "_planck_clr_all, _planck_clr_all_mcica, sw_solver_2stream_inc and "
+                                           "sw_solver_2stream_rfmip entries do)");
+  if (rq.byband) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an aerosol increment together with by-band outputs");
+  if (rq.jac.armed) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an aerosol increment together with the flux Jacobian");
+  if (mode == kAerLw && (rq.aer.ssa || rq.aer.g))
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": a longwave entry takes a 1scl aerosol (ssa_aer and g_aer null)");
+  if (mode == kAerSw && (!rq.aer.ssa || !rq.aer.g))
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
+  if (rq.aer.nbnd != nbnd || rq.aer.nlay != nlay || rq.aer.ncol != ncol)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested aerosol's extents (nbnd, nlay, ncol) are not this call's");
+  ex.aer_tau = rq.aer.tau;
+  ex.aer_ssa = rq.aer.ssa;
+  ex.aer_g = rq.aer.g;
+  return RRTMGPNN_OK;
+}
 // ... and with g-point outputs beside it
 static int jacobian_no_gpt(const char *entry, const SolverExtras &ex, const float *gpt_up, const float *gpt_dn)
 {
@@ -182,6 +212,7 @@ static int take_byband(const char *entry, rrtmgpnn_context *ctx, int ngpt, int n
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
   if (rq.byband_rc) return rq.byband_rc;
+  if (int rc = take_aerosol(entry, rq, kAerRefuse, 0, nlay, ncol, ex)) return rc;
   if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, kNoMaskMsg);
   return take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex, jac_refusal);
 }
@@ -189,10 +220,11 @@ static int take_byband(const char *entry, rrtmgpnn_context *ctx, int ngpt, int n
 // the three that honour it, alone or paired with by-band outputs: the mask against the call's extents, then into the
 // call's extras
 static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
-                               JacMode jac = kJacRefuse)
+                               JacMode jac = kJacRefuse, AerMode aer = kAerRefuse, int nbnd = 0)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
   if (rq.byband_rc) return rq.byband_rc;
+  if (int rc = take_aerosol(entry, rq, aer, nbnd, nlay, ncol, ex)) return rc;
   if (int rc = take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex)) return rc;
   if (!rq.mask.armed) return RRTMGPNN_OK;
   // both armed: only as the pair rrtmgpnn_solver_request_byband_mcica states (a by-band request left over from an
@@ -207,11 +239,13 @@ static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngp
   return RRTMGPNN_OK;
 }
 
-// the two _clr_all entries have neither by-band nor request-masked instances: `mask_msg` is the entry's refusal
-static int refuse_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, const char *mask_msg)
+// the two _clr_all entries have neither by-band nor request-masked instances: `mask_msg` is the entry's refusal.  They
+// take an aerosol request, into `ex`
+static int refuse_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nbnd, int nlay, int ncol,
+                           SolverExtras &ex, const char *mask_msg)
 {
-  SolverExtras ex;
   const Requests rq = take_requests(ctx, ngpt, ex);
+  if (int rc = take_aerosol(entry, rq, kAerLw, nbnd, nlay, ncol, ex)) return rc;
   if (rq.byband)
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": by-band outputs are not available from this entry (the "
                                                             "_planck and _planck_inc entries have them)");
@@ -953,7 +987,8 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          const float *sfc_emis, float *flux_up, float *flux_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol, ex, kJacFused)) return rc;
+  if (int rc = take_byband_or_mask("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol, ex, kJacFused, kAerLw, nbnd))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
   LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
@@ -974,7 +1009,8 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
                                              int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn,
                                              float *flux_up_clr, float *flux_dn_clr)
 {
-  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all", ctx, ngpt, kNoMaskMsg)) return rc;
+  SolverExtras ex;
+  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all", ctx, ngpt, nbnd, nlay, ncol, ex, kNoMaskMsg)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
   LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
@@ -982,8 +1018,8 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
   if (int rc = planck_args("lw_solver_noscat_planck_clr_all", p, in, nbnd, band_lims_gpt, true,
                            flux_up_clr && flux_dn_clr))
     return rc;
-  return launch_lw_noscat_planck_clr_all(ctx, SolverExtras{}, lw_clr_all_dual(ctx, kLwClrAllDefaultMode), p, in,
-                                         flux_up_clr, flux_dn_clr);
+  return launch_lw_noscat_planck_clr_all(ctx, ex, lw_clr_all_dual(ctx, kLwClrAllDefaultMode), p, in, flux_up_clr,
+                                         flux_dn_clr);
 }
 
 // mode 0 of rrtmgpnn_context_set_lw_clr_all for the McICA entry: the masked dual kernel
@@ -999,7 +1035,8 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ng
                                                    float *flux_up, float *flux_dn, float *flux_up_clr,
                                                    float *flux_dn_clr, const unsigned int *mask_bits)
 {
-  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all_mcica", ctx, ngpt,
+  SolverExtras ex;
+  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all_mcica", ctx, ngpt, nbnd, nlay, ncol, ex,
                                "lw_solver_noscat_planck_clr_all_mcica: the cloud mask is this entry's mask_bits "
                                "argument, not a solver_request_cloud_mask request"))
     return rc;
@@ -1011,7 +1048,6 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ng
   if (int rc = planck_args("lw_solver_noscat_planck_clr_all_mcica", p, in, nbnd, band_lims_gpt, true,
                            flux_up_clr && flux_dn_clr))
     return rc;
-  SolverExtras ex;
   ex.mask_bits = mask_bits;
   return launch_lw_noscat_planck_clr_all(ctx, ex, lw_clr_all_dual(ctx, kLwClrAllMcicaDefaultMode), p, in, flux_up_clr,
                                          flux_dn_clr);
@@ -1096,7 +1132,8 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    float *flux_dn, float *flux_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol, ex)) return rc;
+  if (int rc = take_byband_or_mask("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !tau_bnd || !ssa_bnd || !g_bnd || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt ||
       !flux_up || !flux_dn || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
@@ -1162,6 +1199,28 @@ int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, 
   rq.ncol = ncol;
   rq.sfc_jac = sfc_source_Jac;
   rq.flux_up = flux_up_Jac;
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_solver_request_aerosol(rrtmgpnn_context *ctx, int nbnd, int nlay, int ncol, const float *tau_aer,
+                                    const float *ssa_aer, const float *g_aer)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->aerosol = rrtmgpnn_context::AerosolRequest{};
+  if (!tau_aer && !ssa_aer && !g_aer) return RRTMGPNN_OK;  // nothing wanted: nothing armed
+  if (!tau_aer) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_aerosol: tau_aer is null");
+  if ((ssa_aer == nullptr) != (g_aer == nullptr))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_aerosol: ssa_aer and g_aer are both null (1scl) or both set (2str)");
+  if (nbnd < 1 || nbnd > kMaxBands || nlay < 1 || ncol < 0)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_aerosol: bad extents");
+  auto &rq = ctx->aerosol;
+  rq.armed = true;
+  rq.nbnd = nbnd;
+  rq.nlay = nlay;
+  rq.ncol = ncol;
+  rq.tau = tau_aer;
+  rq.ssa = ssa_aer;
+  rq.g = g_aer;
   return RRTMGPNN_OK;
 }
 
@@ -1562,7 +1621,8 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      float *flux_up, float *flux_dn, float *flux_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol, ex)) return rc;
+  if (int rc = take_byband_or_mask("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd))
+    return rc;
   if (ex.mask_bits && nbnd <= 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream_rfmip: a cloud mask needs the band increment (nbnd > 0)");
   if (int rc = check_ctx(ctx)) return rc;

@@ -70,6 +70,12 @@ struct SolverExtras {
   // no-scattering and rescaled launchers have Jacobian instances, without by-band or g-point outputs
   const float *sfc_jac = nullptr;
   float *jac_up = nullptr;
+  // rrtmgpnn_solver_request_aerosol: a second, unmasked band increment (nbnd, nlay, ncol) on the call's own bands, applied
+  // in front of the call's fused band increment (which a mask may switch; this one never).  aer_ssa / aer_g are both
+  // null for a 1scl (LW) aerosol and both set for a 2str (SW) one.  Only the fused-Planck incremented LW launchers and
+  // the checkpointed SW launcher (band-pair increment) have aerosol instances, without by-band, g-point or Jacobian
+  // outputs and without lw_Ds
+  const float *aer_tau = nullptr, *aer_ssa = nullptr, *aer_g = nullptr;
 };
 
 // Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction (a kernel argument)
@@ -151,6 +157,12 @@ struct rrtmgpnn_context {
     const float *sfc_jac = nullptr;
     float *flux_up = nullptr;
   } jacobian;
+  // rrtmgpnn_solver_request_aerosol: armed for the next solver call on this context, which clears it
+  struct AerosolRequest {
+    bool armed = false;
+    int nbnd = 0, nlay = 0, ncol = 0;
+    const float *tau = nullptr, *ssa = nullptr, *g = nullptr;
+  } aerosol;
   void *ws = nullptr;
   size_t ws_bytes = 0;
   bool ws_pinned = false;

@@ -168,8 +168,15 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // (part gains the plane [nlev][4] after up); the down pass keeps chunks of kRing.  With several angles fac * J is
 // accumulated in a third per-g plane behind gup's and summed as flux_up is.  Summed with flux_up's convention at every
 // angle count: the bare J when ngpt % 4 != 0 at one angle.
+//
+// kAer (with kInc, without kBand and kJac; rrtmgpnn_solver_request_aerosol): a second, unmasked band increment tau_aer
+// (nbnd, nlay, ncol) in front of tau_bnd -- aerosols, then clouds, as rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90
+// orders them (:155-157, :160-162): ta = tau + tau_aer(band), t = ta + [bit ?] tau_bnd(band), two separately rounded
+// adds (the sum of the two increments, or the other order, gives other float32 values).  One more band value per
+// prefetched layer, read as ld_inc reads the cloud's.  The mask never touches it.  With kDual the clear radiance takes
+// ta * D: the clear sky is gases plus aerosols (:155-157).
 template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false, bool kMask = false,
-          bool kMaskS = false, bool kJac = false>
+          bool kMaskS = false, bool kJac = false, bool kAer = false>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
@@ -178,7 +185,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
                                            float *__restrict__ gdn, float *__restrict__ gup, long long gcs,
                                            float *__restrict__ flux_up, float *__restrict__ flux_dn, BandOut bo,
                                            const uint32_t *__restrict__ cmask, const float *__restrict__ sfc_jac,
-                                           float *__restrict__ flux_jac)
+                                           float *__restrict__ flux_jac, const float *__restrict__ tau_aer)
 {
   constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
   // kJac with one angle: the down pass' chunk, the up pass' (two rings), and the ring's rows
@@ -189,6 +196,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   static_assert(kRu % kPF == 0, "prefetch depth must divide the up pass' ring");
   static_assert(!kMask || (kInc && (!kBand || !kDual)), "the cloud mask switches the fused band increment");
   static_assert(!kMaskS || (kMask && kDual), "the wave-uniform mask pair is the dual masked instance's");
+  static_assert(!kAer || (kInc && !kBand && !kJac), "the aerosol increment goes in front of the fused band increment");
   using mask_t = std::conditional_t<kMaskS, uint64_t, uint32_t>;  // one layer's mask: the wave's pair, or the lane's word
   static_assert(kR % kPF == 0, "prefetch depth must divide the ring");
   // the fused down pass takes lev(l+1)'s Planck fraction from the neighbouring prefetch slot, py[(r+1) % kPF]: with
@@ -227,6 +235,13 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   const uint32_t irow = 4u * (uint32_t)bands.nbnd, vb = kInc ? 4u * (uint32_t)band_of(bands, gc) : 0u;
   const ColArr Tinc(kInc ? tau_bnd : tau, kInc ? (size_t)bands.nbnd * nlay * icol : 0, irow * nlay);
   auto ld_inc = [&](int l) { return kInc ? Tinc.ld(vb, irow * (uint32_t)l) : 0.0f; };
+  // kAer: the aerosol's value of the same band and layer, its own column base
+  const ColArr Taer(kAer ? tau_aer : tau, kAer ? (size_t)bands.nbnd * nlay * icol : 0, irow * nlay);
+  auto ld_aer = [&](int l) { return kAer ? Taer.ld(vb, irow * (uint32_t)l) : 0.0f; };
+  auto aer_of = [&](float t, const float (&a)[kPF], int p) {
+    if constexpr (kAer) return t + a[p];
+    else return t;
+  };
   // kMask: this lane's mask word, one per layer at stride nw, and its g-point's bit
   const uint32_t mrow = kMask ? 4u * (uint32_t)((ngpt + 31) / 32) : 0u, vm = 4u * (uint32_t)(gc >> 5);
   const uint32_t mbit = 1u << (gc & 31);
@@ -391,7 +406,8 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   // spills them across the layer loops (2 VGPRs, 12 bytes of scratch); with the count known they are formed in place.
   // (Every !kMulti instance runs one angle; stating it for all of them is left as a change of its own, since it moves the
   // other one-angle instances' register allocation: DESIGN.md section 8.)
-  const int nmus = ((kMask && kBand && !kMulti) || kJac1) ? 1 : ang.nmus;  // kJac1: as stated, for the same reason
+  // kJac1, and kAer with one angle: as stated, for the same reason
+  const int nmus = ((kMask && kBand && !kMulti) || kJac1 || (kAer && !kMulti)) ? 1 : ang.nmus;
   for (int imu = 0; imu < nmus; imu++) {
     // lw_Ds (rte/mo_rte_lw.F90:329-341): the kernel's D(igpt, icol), one angle
     const float D = ang.Dg ? ang.Dg[gc + (size_t)ngpt * icol] : ang.D[imu];
@@ -406,7 +422,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     flush(pdn, 1, top, 1, bdn);
     // downward: lw_transport_noscat_dn (:982-1009)
     {
-      float pt[kPF], py[kPF], pv[kPF], pi[kPF];
+      float pt[kPF], py[kPF], pv[kPF], pi[kPF], pa[kPF];
       mask_t pm[kPF];
       if (kEarly && imu == 0) {  // loaded ahead of the prologue
 #pragma unroll
@@ -420,6 +436,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           pt[p] = Ttau.ld(vg, row * l); py[p] = Tlay.ld(vg, row * l); pi[p] = ld_inc(l);
           if constexpr (!kFused) pv[p] = lev_ld(l + 1);
           if constexpr (kMask) pm[p] = ld_msk(l);
+          if constexpr (kAer) pa[p] = ld_aer(l);
         }
       }
       // fused: lev(l+1)'s Planck fraction pfrac(min(l+1, nlay-1)) is a neighbour's in walk order, already loaded --
@@ -433,8 +450,9 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         const int p = r % kPF, l = lay_dn(min(j, nlay - 1));
         const float y_next = py[(r + 1) % kPF], y_own = py[p];
         const float v = kFused ? (top_at_1 ? y_next : (j == 0 ? y_own : py_prev)) : pv[p];
-        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : mask_t(0)) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
-        const float tc = kDual ? pt[p] * D : 0.0f;
+        const float ta = aer_of(pt[p], pa, p);
+        const float t = tau_of(ta, pi[p], kMask ? pm[p] : mask_t(0)) * D, ly = lay_src(y_own, l), lvdn = lev_src(v, l + 1);
+        const float tc = kDual ? ta * D : 0.0f;
         py_prev = y_own;
         {
           const int ln = lay_dn(min(j + kPF, nlay - 1));
@@ -442,6 +460,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           if constexpr (!kFused) pv[p] = lev_ld(ln + 1);
           pi[p] = ld_inc(ln);
           if constexpr (kMask) pm[p] = ld_msk(ln);
+          if constexpr (kAer) pa[p] = ld_aer(ln);
         }
         if (j < nlay) {
           const float T = solver_exp_neg(-t, etab);
@@ -468,7 +487,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     // kPF layers are loaded before the surface level's flush, whose barrier would otherwise hold the loads back (with
     // several angles there is no flush, and the registers would spill)
     auto lay_up = [&](int j) { return top_at_1 ? nlay - 1 - j : j; };
-    float ptu[kPF], pyu[kPF], pvu[kPF], piu[kPF];
+    float ptu[kPF], pyu[kPF], pvu[kPF], piu[kPF], pau[kPF];
     mask_t pmu[kPF];
     if constexpr (!kMulti) {
 #pragma unroll
@@ -476,6 +495,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         const int l = lay_up(min(p, nlay - 1));
         ptu[p] = Ttau.ld(vg, row * l); pyu[p] = Tlay.ld(vg, row * l); piu[p] = ld_inc(l);
         if constexpr (kMask) pmu[p] = ld_msk(l);
+        if constexpr (kAer) pau[p] = ld_aer(l);
         pvu[p] = kFused ? 0.0f : Tlev.ld(vg, row * l);
       }
     }
@@ -501,31 +521,35 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
     if constexpr (kJac1) flush_jac(pup, 1, sfcl, 1);
     else flush(pup, 1, sfcl, 1, bup);
     {
-      float pt[kPF], py[kPF], pv[kPF], pi[kPF];
+      float pt[kPF], py[kPF], pv[kPF], pi[kPF], pa[kPF];
       mask_t pm[kPF];
 #pragma unroll
       for (int p = 0; p < kPF; p++) {
         if constexpr (!kMulti) {
           pt[p] = ptu[p]; py[p] = pyu[p]; pi[p] = piu[p]; pv[p] = pvu[p];
           if constexpr (kMask) pm[p] = pmu[p];
+          if constexpr (kAer) pa[p] = pau[p];
         } else {
           const int l = lay_up(min(p, nlay - 1));
           pt[p] = Ttau.ld(vg, row * l); py[p] = Tlay.ld(vg, row * l); pi[p] = ld_inc(l);
           if constexpr (!kFused) pv[p] = Tlev.ld(vg, row * l);
           if constexpr (kMask) pm[p] = ld_msk(l);
+          if constexpr (kAer) pa[p] = ld_aer(l);
         }
       }
       auto step = [&](int j, int r) {
         const int p = r % kPF, l = lay_up(min(j, nlay - 1));
         // fused: lev(l) = pfrac(l) * B(tlev(l)) (l < nlay), from the layer's own pfrac
-        const float t = tau_of(pt[p], pi[p], kMask ? pm[p] : mask_t(0)) * D, ly = lay_src(py[p], l);
+        const float ta = aer_of(pt[p], pa, p);
+        const float t = tau_of(ta, pi[p], kMask ? pm[p] : mask_t(0)) * D, ly = lay_src(py[p], l);
         const float lvup = lev_src(kFused ? py[p] : pv[p], l);
-        const float tc = kDual ? pt[p] * D : 0.0f;
+        const float tc = kDual ? ta * D : 0.0f;
         {
           const int ln = lay_up(min(j + kPF, nlay - 1));
           pt[p] = Ttau.ld(vg, row * ln); py[p] = Tlay.ld(vg, row * ln); pi[p] = ld_inc(ln);
           if constexpr (!kFused) pv[p] = Tlev.ld(vg, row * ln);
           if constexpr (kMask) pm[p] = ld_msk(ln);
+          if constexpr (kAer) pa[p] = ld_aer(ln);
         }
         if (j < nlay) {
           const float T = solver_exp_neg(-t, etab);
@@ -636,6 +660,16 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   if (jac && (ex.sfc_jac == nullptr) != kFused)
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: the flux Jacobian needs sfc_source_Jac with source arrays, and none "
                                        "with the fused Planck sources");
+  // the aerosol increment in front of the fused one (rrtmgpnn_solver_request_aerosol)
+  const bool aer = ex.aer_tau != nullptr;
+  if (aer && (!kFused || !kInc))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: an aerosol increment needs the fused band increment behind it");
+  // (Not reachable through the C ABI as it stands: the entries that take the request have no g-point or lw_Ds
+  // arguments and refuse a by-band or Jacobian request beside it themselves.  Kept so that the launcher never runs an
+  // instance it does not have, whoever fills the extras.)
+  if (aer && (gpt || bb || jac || ex.lw_Ds))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: an aerosol increment with by-band or g-point outputs, lw_Ds or the "
+                                          "flux Jacobian");
   const bool multi = nmus > 1 || gpt;
   LwAngles a{};
   a.nmus = nmus;
@@ -669,12 +703,23 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
     hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
                        p.tau, src, kFused ? src : lev_source, p.sfc_emis, sfc_source, in.pl, in.bands,
                        kInc ? in.tau_bnd : nullptr, gdn, gup, gcs, p.flux_up, p.flux_dn, bo, ex.mask_bits, ex.sfc_jac,
-                       ex.jac_up);
+                       ex.jac_up, ex.aer_tau);
   };
   if constexpr (kFused && kInc) {
     if (dual) {
       gdn = dn_clr;
       gup = up_clr;
+      if (aer) {
+        // the dual instances' aerosol twins: the clear set is gases plus aerosols
+        if (ex.mask_bits && ngpt % 64 == 0 && (reinterpret_cast<uintptr_t>(ex.mask_bits) & 7u) == 0)
+          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, true, false, true>);
+        else if (ex.mask_bits)
+          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, false, false, true>);
+        else
+          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, false, false, false, true>);
+        RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual, aerosol)");
+        return RRTMGPNN_OK;
+      }
       if (ex.mask_bits) {
         // McICA beside clear-sky: the wave-uniform pair where every wave is full and the pair can be read as one
         // 8-byte scalar, the per-lane word otherwise
@@ -687,6 +732,17 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
       }
       go(lw_noscat_kernel<kFused, kInc, PF, false, false, true>);
       RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual)");
+      return RRTMGPNN_OK;
+    }
+  }
+  if constexpr (kFused && kInc) {
+    if (aer) {
+      // aerosols in front of the (masked) cloud increment: one angle or several, with or without the mask
+      if (ex.mask_bits && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true, false, false, true>);
+      else if (ex.mask_bits)     go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true, false, false, true>);
+      else if (multi)            go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, false, false, false, true>);
+      else                       go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, false, false, false, true>);
+      RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (aerosol)");
       return RRTMGPNN_OK;
     }
   }
@@ -749,6 +805,15 @@ int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &e
   LwNoscat clear = p;
   clear.flux_up = flux_up_clr;
   clear.flux_dn = flux_dn_clr;
+  if (ex.aer_tau) {
+    // ex.aer_tau (rrtmgpnn_solver_request_aerosol): the clear launch is the incremented instance with the aerosol as
+    // its increment, the all-sky launch the aerosol instance
+    clear_ex.aer_tau = nullptr;
+    LwPlanckIn clear_in = in;
+    clear_in.tau_bnd = ex.aer_tau;
+    if (int rc = launch_lw_impl<true, true>(ctx, clear_ex, clear, nullptr, nullptr, nullptr, clear_in)) return rc;
+    return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
+  }
   if (int rc = launch_lw_impl<true, false>(ctx, clear_ex, clear, nullptr, nullptr, nullptr, in)) return rc;
   return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
 }
@@ -1082,6 +1147,15 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
   if (ex.mask_bits && (!ck || gpt))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask is taken by the checkpointed kernel only (even ngpt, "
                                           "rrtmgpnn_context_set_sw_kernel mode 0 or 3), without g-point outputs");
+  // aerosols (rrtmgpnn_solver_request_aerosol): only the checkpointed kernel has aerosol instances
+  if (ex.aer_tau && !inc)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: an aerosol increment needs the fused band increment behind it");
+  // (gpt and bb beside an aerosol are refused by the entries before they get here; !ck -- odd ngpt, or kernel mode 1
+  // or 2 -- is the refusal a caller can meet)
+  if (ex.aer_tau && (!ck || gpt || bb))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment is taken by the checkpointed kernel only (even "
+                                          "ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band or g-point "
+                                          "outputs");
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
   // the other kernels read them from memory, formed there first by sw_boundary_kernel
   SwBcDev bcd{};

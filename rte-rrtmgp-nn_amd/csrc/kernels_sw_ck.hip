@@ -184,10 +184,17 @@ constexpr int kCkAheadSmall = 1;
 // separately (g is even, so they share the word), also in the band-pair form; the word is loaded with the layer's
 // band values.  With kBand (rrtmgpnn_solver_request_byband_mcica) the flush's band sums are those of the sampled
 // columns; the by-band limits are the request's, not the increment's.
+// kAer (with kInc and kBandPair, two g-points per lane, no by-band or g-point outputs; rrtmgpnn_solver_request_aerosol):
+// a second, unmasked band increment (tau, ssa, g)_aer on the same bands in front of the maskable one -- aerosols, then
+// clouds, as rte_sw of extensions/mo_rrtmgp_clr_all_sky.F90 orders them (:288-290, :297-299): ck_inc by the aerosol,
+// then ck_inc by the (selected) cloud, inc_2stream_by_2stream_bybnd twice, unchanged.  Three more band values per chunk
+// layer, loaded as ld_bnd loads the cloud's; pass 1, which needs the optical depth only, takes (tau + tau_aer) +
+// sel(tau_cld).  With gg == NULL the gas g going into the first increment is the literal 0, so gas optics never writes
+// a g array.  The mask never touches the aerosol.
 template <bool kHasG, bool kInc, int K, bool kGpt = false, int R = kCkRing,
           int WAVES = (!kHasG && !kInc && !kGpt) ? kCkWavesNN : kCkWaves, bool kTn = false,
           class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1,
-          bool kBand = false, bool kMask = false>
+          bool kBand = false, bool kMask = false, bool kAer = false>
 __global__ void __launch_bounds__(512, WAVES)
     sw_2stream_ck_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
@@ -197,9 +204,12 @@ __global__ void __launch_bounds__(512, WAVES)
                          const float *__restrict__ g_bnd, float *__restrict__ ws, float *__restrict__ flux_up,
                          float *__restrict__ flux_dn, float *__restrict__ flux_dir, float *__restrict__ gpt_up,
                          float *__restrict__ gpt_dn, float *__restrict__ gpt_dir, SwBcDev bc, BandOut bo,
-                         const uint32_t *__restrict__ cmask)
+                         const uint32_t *__restrict__ cmask, const float *__restrict__ tau_aer,
+                         const float *__restrict__ ssa_aer, const float *__restrict__ g_aer)
 {
   static_assert(R % K == 0, "the flux ring must hold whole chunks");
+  static_assert(!kAer || (kInc && kBandPair && sizeof(V) == 8 && !kGpt && !kBand),
+                "the aerosol increment goes in front of the fused band-pair increment");
   static_assert(!kMask || (kInc && sizeof(V) == 8 && !kGpt), "the cloud mask switches the fused band increment");
   constexpr bool kG0 = !kHasG && !kInc;  // g is the literal 0 (the NN path)
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -256,6 +266,9 @@ __global__ void __launch_bounds__(512, WAVES)
   const uint32_t bB = kInc ? (uint32_t)nc * brow * nlay : 0u;
   const CA_ Bt(kInc ? tau_bnd : tau, kInc ? cb : 0, bB), Bw(kInc ? ssa_bnd : tau, kInc ? cb : 0, bB),
       Bg(kInc ? g_bnd : tau, kInc ? cb : 0, bB);
+  // kAer: the aerosol's arrays, on the same bands (same offsets, their own column base)
+  const CA_ At(kAer ? tau_aer : tau, kAer ? cb : 0, kAer ? bB : 0u), Aw(kAer ? ssa_aer : tau, kAer ? cb : 0, kAer ? bB : 0u),
+      Ag(kAer ? g_aer : tau, kAer ? cb : 0, kAer ? bB : 0u);
   auto ld_bnd = [&](const CA_ &a, int l) -> V {
     if constexpr (!kInc) return (V)0.0f;
     else if constexpr (NPL == 2 && kBandPair) {
@@ -305,6 +318,7 @@ __global__ void __launch_bounds__(512, WAVES)
     for (int p = 0; p < P1; p++) {
       const int l = lay(c1 * P1 + p);
       b.t[p] = Ttau.ldv(vL, row * (uint32_t)l);
+      if constexpr (kAer) b.t[p] += ld_bnd(At, l);
       if constexpr (kMask) b.t[p] += sel(ld_bnd(Bt, l), ld_msk(l));
       else if constexpr (kInc) b.t[p] += ld_bnd(Bt, l);
     }
@@ -338,6 +352,7 @@ __global__ void __launch_bounds__(512, WAVES)
   struct Chunk {
     V t[K], w[K], g[K], qt[K], qw[K], qg[K], tn[K], em[K], fb, ae, se;
     uint32_t qm[kMask ? K : 1];
+    V at[kAer ? K : 1], aw[kAer ? K : 1], ag[kAer ? K : 1];
   };
   // pass: 2 or 3
   auto load_chunk = [&](Chunk &ch, int ck, int pass) {
@@ -355,6 +370,11 @@ __global__ void __launch_bounds__(512, WAVES)
         ch.qw[p] = ld_bnd(Bw, l);
         ch.qg[p] = ld_bnd(Bg, l);
         if constexpr (kMask) ch.qm[p] = ld_msk(l);
+        if constexpr (kAer) {
+          ch.at[p] = ld_bnd(At, l);
+          ch.aw[p] = ld_bnd(Aw, l);
+          ch.ag[p] = ld_bnd(Ag, l);
+        }
       } else {
         ch.qt[p] = ch.qw[p] = ch.qg[p] = (V)0.0f;
       }
@@ -372,6 +392,7 @@ __global__ void __launch_bounds__(512, WAVES)
     t = ch.t[p];
     w = ch.w[p];
     g0 = kHasG ? ch.g[p] : (V)0.0f;
+    if constexpr (kAer) ck_inc(t, w, g0, ch.at[p], ch.aw[p], ch.ag[p]);
     if constexpr (kMask) ck_inc(t, w, g0, sel(ch.qt[p], ch.qm[p]), sel(ch.qw[p], ch.qm[p]), sel(ch.qg[p], ch.qm[p]));
     else if constexpr (kInc) ck_inc(t, w, g0, ch.qt[p], ch.qw[p], ch.qg[p]);
   };
@@ -637,10 +658,53 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
                        p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tb, sb, gb, (float *)ws,
-                       p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits);
+                       p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits,
+                       ex.aer_tau, ex.aer_ssa, ex.aer_g);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
+  if (ex.aer_tau) {
+    // aerosols in front of the (masked) cloud increment (rrtmgpnn_solver_request_aerosol): the band-pair layout only,
+    // with the all-sky instances' transmittance plane or, when that workspace did not fit, without it (the same bits)
+    if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: an aerosol increment needs the fused band increment behind it");
+    if (!ex.aer_ssa || !ex.aer_g)
+      return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
+    // (as in launch_lw_impl: not reachable through the C ABI as it stands -- the two entries have no g-point arguments
+    // and refuse a by-band request beside the aerosol themselves, and launch_sw_2stream checks both again)
+    if (bb || ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment with by-band or g-point outputs");
+    for (int i = 0; i < b.nbnd; i++)
+      if ((b.lims[2 * i] - 1) % 2 != 0)
+        return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment needs every band to start at an odd "
+                                              "(1-based) g-point, the band-pair layout");
+    constexpr int W = kCkWaves, P = kCkP1;
+    constexpr bool T = kCkTnInc, E = kCkEmkInc;
+    const bool m = ex.mask_bits != nullptr;
+    if (!planes) {
+      if (g && m)
+        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      if (g)
+        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, false, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      if (m)
+        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true, true>,
+                  tau_bnd, ssa_bnd, g_bnd);
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, false, true>,
+                tau_bnd, ssa_bnd, g_bnd);
+    }
+    if (g && m)
+      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (g)
+      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, false, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    if (m)
+      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true, true>, tau_bnd,
+                ssa_bnd, g_bnd);
+    return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, false, true>, tau_bnd,
+              ssa_bnd, g_bnd);
+  }
   if (ex.mask_bits) {
     // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask), as the instances below
     if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");

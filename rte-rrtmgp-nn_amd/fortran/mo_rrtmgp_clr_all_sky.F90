@@ -13,6 +13,13 @@
 ! (ty_source_func_lw%planck_deferred), and both flux objects want broadband up / down fluxes only.  Every other case
 ! -- 2str clouds (the rescaled solver), clouds on g-points, g-point, by-band or net outputs -- runs the two solves with
 ! mo_rte_lw's rte_lw.  rte_sw always runs the two solves.
+!
+! aer_props: where rte_lw takes the dual entry and the aerosols are of the fused kind (1scl, defined by band on the
+! k-distribution's bands, the same ncol and nlay), they are not added to the g-point array by aer_props%increment but
+! armed as the solver's aerosol request (rrtmgpnn_solver_request_aerosol), and the kernel adds them, then the clouds,
+! as it reads tau: the clear-sky fluxes are those of tau + tau_aer(band), the all-sky ones those of that + the cloud's,
+! bit for bit the reference's sequence.  Every other case (2str or g-point aerosols, no dual entry) keeps
+! aer_props%increment; so does rte_sw, which calls no fused increment entry.
 module mo_rrtmgp_clr_all_sky
   use, intrinsic :: iso_c_binding
   use mo_rte_kind,           only: wp
@@ -63,7 +70,7 @@ contains
     class(ty_optical_props_arry), allocatable :: optical_props
     type(ty_source_func_lw) :: sources
     integer :: ncol, nlay, ngpt, nband, nmus
-    logical :: top_at_1, dual
+    logical :: top_at_1, dual, aer_req
 
     error_msg = ""
     ncol  = size(p_lay, 2)
@@ -102,11 +109,9 @@ contains
     error_msg = sources%alloc(ncol, nlay, k_dist)
     if (error_msg /= '') return
 
-    ! gas optics once (:150-153), then the aerosols (:157)
+    ! gas optics once (:150-153)
     error_msg = k_dist%gas_optics(p_lay, p_lev, t_lay, t_sfc, gas_concs, optical_props, sources, col_dry, t_lev, &
                                   neural_nets)
-    if (error_msg /= '') return
-    if (present(aer_props)) error_msg = aer_props%increment(optical_props)
     if (error_msg /= '') return
 
     nmus = 1
@@ -120,6 +125,20 @@ contains
              broadband_only(allsky_fluxes) .and. broadband_only(clrsky_fluxes) .and. nmus >= 1 .and. nmus <= 4 .and. &
              all(shape(sfc_emis) == [nband, ncol])
     end select
+    ! the aerosols (:157).  In the dual case, aerosols of the fused kind -- 1scl, by band on the k-distribution's bands,
+    ! the same extents -- go to the solver as its aerosol request (rrtmgpnn_solver_request_aerosol: tau + tau_aer(band),
+    ! then + the cloud's, as tau is read; the same two increments in the same order, the same bits); every other case
+    ! adds them to the g-point array here
+    aer_req = .false.
+    if (present(aer_props) .and. dual) then
+      select type (aer_props)
+      class is (ty_optical_props_1scl)
+        aer_req = aer_props%bands_are_equal(optical_props) .and. .not. aer_props%gpoints_are_equal(optical_props) .and. &
+                  aer_props%get_ngpt() == nband .and. aer_props%get_ncol() == ncol .and. aer_props%get_nlay() == nlay
+      end select
+    end if
+    if (present(aer_props) .and. .not. aer_req) error_msg = aer_props%increment(optical_props)
+    if (error_msg /= '') return
     if (dual) then
       error_msg = allsky_fluxes%check_extents(nlay + 1, ncol)
       if (error_msg == '') error_msg = clrsky_fluxes%check_extents(nlay + 1, ncol)
@@ -159,6 +178,11 @@ contains
       d_inc = c_null_ptr
       if (present(inc_flux)) d_inc = dev_stage(inc_flux, int(ngpt, c_long_long) * ncol)
       d_up = dev_scratch(nv); d_dn = dev_scratch(nv); d_upc = dev_scratch(nv); d_dnc = dev_scratch(nv)
+      ! armed for the solver call below, which clears it whatever it returns
+      if (aer_req) error_msg = rrtmgpnn_check(c_rrtmgpnn_solver_request_aerosol(rrtmgpnn_ctx(), nband, nlay, ncol, &
+                    dev_present(aer_props%tau, size(aer_props%tau, kind=c_long_long), PRESENT_READ), c_null_ptr, &
+                    c_null_ptr), "rte_lw: solver_request_aerosol")
+      if (error_msg == '') &
       error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
                     merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
                     dev_present(optical_props%tau, ng, PRESENT_READ), &

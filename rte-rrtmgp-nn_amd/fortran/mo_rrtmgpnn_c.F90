@@ -22,6 +22,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
   public :: c_rrtmgpnn_solver_request_byband_mcica
   public :: c_rrtmgpnn_solver_request_jacobian
+  public :: c_rrtmgpnn_solver_request_aerosol
   public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
             c_rrtmgpnn_draw_samples
   public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
@@ -327,6 +328,14 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, mask_bits
       integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    ! aerosols: a band increment (nbnd, nlay, ncol) the next solver call applies in front of its own band increment;
+    ! ssa_aer and g_aer both c_null_ptr for a 1scl (LW) set
+    integer(c_int) function c_rrtmgpnn_solver_request_aerosol(ctx, nbnd, nlay, ncol, tau_aer, ssa_aer, g_aer) &
+        bind(C, name="rrtmgpnn_solver_request_aerosol")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, tau_aer, ssa_aer, g_aer
+      integer(c_int), value :: nbnd, nlay, ncol
     end function
     ! the two requests above as a pair: by-band outputs of the next solver call under its McICA mask
     integer(c_int) function c_rrtmgpnn_solver_request_byband_mcica(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, &

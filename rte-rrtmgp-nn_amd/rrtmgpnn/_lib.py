@@ -105,6 +105,7 @@ SIGNATURES = {
     "rrtmgpnn_solver_request_byband": (c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp]),
     "rrtmgpnn_solver_request_cloud_mask": (c_int, [c_vp, c_int, c_int, c_int, c_vp]),
     "rrtmgpnn_solver_request_jacobian": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "rrtmgpnn_solver_request_aerosol": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "rrtmgpnn_solver_request_byband_mcica":(c_int, [c_vp, c_int, P(c_int), c_vp, c_vp, c_vp, c_int, c_int, c_int,
                                                      c_vp]),
     "rrtmgpnn_sampled_mask_max_ran": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -220,6 +220,19 @@ def arm_cloud_mask(ctx, ngpt, mask_bits):
           "solver_request_cloud_mask")
 
 
+def arm_aerosol(ctx, aer_props):
+    """Arm aer_props (by band: tau (ncol, nlay, nbnd), with ssa and g when 2str) as the aerosol increment of the next
+    solver call on ctx (rrtmgpnn_solver_request_aerosol), which applies it in front of its own band increment and
+    clears it.  aer_props None disarms."""
+    if aer_props is None:
+        check(_lib.lib().rrtmgpnn_solver_request_aerosol(ctx.h, 0, 0, 0, None, None, None), "solver_request_aerosol")
+        return
+    ncol, nlay, nbnd = aer_props.tau.shape
+    check(_lib.lib().rrtmgpnn_solver_request_aerosol(
+        ctx.h, nbnd, nlay, ncol, _p(aer_props.tau), _p(getattr(aer_props, "ssa", None)),
+        _p(getattr(aer_props, "g", None))), "solver_request_aerosol")
+
+
 def arm_cloud_mask_byband(ctx, ngpt, mask_bits, band_lims_gpt, bnd_up, bnd_dn, bnd_dir=None):
     """Arm the packed mask mask_bits (ncol, nlay, ceil(ngpt / 32)) together with by-band outputs (ncol, nlay + 1, nbnd)
     over band_lims_gpt (nbnd, 2; 1-based, inclusive) for the next solver call on ctx

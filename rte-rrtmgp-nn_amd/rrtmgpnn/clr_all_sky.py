@@ -18,6 +18,16 @@ cloud is sampled per g-point by a mask from cloud_sampling.sampled_mask_*.  Wher
 takes its masked twin (rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica) on the packed mask, and rte_sw's all-sky solve is
 the library's masked fused solve; the cases that fall back run draw_samples on the byte mask ahead of the reference's
 sequence.
+
+aer_props: where rte_lw takes a dual entry, or rte_sw the masked fused solve, and the aerosols are of the fused kind
+(aerosol_by_request), they are not added to the g-point arrays by aer_props.increment but armed as the solver's
+aerosol request (rrtmgpnn_solver_request_aerosol): the solver adds them, then the clouds, as it reads the gas
+properties -- the same two increments in the same order, the same bits.  The SW clear solve is then the fused solve with
+the aerosol as its band increment; both solves get g = NULL for the gas properties, so the g array gas optics wrote
+(zeros) is not read.  Every other case keeps the reference's sequence.  AEROSOL_REQUEST = False keeps it everywhere (the
+comparison route).  As for the masked fused SW solve itself, the SW route needs the checkpointed SW kernel
+(rrtmgpnn_context_set_sw_kernel mode 0 or 3, the default): the class layer does not know a context's mode, and the call
+raises under modes 1 and 2.
 """
 import torch
 
@@ -25,6 +35,19 @@ from . import _lib, api, cloud_sampling
 from ._lib import check, float_array, int_array
 from .api import (GAUSS_DS, GAUSS_WTS, FluxesByBand, OpticalProps1scl, OpticalProps2str, SourceFuncLW, _f32dev, _p,
                   context)
+
+
+# the aerosol request route may be taken (False: always aer_props.increment, the reference's sequence)
+AEROSOL_REQUEST = True
+
+
+def aerosol_by_request(aer_props, optical_props, kind):
+    """Are these aerosols of the fused kind for a solve on optical_props -- `kind` (OpticalProps1scl for the LW,
+    OpticalProps2str for the SW), defined by band (ngpt == nband) on optical_props' bands, the same (ncol, nlay)?"""
+    return (aer_props is not None and isinstance(aer_props, kind) and isinstance(optical_props, kind)
+            and aer_props.bands_are_equal(optical_props) and aer_props.get_ngpt() == optical_props.get_nband()
+            and not aer_props.gpoints_are_equal(optical_props)
+            and (aer_props.get_ncol(), aer_props.get_nlay()) == (optical_props.get_ncol(), optical_props.get_nlay()))
 
 
 def _shape(a):
@@ -133,13 +156,17 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
                           neural_nets=neural_nets, defer_planck=dual)
     if e:
         return e
-    if aer_props is not None:
+    dual = dual and sources.planck_deferred is not None
+    aer_req = dual and AEROSOL_REQUEST and aerosol_by_request(aer_props, optical_props, OpticalProps1scl)
+    if aer_props is not None and not aer_req:
         e = aer_props.increment(optical_props)
         if e:
             return e
-    if dual and sources.planck_deferred is not None:
+    if dual:
         tlay_d, tlev_d, tsfc_d, sfc_lay = sources.planck_deferred
         ctx = context(dev.index)
+        if aer_req:
+            cloud_sampling.arm_aerosol(ctx, aer_props)
         emis = _f32dev(sfc_emis, dev)
         args = (ctx.h, ngpt, nlay, ncol, int(top_at_1), nmu, float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]),
                 _p(inc_flux), _p(optical_props.tau), _p(cloud_props.tau), _p(sources.lay_source), nband,
@@ -208,10 +235,6 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
         toa_flux.copy_(_f32dev(inc_flux, dev))
     if tsi_scaling is not None:
         toa_flux.mul_(float(tsi_scaling))
-    if aer_props is not None:
-        e = aer_props.increment(optical_props)
-        if e:
-            return e
     ctx = context(dev.index)
     albs = []
     for a in (sfc_alb_dir, sfc_alb_dif):
@@ -224,9 +247,7 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
             a = g
         albs.append(a)
     mu0 = _f32dev(mu0, dev)
-    e = api.rte_sw(optical_props, top_at_1, mu0, toa_flux, albs[0], albs[1], clrsky_fluxes)
-    if e:
-        return e
+    fused = False
     if masked:
         fused = (mask_bits is not None and isinstance(optical_props, OpticalProps2str) and ngpt % 2 == 0
                  and cloud_props.bands_are_equal(optical_props) and not cloud_props.gpoints_are_equal(optical_props)
@@ -236,13 +257,40 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
                  and not (isinstance(allsky_fluxes, FluxesByBand) and allsky_fluxes.are_desired_byband())
                  and allsky_fluxes.are_desired()
                  and all(_shape(a) == (ncol, ngpt) for a in albs))
+    f = lambda t: t if t is not None else torch.empty((ncol, nlay + 1), dtype=torch.float32, device=dev)  # noqa: E731
+    lims = int_array(k_dist.band_lims_gpt.ravel())
+    # aerosols by request: the masked fused solve is taken and the clear fluxes are broadband ones as well
+    # (band-pair layout: the solver's aerosol instances need every band to start at an odd 1-based g-point)
+    aer_req = (fused and AEROSOL_REQUEST and aerosol_by_request(aer_props, optical_props, OpticalProps2str)
+               and all((int(lo) - 1) % 2 == 0 for lo in k_dist.band_lims_gpt[:, 0])
+               and not clrsky_fluxes.are_desired_gpt() and clrsky_fluxes.are_desired()
+               and not (isinstance(clrsky_fluxes, FluxesByBand) and clrsky_fluxes.are_desired_byband()))
+    if aer_props is not None and not aer_req:
+        e = aer_props.increment(optical_props)
+        if e:
+            return e
+    if aer_req:
+        # the clear solve: the fused solve with the aerosol as its band increment; the gas g (0) is never read
+        up, dn, dr = f(clrsky_fluxes.flux_up), f(clrsky_fluxes.flux_dn), f(clrsky_fluxes.flux_dn_dir)
+        check(_lib.lib().rrtmgpnn_sw_solver_2stream_inc(
+            ctx.h, ngpt, nlay, ncol, int(top_at_1), _p(toa_flux), None, _p(optical_props.tau), _p(optical_props.ssa),
+            None, nband, lims, _p(aer_props.tau), _p(aer_props.ssa), _p(aer_props.g), _p(mu0), _p(albs[0]),
+            _p(albs[1]), _p(up), _p(dn), _p(dr)), "sw_solver_2stream_inc")
+        if clrsky_fluxes.flux_net is not None:
+            torch.sub(dn, up, out=clrsky_fluxes.flux_net)
+    else:
+        e = api.rte_sw(optical_props, top_at_1, mu0, toa_flux, albs[0], albs[1], clrsky_fluxes)
+        if e:
+            return e
+    if masked:
         if fused:
-            f = lambda t: t if t is not None else torch.empty((ncol, nlay + 1), dtype=torch.float32, device=dev)  # noqa: E731
             up, dn, dr = f(allsky_fluxes.flux_up), f(allsky_fluxes.flux_dn), f(allsky_fluxes.flux_dn_dir)
+            if aer_req:
+                cloud_sampling.arm_aerosol(ctx, aer_props)
             cloud_sampling.arm_cloud_mask(ctx, ngpt, mask_bits)
             check(_lib.lib().rrtmgpnn_sw_solver_2stream_inc(
                 ctx.h, ngpt, nlay, ncol, int(top_at_1), _p(toa_flux), None, _p(optical_props.tau),
-                _p(optical_props.ssa), _p(optical_props.g), nband, int_array(k_dist.band_lims_gpt.ravel()),
+                _p(optical_props.ssa), None if aer_req else _p(optical_props.g), nband, lims,
                 _p(cloud_props.tau), _p(cloud_props.ssa), _p(cloud_props.g), _p(mu0), _p(albs[0]), _p(albs[1]),
                 _p(up), _p(dn), _p(dr)), "sw_solver_2stream_inc")
             if allsky_fluxes.flux_net is not None:

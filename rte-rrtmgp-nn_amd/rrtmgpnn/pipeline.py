@@ -56,6 +56,16 @@ for a host model that updates its LW fluxes between radiation calls -- and arms 
 before the LW solver call, which then carries the Jacobian beside its upward radiance: fused, sfc_source_Jac is formed
 in-kernel; unfused, it is the array compute_planck_source_nn already writes.  Clear-sky, overcast or McICA clouds; not
 with by-band or clear-sky outputs, which have no Jacobian instances.
+
+aerosols={"lw_tau": (ncol, nlay, nband_lw), "sw_tau": ..., "sw_ssa": ..., "sw_g": (ncol, nlay, nband_sw)}: aerosol
+optical properties by band (the host's, delta-scaled by the host), which mo_rrtmgp_clr_all_sky.F90 adds to the gas
+properties ahead of the clear solve (:155-157, :288-290): the clear sky is gases plus aerosols.  The step owns device
+buffers of them, which set_aerosols refills between steps or replays.  Fused without clouds, the aerosol is the solver
+call's own band increment (_planck_inc, _rfmip with nbnd > 0); with clouds each chain arms
+rrtmgpnn_solver_request_aerosol right before its solver, which then adds the aerosol and the (sampled) cloud as it reads
+the gas properties, and the clear SW launch takes the aerosol as its increment.  Unfused, rrtmgpnn_increment_bybnd by the
+aerosol follows gas optics, the reference's sequence.  Not with byband, jacobian or mcica["byband"], for which the
+solvers have no aerosol instances.
 """
 
 from types import SimpleNamespace
@@ -71,17 +81,18 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
             "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask",
-            "mcica_randoms_sw", "sw_mask_byband"}
+            "mcica_randoms_sw", "sw_mask_byband", "sw_aerosol", "increment_aer_sw"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
 # (lw_byband / sw_byband: a byband step's by-band requests, host-only calls issued right before their solver;
 # mcica_mask_*: a McICA step's mask kernels, which depend on no network; lw_mask / sw_mask: its cloud-mask requests,
 # host-only like the by-band ones; lw_mask_byband / sw_mask_byband: the two as one paired request, mcica={"byband": True};
-# lw_jacobian: a jacobian=True step's request, host-only too)
+# lw_jacobian: a jacobian=True step's request, host-only too; lw_aerosol / sw_aerosol: an aerosols= step's requests
+# beside clouds, host-only)
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
-               "predict_nn_lw", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
-               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_solver"]
+               "predict_nn_lw", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
+               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_solver"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -134,19 +145,25 @@ class ClearSkyStep:
     themselves are refused with mcica.
     jacobian: the step also owns lw_up_jac (ncol, nlay+1), the Jacobian of lw_up with respect to the surface
     temperature (rte_lw's flux_up_Jac), requested from the LW solver call; refused with byband, clrsky and their mcica
-    keys."""
+    keys.
+    aerosols: aerosol optical properties by band, {"lw_tau": (ncol, nlay, nband_lw), "sw_tau", "sw_ssa", "sw_g": (ncol,
+    nlay, nband_sw)} (the SW keys only with sw=True), in step-owned device buffers (aer_tau_lw, aer_tau_sw, aer_ssa_sw,
+    aer_g_sw) that set_aerosols refills between steps or replays: added to the gas properties ahead of the clear solve,
+    so the clear-sky fluxes are those of gases plus aerosols; refused with byband, jacobian and mcica["byband"]."""
 
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
-                 clrsky=False, mcica=None, jacobian=False):
-        self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica)
+                 clrsky=False, mcica=None, jacobian=False, aerosols=None):
+        self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica, aerosols, jacobian)
         self.jacobian = bool(jacobian)
         if self.jacobian and (self.byband or self.clrsky):
             raise ValueError("jacobian=True with by-band or clear-sky outputs (byband, clrsky or the mcica keys) is not "
                              "supported: the solvers' by-band and clear + all-sky instances carry no Jacobian")
         self._open_device(device, ctx, lw_models, sw_models, icergh, cloud_lut)
         self._allocate(prob, clouds, mcica)
+        if self.aerosols:
+            self._allocate_aerosols(aerosols)
         self._prepare_arguments(nmus)
         # unfused, the SW boundary conditions follow get_col_dry, the call the SW stream forks after
         self.calls = self._col_dry() + self._sw_boundary() + self._lw_chain() + (self._sw_chain() if sw else [])
@@ -155,8 +172,16 @@ class ClearSkyStep:
         else:
             self._finish(False)
 
-    def _resolve_options(self, fused, clouds, sw, sw_priority, byband, clrsky, mcica):
+    def _resolve_options(self, fused, clouds, sw, sw_priority, byband, clrsky, mcica, aerosols=None, jacobian=False):
         """Every option check, and the flags derived from the options, before any device object exists."""
+        self.aerosols = aerosols is not None
+        if self.aerosols:
+            if byband or jacobian or (mcica is not None and mcica.get("byband")):
+                raise ValueError("aerosols with byband=True, jacobian=True or mcica['byband'] is not supported: the "
+                                 "solvers' aerosol instances have no by-band or Jacobian outputs")
+            want = {"lw_tau"} | ({"sw_tau", "sw_ssa", "sw_g"} if sw else set())
+            if set(aerosols) != want:
+                raise ValueError("aerosols: expected the keys %s, got %s" % (sorted(want), sorted(aerosols)))
         self.mcica = mcica is not None
         if self.mcica and clouds is None:
             raise ValueError("mcica: sampled clouds need clouds=(lwp, iwp, rel, rei)")
@@ -267,6 +292,38 @@ class ClearSkyStep:
                 self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (
                     f(ncol, nlay + 1, self.kd_sw["nband"]) for _ in range(3))
 
+    def _allocate_aerosols(self, aerosols):
+        """An aerosols= step's band properties, step-owned: the solver calls hold their addresses."""
+        ncol, nlay = self.ncol, self.nlay
+        self.nb_sw = self.kd_sw["nband"]
+        want = {"lw_tau": (ncol, nlay, self.nb_lw)}
+        if self.sw:
+            want.update({k: (ncol, nlay, self.nb_sw) for k in ("sw_tau", "sw_ssa", "sw_g")})
+        for k, shape in want.items():
+            if tuple(np.shape(aerosols[k])) != shape:
+                raise ValueError("aerosols: %s has shape %s, expected %s" % (k, tuple(np.shape(aerosols[k])), shape))
+            w, q = k.split("_")
+            setattr(self, "aer_%s_%s" % (q, w), torch.empty(shape, dtype=torch.float32, device=self.dev))
+        self.set_aerosols(**aerosols)
+
+    def set_aerosols(self, lw_tau=None, sw_tau=None, sw_ssa=None, sw_g=None):
+        """Copy new aerosol properties into the step's buffers (None keeps an array) between steps or graph replays;
+        complete on return."""
+        if not self.aerosols:
+            raise ValueError("set_aerosols: the step was built without aerosols=")
+        torch.cuda.synchronize(self.dev)  # nothing in flight reads the buffers
+        for name, src in (("aer_tau_lw", lw_tau), ("aer_tau_sw", sw_tau), ("aer_ssa_sw", sw_ssa), ("aer_g_sw", sw_g)):
+            if src is None:
+                continue
+            dst = getattr(self, name, None)
+            if dst is None:
+                raise ValueError("set_aerosols: an LW-only step holds no SW aerosols")
+            src = src if isinstance(src, torch.Tensor) else _t(src, self.dev)
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError("set_aerosols: %s has shape %s, expected %s" % (name, tuple(src.shape), tuple(dst.shape)))
+            dst.copy_(src)
+        torch.cuda.synchronize(self.dev)
+
     def _allocate_mcica(self, mcica, f):
         """A McICA step's cloud fraction, overlap parameter, random numbers (or seed words) and masks."""
         ncol, nlay, dev = self.ncol, self.nlay, self.dev
@@ -332,7 +389,7 @@ class ClearSkyStep:
             (lambda stem: p(stem + "tau_sw", stem + "ssa_sw", stem + "g_sw"))
         mask, bits, randoms, rng = p("mask_" + w, "mask_bits_" + w, "randoms_" + w, "rng_" + w)
         return SimpleNamespace(sfx=w, ngpt=kd["ngpt"], nband=kd["nband"], lims=lims, props=triple(""),
-                               cld=triple("cld_"), smp=triple("smp_"), mask=mask, bits=bits, randoms=randoms, rng=rng,
+                               cld=triple("cld_"), smp=triple("smp_"), aer=triple("aer_"), mask=mask, bits=bits, randoms=randoms, rng=rng,
                                bnd=p(w + "_bnd_up", w + "_bnd_dn") + (p("sw_bnd_dir") if w == "sw" else (None,)))
 
     # ---- the sequences both chains issue, from a chain's record ----
@@ -378,6 +435,21 @@ class ClearSkyStep:
         if self.byband:
             return [(ch.sfx + "_byband", L.rrtmgpnn_solver_request_byband, (c, ch.nband, ch.lims) + ch.bnd)]
         return []
+
+    def _aerosol_request(self, ch):
+        """A fused aerosols= step's request beside clouds, armed right before the chain's all-sky solver call, which adds
+        the aerosol in front of its own (cloud) increment."""
+        if not (self.aerosols and self.fused and self.allsky):
+            return []
+        return [(ch.sfx + "_aerosol", self.L.rrtmgpnn_solver_request_aerosol,
+                 (self.ctx.h, ch.nband, self.nlay, self.ncol) + ch.aer)]
+
+    def _aerosols_in(self, ch):
+        """An unfused aerosols= step's aer_props%increment(optical_props), right after gas optics."""
+        if not self.aerosols or self.fused:
+            return []
+        return [("increment_aer_" + ch.sfx, self.L.rrtmgpnn_increment_bybnd,
+                 (self.ctx.h, self.ncol, self.nlay, ch.ngpt, ch.nband, ch.lims) + ch.props + ch.aer)]
 
     def _jacobian_request(self):
         """A jacobian=True step's request, armed right before the LW solver call (after the chain's other request, which
@@ -443,6 +515,7 @@ class ClearSkyStep:
                 # (the clear + all-sky McICA entry takes the mask as an argument)
                 *self._request(ch, mask=not self.clrsky),
                 *self._jacobian_request(),
+                *self._aerosol_request(ch),
                 self._lw_solver_fused(),
             ]
         planck = (self.nb_lw, self.ng_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") + (
@@ -458,6 +531,7 @@ class ClearSkyStep:
             ("predict_nn_lw", L.rrtmgpnn_predict_nn_lw,
              (c, ncol, nlay, self.ng_lw, self.nx_lw) + p("x_lw", "col_dry") + (self._nets_lw, len(self.lw_nets))
              + p("tau_lw", "lay_src")),
+            *self._aerosols_in(ch),
             *self._cloud_optics_call(ch),
             # clouds%increment(atmos) before rte_lw (rrtmgp_allsky.F90:383-395) ...
             *([] if self.clrsky else clouds),
@@ -480,7 +554,8 @@ class ClearSkyStep:
         of a request."""
         L, p = self.L, self._p
         args = (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W, None) \
-            + p("tau_lw") + (p("cld_tau_lw") if self.allsky else ()) + p("lay_src") \
+            + p("tau_lw") + (p("cld_tau_lw") if self.allsky else p("aer_tau_lw") if self.aerosols else ()) \
+            + p("lay_src") \
             + (self.nb_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") \
             + (self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"])) \
             + p("totplnk") + (1,) + p("sfc_emis", "lw_up", "lw_dn")
@@ -489,7 +564,9 @@ class ClearSkyStep:
                     args + p("lw_up_clr", "lw_dn_clr", "mask_bits_lw"))
         if self.clrsky:
             return ("lw_solver", L.rrtmgpnn_lw_solver_noscat_planck_clr_all, args + p("lw_up_clr", "lw_dn_clr"))
-        entry = L.rrtmgpnn_lw_solver_noscat_planck_inc if self.allsky else L.rrtmgpnn_lw_solver_noscat_planck
+        # (clear sky with aerosols: the aerosol is the entry's own increment)
+        inc = self.allsky or self.aerosols
+        entry = L.rrtmgpnn_lw_solver_noscat_planck_inc if inc else L.rrtmgpnn_lw_solver_noscat_planck
         return ("lw_solver", entry, args)
 
     def _sw_chain(self):
@@ -501,7 +578,10 @@ class ClearSkyStep:
         if self.fused:
             # the boundary conditions and (all sky) clouds%increment(atmos) fused into the solver
             # (rrtmgpnn_sw_solver_2stream_rfmip; same bits as sw_boundary_rfmip + sw_solver_2stream[_inc])
-            band_inc = (self.nb_sw, self._lims_sw) + ch.cld if self.allsky else (0, None, None, None, None)
+            no_inc = (0, None, None, None, None)
+            # aerosols: the clear launch's own increment, and with clouds a request ahead of the all-sky launch
+            aer_inc = (self.nb_sw, self._lims_sw) + ch.aer if self.aerosols else no_inc
+            band_inc = (self.nb_sw, self._lims_sw) + ch.cld if self.allsky else aer_inc
             solver = lambda name, inc, *out: (  # noqa: E731
                 name, L.rrtmgpnn_sw_solver_2stream_rfmip,
                 (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("solar_source", "tsi", "sfc_alb", "sza")
@@ -514,12 +594,13 @@ class ClearSkyStep:
                 *delta_scale,
                 *self._clouds_in(ch),
                 *self._request(ch),
+                *self._aerosol_request(ch),
                 solver("sw_solver", band_inc, "sw_up", "sw_dn", "sw_dir"),
                 # clear-sky fluxes: one more solver launch on the SW chain, on the gas optics' own properties (the fused
                 # solver leaves tau / ssa as they were).  Through the same entry without an increment: the
                 # checkpointed kernel forms the boundary conditions in its prologue and never stores them, so there is
                 # nothing in toa / alb / mu0 for a plain solver call to read
-                *([solver("sw_solver_clr", (0, None, None, None, None), "sw_up_clr", "sw_dn_clr", "sw_dir_clr")]
+                *([solver("sw_solver_clr", aer_inc, "sw_up_clr", "sw_dn_clr", "sw_dir_clr")]
                   if self.clrsky else []),
             ]
         solver = lambda name, *out: (  # noqa: E731
@@ -530,6 +611,7 @@ class ClearSkyStep:
              (c, ncol, nlay, self.nx_sw) + p("play", "tlay") + (self._g_sw, self._nd_sw, self.sw_nets[0]) + p("x_sw")),
             ("predict_nn_sw", L.rrtmgpnn_predict_nn_sw,
              (c, ncol, nlay, self.ng_sw, self.nx_sw) + p("x_sw", "col_dry") + (self._nets_sw,) + ch.props),
+            *self._aerosols_in(ch),
             # clouds%delta_scale(); clouds%increment(atmos) before rte_sw (rrtmgp_allsky.F90:420-433), and with clear-sky
             # fluxes the clear solve before the increment (mo_rrtmgp_clr_all_sky.F90:246-259)
             *self._cloud_optics_call(ch),
