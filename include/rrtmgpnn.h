@@ -326,6 +326,34 @@ int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int nco
                               const float *Ds, const float *weights, const float *inc_flux, const float *tau,
                               const float *ssa, const float *g, const float *lay_source, const float *lev_source,
                               const float *sfc_emis_gpt, const float *sfc_source, float *flux_up, float *flux_dn);
+/* rrtmgpnn_lw_solver_1rescl on the fused-Planck path with the atmosphere incremented by band-resolved two-stream
+ * properties (tau_bnd, ssa_bnd, g_bnd; (nbnd, nlay, ncol) DEVICE, all three required: NULL is RRTMGPNN_ERR_ARGUMENT),
+ * e.g. LW cloud optics with scattering: the arguments of rrtmgpnn_lw_solver_noscat_planck_inc with ssa_bnd and g_bnd
+ * after tau_bnd.  Per column, layer and g-point of band b, in float32: the optical properties are
+ * inc_2stream_by_2stream_bybnd (rte/kernels/mo_optical_props_kernels.F90:430-463) of (tau, 0, 0) by
+ * (tau_bnd(b), ssa_bnd(b), g_bnd(b)) -- the gas atmosphere is 1scl, its ssa and g the literal zeros a 2str copy of it
+ * would hold, so no such arrays exist; the sources are formed in-kernel from pfrac as in rrtmgpnn_lw_solver_noscat_planck;
+ * the transport is rrtmgpnn_lw_solver_1rescl's.  The fluxes are bit for bit those of rrtmgpnn_compute_planck_source_nn,
+ * zero-filled ssa / g, rrtmgpnn_increment_bybnd and rrtmgpnn_lw_solver_1rescl on the same inputs; tau and pfrac are only
+ * read.  Under rrtmgpnn_solver_request_cloud_mask the three band operands are 0 where the g-point's bit is clear: bit
+ * for bit rrtmgpnn_draw_samples (2str) + rrtmgpnn_increment + rrtmgpnn_lw_solver_1rescl (an all-zero mask therefore
+ * gives rrtmgpnn_lw_solver_noscat_planck's fluxes: the rescaled solver with ssa = 0 is the no-scattering one).
+ * nmus 1..4, both orientations, ngpt <= 256, emis_by_band 0 or 1, inc_flux may be NULL.  Broadband fluxes only: an armed
+ * by-band request (separate or paired with a mask), a flux-Jacobian request and an aerosol request are each refused
+ * with RRTMGPNN_ERR_ARGUMENT and a message naming this entry, and cleared as every solver entry clears them.  The
+ * workspace is one (ngpt, nlay+1, ncol) plane (three with several angles): half of rrtmgpnn_lw_solver_1rescl's, since
+ * the first-pass radiance at a level is read for the last time just before the upward radiance of that level is
+ * stored.  Nothing is allocated beyond the context workspace, so a warmed-up call can be captured in a hipGraph.
+ * OPERAND BOUND: ssa_bnd * (1 + g_bnd) / 2 < 1, so that the scaling 1 - ssa + ssa (1 - g) / 2 does not vanish (as in the
+ * reference).  No reference counterpart as one call. */
+int rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                         int nmus, const float *Ds, const float *weights, const float *inc_flux,
+                                         const float *tau, const float *tau_bnd, const float *ssa_bnd,
+                                         const float *g_bnd, const float *pfrac, int nbnd, int nPlanckTemp,
+                                         const float *tlay, const float *tlev, const float *tsfc, int sfc_lay,
+                                         const int *band_lims_gpt, float temp_ref_min, float totplnk_delta,
+                                         const float *totplnk, int emis_by_band, const float *sfc_emis,
+                                         float *flux_up, float *flux_dn);
 /* rte_lw(..., use_2stream=.true.): lw_solver_2stream (rte/kernels/mo_rte_solver_kernels.F90:426-486) with
  * lw_two_stream (:1018-1069), lw_source_2str (:1112-1162) and adding (:1526-1637).  inc_flux (ngpt, ncol) is a flux
  * (NULL: zero); the layer sources are not used (as in the reference).  Broadband sums are sequential over g
@@ -583,11 +611,12 @@ int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
  * everything downstream is the _inc arithmetic, so the fluxes are bit for bit those of rrtmgpnn_draw_samples +
  * rrtmgpnn_increment (same resolution; inc_2stream_by_2stream with a zero increment still rounds
  * tau * ssa / max(eps, tau), and so does this) + the solver, without the g-point cloud arrays.  Honoured by
- * rrtmgpnn_lw_solver_noscat_planck_inc (every nmus), rrtmgpnn_sw_solver_2stream_inc and
+ * rrtmgpnn_lw_solver_noscat_planck_inc and rrtmgpnn_lw_solver_1rescl_planck_inc (every nmus; the latter switches
+ * tau_bnd, ssa_bnd and g_bnd), rrtmgpnn_sw_solver_2stream_inc and
  * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, the SW ones on the checkpointed kernel (the default of
  * rrtmgpnn_context_set_sw_kernel: even ngpt; other modes, and odd ngpt, RRTMGPNN_ERR_UNSUPPORTED).  Extents other than
  * the call's: RRTMGPNN_ERR_ARGUMENT; every other solver entry (the plain ones, _clr_all, _clr_all_mcica, which takes
- * its mask as an argument, the _gpt entries, the scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT;
+ * its mask as an argument, the _gpt entries, the other scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT;
  * together with a separate by-band request: RRTMGPNN_ERR_UNSUPPORTED (rrtmgpnn_solver_request_byband_mcica below
  * requests the pair).  The pointer becomes a kernel argument and nothing is allocated, so an armed call can be captured
  * in a hipGraph.  No reference counterpart (the reference samples into g-point arrays, draw_samples). */

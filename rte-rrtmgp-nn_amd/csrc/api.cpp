@@ -1072,6 +1072,39 @@ int rrtmgpnn_lw_solver_1rescl_gpt(rrtmgpnn_context *ctx, int ngpt, int nlay, int
   return lw_1rescl(ctx, p, ssa, g, lay_source, lev_source, sfc_source, gpt_flux_up, gpt_flux_dn);
 }
 
+int rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                         int nmus, const float *Ds, const float *weights, const float *inc_flux,
+                                         const float *tau, const float *tau_bnd, const float *ssa_bnd,
+                                         const float *g_bnd, const float *pfrac, int nbnd, int nPlanckTemp,
+                                         const float *tlay, const float *tlev, const float *tsfc, int sfc_lay,
+                                         const int *band_lims_gpt, float temp_ref_min, float totplnk_delta,
+                                         const float *totplnk, int emis_by_band, const float *sfc_emis,
+                                         float *flux_up, float *flux_dn)
+{
+  // broadband fluxes of McICA-sampled (or overcast) scattering clouds: the cloud mask is the one request with an
+  // instance here; by-band outputs, the flux Jacobian and an aerosol increment are refused, naming this entry
+  static const char kEntry[] = "lw_solver_1rescl_planck_inc";
+  SolverExtras ex;
+  const Requests rq = take_requests(ctx, ngpt, ex);
+  if (rq.byband)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": by-band outputs are not available from this entry (the "
+                                                             "lw_solver_1rescl entry has them, without a mask)");
+  if (int rc = take_aerosol(kEntry, rq, kAerRefuse, nbnd, nlay, ncol, ex)) return rc;
+  if (int rc = take_jacobian(kEntry, rq, kJacRefuse, ngpt, nlay, ncol, ex)) return rc;
+  if (rq.mask.armed) {
+    if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
+      return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
+                                                               "are not this call's");
+    ex.mask_bits = rq.mask.bits;
+  }
+  if (int rc = check_ctx(ctx)) return rc;
+  const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
+  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+                pfrac, {}, tau_bnd};
+  if (int rc = planck_args(kEntry, p, in, nbnd, band_lims_gpt, true, ssa_bnd && g_bnd)) return rc;
+  return launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd);
+}
+
 int rrtmgpnn_lw_solver_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
                                const float *inc_flux, const float *tau, const float *ssa, const float *g,
                                const float *lev_source, const float *sfc_emis_gpt, const float *sfc_source,

@@ -337,6 +337,10 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
 // kernels_lw_scat.hip
 int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *ssa, const float *g,
                     const float *lay_source, const float *lev_source, const float *sfc_source);
+// the rescaled solver on the fused-Planck path, tau incremented in-kernel by the band-resolved 2str set
+// (in.tau_bnd, ssa_bnd, g_bnd), which ex.mask_bits (or null) switches per g-point; broadband fluxes only
+int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in,
+                               const float *ssa_bnd, const float *g_bnd);
 int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,
                       const float *inc_flux, const float *tau, const float *ssa, const float *g,
                       const float *lev_source, const float *sfc_emis, const float *sfc_source, float *flux_up,

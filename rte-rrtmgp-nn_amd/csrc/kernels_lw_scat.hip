@@ -7,6 +7,9 @@
 //                        with the adjustment terms
 //  * lw_2stream_kernel : lw_solver_2stream (:426-486) with lw_two_stream (:1018-1069, Fu et al. coefficients),
 //                        lw_source_2str (:1112-1162) and adding (:1526-1637); sum_broadband_nocol sums
+//  * lw_rescl_planck_inc_kernel : lw_rescl_kernel's transport on a 1scl gas atmosphere incremented in-kernel by
+//                        band-resolved two-stream clouds (McICA-maskable), the Planck sources formed in-kernel: two
+//                        g-point arrays read instead of five, one workspace plane instead of two (row f-9)
 //
 // Same layout and launch shape as the no-scattering solver: one block per column, one lane per g-point,
 // the vertical recurrences in registers, level values that a later pass needs parked in a per-column
@@ -225,6 +228,245 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// lw_rescl_planck_inc_kernel (rrtmgpnn_lw_solver_1rescl_planck_inc): the rescaled solver on a 1scl gas atmosphere
+// incremented by band-resolved two-stream clouds, with the Planck sources formed in-kernel.  What
+// compute_Planck_source_nn, zeroed gas ssa / g, [draw_samples,] increment and lw_rescl_kernel give, bit for bit, from
+// two g-point arrays (tau, pfrac) and three band arrays instead of five g-point arrays:
+//  * optics: inc_2str(tau, 0, 0, tau_bnd(b), ssa_bnd(b), g_bnd(b)) -- the gas operands are the literal zeros the host
+//    would have stored, kept in the expressions (the sign of a zero g depends on them);
+//  * kMask: where the g-point's bit of cmask (nw, nlay, ncol) is clear the three band operands are 0, which is what
+//    draw_samples leaves there for increment to add;
+//  * sources: lay = pfrac(l) * B_b(tlay(l)), lev(li) = pfrac(min(li, nlay-1)) * B_b(tlev(li)), sfc = pfrac(sfc_lay) *
+//    B_b(tsfc), the band Planck values interpolated once per column into LDS as lw_noscat_kernel's kFused instances do;
+//  * transport: rs_layer and the three passes of lw_rescl_kernel, the same ring and ordered flush.
+// A layer's inputs -- tau, pfrac, the neighbouring pfrac of lev(l+1), three band values (one address per band: the
+// loads broadcast), kMask: one mask word -- are loaded kPF layers ahead of the recurrence in every pass, and so is the
+// workspace value that passes 2 and 3 read.
+// Workspace: ONE plane (nlev, ngpt) per column.  Pass 1 parks radn_dn there; pass 2 reads level ltop's value and then
+// writes its radn_up to the same element (read first, by the same lane), never reading the surface element, which the
+// surface step overwrote; pass 3 reads only radn_up.  With several angles two accumulator planes follow.
+// LDS: etab | B [nbnd][2*nlay+1], Bsfc [nbnd] | ring [kScatRing][ngpt] | part [2][nlev][4]
+// ------------------------------------------------------------------------------------------
+#ifndef RRTMGPNN_LW_SCAT_PF
+#define RRTMGPNN_LW_SCAT_PF 1
+#endif
+constexpr int kScatPf = RRTMGPNN_LW_SCAT_PF;  // layers of inputs in flight per lane
+static_assert(kScatPf >= 1 && kScatRing % kScatPf == 0, "prefetch depth must divide the ring");
+
+struct RsIn {
+  float t, y, yn, tb, wb, gb;
+  uint32_t m;
+};
+
+template <bool kMask, int kPF>
+__global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
+    int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang, const float *__restrict__ inc_flux,
+    const float *__restrict__ tau, const float *__restrict__ pfrac, const float *__restrict__ tau_bnd,
+    const float *__restrict__ ssa_bnd, const float *__restrict__ g_bnd, const float *__restrict__ emis, LwPlanck pl,
+    BandArgs bands, const uint32_t *__restrict__ cmask, float *__restrict__ ws, float *__restrict__ flux_up,
+    float *__restrict__ flux_dn)
+{
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int icol = blockIdx.x, g = threadIdx.x;
+  const bool on = g < ngpt;
+  const int gc = on ? g : ngpt - 1;  // clamped g-point for unconditional loads
+  const int nlev = nlay + 1, nbnd = bands.nbnd, brow = 2 * nlay + 1;
+  uint64_t *etab = (uint64_t *)(smem + kExpTabOff);
+  float *btab = smem + kExpTabFloats;
+  float *ring = btab + lw_btab_floats(nbnd, nlay);  // [kScatRing][ngpt]
+  float *part = ring + (size_t)kScatRing * ngpt;    // [2][nlev][4]: 0 = dn, 1 = up
+  load_exp_table(etab);
+  const bool multi = ang.nmus > 1;
+  float *W = ws + (size_t)(multi ? 3 : 1) * nlev * ngpt * icol, *acc_base = W + (size_t)nlev * ngpt;
+  auto X = [&](int l) { return (size_t)gc + (size_t)ngpt * l; };
+  // column-local descriptors (rte_device.hpp): the layer offset is an SGPR, the lane's offset a VGPR
+  const int b = band_of(bands, gc);
+  const uint32_t vg = 4u * (uint32_t)gc, row = 4u * (uint32_t)ngpt, vb = 4u * (uint32_t)b, irow = 4u * (uint32_t)nbnd;
+  const uint32_t nw = (uint32_t)((ngpt + 31) / 32), vm = 4u * (uint32_t)(gc >> 5), mrow = 4u * nw;
+  const uint32_t mbit = 1u << (gc & 31);
+  const ColArr Ttau(tau, (size_t)ngpt * nlay * icol, row * nlay), Tpf(pfrac, (size_t)ngpt * nlay * icol, row * nlay);
+  const size_t cb = (size_t)nbnd * nlay * icol;
+  const ColArr Ttb(tau_bnd, cb, irow * nlay), Twb(ssa_bnd, cb, irow * nlay), Tgb(g_bnd, cb, irow * nlay);
+  const ColArr Tmsk(kMask ? (const float *)cmask : tau, kMask ? (size_t)nw * nlay * icol : 0, mrow * nlay);
+  auto load = [&](int l) {
+    RsIn d;
+    d.t = Ttau.ld(vg, row * (uint32_t)l);
+    d.y = Tpf.ld(vg, row * (uint32_t)l);
+    d.yn = Tpf.ld(vg, row * (uint32_t)min(l + 1, nlay - 1));
+    d.tb = Ttb.ld(vb, irow * (uint32_t)l);
+    d.wb = Twb.ld(vb, irow * (uint32_t)l);
+    d.gb = Tgb.ld(vb, irow * (uint32_t)l);
+    d.m = kMask ? __float_as_uint(Tmsk.ld(vm, mrow * (uint32_t)l)) : 0u;
+    return d;
+  };
+  const float ysfc = Tpf.ld(vg, row * (uint32_t)(pl.sfc_lay - 1));
+  const float e = pl.emis_by_band ? emis[b + (size_t)nbnd * icol] : emis[gc + (size_t)ngpt * icol];
+  const float inc = inc_flux ? inc_flux[gc + (size_t)ngpt * icol] : 0.0f;
+  {
+    // band Planck values of this column (the table loop of lw_noscat_kernel): B_b(tlay(l)) at [b][l], B_b(tlev(l)) at
+    // [b][nlay+l], B_b(tsfc) at [nbnd*brow + b]
+    const float *tl = pl.tlay + (size_t)nlay * icol, *tv = pl.tlev + (size_t)nlev * icol;
+    constexpr int kBtabU = 8;
+    const int ntab = nbnd * (brow + 1), nrow = nbnd * brow;
+    for (int i0 = threadIdx.x; i0 < ntab; i0 += kBtabU * (int)blockDim.x) {
+      float T[kBtabU];
+      int bb[kBtabU];
+#pragma unroll
+      for (int u = 0; u < kBtabU; u++) {
+        const int i = min(i0 + u * (int)blockDim.x, ntab - 1);  // clamped: past-the-end entries are not stored
+        const int ib = i < nrow ? i / brow : i - nrow;
+        const int k = i < nrow ? i - ib * brow : -1;
+        bb[u] = ib;
+        const float *p = k < 0 ? pl.tsfc + icol : (k < nlay ? tl + k : tv + (k - nlay));
+        T[u] = *p;
+      }
+      float v[kBtabU];
+#pragma unroll
+      for (int u = 0; u < kBtabU; u++)
+        v[u] = interp1d(T[u], pl.tmin, pl.tdelta, pl.ntemp, pl.totplnk + (size_t)pl.ntemp * bb[u]);
+#pragma unroll
+      for (int u = 0; u < kBtabU; u++) {
+        const int i = i0 + u * (int)blockDim.x;
+        if (i < ntab) btab[i] = v[u];
+      }
+    }
+  }
+  const float *bl = btab + (size_t)b * brow;  // this lane's band row
+  __syncthreads();
+  const float ss = ysfc * btab[(size_t)nbnd * brow + b];
+  auto layer = [&](const RsIn &d, int l, float D) {
+    const bool cld = !kMask || (d.m & mbit) != 0;
+    float t = d.t, w = 0.0f, gq = 0.0f;
+    inc_2str(t, w, gq, cld ? d.tb : 0.0f, cld ? d.wb : 0.0f, cld ? d.gb : 0.0f);
+    return rs_layer(t, w, gq, D, d.y * bl[l], d.y * bl[nlay + l], d.yn * bl[nlay + l + 1], etab);
+  };
+  const int top = top_at_1 ? 0 : nlay, sfcl = top_at_1 ? nlay : 0, dl_dn = top_at_1 ? 1 : -1;
+  auto lay_dn = [&](int j) { return top_at_1 ? j : nlay - 1 - j; };  // j-th layer from the top
+  auto lay_up = [&](int j) { return top_at_1 ? nlay - 1 - j : j; };  // j-th layer from the surface
+  float *pdn = part, *pup = part + (size_t)nlev * 4;
+
+  for (int imu = 0; imu < ang.nmus; imu++) {
+    const float D = ang.D[imu];
+    const float fac = (multi || (ngpt & 3) == 0) ? 2.0f * kPi * ang.w[imu] : 1.0f;  // quirk B-5 as noscat
+    const bool acc = imu > 0;
+    // v = fac * radiance of plane q (0 = dn, 1 = up)
+    auto put = [&](float v, int r, int q, int level) {
+      if (!on) return;
+      if (multi) {
+        float *w = acc_base + ((size_t)q * nlev + level) * ngpt + g;
+        *w = acc ? *w + v : v;
+      } else {
+        ring[(size_t)r * ngpt + g] = v;
+      }
+    };
+    auto flush = [&](float *pq, int n, int lev0, int dl) {
+      if (!multi) ring_flush<kScatRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
+    };
+    RsIn pf[kPF];
+    float pw[kPF];
+    // 1: no-scattering transport down with the rescaled optics (lw_transport_noscat_dn)
+    const float I0 = inc / (2.0f * kPi * ang.w[imu]);
+    float I = I0;
+    if (on) W[X(top)] = I;
+#pragma unroll
+    for (int p = 0; p < kPF; p++) pf[p] = load(lay_dn(min(p, nlay - 1)));
+    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
+#pragma unroll
+      for (int s = 0; s < kScatRing; s++) {
+        const int j = j0 + s, p = s % kPF, l = lay_dn(min(j, nlay - 1));
+        const RsIn d = pf[p];
+        pf[p] = load(lay_dn(min(j + kPF, nlay - 1)));
+        if (j < nlay) {
+          const RsLayer r = layer(d, l, D);
+          I = r.trans * I + r.sdn;
+          if (on) W[X(top_at_1 ? l + 1 : l)] = I;
+        }
+      }
+    }
+    // surface reflection and emission
+    float U = I * (1.0f - e) + e * ss;
+    if (on) W[X(sfcl)] = U;
+    put(fac * U, 0, 1, sfcl);
+    flush(pup, 1, sfcl, 1);
+    // 2: up with the adjustment from the first-pass radiance at the layer top (lw_transport_1rescl); the layer top's
+    //    element of W is read (radn_dn), then written (radn_up)
+    auto ltop_of = [&](int l) { return top_at_1 ? l : l + 1; };
+#pragma unroll
+    for (int p = 0; p < kPF; p++) {
+      const int l = lay_up(min(p, nlay - 1));
+      pf[p] = load(l);
+      pw[p] = W[X(ltop_of(l))];
+    }
+    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
+#pragma unroll
+      for (int s = 0; s < kScatRing; s++) {
+        const int j = j0 + s, p = s % kPF, l = lay_up(min(j, nlay - 1)), ltop = ltop_of(l);
+        const RsIn d = pf[p];
+        const float wd = pw[p];
+        {
+          const int ln = lay_up(min(j + kPF, nlay - 1));
+          pf[p] = load(ln);
+          pw[p] = W[X(ltop_of(ln))];
+        }
+        if (j < nlay) {
+          const RsLayer r = layer(d, l, D);
+          const float adj = r.Cn * (r.An * wd - r.trans * r.sdn - r.sup);
+          U = r.trans * U + r.sup + adj;
+          if (on) W[X(ltop)] = U;
+          put(fac * U, s, 1, ltop);
+        }
+      }
+      flush(pup, min(kScatRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
+    }
+    // 3: down again with the adjustment from radn_up(l) in array order: the layer top when top_at_1, the
+    //    layer bottom otherwise (:1761-1767 vs :1783-1789, reproduced)
+    I = I0;
+    put(fac * I, 0, 0, top);
+#pragma unroll
+    for (int p = 0; p < kPF; p++) {
+      const int l = lay_dn(min(p, nlay - 1));
+      pf[p] = load(l);
+      pw[p] = W[X(l)];
+    }
+    flush(pdn, 1, top, 1);
+    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
+#pragma unroll
+      for (int s = 0; s < kScatRing; s++) {
+        const int j = j0 + s, p = s % kPF, l = lay_dn(min(j, nlay - 1));
+        const RsIn d = pf[p];
+        const float wu = pw[p];
+        {
+          const int ln = lay_dn(min(j + kPF, nlay - 1));
+          pf[p] = load(ln);
+          pw[p] = W[X(ln)];
+        }
+        if (j < nlay) {
+          const RsLayer r = layer(d, l, D);
+          const float adj = r.Cn * (r.An * wu - r.trans * r.sup - r.sdn);
+          I = r.trans * I + r.sdn + adj;
+          put(fac * I, s, 0, top_at_1 ? l + 1 : l);
+        }
+      }
+      flush(pdn, min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
+    }
+  }
+  if (multi) {
+    __syncthreads();
+    for (int t = g; t < 2 * nlev; t += blockDim.x) {
+      const float *w = acc_base + (size_t)t * ngpt;
+      float s = 0.0f;
+      for (int i = 0; i < ngpt; i++) s = s + w[i];  // sum_broadband: sequential over g
+      (t < nlev ? flux_dn : flux_up)[(t % nlev) + (size_t)nlev * icol] = s;
+    }
+    return;
+  }
+  for (int l = g; l < nlev; l += blockDim.x) {
+    flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
+    flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
+  }
+}
+
 // lw_two_stream (:1018-1069) and lw_source_2str (:1112-1162) for one layer
 struct L2Layer {
   float Rdif, Tdif, sdn, sup;
@@ -391,6 +633,38 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNosca
                        a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
                        p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{}, nullptr, nullptr);
   RRTMGPNN_LAUNCH_CHECK("lw_rescl_kernel");
+  return RRTMGPNN_OK;
+}
+
+// in.tau_bnd, ssa_bnd, g_bnd: the band-resolved two-stream increment; ex.mask_bits, or null: the McICA mask that
+// switches it.  No other extras have an instance (the entry refuses them).
+int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in,
+                               const float *ssa_bnd, const float *g_bnd)
+{
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol, nmus = p.nmus;
+  if (ncol == 0) return RRTMGPNN_OK;
+  if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
+  if (ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
+  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.aer_tau || ex.lw_Ds)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): broadband fluxes only");
+  LwAngles a{};
+  a.nmus = nmus;
+  for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
+  const int threads = (ngpt + 63) / 64 * 64;
+  const size_t lds = sizeof(float) * (kExpTabFloats + lw_btab_floats(in.bands.nbnd, nlay) + (size_t)kScatRing * ngpt +
+                                      (size_t)2 * (nlay + 1) * 4);
+  if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
+  void *ws = nullptr;
+  const int planes = nmus > 1 ? 3 : 1;  // the shared radn_dn / radn_up plane, and the two angle accumulators
+  if (int rc = ctx->workspace(sizeof(float) * planes * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
+                       p.tau, in.pfrac, in.tau_bnd, ssa_bnd, g_bnd, p.sfc_emis, in.pl, in.bands, ex.mask_bits,
+                       (float *)ws, p.flux_up, p.flux_dn);
+  };
+  if (ex.mask_bits) go(lw_rescl_planck_inc_kernel<true, kScatPf>);
+  else              go(lw_rescl_planck_inc_kernel<false, kScatPf>);
+  RRTMGPNN_LAUNCH_CHECK("lw_rescl_planck_inc_kernel");
   return RRTMGPNN_OK;
 }
 

@@ -891,17 +891,8 @@ __device__ __forceinline__ SwCoef sw_two_stream(float tau, float w0, float g, fl
   return c;
 }
 
-// inc_2stream_by_2stream_bybnd (rte/kernels/mo_optical_props_kernels.F90:430-463) for one g-point: the
-// same expressions as increment_bybnd_kernel, so the incremented properties are bit-identical.
-__device__ __forceinline__ void inc_2str(float &t1, float &w1, float &g1, float t2, float w2, float g2)
-{
-  const float eps = 3.0f * FLT_MIN;
-  const float tau12 = t1 + t2;
-  const float tauscat12 = t1 * w1 + t2 * w2;
-  g1 = (t1 * w1 * g1 + t2 * w2 * g2) / fmaxf(eps, tauscat12);
-  w1 = tauscat12 / fmaxf(eps, tau12);
-  t1 = tau12;
-}
+// inc_2str (inc_2stream_by_2stream_bybnd for one g-point) lives in rte_device.hpp: the fused rescaled LW kernel
+// (kernels_lw_scat.hip) forms the same increment.
 
 // kInc: the atmosphere is incremented by band-resolved two-stream properties (tau, ssa, g)_bnd as it is read
 // (clouds%increment(atmos) fused).  Pass 1 needs only tau + tau_bnd; pass 2 forms the full increment and

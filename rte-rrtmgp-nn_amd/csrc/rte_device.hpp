@@ -77,6 +77,18 @@ __host__ __device__ constexpr size_t lw_btab_floats(int nbnd, int nlay, bool jac
   return ((size_t)nbnd * (2 * nlay + 2 + (jac ? 1 : 0)) + 3) & ~(size_t)3;
 }
 
+// inc_2stream_by_2stream_bybnd (rte/kernels/mo_optical_props_kernels.F90:430-463) for one g-point: the
+// same expressions as increment_bybnd_kernel, so the incremented properties are bit-identical.
+__device__ __forceinline__ void inc_2str(float &t1, float &w1, float &g1, float t2, float w2, float g2)
+{
+  const float eps = 3.0f * FLT_MIN;
+  const float tau12 = t1 + t2;
+  const float tauscat12 = t1 * w1 + t2 * w2;
+  g1 = (t1 * w1 * g1 + t2 * w2 * g2) / fmaxf(eps, tauscat12);
+  w1 = tauscat12 / fmaxf(eps, tau12);
+  t1 = tau12;
+}
+
 // Gauss-Jacobi quadrature of the LW no-scattering solvers (secants and weights, nmus <= 4)
 struct LwAngles {
   float D[4], w[4];

@@ -10,9 +10,13 @@
 ! rte_lw takes the library's dual entry (rrtmgpnn_lw_solver_noscat_planck_clr_all: tau, the Planck fraction and the
 ! band cloud optical depth read once, both flux sets from one kernel with one angle) when the cloud properties are
 ! 1scl and defined by band on the k-distribution's bands, gas optics left the Planck sources unformed
-! (ty_source_func_lw%planck_deferred), and both flux objects want broadband up / down fluxes only.  Every other case
-! -- 2str clouds (the rescaled solver), clouds on g-points, g-point, by-band or net outputs -- runs the two solves with
-! mo_rte_lw's rte_lw.  rte_sw always runs the two solves.
+! (ty_source_func_lw%planck_deferred), and both flux objects want broadband up / down fluxes only.  With 2str clouds
+! (LW scattering: the rescaled solver) in the same situation and no aerosols it takes the fused scattering route: gas
+! optics into a 1scl object (no ssa / g arrays), the clear solve rrtmgpnn_lw_solver_noscat_planck (the rescaled solver
+! with ssa = g = 0 is the no-scattering one, bit for bit) and the all-sky solve rrtmgpnn_lw_solver_1rescl_planck_inc,
+! which increments tau by the two-stream band cloud as it reads it.  Every other case -- 2str clouds with aerosols,
+! clouds on g-points, g-point, by-band or net outputs -- runs the two solves with mo_rte_lw's rte_lw.  rte_sw always
+! runs the two solves.
 !
 ! aer_props: where rte_lw takes the dual entry and the aerosols are of the fused kind (1scl, defined by band on the
 ! k-distribution's bands, the same ncol and nlay), they are not added to the g-point array by aer_props%increment but
@@ -70,7 +74,7 @@ contains
     class(ty_optical_props_arry), allocatable :: optical_props
     type(ty_source_func_lw) :: sources
     integer :: ncol, nlay, ngpt, nband, nmus
-    logical :: top_at_1, dual, aer_req
+    logical :: top_at_1, dual, aer_req, scat
 
     error_msg = ""
     ncol  = size(p_lay, 2)
@@ -99,6 +103,25 @@ contains
     end select
     error_msg = optical_props%init(k_dist)
     if (len_trim(error_msg) > 0) return
+    nmus = 1
+    if (present(n_gauss_angles)) nmus = n_gauss_angles
+    ! scattering clouds by band, no aerosols, broadband fluxes: the gas atmosphere stays 1scl (its ssa and g are the
+    ! solver's literal zeros, never arrays)
+    scat = .false.
+    select type (cloud_props)
+    class is (ty_optical_props_2str)
+      scat = .not. present(aer_props) .and. cloud_props%bands_are_equal(optical_props) .and. &
+             .not. cloud_props%gpoints_are_equal(optical_props) .and. cloud_props%get_ngpt() == nband .and. &
+             cloud_props%get_ncol() == ncol .and. cloud_props%get_nlay() == nlay .and. &
+             broadband_only(allsky_fluxes) .and. broadband_only(clrsky_fluxes) .and. nmus >= 1 .and. nmus <= 4 .and. &
+             all(shape(sfc_emis) == [nband, ncol])
+    end select
+    if (scat) then
+      deallocate(optical_props)
+      allocate(ty_optical_props_1scl :: optical_props)
+      error_msg = optical_props%init(k_dist)
+      if (len_trim(error_msg) > 0) return
+    end if
     select type (optical_props)
     class is (ty_optical_props_1scl)
       error_msg = optical_props%alloc_1scl(ncol, nlay)
@@ -114,8 +137,10 @@ contains
                                   neural_nets)
     if (error_msg /= '') return
 
-    nmus = 1
-    if (present(n_gauss_angles)) nmus = n_gauss_angles
+    if (scat .and. .not. sources%planck_deferred) then
+      error_msg = "rte_lw: gas optics left the Planck sources formed; the fused scattering solve forms them itself"
+      return
+    end if
     dual = .false.
     select type (cloud_props)
     class is (ty_optical_props_1scl)
@@ -144,6 +169,11 @@ contains
       if (error_msg == '') error_msg = clrsky_fluxes%check_extents(nlay + 1, ncol)
       if (error_msg /= '') return
       call solve_dual()
+    else if (scat) then
+      error_msg = allsky_fluxes%check_extents(nlay + 1, ncol)
+      if (error_msg == '') error_msg = clrsky_fluxes%check_extents(nlay + 1, ncol)
+      if (error_msg /= '') return
+      call solve_scat()
     else
       ! the clear solve, clouds%increment, the all-sky solve (:160-172)
       error_msg = base_rte_lw(optical_props, top_at_1, sources, sfc_emis, clrsky_fluxes, inc_flux, n_gauss_angles)
@@ -203,6 +233,52 @@ contains
       call dev_release(d_emis); call dev_release(d_inc)
       call dev_release(d_up); call dev_release(d_dn); call dev_release(d_upc); call dev_release(d_dnc)
     end subroutine solve_dual
+
+    ! scattering clouds: the clear solve of tau by the no-scattering fused-Planck entry, then the all-sky solve by the
+    ! rescaled one, which increments (tau, 0, 0) by the cloud's (tau, ssa, g)(band) as it reads tau
+    subroutine solve_scat()
+      integer(c_long_long) :: ng, nv, nc
+      integer(c_int), allocatable :: lims(:,:)
+      type(c_ptr) :: d_emis, d_inc, d_up, d_dn, d_upc, d_dnc, d_tau, d_pf, d_tlay, d_tlev, d_tsfc
+      lims = optical_props%get_band_lims_gpoint()
+      ng = int(ngpt, c_long_long) * nlay * ncol
+      nv = int(nlay + 1, c_long_long) * ncol
+      nc = int(nband, c_long_long) * nlay * ncol
+      d_emis = dev_stage(sfc_emis, int(nband, c_long_long) * ncol)
+      d_inc = c_null_ptr
+      if (present(inc_flux)) d_inc = dev_stage(inc_flux, int(ngpt, c_long_long) * ncol)
+      d_up = dev_scratch(nv); d_dn = dev_scratch(nv); d_upc = dev_scratch(nv); d_dnc = dev_scratch(nv)
+      d_tau = dev_present(optical_props%tau, ng, PRESENT_READ)
+      d_pf = dev_present(sources%lay_source, ng, PRESENT_READ)
+      d_tlay = dev_present(sources%pk_tlay, size(sources%pk_tlay, kind=c_long_long), PRESENT_READ)
+      d_tlev = dev_present(sources%pk_tlev, size(sources%pk_tlev, kind=c_long_long), PRESENT_READ)
+      d_tsfc = dev_present(sources%pk_tsfc, size(sources%pk_tsfc, kind=c_long_long), PRESENT_READ)
+      error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                    merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
+                    d_tau, d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
+                    sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_upc, d_dnc), &
+                    "rte_lw: lw_solver_noscat (clear sky)")
+      select type (cloud_props)
+      class is (ty_optical_props_2str)
+        if (error_msg == '') &
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                      merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
+                      d_tau, dev_present(cloud_props%tau, nc, PRESENT_READ), &
+                      dev_present(cloud_props%ssa, nc, PRESENT_READ), dev_present(cloud_props%g, nc, PRESENT_READ), &
+                      d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
+                      sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_up, d_dn), &
+                      "rte_lw: lw_solver_1rescl (all sky, scattering clouds)")
+      end select
+      if (error_msg == '') then
+        call dev_copy_out(allsky_fluxes%flux_up, d_up, nv)
+        call dev_copy_out(allsky_fluxes%flux_dn, d_dn, nv)
+        call dev_copy_out(clrsky_fluxes%flux_up, d_upc, nv)
+        call dev_copy_out(clrsky_fluxes%flux_dn, d_dnc, nv)
+      end if
+      call rrtmgpnn_sync(error_msg, "rte_lw")
+      call dev_release(d_emis); call dev_release(d_inc)
+      call dev_release(d_up); call dev_release(d_dn); call dev_release(d_upc); call dev_release(d_dnc)
+    end subroutine solve_scat
   end function rte_lw
 
   ! does this flux object want exactly the broadband up and down fluxes (what the dual entry writes)?

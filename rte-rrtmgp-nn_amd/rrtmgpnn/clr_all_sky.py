@@ -10,8 +10,13 @@ typos included ('rrtmpg_lw: ...').
 rte_lw takes the library's dual entry (rrtmgpnn_lw_solver_noscat_planck_clr_all: tau, the Planck fraction and the
 band cloud optical depth read once, both flux sets from one kernel with one angle) when the cloud properties are
 1scl and defined by band on k_dist's bands and both flux objects want broadband up / down fluxes only; gas optics then
-leaves the Planck sources unformed and the kernel forms them.  Every other case -- 2str clouds (the rescaled solver),
-clouds on g-points, g-point or by-band outputs -- runs the two solves with api.rte_lw.  rte_sw always runs two solves.
+leaves the Planck sources unformed and the kernel forms them.  With 2str clouds (LW scattering: the rescaled solver) in
+the same situation and no aerosols it takes the fused scattering route: gas optics into a 1scl object (no ssa / g
+arrays), the clear solve rrtmgpnn_lw_solver_noscat_planck (the rescaled solver with ssa = g = 0 is the no-scattering
+one, bit for bit) and the all-sky solve rrtmgpnn_lw_solver_1rescl_planck_inc, the cloud mask armed when mask_bits is
+given; LW_SCAT_FUSED = False keeps the sequence below (the comparison route).  Every other case -- 2str clouds with
+aerosols, clouds on g-points, g-point or by-band outputs -- runs the two solves with api.rte_lw.  rte_sw always runs two
+solves.
 
 mask_bits= / cloud_mask= (both functions; not in the reference's interface) make the all-sky solve a McICA one: the band
 cloud is sampled per g-point by a mask from cloud_sampling.sampled_mask_*.  Where rte_lw would take the dual entry it
@@ -39,6 +44,9 @@ from .api import (GAUSS_DS, GAUSS_WTS, FluxesByBand, OpticalProps1scl, OpticalPr
 
 # the aerosol request route may be taken (False: always aer_props.increment, the reference's sequence)
 AEROSOL_REQUEST = True
+# the fused LW scattering route may be taken (False: always gas optics into 2str properties, [draw_samples,] increment
+# and the rescaled solver)
+LW_SCAT_FUSED = True
 
 
 def aerosol_by_request(aer_props, optical_props, kind):
@@ -66,18 +74,29 @@ def _aer_check(aer_props, ncol, nlay, ngpt, nband, msg):
     return e
 
 
+def _init_like(cloud_props, k_dist, which, kind=None):
+    """optical_props of cloud_props' class (or of `kind`) on k_dist's spectral grid, initialised but holding no arrays
+    yet (:117-126)."""
+    if kind is None:
+        if isinstance(cloud_props, OpticalProps2str):
+            kind = OpticalProps2str
+        elif isinstance(cloud_props, OpticalProps1scl):
+            kind = OpticalProps1scl
+        else:
+            return None, which + "_solver(...ty_optical_props_nstr...) not yet implemented"
+    op = kind()
+    return op, op.init(k_dist.get_band_lims_wavenumber(), k_dist.get_band_lims_gpoint())
+
+
+def _alloc(op, ncol, nlay, device):
+    """The arrays of an initialised optical_props (:128-137)."""
+    return (op.alloc_2str if isinstance(op, OpticalProps2str) else op.alloc_1scl)(ncol, nlay, device=device)
+
+
 def _alloc_like(cloud_props, k_dist, ncol, nlay, device, which):
     """optical_props of cloud_props' class on k_dist's spectral grid (:117-137)."""
-    if isinstance(cloud_props, OpticalProps2str):
-        op = OpticalProps2str()
-        alloc = op.alloc_2str
-    elif isinstance(cloud_props, OpticalProps1scl):
-        op = OpticalProps1scl()
-        alloc = op.alloc_1scl
-    else:
-        return None, which + "_solver(...ty_optical_props_nstr...) not yet implemented"
-    e = op.init(k_dist.get_band_lims_wavenumber(), k_dist.get_band_lims_gpoint()) or alloc(ncol, nlay, device=device)
-    return op, e
+    op, e = _init_like(cloud_props, k_dist, which)
+    return op, e or _alloc(op, ncol, nlay, device)
 
 
 def _broadband_only(fluxes):
@@ -139,7 +158,9 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
     masked = mask_bits is not None or cloud_mask is not None
     top_at_1 = bool(p_lay[0, 0] < p_lay[0, nlay - 1])
     dev = p_lay.device
-    optical_props, e = _alloc_like(cloud_props, k_dist, ncol, nlay, dev, "lw")
+    # the route is decided on an initialised object that holds no arrays yet, so that each route allocates only the
+    # arrays it uses
+    optical_props, e = _init_like(cloud_props, k_dist, "lw")
     if e:
         return e
     sources = SourceFuncLW()
@@ -147,16 +168,46 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
     if e:
         return e
     nmu = 1 if n_gauss_angles is None else int(n_gauss_angles)
-    dual = (isinstance(optical_props, OpticalProps1scl) and cloud_props.bands_are_equal(optical_props)
-            and not cloud_props.gpoints_are_equal(optical_props) and cloud_props.get_ngpt() == nband
-            and (cloud_props.get_ncol(), cloud_props.get_nlay()) == (ncol, nlay)
-            and _broadband_only(allsky_fluxes) and _broadband_only(clrsky_fluxes) and 1 <= nmu <= 4
-            and _shape(sfc_emis) == (ncol, nband) and (not masked or mask_bits is not None))
+    fusable = (cloud_props.bands_are_equal(optical_props)
+               and not cloud_props.gpoints_are_equal(optical_props) and cloud_props.get_ngpt() == nband
+               and (cloud_props.get_ncol(), cloud_props.get_nlay()) == (ncol, nlay)
+               and _broadband_only(allsky_fluxes) and _broadband_only(clrsky_fluxes) and 1 <= nmu <= 4
+               and _shape(sfc_emis) == (ncol, nband) and (not masked or mask_bits is not None))
+    dual = fusable and isinstance(optical_props, OpticalProps1scl)
+    scat = fusable and LW_SCAT_FUSED and isinstance(optical_props, OpticalProps2str) and aer_props is None
+    if scat:
+        # the gas atmosphere stays 1scl: its ssa and g are the solver's literal zeros, never arrays
+        optical_props, e = _init_like(cloud_props, k_dist, "lw", OpticalProps1scl)
+        if e:
+            return e
+    e = _alloc(optical_props, ncol, nlay, dev)
+    if e:
+        return e
     e = k_dist.gas_optics(p_lay, p_lev, t_lay, t_sfc, gas_concs, optical_props, sources, col_dry=col_dry, tlev=t_lev,
-                          neural_nets=neural_nets, defer_planck=dual)
+                          neural_nets=neural_nets, defer_planck=dual or scat)
     if e:
         return e
     dual = dual and sources.planck_deferred is not None
+    if scat and sources.planck_deferred is None:
+        # (gas optics defers whenever it is asked to; the 1scl gas properties leave no sequence to fall back to)
+        return "rte_lw: gas optics left the Planck sources formed; the fused scattering solve forms them itself"
+    if scat:
+        tlay_d, tlev_d, tsfc_d, sfc_lay = sources.planck_deferred
+        ctx = context(dev.index)
+        emis = _f32dev(sfc_emis, dev)
+        head = (ctx.h, ngpt, nlay, ncol, int(top_at_1), nmu, float_array(GAUSS_DS[nmu]), float_array(GAUSS_WTS[nmu]),
+                _p(inc_flux), _p(optical_props.tau))
+        tail = (_p(sources.lay_source), nband, k_dist.get_nPlanckTemp(), _p(tlay_d), _p(tlev_d), _p(tsfc_d), sfc_lay,
+                int_array(k_dist.band_lims_gpt.ravel()), k_dist.temp_ref_min, k_dist.totplnk_delta, _p(k_dist.totplnk),
+                1, _p(emis))
+        check(_lib.lib().rrtmgpnn_lw_solver_noscat_planck(*head, *tail, _p(clrsky_fluxes.flux_up),
+                                                          _p(clrsky_fluxes.flux_dn)), "lw_solver_noscat_planck")
+        if masked:
+            cloud_sampling.arm_cloud_mask(ctx, ngpt, mask_bits)
+        check(_lib.lib().rrtmgpnn_lw_solver_1rescl_planck_inc(
+            *head, _p(cloud_props.tau), _p(cloud_props.ssa), _p(cloud_props.g), *tail, _p(allsky_fluxes.flux_up),
+            _p(allsky_fluxes.flux_dn)), "lw_solver_1rescl_planck_inc")
+        return ""
     aer_req = dual and AEROSOL_REQUEST and aerosol_by_request(aer_props, optical_props, OpticalProps1scl)
     if aer_props is not None and not aer_req:
         e = aer_props.increment(optical_props)

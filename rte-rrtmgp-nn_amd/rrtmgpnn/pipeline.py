@@ -66,6 +66,14 @@ rrtmgpnn_solver_request_aerosol right before its solver, which then adds the aer
 the gas properties, and the clear SW launch takes the aerosol as its increment.  Unfused, rrtmgpnn_increment_bybnd by the
 aerosol follows gas optics, the reference's sequence.  Not with byband, jacobian or mcica["byband"], for which the
 solvers have no aerosol instances.
+
+lw_scattering=True (with clouds, fused): the LW clouds scatter.  LW cloud optics run with three outputs (cld_tau_lw,
+cld_ssa_lw, cld_g_lw by band) and the chain's all-sky solver call is rrtmgpnn_lw_solver_1rescl_planck_inc: rte_lw's
+rescaled solver on the gas optical depth incremented in-kernel by the two-stream band cloud, the Planck sources formed
+in-kernel.  mcica= arms the cloud mask for it as for the absorbing clouds; clrsky=True (or mcica's "clrsky") adds a
+rrtmgpnn_lw_solver_noscat_planck launch for the clear set ahead of it (the rescaled solver without scattering is the
+no-scattering one, bit for bit).  Not with fused=False, byband, mcica["byband"], jacobian or aerosols, for which the
+entry has no instances.  Off (the default), nothing of the step changes.
 """
 
 from types import SimpleNamespace
@@ -90,8 +98,9 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
 # host-only like the by-band ones; lw_mask_byband / sw_mask_byband: the two as one paired request, mcica={"byband": True};
 # lw_jacobian: a jacobian=True step's request, host-only too; lw_aerosol / sw_aerosol: an aerosols= step's requests
 # beside clouds, host-only)
+# (lw_solver_clr: an lw_scattering step's clear launch, ahead of the mask request its all-sky launch consumes)
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
-               "predict_nn_lw", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
+               "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
                "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_solver"]
 
 
@@ -154,9 +163,16 @@ class ClearSkyStep:
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
-                 clrsky=False, mcica=None, jacobian=False, aerosols=None):
+                 clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False):
         self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica, aerosols, jacobian)
         self.jacobian = bool(jacobian)
+        self.lw_scattering = bool(lw_scattering)
+        if self.lw_scattering:
+            bad = [w for w, on in (("fused=False", not fused), ("byband", self.byband), ("jacobian", self.jacobian),
+                                   ("aerosols", self.aerosols), ("no clouds", clouds is None)) if on]
+            if bad:
+                raise ValueError("lw_scattering=True with %s is not supported: the fused rescaled LW solve takes band "
+                                 "clouds (clouds=) and gives broadband fluxes only" % ", ".join(bad))
         if self.jacobian and (self.byband or self.clrsky):
             raise ValueError("jacobian=True with by-band or clear-sky outputs (byband, clrsky or the mcica keys) is not "
                              "supported: the solvers' by-band and clear + all-sky instances carry no Jacobian")
@@ -275,6 +291,8 @@ class ClearSkyStep:
         if self.allsky:
             self.lwp, self.iwp, self.rel, self.rei = ins[-4:]
             self.cld_tau_lw = f(ncol, nlay, self.nb_lw)
+            if self.lw_scattering:
+                self.cld_ssa_lw, self.cld_g_lw = f(ncol, nlay, self.nb_lw), f(ncol, nlay, self.nb_lw)
             self.cld_tau_sw, self.cld_ssa_sw, self.cld_g_sw = (f(ncol, nlay, self.nb_sw) for _ in range(3))
         if self.mcica:
             self._allocate_mcica(mcica, f)
@@ -381,11 +399,13 @@ class ClearSkyStep:
     def _chain_record(self, w, kd, lims):
         """What the cloud handling of the two chains differs in: the sizes and band limits, and the addresses (or None)
         of the optical properties, the clouds by band, the sampled clouds, the masks, the random numbers and the
-        by-band outputs.  The LW chain carries tau alone, so the ssa and g slots of its triples are NULL; the SW
+        by-band outputs.  The LW chain carries tau alone, so the ssa and g slots of its triples are NULL (but for an
+        lw_scattering step's band clouds, cld_ssa_lw and cld_g_lw); the SW
         asymmetry parameter is NULL in the fused step (quirk B-6: identically zero in the NN path, which the SW kernels
         take as a literal 0 instead of writing and re-reading a zero array; same fluxes, bit for bit)."""
         p = self._p
-        triple = (lambda stem: p(stem + "tau_lw") + (None, None)) if w == "lw" else \
+        triple = (lambda stem: p(stem + "tau_lw") + (p(stem + "ssa_lw", stem + "g_lw") if stem == "cld_" else (None, None))) \
+            if w == "lw" else \
             (lambda stem: p(stem + "tau_sw", stem + "ssa_sw", stem + "g_sw"))
         mask, bits, randoms, rng = p("mask_" + w, "mask_bits_" + w, "randoms_" + w, "rng_" + w)
         return SimpleNamespace(sfx=w, ngpt=kd["ngpt"], nband=kd["nband"], lims=lims, props=triple(""),
@@ -512,8 +532,9 @@ class ClearSkyStep:
                  + (self._g_lw, self._nd_lw, self._nets_lw, len(self.lw_nets)) + p("tau_lw", "lay_src")),
                 *self._cloud_optics_call(ch),
                 *self._clouds_in(ch),
+                *self._lw_clear_scattering(),
                 # (the clear + all-sky McICA entry takes the mask as an argument)
-                *self._request(ch, mask=not self.clrsky),
+                *self._request(ch, mask=not self.clrsky or self.lw_scattering),
                 *self._jacobian_request(),
                 *self._aerosol_request(ch),
                 self._lw_solver_fused(),
@@ -546,6 +567,23 @@ class ClearSkyStep:
             solver("lw_solver", "lw_up", "lw_dn"),
         ]
 
+    def _lw_planck_args(self, inc, up, dn):
+        """The arguments of a fused-Planck LW entry: `inc` the names of its band increment's arrays."""
+        p = self._p
+        return (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W, None) \
+            + p("tau_lw", *inc, "lay_src") \
+            + (self.nb_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") \
+            + (self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"])) \
+            + p("totplnk") + (1,) + p("sfc_emis", up, dn)
+
+    def _lw_clear_scattering(self):
+        """An lw_scattering step's clear launch (clrsky): the no-scattering fused-Planck entry on the gas optical depth,
+        issued ahead of the cloud-mask request, which belongs to the all-sky launch."""
+        if not (self.lw_scattering and self.clrsky):
+            return []
+        return [("lw_solver_clr", self.L.rrtmgpnn_lw_solver_noscat_planck,
+                 self._lw_planck_args((), "lw_up_clr", "lw_dn_clr"))]
+
     def _lw_solver_fused(self):
         """The fused step's LW solver call: compute_Planck_source_nn fused into the solver (sources formed in-kernel
         from pfrac; the surface emissivity goes in by band, as rte_lw takes it, and is expanded in-kernel).  All-sky,
@@ -553,6 +591,11 @@ class ClearSkyStep:
         from one call of the dual entry (_clr_all), whose McICA twin takes the packed mask as its last argument instead
         of a request."""
         L, p = self.L, self._p
+        if self.lw_scattering:
+            # scattering clouds: the rescaled solver with the two-stream band increment (a McICA step's mask is armed
+            # by request, with or without clear-sky fluxes)
+            return ("lw_solver", L.rrtmgpnn_lw_solver_1rescl_planck_inc,
+                    self._lw_planck_args(("cld_tau_lw", "cld_ssa_lw", "cld_g_lw"), "lw_up", "lw_dn"))
         args = (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W, None) \
             + p("tau_lw") + (p("cld_tau_lw") if self.allsky else p("aer_tau_lw") if self.aerosols else ()) \
             + p("lay_src") \
