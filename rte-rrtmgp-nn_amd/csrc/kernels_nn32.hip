@@ -24,6 +24,7 @@
 //   The output layer computes Y^T (g-points x samples) with the weights as A: lane (j, h) holds g = 32go + 8b + 4h + i
 //   (b, i = 0..3) of sample j, 4 float4 stores per output array and g-tile.
 #include "nn_device.hpp"
+#include "rte_device.hpp"  // CachePolicy
 
 #include <algorithm>
 #include <atomic>
@@ -147,20 +148,37 @@ struct Buf {
   __amdgpu_buffer_rsrc_t r;
   __device__ __forceinline__ Buf(const void *base, uint32_t bytes)
       : r(__builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000)) {}
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ float ld(uint32_t voff) const
   {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, (int)CP));
   }
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ void st(float v, uint32_t voff) const
   {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, (int)CP);
   }
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ void st4(const floatx4 &v, uint32_t voff) const
   {
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), r, voff, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), r, voff, 0, (int)CP);
   }
 };
+
+// Cache policies of the network's output stores (CachePolicy, rte_device.hpp), one per pair; each can be set from the
+// command line (-DRRTMGPNN_CP_NN_LW_ST=2).  The LW pair's tau and pfrac are first read by the LW solver after the whole
+// kernel; the SW pair's tau and ssa by the SW solver's pass 1 at once (a hand-off).  MLP_LW_BOTH is outside the
+// benchmarked configs and keeps the default.  Both stay default (profiles/cache_policy_ab.txt, the networks alone,
+// alternating): the LW pair with kNT stores is 5 % faster at C4 but 2.8 % slower at C3 (one instance serves both), the
+// SW pair 4 % slower at C3.
+#ifndef RRTMGPNN_CP_NN_LW_ST
+#define RRTMGPNN_CP_NN_LW_ST 0
+#endif
+#ifndef RRTMGPNN_CP_NN_SW_ST
+#define RRTMGPNN_CP_NN_SW_ST 0
+#endif
+constexpr CachePolicy kCpNnLwSt = (CachePolicy)RRTMGPNN_CP_NN_LW_ST, kCpNnSwSt = (CachePolicy)RRTMGPNN_CP_NN_SW_ST;
 
 struct Mlp32Args {
   const float *x;        // (nx, nbatch)
@@ -457,8 +475,8 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
           const float vray = pow8(tr) * cdr[r];
           const float tot = vabs + vray, ssa = vray / tot;
           const uint32_t off = vo[r] + 128u * go;
-          o0.st(tot, off);
-          o1.st(ssa, off);
+          o0.st<kCpNnSwSt>(tot, off);
+          o1.st<kCpNnSwSt>(ssa, off);
         }
         // g = 0 only when the caller asked for the array (the fused step and the class layer's NN path pass none):
         // one uniform branch per g-tile instead of a dropped store per element
@@ -475,8 +493,8 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
           const float p = yB[r] + bB;
           const float tau = pow8(t) * cdr[r], pf = p * p;
           const uint32_t off = vo[r] + 128u * go;
-          o0.st(tau, off);
-          o1.st(pf, off);
+          o0.st<kCpNnLwSt>(tau, off);
+          o1.st<kCpNnLwSt>(pf, off);
         }
       } else {  // MLP_LW_BOTH: outputs [0, ngpt) -> tau, [ngpt, 2 ngpt) -> pfrac (mo_gas_optics_kernels.F90:754-766);
                 // ngpt % 32 == 0, so a g-tile is all tau or all pfrac

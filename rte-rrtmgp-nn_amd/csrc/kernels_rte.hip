@@ -94,6 +94,30 @@ int launch_planck_source(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, in
 #define SW_BOUNDS __launch_bounds__(256, 8)
 static constexpr int kRing = 8, kRingSw = 6;
 static constexpr int kLwPf = 4, kLwfPf = 2, kSwPf = 2;
+// Cache policies (CachePolicy, rte_device.hpp) of lw_noscat_kernel's tau and layer-source (pfrac when fused) loads: the
+// down pass' lines are read again by the same block's up pass in reverse order, the one-angle up pass' lines by nobody.
+// One pair for the fused clear-sky instance (C3, C5), one for every other instance (C4's all-sky ones among them);
+// with several angles both passes run once per angle and keep the default.  Each can be set from the command line
+// (-DRRTMGPNN_CP_LW_UP=2).  Alone, alternating (profiles/cache_policy_ab.txt): the up pass with kNT is 1.5 % faster in
+// the all-sky instance at C4 and 3.8 % in the fused clear-sky instance at the C5 shard, but 18 % slower in that same
+// instance at C3 (presumably because there tau and pfrac, 221 MB, fit the 256 MiB Infinity Cache and kNT gives that
+// up); the down pass with kNT loses everywhere (C3 +18 %, C4 +6 %).  All four stay default: the fused clear-sky
+// instance serves C3 and C5, and the other instances run at small grids too, where nothing says they would fare better.
+#ifndef RRTMGPNN_CP_LW_DN
+#define RRTMGPNN_CP_LW_DN 0
+#endif
+#ifndef RRTMGPNN_CP_LW_UP
+#define RRTMGPNN_CP_LW_UP 0
+#endif
+#ifndef RRTMGPNN_CP_LW_DN_OTHER
+#define RRTMGPNN_CP_LW_DN_OTHER 0
+#endif
+#ifndef RRTMGPNN_CP_LW_UP_OTHER
+#define RRTMGPNN_CP_LW_UP_OTHER 0
+#endif
+static constexpr CachePolicy kCpLwDn = (CachePolicy)RRTMGPNN_CP_LW_DN, kCpLwUp = (CachePolicy)RRTMGPNN_CP_LW_UP;
+static constexpr CachePolicy kCpLwDnOther = (CachePolicy)RRTMGPNN_CP_LW_DN_OTHER,
+                             kCpLwUpOther = (CachePolicy)RRTMGPNN_CP_LW_UP_OTHER;
 // ring_flush_lanes walks slot s's 4 partials with lanes 4s .. 4s+3: a flush of kRing slots needs 4 * kRing lanes, and
 // the smallest LW block (ngpt <= 64) has 64
 static_assert(4 * kRing <= 64, "the LW ring's lane-per-partial flush needs 4 lanes per slot within one wave");
@@ -203,6 +227,9 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   // one slot that would be the layer's own pfrac
   static_assert(!kFused || kPF >= 2, "the fused down pass needs at least two prefetch slots");
   static_assert(!kDual || (kFused && kInc && !kMulti && !kBand), "the dual instance is the one-angle fused-Planck path");
+  constexpr bool kCpFam = kFused && !kInc;  // the fused clear-sky instance's policies, or the others'
+  constexpr CachePolicy kCpDn = kMulti ? CachePolicy::kDefault : (kCpFam ? kCpLwDn : kCpLwDnOther);
+  constexpr CachePolicy kCpUp = kMulti ? CachePolicy::kDefault : (kCpFam ? kCpLwUp : kCpLwUpOther);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
   const bool on = g < ngpt;
@@ -274,8 +301,8 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
 #pragma unroll
   for (int p = 0; p < kPF; p++) {
     const int l = lay_dn(min(p, nlay - 1));
-    pt0[p] = kEarly ? Ttau.ld(vg, row * l) : 0.0f;
-    py0[p] = kEarly ? Tlay.ld(vg, row * l) : 0.0f;
+    pt0[p] = kEarly ? Ttau.ld<kCpDn>(vg, row * l) : 0.0f;
+    py0[p] = kEarly ? Tlay.ld<kCpDn>(vg, row * l) : 0.0f;
     pi0[p] = 0.0f;
     pv0[p] = (kEarly && !kFused) ? lev_ld(l + 1) : 0.0f;
   }
@@ -433,7 +460,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
 #pragma unroll
         for (int p = 0; p < kPF; p++) {
           const int l = lay_dn(min(p, nlay - 1));
-          pt[p] = Ttau.ld(vg, row * l); py[p] = Tlay.ld(vg, row * l); pi[p] = ld_inc(l);
+          pt[p] = Ttau.ld<kCpDn>(vg, row * l); py[p] = Tlay.ld<kCpDn>(vg, row * l); pi[p] = ld_inc(l);
           if constexpr (!kFused) pv[p] = lev_ld(l + 1);
           if constexpr (kMask) pm[p] = ld_msk(l);
           if constexpr (kAer) pa[p] = ld_aer(l);
@@ -456,7 +483,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         py_prev = y_own;
         {
           const int ln = lay_dn(min(j + kPF, nlay - 1));
-          pt[p] = Ttau.ld(vg, row * ln); py[p] = Tlay.ld(vg, row * ln);
+          pt[p] = Ttau.ld<kCpDn>(vg, row * ln); py[p] = Tlay.ld<kCpDn>(vg, row * ln);
           if constexpr (!kFused) pv[p] = lev_ld(ln + 1);
           pi[p] = ld_inc(ln);
           if constexpr (kMask) pm[p] = ld_msk(ln);
@@ -493,7 +520,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
 #pragma unroll
       for (int p = 0; p < kPF; p++) {
         const int l = lay_up(min(p, nlay - 1));
-        ptu[p] = Ttau.ld(vg, row * l); pyu[p] = Tlay.ld(vg, row * l); piu[p] = ld_inc(l);
+        ptu[p] = Ttau.ld<kCpUp>(vg, row * l); pyu[p] = Tlay.ld<kCpUp>(vg, row * l); piu[p] = ld_inc(l);
         if constexpr (kMask) pmu[p] = ld_msk(l);
         if constexpr (kAer) pau[p] = ld_aer(l);
         pvu[p] = kFused ? 0.0f : Tlev.ld(vg, row * l);
@@ -531,7 +558,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
           if constexpr (kAer) pa[p] = pau[p];
         } else {
           const int l = lay_up(min(p, nlay - 1));
-          pt[p] = Ttau.ld(vg, row * l); py[p] = Tlay.ld(vg, row * l); pi[p] = ld_inc(l);
+          pt[p] = Ttau.ld<kCpUp>(vg, row * l); py[p] = Tlay.ld<kCpUp>(vg, row * l); pi[p] = ld_inc(l);
           if constexpr (!kFused) pv[p] = Tlev.ld(vg, row * l);
           if constexpr (kMask) pm[p] = ld_msk(l);
           if constexpr (kAer) pa[p] = ld_aer(l);
@@ -546,7 +573,7 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
         const float tc = kDual ? ta * D : 0.0f;
         {
           const int ln = lay_up(min(j + kPF, nlay - 1));
-          pt[p] = Ttau.ld(vg, row * ln); py[p] = Tlay.ld(vg, row * ln); pi[p] = ld_inc(ln);
+          pt[p] = Ttau.ld<kCpUp>(vg, row * ln); py[p] = Tlay.ld<kCpUp>(vg, row * ln); pi[p] = ld_inc(ln);
           if constexpr (!kFused) pv[p] = Tlev.ld(vg, row * ln);
           if constexpr (kMask) pm[p] = ld_msk(ln);
           if constexpr (kAer) pa[p] = ld_aer(ln);

@@ -173,6 +173,80 @@ constexpr int kCkP1Small = 2;
 // flight (tools/bw_width.hip), i.e. a chunk's loads are not always back when its body starts
 constexpr int kCkAheadSmall = 1;
 
+// Cache policies (CachePolicy, rte_device.hpp) of the kernel's global streams, one set per instance family: the
+// small-grid clear-sky instance (C3), the large clear-sky NN instance (C5: _NN) and the all-sky instances (C4: _INC);
+// every other instance keeps the default.  Each can be set from the command line (-DRRTMGPNN_CP_SW_P3_LD=2).
+//   p1_ld   : pass 1's tau loads (pass 2 reads them again: a control);
+//   p1_st   : pass 1's transmittance plane and beam checkpoints (read by pass 2: a control);
+//   p2_last : pass 2's last-use loads: the beam checkpoint, and tau where pass 3 reads exp(-k tau) from its plane
+//             instead (kEmk; without that plane tau stays default in pass 2 whatever this says);
+//   p2_st   : pass 2's exp(-k tau) plane and albedo / source checkpoints (read by pass 3: a control);
+//   p3_ld   : all of pass 3's loads (ssa, g, both planes, the checkpoints, and tau without the exp(-k tau) plane).
+// Shipped in all three families: p2_last and p3_ld (kNT).  Alone, alternating (profiles/cache_policy_ab.txt): p3_ld C3
+// -1.3 %, C4 -1.8 %; p2_last within the spread by itself; both C3 -1.6 %, C4 -1.9 %, C5 shard -2.5 %.  Whole steps with
+// both (profiles/cache_policy_bench_ab.txt): C3 -2.2 %, C4 -1.45 %, C5 shard -1.25 %; without p2_last C3 -1.6 %, C5
+// -0.8 %.  The controls stay default: p1_ld +2.5 % alone at C3 (+0.3 % C4), p1_st +3.3 % (+0.6 %), p2_st equal.
+struct SwCkCp {
+  CachePolicy p1_ld, p1_st, p2_last, p2_st, p3_ld;
+};
+#define RRTMGPNN_CP_(x) ((CachePolicy)(x))
+#ifndef RRTMGPNN_CP_SW_P1_LD
+#define RRTMGPNN_CP_SW_P1_LD 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P1_ST
+#define RRTMGPNN_CP_SW_P1_ST 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P2_LAST
+#define RRTMGPNN_CP_SW_P2_LAST 2
+#endif
+#ifndef RRTMGPNN_CP_SW_P2_ST
+#define RRTMGPNN_CP_SW_P2_ST 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P3_LD
+#define RRTMGPNN_CP_SW_P3_LD 2
+#endif
+#ifndef RRTMGPNN_CP_SW_P1_LD_NN
+#define RRTMGPNN_CP_SW_P1_LD_NN 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P1_ST_NN
+#define RRTMGPNN_CP_SW_P1_ST_NN 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P2_LAST_NN
+#define RRTMGPNN_CP_SW_P2_LAST_NN 2
+#endif
+#ifndef RRTMGPNN_CP_SW_P2_ST_NN
+#define RRTMGPNN_CP_SW_P2_ST_NN 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P3_LD_NN
+#define RRTMGPNN_CP_SW_P3_LD_NN 2
+#endif
+#ifndef RRTMGPNN_CP_SW_P1_LD_INC
+#define RRTMGPNN_CP_SW_P1_LD_INC 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P1_ST_INC
+#define RRTMGPNN_CP_SW_P1_ST_INC 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P2_LAST_INC
+#define RRTMGPNN_CP_SW_P2_LAST_INC 2
+#endif
+#ifndef RRTMGPNN_CP_SW_P2_ST_INC
+#define RRTMGPNN_CP_SW_P2_ST_INC 0
+#endif
+#ifndef RRTMGPNN_CP_SW_P3_LD_INC
+#define RRTMGPNN_CP_SW_P3_LD_INC 2
+#endif
+constexpr SwCkCp kCpSwSmall = {RRTMGPNN_CP_(RRTMGPNN_CP_SW_P1_LD), RRTMGPNN_CP_(RRTMGPNN_CP_SW_P1_ST),
+                               RRTMGPNN_CP_(RRTMGPNN_CP_SW_P2_LAST), RRTMGPNN_CP_(RRTMGPNN_CP_SW_P2_ST),
+                               RRTMGPNN_CP_(RRTMGPNN_CP_SW_P3_LD)};
+constexpr SwCkCp kCpSwNN = {RRTMGPNN_CP_(RRTMGPNN_CP_SW_P1_LD_NN), RRTMGPNN_CP_(RRTMGPNN_CP_SW_P1_ST_NN),
+                            RRTMGPNN_CP_(RRTMGPNN_CP_SW_P2_LAST_NN), RRTMGPNN_CP_(RRTMGPNN_CP_SW_P2_ST_NN),
+                            RRTMGPNN_CP_(RRTMGPNN_CP_SW_P3_LD_NN)};
+constexpr SwCkCp kCpSwInc = {RRTMGPNN_CP_(RRTMGPNN_CP_SW_P1_LD_INC), RRTMGPNN_CP_(RRTMGPNN_CP_SW_P1_ST_INC),
+                             RRTMGPNN_CP_(RRTMGPNN_CP_SW_P2_LAST_INC), RRTMGPNN_CP_(RRTMGPNN_CP_SW_P2_ST_INC),
+                             RRTMGPNN_CP_(RRTMGPNN_CP_SW_P3_LD_INC)};
+constexpr SwCkCp kCpSwOther = {};
+#undef RRTMGPNN_CP_
+
 // V: f2 (two g-points per lane) or float (one per lane).  kBandPair (fused increment, two g-points per lane): every
 // band starts at an even g-point, so both g-points of a lane lie in one band and its band values are one load each
 // (the RRTMGP g-point sets: 16 per band).  Round 4, C4: SW solver -1.7 % alone, steps -0.8 % (3 alternating pairs)
@@ -237,6 +311,8 @@ __global__ void __launch_bounds__(512, WAVES)
     for (int i = threadIdx.x; i < ngpt; i += blockDim.x) bsrc[i] = bc.solar_source[i];
   // small-grid instance: the barrier comes after pass 1's first loads (kEarly below)
   constexpr bool kEarly = !kInc && WAVES == kCkWavesSmall;
+  // the instance family's cache policies: small-grid clear sky, all sky, large-grid clear-sky NN, or none
+  constexpr SwCkCp kCp = kEarly ? kCpSwSmall : (kInc ? kCpSwInc : ((kG0 && !kGpt) ? kCpSwNN : kCpSwOther));
   if constexpr (!kEarly) __syncthreads();
   const int dl_dn = top_at_1 ? 1 : -1;
   const uint32_t row = 4u * (uint32_t)ngpt;
@@ -317,7 +393,7 @@ __global__ void __launch_bounds__(512, WAVES)
 #pragma unroll
     for (int p = 0; p < P1; p++) {
       const int l = lay(c1 * P1 + p);
-      b.t[p] = Ttau.ldv(vL, row * (uint32_t)l);
+      b.t[p] = Ttau.template ldv<kCp.p1_ld>(vL, row * (uint32_t)l);
       if constexpr (kAer) b.t[p] += ld_bnd(At, l);
       if constexpr (kMask) b.t[p] += sel(ld_bnd(Bt, l), ld_msk(l));
       else if constexpr (kInc) b.t[p] += ld_bnd(Bt, l);
@@ -354,17 +430,21 @@ __global__ void __launch_bounds__(512, WAVES)
     uint32_t qm[kMask ? K : 1];
     V at[kAer ? K : 1], aw[kAer ? K : 1], ag[kAer ? K : 1];
   };
-  // pass: 2 or 3
-  auto load_chunk = [&](Chunk &ch, int ck, int pass) {
+  // pass: 2 or 3 (a constant: it selects the streams' cache policies).  Pass 3's loads are all last uses; pass 2's are
+  // the beam checkpoint's and, when pass 3 reads exp(-k tau) from its plane and so no tau, tau's
+  auto load_chunk = [&](Chunk &ch, int ck, auto pass_c) {
+    constexpr int pass = decltype(pass_c)::value;
+    constexpr CachePolicy cpT = pass == 3 ? kCp.p3_ld : (kEmk ? kCp.p2_last : CachePolicy::kDefault);
+    constexpr CachePolicy cp3 = pass == 3 ? kCp.p3_ld : CachePolicy::kDefault;
 #pragma unroll
     for (int p = 0; p < K; p++) {
       const int l = lay(ck * K + p);
       const uint32_t s = row * (uint32_t)l;
-      ch.t[p] = Ttau.ldv(vL, s);
-      ch.tn[p] = kTn ? CT.ldv(vL, s) : (V)0.0f;
-      ch.em[p] = (kEmk && pass == 3) ? CE.ldv(vL, s) : (V)0.0f;
-      ch.w[p] = Tssa.ldv(vL, s);
-      ch.g[p] = kHasG ? Tg.ldv(vL, s) : (V)0.0f;
+      ch.t[p] = Ttau.template ldv<cpT>(vL, s);
+      ch.tn[p] = kTn ? CT.template ldv<cp3>(vL, s) : (V)0.0f;
+      ch.em[p] = (kEmk && pass == 3) ? CE.template ldv<cp3>(vL, s) : (V)0.0f;
+      ch.w[p] = Tssa.template ldv<cp3>(vL, s);
+      ch.g[p] = kHasG ? Tg.template ldv<cp3>(vL, s) : (V)0.0f;
       if constexpr (kInc) {
         ch.qt[p] = ld_bnd(Bt, l);
         ch.qw[p] = ld_bnd(Bw, l);
@@ -379,12 +459,12 @@ __global__ void __launch_bounds__(512, WAVES)
         ch.qt[p] = ch.qw[p] = ch.qg[p] = (V)0.0f;
       }
     }
-    if (pass == 2) {
-      ch.fb = CW.ldv(vW, row * (uint32_t)ck);
+    if constexpr (pass == 2) {
+      ch.fb = CW.template ldv<kCp.p2_last>(vW, row * (uint32_t)ck);
     } else {
       const uint32_t sE = row * (uint32_t)min(ck + 1, nck);
-      ch.ae = CW.ldv(vW, sA0 + sE);
-      ch.se = CW.ldv(vW, sS0 + sE);
+      ch.ae = CW.template ldv<cp3>(vW, sA0 + sE);
+      ch.se = CW.template ldv<cp3>(vW, sS0 + sE);
     }
   };
   // the (incremented) properties of layer p of a chunk
@@ -438,11 +518,12 @@ __global__ void __launch_bounds__(512, WAVES)
       exp_beam_batch(arg, Tn, etab);
       if constexpr (kTn) {
 #pragma unroll
-        for (int p = 0; p < P1; p++) CT.stv(Tn[p], (on && p < n) ? vL : kBufOOB, row * (uint32_t)lay(c1 * P1 + p));
+        for (int p = 0; p < P1; p++)
+          CT.template stv<kCp.p1_st>(Tn[p], (on && p < n) ? vL : kBufOOB, row * (uint32_t)lay(c1 * P1 + p));
       }
 #pragma unroll
       for (int p = 0; p < P1; p++) {
-        if (p % K == 0) CW.stv(Fd, (p < n) ? vWs : kBufOOB, row * (uint32_t)(c1 * P1C + p / K));
+        if (p % K == 0) CW.template stv<kCp.p1_st>(Fd, (p < n) ? vWs : kBufOOB, row * (uint32_t)(c1 * P1C + p / K));
         Fd = (p < n) ? Tn[p] * Fd : Fd;
       }
     };
@@ -451,11 +532,11 @@ __global__ void __launch_bounds__(512, WAVES)
   // ---- pass 2: bottom -> top adding; albedo / source checkpoint at every chunk top and at the surface ----
   V alb_b = bcf ? alb_bc : ld_col(alb_dif);
   V src_b = Fd * (bcf ? alb_bc : ld_col(alb_dir));
-  CW.stv(alb_b, vWs, sA0 + row * (uint32_t)nck);
-  CW.stv(src_b, vWs, sS0 + row * (uint32_t)nck);
+  CW.template stv<kCp.p2_st>(alb_b, vWs, sA0 + row * (uint32_t)nck);
+  CW.template stv<kCp.p2_st>(src_b, vWs, sS0 + row * (uint32_t)nck);
   {
     Chunk A, B;
-    auto load2 = [&](Chunk &ch, int ck) { load_chunk(ch, ck, 2); };
+    auto load2 = [&](Chunk &ch, int ck) { load_chunk(ch, ck, std::integral_constant<int, 2>{}); };
     auto body2 = [&](Chunk &cur, int ck, bool valid) {
       const int n = valid ? min(K, nlay - ck * K) : 0;
       V t[K], w[K], g0[K], Tn[K], Fin[K];
@@ -483,7 +564,8 @@ __global__ void __launch_bounds__(512, WAVES)
       ck_two_stream_k<kG0, K, V, kEmk ? 1 : 0>(t, w, g0, mu0, Tn, Fin, cf, etab, em);
       if constexpr (kEmk) {
 #pragma unroll
-        for (int p = 0; p < K; p++) CE.stv(em[p], (on && p < n) ? vL : kBufOOB, row * (uint32_t)lay(ck * K + p));
+        for (int p = 0; p < K; p++)
+          CE.template stv<kCp.p2_st>(em[p], (on && p < n) ? vL : kBufOOB, row * (uint32_t)lay(ck * K + p));
       }
 #pragma unroll
       for (int p = K - 1; p >= 0; p--) {
@@ -493,8 +575,8 @@ __global__ void __launch_bounds__(512, WAVES)
         alb_b = (p < n) ? alb : alb_b;
         src_b = (p < n) ? src : src_b;
       }
-      CW.stv(alb_b, valid && ck > 0 ? vWs : kBufOOB, sA0 + row * (uint32_t)ck);
-      CW.stv(src_b, valid && ck > 0 ? vWs : kBufOOB, sS0 + row * (uint32_t)ck);
+      CW.template stv<kCp.p2_st>(alb_b, valid && ck > 0 ? vWs : kBufOOB, sA0 + row * (uint32_t)ck);
+      CW.template stv<kCp.p2_st>(src_b, valid && ck > 0 ? vWs : kBufOOB, sS0 + row * (uint32_t)ck);
     };
     if constexpr (AHEAD == 2) {
       Chunk C;
@@ -544,7 +626,7 @@ __global__ void __launch_bounds__(512, WAVES)
   {
     Chunk A, B;
     V Fd3 = Ftop;
-    auto load3 = [&](Chunk &ch, int ck) { load_chunk(ch, ck, 3); };
+    auto load3 = [&](Chunk &ch, int ck) { load_chunk(ch, ck, std::integral_constant<int, 3>{}); };
     auto body3 = [&](Chunk &cur, int ck, bool valid) {
       const int n = valid ? min(K, nlay - ck * K) : 0;
       // the chunk's coefficients, top down, the beam carried as pass 1 carries it

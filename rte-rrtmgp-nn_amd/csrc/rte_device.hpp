@@ -392,17 +392,27 @@ inline int columns_per_block(int lanes)
 // can issue the same stores as the others without a branch.
 static constexpr uint32_t kBufOOB = 0x7ffff000u;
 
+// The cache policy of one global stream: the raw buffer builtins' last (immediate) argument, so a template argument of
+// every load and store helper.  kNT marks lines that nothing reads again (the `nt` modifier on gfx950); the scope bits
+// (sc0 = 1, sc1 = 16) change coherence and stay 0 everywhere.  The out-of-range offsets above do not depend on it.
+// Which stream carries which policy: the kCp* constants beside each kernel's tuning constants (DESIGN.md section 3,
+// "Cache policies per stream").
+enum class CachePolicy : int { kDefault = 0, kNT = 2 };
+
 struct ColArr {
   __amdgpu_buffer_rsrc_t r;
   __device__ __forceinline__ ColArr() = default;
   __device__ __forceinline__ ColArr(const float *base, size_t col_off, uint32_t bytes)
-      : r(__builtin_amdgcn_make_buffer_rsrc((void *)(base + col_off), 0, (int)bytes, 0x00020000)) {}  __device__ __forceinline__ float ld(uint32_t voff, uint32_t soff) const
+      : r(__builtin_amdgcn_make_buffer_rsrc((void *)(base + col_off), 0, (int)bytes, 0x00020000)) {}
+  template <CachePolicy CP = CachePolicy::kDefault>
+  __device__ __forceinline__ float ld(uint32_t voff, uint32_t soff) const
   {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, (int)CP));
   }
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ void st(float v, uint32_t voff, uint32_t soff) const
   {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, (int)CP);
   }
 };
 

@@ -101,18 +101,21 @@ struct ColArr2 {
   __amdgpu_buffer_rsrc_t r;
   __device__ __forceinline__ ColArr2(const float *base, size_t col_off, uint32_t bytes)
       : r(__builtin_amdgcn_make_buffer_rsrc((void *)(base + col_off), 0, (int)bytes, 0x00020000)) {}
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ f2 ld(uint32_t voff, uint32_t soff) const
   {
-    return __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+    return __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, (int)CP));
   }
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ float ld1(uint32_t voff, uint32_t soff) const
   {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, (int)CP));
   }
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ void st(f2 v, uint32_t voff, uint32_t soff) const
   {
     typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, voff, soff, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, voff, soff, (int)CP);
   }
 };
 
@@ -120,15 +123,17 @@ struct ColArr2 {
 template <class V>
 struct ColArrV : ColArr2 {
   __device__ __forceinline__ ColArrV(const float *base, size_t col_off, uint32_t bytes) : ColArr2(base, col_off, bytes) {}
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ V ldv(uint32_t voff, uint32_t soff) const
   {
-    if constexpr (sizeof(V) == 8) return ld(voff, soff);
-    else return ld1(voff, soff);
+    if constexpr (sizeof(V) == 8) return ld<CP>(voff, soff);
+    else return ld1<CP>(voff, soff);
   }
+  template <CachePolicy CP = CachePolicy::kDefault>
   __device__ __forceinline__ void stv(V v, uint32_t voff, uint32_t soff) const
   {
-    if constexpr (sizeof(V) == 8) st(v, voff, soff);
-    else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
+    if constexpr (sizeof(V) == 8) st<CP>(v, voff, soff);
+    else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, (int)CP);
   }
 };
 
