@@ -67,6 +67,22 @@ int rrtmgpnn_context_set_sw_kernel(rrtmgpnn_context *ctx, int mode);
  * masked twins: 0 is mode 1 there too, measured 21 % faster than mode 2 at 10 000 x 60 columns.
  * ctx == NULL sets the default of every context not set itself. */
 int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode);
+/* MI355X tuning, no reference counterpart: how rrtmgpnn_sw_solver_2stream_clr_all and
+ * rrtmgpnn_sw_solver_2stream_rfmip_clr_all produce their two flux sets.
+ * 0 (default): mode 2 -- at 10 000 x 60 columns the dual kernel's gain over the two launches (1.3-1.8 % in four runs)
+ * did not exceed their sample spread in the run that decided it; mode 1 is 12 % faster there with a mask and aerosols
+ * armed and 6.5 % faster at 1800 x 60.
+ * 1: the dual kernel, one launch of the checkpointed solver in which a lane owns one g-point and carries
+ * its all-sky and its clear-sky solve side by side (tau, ssa, g, the band rows and the mask word read once for both).
+ * 2: two launches of the single-sky instances inside the entry, the
+ * all-sky one with the armed requests, the clear one on the gases alone or with the requested aerosol as its band
+ * increment; also what runs when the checkpointed kernel is not the context's SW kernel (rrtmgpnn_context_set_sw_kernel
+ * mode 1 or 2).  Bit-identical fluxes wherever both modes take the call.  The two launches accept less: with an
+ * aerosol request they need every band to start at an odd 1-based g-point (the single-sky aerosol instances' band-pair
+ * layout; RRTMGPNN_ERR_UNSUPPORTED otherwise, where the dual kernel has no such restriction), and under SW kernel mode
+ * 1 or 2 a cloud-mask or aerosol request is refused as rrtmgpnn_sw_solver_2stream_inc refuses it.  ctx == NULL sets the
+ * default of every context not set itself. */
+int rrtmgpnn_context_set_sw_clr_all(rrtmgpnn_context *ctx, int mode);
 /* MI355X tuning, no reference counterpart: the MFMA tiling of the gas-optics networks (rrtmgpnn_predict_nn_lw/_sw,
  * rrtmgpnn_gas_optics_lw_nn/_sw_nn).  0 (default): v_mfma_f32_32x32x2_f32 tiles where an instance exists for the
  * networks (the shipped LW g256 pair, LW g128 single model and SW g224 pair, softsign/softsign/linear, ngpt a
@@ -438,6 +454,22 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, const float *mu0,
                                    const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
                                    float *flux_dn, float *flux_dir);
+/* Clear-sky beside all-sky SW fluxes of the same columns: rte_sw on the gases (and aerosols), then on the atmosphere
+ * incremented by the clouds, as rte_sw of extensions/mo_rrtmgp_clr_all_sky.F90:283-304 calls it twice.  The arguments
+ * of rrtmgpnn_sw_solver_2stream_inc in its order, then the clear-sky outputs flux_*_clr (nlay+1, ncol).  flux_up / dn /
+ * dir: bit for bit rrtmgpnn_sw_solver_2stream_inc's with the same requests; flux_*_clr: bit for bit
+ * rrtmgpnn_sw_solver_2stream's on (tau, ssa, g).  Requests (below): a cloud mask (rrtmgpnn_solver_request_cloud_mask)
+ * switches the cloud in the all-sky set only; a 2str aerosol (rrtmgpnn_solver_request_aerosol) goes into both sets,
+ * the reference's clear sky being gases plus aerosols (:288-299) -- flux_*_clr are then rrtmgpnn_sw_solver_2stream_inc's
+ * with the aerosol as its increment.  Refused: a by-band or Jacobian request, a 1scl aerosol, nbnd == 0, ngpt odd or
+ * over 256.  rrtmgpnn_context_set_sw_clr_all selects one launch or two. */
+int rrtmgpnn_sw_solver_2stream_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                       const float *inc_flux, const float *inc_flux_dif, const float *tau,
+                                       const float *ssa, const float *g, int nbnd, const int *band_lims_gpt,
+                                       const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, const float *mu0,
+                                       const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
+                                       float *flux_dn, float *flux_dir, float *flux_up_clr, float *flux_dn_clr,
+                                       float *flux_dir_clr);
 /* ---- by-band fluxes: ty_fluxes_byband (extensions/mo_fluxes_byband.F90:31-131) ------------------
  * rrtmgpnn_solver_request_byband arms by-band outputs for the NEXT solver call on this context (any of the
  * rrtmgpnn_lw_solver_* / rrtmgpnn_sw_solver_* entries); that call clears the request whether it succeeds or fails.
@@ -540,6 +572,18 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      const int *band_lims_gpt, const float *tau_bnd, const float *ssa_bnd,
                                      const float *g_bnd, float *toa_flux, float *sfc_alb_gpt, float *mu0,
                                      float *flux_up, float *flux_dn, float *flux_dir);
+/* rrtmgpnn_sw_solver_2stream_rfmip's arguments (nbnd > 0 required), then the clear-sky outputs: the driver's boundary
+ * conditions (rrtmgp_rfmip_sw.F90:403-441) formed once, in the dual kernel's prologue, for both skies of
+ * rrtmgpnn_sw_solver_2stream_clr_all (extensions/mo_rrtmgp_clr_all_sky.F90:283-304).  Same requests, refusals and bits
+ * as there: rrtmgpnn_sw_boundary_rfmip followed by rrtmgpnn_sw_solver_2stream_clr_all. */
+int rrtmgpnn_sw_solver_2stream_rfmip_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                             const float *solar_source, const float *tsi, const float *sfc_alb,
+                                             const float *sza, const float *tau, const float *ssa, const float *g,
+                                             int nbnd, const int *band_lims_gpt, const float *tau_bnd,
+                                             const float *ssa_bnd, const float *g_bnd, float *toa_flux,
+                                             float *sfc_alb_gpt, float *mu0, float *flux_up, float *flux_dn,
+                                             float *flux_dir, float *flux_up_clr, float *flux_dn_clr,
+                                             float *flux_dir_clr);
 /* ---- McICA cloud sampling: extensions/cloud_optics/mo_cloud_sampling.F90 ---------------------------
  * The extension predates this fork's layout (as mo_heating_rates does).  Here, first index fastest, DEVICE arrays:
  *   randoms (ngpt, nlay, ncol), read only where cloud_frac > 0, as in the reference (:17-18);
@@ -612,8 +656,9 @@ int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, i
  * rrtmgpnn_increment (same resolution; inc_2stream_by_2stream with a zero increment still rounds
  * tau * ssa / max(eps, tau), and so does this) + the solver, without the g-point cloud arrays.  Honoured by
  * rrtmgpnn_lw_solver_noscat_planck_inc and rrtmgpnn_lw_solver_1rescl_planck_inc (every nmus; the latter switches
- * tau_bnd, ssa_bnd and g_bnd), rrtmgpnn_sw_solver_2stream_inc and
- * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, the SW ones on the checkpointed kernel (the default of
+ * tau_bnd, ssa_bnd and g_bnd), rrtmgpnn_sw_solver_2stream_inc,
+ * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0 and rrtmgpnn_sw_solver_2stream_clr_all / _rfmip_clr_all (the all-sky
+ * set only), the SW ones on the checkpointed kernel (the default of
  * rrtmgpnn_context_set_sw_kernel: even ngpt; other modes, and odd ngpt, RRTMGPNN_ERR_UNSUPPORTED).  Extents other than
  * the call's: RRTMGPNN_ERR_ARGUMENT; every other solver entry (the plain ones, _clr_all, _clr_all_mcica, which takes
  * its mask as an argument, the _gpt entries, the other scattering LW entries, _rfmip with nbnd == 0): RRTMGPNN_ERR_ARGUMENT;
@@ -683,8 +728,9 @@ int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, 
  * and by rrtmgpnn_lw_solver_noscat_planck_clr_all and _clr_all_mcica, whose clear-sky outputs are then the fluxes of
  * tau + tau_aer(band) (gases plus aerosols, as the reference defines clear sky) and whose all-sky outputs those of
  * (tau + tau_aer(band)) + [bit ?] tau_bnd(band); with two launches (mode 2, or nmus > 1) the clear launch is the _planck_inc
- * instance with the aerosol as its increment.  Honoured, for a 2str aerosol, by rrtmgpnn_sw_solver_2stream_inc and
- * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0, on the checkpointed kernel (even ngpt, rrtmgpnn_context_set_sw_kernel
+ * instance with the aerosol as its increment.  Honoured, for a 2str aerosol, by rrtmgpnn_sw_solver_2stream_inc,
+ * rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0 and rrtmgpnn_sw_solver_2stream_clr_all / _rfmip_clr_all (both flux
+ * sets; the dual kernel, mode 1 of rrtmgpnn_context_set_sw_clr_all, takes any band layout), on the checkpointed kernel (even ngpt, rrtmgpnn_context_set_sw_kernel
  * mode 0 or 3) with every band starting at an odd 1-based g-point, with or without a cloud-mask request; the
  * transmittance plane of the all-sky instances is used when its workspace fits, the same bits without it.
  * Clear sky with aerosols and no clouds needs no request and no kernel of its own: it is the existing

@@ -19,6 +19,7 @@ static thread_local std::string g_last_error;
 int g_sw_kernel_default = 0;
 int g_mlp_kernel_default = 0;
 int g_lw_clr_all_default = 0;
+int g_sw_clr_all_default = 0;
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -146,7 +147,7 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
 
 // the entries without masked instances refuse an armed cloud mask
 static const char kNoMaskMsg[] = "solver_request_cloud_mask: this solver entry takes no cloud mask (the _planck_inc, "
-                                 "_2stream_inc and _2stream_rfmip entries do)";
+                                 "_2stream_inc, _2stream_rfmip, _2stream_clr_all and _2stream_rfmip_clr_all entries do)";
 // What an entry does with an armed Jacobian request (rrtmgpnn_solver_request_jacobian): the LW entries that read source
 // arrays need its sfc_source_Jac, the fused-Planck ones form it in-kernel and take none, every other entry refuses
 // (`refusal`, or a message naming the entry).  The extents are the call's; by-band outputs do not go with it.
@@ -184,8 +185,9 @@ static int take_aerosol(const char *entry, const Requests &rq, AerMode mode, int
   const std::string e(entry);
   if (mode == kAerRefuse)
     return fail(RRTMGPNN_ERR_ARGUMENT, e + ": this solver entry takes no aerosol request (the lw_solver_noscat_planck_inc, "
-                                           "_planck_clr_all, _planck_clr_all_mcica, sw_solver_2stream_inc and "
-                                           "sw_solver_2stream_rfmip entries do)");
+                                           "_planck_clr_all, _planck_clr_all_mcica, sw_solver_2stream_inc, "
+                                           "sw_solver_2stream_rfmip, sw_solver_2stream_clr_all and "
+                                           "sw_solver_2stream_rfmip_clr_all entries do)");
   if (rq.byband) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an aerosol increment together with by-band outputs");
   if (rq.jac.armed) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an aerosol increment together with the flux Jacobian");
   if (mode == kAerLw && (rq.aer.ssa || rq.aer.g))
@@ -470,6 +472,18 @@ int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode)
   }
   if (int rc = check_ctx(ctx)) return rc;
   ctx->lw_clr_all = mode;
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_context_set_sw_clr_all(rrtmgpnn_context *ctx, int mode)
+{
+  if (mode < 0 || mode > 2) return fail(RRTMGPNN_ERR_ARGUMENT, "sw clr_all mode must be 0, 1 or 2");
+  if (!ctx) {
+    rrtmgpnn::g_sw_clr_all_default = mode;
+    return RRTMGPNN_OK;
+  }
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->sw_clr_all = mode;
   return RRTMGPNN_OK;
 }
 
@@ -1179,6 +1193,97 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
   return launch_sw_2stream(ctx, ex, p);
 }
 
+// mode 0 of rrtmgpnn_context_set_sw_clr_all: what the measurement of DESIGN.md section 3 chose (1 the dual kernel, 2 two
+// launches)
+static const int kSwClrAllDefaultMode = 2;
+
+// The two sw_solver_2stream_clr_all entries behind their argument checks: the requests (mask, 2str aerosol; by-band and
+// Jacobian refused), then the dual instance of the checkpointed kernel, or the two launches whose bits it has -- the
+// all-sky one with the requests, the clear one on the gases alone or with the aerosol as its band increment
+static int sw_clr_all_shape(const char *entry, int ngpt, int nbnd);
+
+// (the requests are taken first and cleared whatever follows; the entry's own shape refusals come before what it makes
+// of the requests, so that an armed request of other extents does not hide them)
+static int sw_clr_all_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int nbnd,
+                               SolverExtras &ex)
+{
+  const Requests rq = take_requests(ctx, ngpt, ex);
+  const std::string e(entry);
+  if (int rc = sw_clr_all_shape(entry, ngpt, nbnd)) return rc;
+  if (rq.byband)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": by-band outputs are not available from this entry (the sw_solver_2stream_inc "
+                                           "and sw_solver_2stream_rfmip entries have them)");
+  if (int rc = take_aerosol(entry, rq, kAerSw, nbnd, nlay, ncol, ex)) return rc;
+  if (int rc = take_jacobian(entry, rq, kJacRefuse, ngpt, nlay, ncol, ex)) return rc;
+  if (rq.mask.armed) {
+    if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
+      return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested cloud mask's extents (ngpt, nlay, ncol) are not this call's");
+    ex.mask_bits = rq.mask.bits;
+  }
+  return RRTMGPNN_OK;
+}
+
+static int sw_clr_all_launch(rrtmgpnn_context *ctx, SolverExtras &ex, const Sw2Stream &p, const SwBc *bc,
+                             float *flux_up_clr, float *flux_dn_clr, float *flux_dir_clr)
+{
+  const int mode0 = ctx->sw_clr_all >= 0 ? ctx->sw_clr_all : g_sw_clr_all_default;
+  const int mode = mode0 == 0 ? kSwClrAllDefaultMode : mode0;
+  if (mode == 1 && sw_ck_selected(ctx, p.ngpt)) {
+    ex.clr_up = flux_up_clr;
+    ex.clr_dn = flux_dn_clr;
+    ex.clr_dir = flux_dir_clr;
+    return launch_sw_2stream(ctx, ex, p, bc);
+  }
+  if (int rc = launch_sw_2stream(ctx, ex, p, bc)) return rc;
+  SolverExtras exc;
+  Sw2Stream pc = p;
+  pc.flux_up = flux_up_clr;
+  pc.flux_dn = flux_dn_clr;
+  pc.flux_dir = flux_dir_clr;
+  if (ex.aer_tau) {
+    pc.tau_bnd = ex.aer_tau;
+    pc.ssa_bnd = ex.aer_ssa;
+    pc.g_bnd = ex.aer_g;
+  } else {
+    pc.bands = nullptr;
+    pc.tau_bnd = pc.ssa_bnd = pc.g_bnd = nullptr;
+  }
+  return launch_sw_2stream(ctx, exc, pc, bc);
+}
+
+static int sw_clr_all_shape(const char *entry, int ngpt, int nbnd)
+{
+  const std::string e(entry);
+  if (nbnd <= 0) return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the all-sky set needs the band increment (nbnd > 0)");
+  if (ngpt % 2 != 0 || ngpt > 256)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": ngpt must be even and at most 256");
+  return RRTMGPNN_OK;
+}
+
+int rrtmgpnn_sw_solver_2stream_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                       const float *inc_flux, const float *inc_flux_dif, const float *tau,
+                                       const float *ssa, const float *g, int nbnd, const int *band_lims_gpt,
+                                       const float *tau_bnd, const float *ssa_bnd, const float *g_bnd, const float *mu0,
+                                       const float *sfc_alb_dir_gpt, const float *sfc_alb_dif_gpt, float *flux_up,
+                                       float *flux_dn, float *flux_dir, float *flux_up_clr, float *flux_dn_clr,
+                                       float *flux_dir_clr)
+{
+  static const char entry[] = "sw_solver_2stream_clr_all";
+  SolverExtras ex;
+  if (int rc = sw_clr_all_requests(entry, ctx, ngpt, nlay, ncol, nbnd, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!inc_flux || !tau || !ssa || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt || !flux_up || !flux_dn || !flux_dir ||
+      !flux_up_clr || !flux_dn_clr || !flux_dir_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nbnd < 0 ||
+      (nbnd > 0 && (!tau_bnd || !ssa_bnd || !g_bnd)))
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": bad argument");
+  BandArgs b;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_cover(b, ngpt)) return rc;
+  const Sw2Stream p{ngpt, nlay, ncol, top_at_1, inc_flux, inc_flux_dif, tau, ssa, g, mu0, sfc_alb_dir_gpt,
+                    sfc_alb_dif_gpt, &b, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir};
+  return sw_clr_all_launch(ctx, ex, p, nullptr, flux_up_clr, flux_dn_clr, flux_dir_clr);
+}
+
 int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
                                    float *bnd_flux_dn, float *bnd_flux_dir)
 {
@@ -1674,6 +1779,32 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
   const Sw2Stream p{ngpt, nlay, ncol, top_at_1, toa_flux, nullptr, tau, ssa, g, mu0, sfc_alb_gpt, sfc_alb_gpt,
                     nbnd > 0 ? &b : nullptr, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir};
   return launch_sw_2stream(ctx, ex, p, &bc);
+}
+
+int rrtmgpnn_sw_solver_2stream_rfmip_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                             const float *solar_source, const float *tsi, const float *sfc_alb,
+                                             const float *sza, const float *tau, const float *ssa, const float *g,
+                                             int nbnd, const int *band_lims_gpt, const float *tau_bnd,
+                                             const float *ssa_bnd, const float *g_bnd, float *toa_flux,
+                                             float *sfc_alb_gpt, float *mu0, float *flux_up, float *flux_dn,
+                                             float *flux_dir, float *flux_up_clr, float *flux_dn_clr,
+                                             float *flux_dir_clr)
+{
+  static const char entry[] = "sw_solver_2stream_rfmip_clr_all";
+  SolverExtras ex;
+  if (int rc = sw_clr_all_requests(entry, ctx, ngpt, nlay, ncol, nbnd, ex)) return rc;
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!solar_source || !tsi || !sfc_alb || !sza || !tau || !ssa || !toa_flux || !sfc_alb_gpt || !mu0 || !flux_up ||
+      !flux_dn || !flux_dir || !flux_up_clr || !flux_dn_clr || !flux_dir_clr || ngpt < 1 || nlay < 1 || ncol < 0 ||
+      nbnd < 0 || (nbnd > 0 && (!tau_bnd || !ssa_bnd || !g_bnd)))
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": bad argument");
+  const SwBc bc{solar_source, tsi, sfc_alb, sza, toa_flux, sfc_alb_gpt, mu0};
+  BandArgs b;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_cover(b, ngpt)) return rc;
+  const Sw2Stream p{ngpt, nlay, ncol, top_at_1, toa_flux, nullptr, tau, ssa, g, mu0, sfc_alb_gpt, sfc_alb_gpt,
+                    &b, tau_bnd, ssa_bnd, g_bnd, flux_up, flux_dn, flux_dir};
+  return sw_clr_all_launch(ctx, ex, p, &bc, flux_up_clr, flux_dn_clr, flux_dir_clr);
 }
 
 // ---- data files: RBIN, classic netCDF, netCDF-4 (datafile.cpp) ----

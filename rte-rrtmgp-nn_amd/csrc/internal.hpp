@@ -37,6 +37,7 @@ constexpr int kMaxBands = 64;
 extern int g_sw_kernel_default;  // rrtmgpnn_context_set_sw_kernel(NULL, mode)
 extern int g_mlp_kernel_default;  // rrtmgpnn_context_set_mlp_kernel(NULL, mode)
 extern int g_lw_clr_all_default;  // rrtmgpnn_context_set_lw_clr_all(NULL, mode)
+extern int g_sw_clr_all_default;  // rrtmgpnn_context_set_sw_clr_all(NULL, mode)
 // Raise a kernel's dynamic-LDS limit to 160 KiB on the current device, once per (kernel, device): a function
 // attribute is per device, so a second GPU of the same process gets its own call.  Thread-safe; after the first
 // call for a (kernel, device) pair it makes no HIP call (hipGraph captures stay attribute-free).
@@ -76,6 +77,10 @@ struct SolverExtras {
   // the checkpointed SW launcher (band-pair increment) have aerosol instances, without by-band, g-point or Jacobian
   // outputs and without lw_Ds
   const float *aer_tau = nullptr, *aer_ssa = nullptr, *aer_g = nullptr;
+  // the sw_solver_2stream_clr_all entries' clear-sky outputs, (nlay+1, ncol) each: set (all three), the checkpointed SW
+  // launcher runs its dual instance, which solves the clear sky (the gases and the aerosol, never the fused band
+  // increment) beside the all-sky problem; broadband outputs only
+  float *clr_up = nullptr, *clr_dn = nullptr, *clr_dir = nullptr;
 };
 
 // Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction (a kernel argument)
@@ -126,6 +131,7 @@ struct rrtmgpnn_context {
   int mlp_max_cus = 0;  // rrtmgpnn_context_set_mlp_max_cus: CUs' worth of network blocks, 0 = all
   int mlp_kernel = -1;  // LW network tiling: 0 32x32x2 where instantiated, 1 16x16x4, -1 the library default
   int lw_clr_all = -1;  // clear + all-sky LW entry: 0 default, 1 the dual kernel, 2 two launches, -1 the library default
+  int sw_clr_all = -1;  // clear + all-sky SW entries: the same modes
   // rrtmgpnn_context_get_mlp_path: the kernel of this context's last network launch (kind, A's and B's (K1S, H1T, H2T),
   // flags), written by the launchers
   int mlp_path[8] = {0};
@@ -331,7 +337,11 @@ int launch_sw_noscat(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, in
 // the checkpointed SW kernel's small-grid instance applies (clear sky, g = 0, no g-point outputs, the grid in one round)
 bool sw_ck_small(const rrtmgpnn_context *ctx, int ngpt, int ncol, bool has_g, bool inc, bool gpt);
 // planes: the large-grid instances' workspace planes (kCkTnNN, kCkTnInc, ...); false after that allocation failed
-size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool inc, bool nn, bool planes = true);
+// dual: the clear + all-sky instances (ex.clr_up set): two skies' checkpoints and (planes) their transmittance plane
+size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool inc, bool nn, bool planes = true,
+                               bool dual = false);
+// the checkpointed kernel is what launch_sw_2stream runs for this context and ngpt (without g-point outputs)
+bool sw_ck_selected(const rrtmgpnn_context *ctx, int ngpt);
 int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws,
                          bool planes = true, const SwBcDev *bc = nullptr);
 // kernels_lw_scat.hip

@@ -1136,6 +1136,12 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
   }
 }
 
+bool sw_ck_selected(const rrtmgpnn_context *ctx, int ngpt)
+{
+  const int mode = ctx->sw_kernel >= 0 ? ctx->sw_kernel : g_sw_kernel_default;
+  return (ngpt % 2) == 0 && (mode == 3 || mode == 0);
+}
+
 int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p, const SwBc *bc)
 {
   const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
@@ -1174,6 +1180,12 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment is taken by the checkpointed kernel only (even "
                                           "ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band or g-point "
                                           "outputs");
+  // clear + all-sky fluxes from one launch (the sw_solver_2stream_clr_all entries): only the checkpointed kernel has
+  // dual instances, for up to 256 g-points (one per lane, one column per block); the entries run two launches otherwise
+  const bool dual = ex.clr_up || ex.clr_dn || ex.clr_dir;
+  if (dual && (!ck || !inc || gpt || bb || ngpt > 256))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: clear + all-sky fluxes from one launch are taken by the checkpointed "
+                                          "kernel only (even ngpt <= 256, the fused band increment, broadband outputs)");
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
   // the other kernels read them from memory, formed there first by sw_boundary_kernel
   SwBcDev bcd{};
@@ -1190,14 +1202,14 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
   void *ws = nullptr;
   const size_t nlp = x2 ? sw_2stream_x2_layer_planes(inc) : (inc ? 3 : 0);
   const bool small = ck && sw_ck_small(ctx, ngpt, ncol, g != nullptr, inc, gpt), nn = !g && !inc && !gpt;
-  const size_t nws = ck ? sw_2stream_ck_ws_floats(ngpt, nlay, ncol, small, inc, nn)
+  const size_t nws = ck ? sw_2stream_ck_ws_floats(ngpt, nlay, ncol, small, inc, nn, true, dual)
                         : 4 * (size_t)ngpt * (nlay + 1) * ncol + nlp * (size_t)ngpt * nlay * ncol;
   // RRTMGPNN_SW_NO_PLANES=1 (read once per process): take the fallback below from the start (tests/test_gpu_sw_planes.py)
   static const bool no_planes = [] {
     const char *e = std::getenv("RRTMGPNN_SW_NO_PLANES");
     return e && e[0] == '1';
   }();
-  const size_t nws0 = ck && !small ? sw_2stream_ck_ws_floats(ngpt, nlay, ncol, false, inc, nn, false) : nws;
+  const size_t nws0 = ck && !small ? sw_2stream_ck_ws_floats(ngpt, nlay, ncol, false, inc, nn, false, dual) : nws;
   int rc = no_planes && nws0 < nws ? RRTMGPNN_ERR_DEVICE : ctx->workspace(sizeof(float) * nws, &ws);
   bool planes = true;
   if (rc == RRTMGPNN_ERR_DEVICE && nws0 < nws && !ctx->ws_pinned) {

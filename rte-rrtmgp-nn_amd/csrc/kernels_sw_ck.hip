@@ -120,6 +120,14 @@ __device__ __forceinline__ void ck_inc(V &t1, V &w1, V &g1, V t2, V w2, V g2)
 constexpr bool kCkFlushLanes = true;
 __host__ __device__ constexpr int ck_ring_stride(int ngpt) { return ngpt + 4; }
 
+// a lane's load of one layer: its V, or (kOne: the dual instances, whose lane owns one g-point) one float
+template <bool kOne, CachePolicy CP, class V>
+__device__ __forceinline__ auto ck_ld(const ColArrV<V> &a, uint32_t voff, uint32_t soff)
+{
+  if constexpr (kOne) return a.template ld1<CP>(voff, soff);
+  else return a.template ldv<CP>(voff, soff);
+}
+
 }  // namespace
 
 // K: layers per chunk (checkpoint spacing); kCkRing: levels staged for the ordered broadband sums (a multiple of K).
@@ -146,6 +154,16 @@ constexpr int kCkWavesNN = 3;
 // (the round-4 forms; same bits).
 constexpr bool kCkTnNN = true, kCkEmkNN = true;
 constexpr bool kCkTnInc = true, kCkEmkInc = false;
+// ... and of the dual (clear + all-sky) instances, a pair per g-point each.  Without planes a lane evaluates ten exps
+// per layer (two skies x (pass 1's beam, passes 2 and 3's beam and exp(-k tau))) against five in the two single-sky
+// launches, which have planes, and spills (168 VGPRs, 14-66 spilled).  The SW solver alone at C4, alternating builds
+// and routes on one box, two rounds (tools/sw_clr_all_ab.py, profiles/sw_clr_all_planes_c4.txt), the dual launch against
+// the two launches' 2.46-2.47 ms (spread 0.03-0.05): no plane 2.709 / 2.708 (+10 %), the transmittance plane 2.424 /
+// 2.443 (-1.5 %), exp(-k tau) alone 2.538 / 2.550, both 2.478 / 2.476; with a mask and aerosols 3.904, 2.871 (-10.6 %
+// against 3.21), 3.007, 2.936.  So the transmittance plane alone, as in the all-sky instances (kCkTnInc).
+// (The variants were builds with these two constants changed.)  When the workspace with the plane does not fit, the plane-free
+// instances run (launch_sw_2stream's fallback; the same bits).
+constexpr bool kCkTnDual = true, kCkEmkDual = false;
 
 // kGpt: also store the g-point fluxes (ty_fluxes_flexible: up, total down, direct; (ngpt, nlay+1, ncol)) and sum the
 // broadband down flux from the total as sw_solver_2stream does when it saves them (:572-588, :660-684)
@@ -265,10 +283,21 @@ constexpr SwCkCp kCpSwOther = {};
 // layer, loaded as ld_bnd loads the cloud's; pass 1, which needs the optical depth only, takes (tau + tau_aer) +
 // sel(tau_cld).  With gg == NULL the gas g going into the first increment is the literal 0, so gas optics never writes
 // a g array.  The mask never touches the aerosol.
+// kDual (with kInc, V = f2, no by-band or g-point outputs; rrtmgpnn_sw_solver_2stream_clr_all): clear-sky
+// beside all-sky fluxes of the same columns, rte_sw twice in extensions/mo_rrtmgp_clr_all_sky.F90:283-304.  One column
+// per block, lane t owns g-point t alone, and the two components of V are that g-point's two skies: .x all sky, .y
+// clear.  tau, ssa, the gas g, the band values and the mask word are one scalar load per layer each; props() forms
+// .y from the gas properties as loaded (with kAer: one ck_inc by the aerosol) and .x from .y's values by ck_inc with the
+// (mask-selected) cloud -- the clear component is never incremented by zeros, which would still round.  With gg == NULL
+// .y runs the general gamma / alpha expressions at g = 0, the bits of the kG0 short forms
+// (tools/check_sw_identities.py).  The recurrences, the checkpoints ((2 ngpt, 3 nck + 2, ncol), a lane's pair at
+// 8 g bytes), the planes ((2 ngpt, nlay, ncol) each) and the ring ([2 skies][3][R][rs], the footprint of two columns)
+// are per sky; one flush window reduces both (ring_flush_sw*'s kSkies) and stores sky 1 to clr_up / clr_dn / clr_dir.
+// kBandPair is not used: one g-point has one band whatever the limits are.
 template <bool kHasG, bool kInc, int K, bool kGpt = false, int R = kCkRing,
           int WAVES = (!kHasG && !kInc && !kGpt) ? kCkWavesNN : kCkWaves, bool kTn = false,
           class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1,
-          bool kBand = false, bool kMask = false, bool kAer = false>
+          bool kBand = false, bool kMask = false, bool kAer = false, bool kDual = false>
 __global__ void __launch_bounds__(512, WAVES)
     sw_2stream_ck_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
@@ -279,17 +308,22 @@ __global__ void __launch_bounds__(512, WAVES)
                          float *__restrict__ flux_dn, float *__restrict__ flux_dir, float *__restrict__ gpt_up,
                          float *__restrict__ gpt_dn, float *__restrict__ gpt_dir, SwBcDev bc, BandOut bo,
                          const uint32_t *__restrict__ cmask, const float *__restrict__ tau_aer,
-                         const float *__restrict__ ssa_aer, const float *__restrict__ g_aer)
+                         const float *__restrict__ ssa_aer, const float *__restrict__ g_aer,
+                         float *__restrict__ clr_up, float *__restrict__ clr_dn, float *__restrict__ clr_dir)
 {
   static_assert(R % K == 0, "the flux ring must hold whole chunks");
-  static_assert(!kAer || (kInc && kBandPair && sizeof(V) == 8 && !kGpt && !kBand),
+  static_assert(!kDual || (kInc && sizeof(V) == 8 && !kGpt && !kBand && !kBandPair),
+                "the dual instances: two skies of one g-point per lane, broadband outputs");
+  static_assert(!kAer || (kInc && (kBandPair || kDual) && sizeof(V) == 8 && !kGpt && !kBand),
                 "the aerosol increment goes in front of the fused band-pair increment");
   static_assert(!kMask || (kInc && sizeof(V) == 8 && !kGpt), "the cloud mask switches the fused band increment");
   constexpr bool kG0 = !kHasG && !kInc;  // g is the literal 0 (the NN path)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // `ncb` columns per block: lane t works on column c = t / (ngpt/NPL), g-points g .. g + NPL - 1
-  constexpr int NPL = sizeof(V) / sizeof(float);
+  constexpr int NPL = kDual ? 1 : sizeof(V) / sizeof(float);
   using CA_ = ColArrV<V>;
+  using L = std::conditional_t<kDual, float, V>;  // what a lane loads of a layer's properties
+  const int ncr = kDual ? 2 : ncb;  // rings in the block's LDS (kDual: ncb = 1, a ring per sky)
   const int nlev = nlay + 1, lanes = ngpt / NPL, nck = (nlay + K - 1) / K;
   const int icol0 = blockIdx.x * ncb, nc = min(ncb, ncol - icol0);
   const int craw = (int)threadIdx.x / lanes;
@@ -323,16 +357,21 @@ __global__ void __launch_bounds__(512, WAVES)
   // checkpoints, column by column: (ngpt, 3 nck + 2, ncol) -- rows [0, nck) the beam, [nck, 2 nck + 1) the albedo,
   // [2 nck + 1, 3 nck + 2) the source; one buffer descriptor for the three (the layer offset in the SGPR offset)
   const int nrw = 3 * nck + 2;
-  const size_t pW = (size_t)ngpt * nrw * ncol;
-  const uint32_t vW = 4u * (uint32_t)gc + (uint32_t)c * row * nrw;
-  const CA_ CW(ws, (size_t)ngpt * nrw * icol0, (uint32_t)nc * row * nrw);
-  const uint32_t sA0 = row * (uint32_t)nck, sS0 = row * (uint32_t)(2 * nck + 1);
+  const size_t pW = (size_t)(kDual ? 2 : 1) * ngpt * nrw * ncol;
+  // (kDual: rows of 2 ngpt, the lane's two skies side by side)
+  const uint32_t rowW = kDual ? 2u * row : row;
+  const uint32_t vW = (kDual ? 8u : 4u) * (uint32_t)gc + (uint32_t)c * rowW * nrw;
+  const CA_ CW(ws, (size_t)(kDual ? 2 : 1) * ngpt * nrw * icol0, (uint32_t)nc * rowW * nrw);
+  const uint32_t sA0 = rowW * (uint32_t)nck, sS0 = rowW * (uint32_t)(2 * nck + 1);
   // kTn: the beam transmittances (ngpt, nlay, ncol), addressed as tau.  kEmk: pass 2's exp(-tau k) in the plane after
   // it, which pass 3 reads instead of evaluating the exp again.  (Keeping all four coefficients R_dif, T_dif, S_up, S_dn
   // instead, so that pass 3 forms none, was 23 % slower at C3: four planes written and read cost more than they save.)
-  const size_t plane = (size_t)ngpt * nlay * ncol;
-  const CA_ CT(kTn ? ws + pW : ws, kTn ? cl : 0, kTn ? bL : 0u);
-  const CA_ CE(kEmk ? ws + pW + (kTn ? plane : 0) : ws, kEmk ? cl : 0, kEmk ? bL : 0u);
+  // (kDual: planes of (2 ngpt, nlay, ncol), addressed as the checkpoints' rows: vLp, rowW)
+  constexpr int kSk = kDual ? 2 : 1;
+  const size_t plane = (size_t)kSk * ngpt * nlay * ncol;
+  const uint32_t vLp = kDual ? 8u * (uint32_t)gc + (uint32_t)c * rowW * nlay : vL;
+  const CA_ CT(kTn ? ws + pW : ws, kTn ? kSk * cl : 0, kTn ? kSk * bL : 0u);
+  const CA_ CE(kEmk ? ws + pW + (kTn ? plane : 0) : ws, kEmk ? kSk * cl : 0, kEmk ? kSk * bL : 0u);
   const uint32_t vWs = on ? vW : kBufOOB;
   // band-resolved increments: one band offset per g-point of the lane
   const size_t cb = (size_t)bands.nbnd * nlay * icol0;
@@ -345,8 +384,9 @@ __global__ void __launch_bounds__(512, WAVES)
   // kAer: the aerosol's arrays, on the same bands (same offsets, their own column base)
   const CA_ At(kAer ? tau_aer : tau, kAer ? cb : 0, kAer ? bB : 0u), Aw(kAer ? ssa_aer : tau, kAer ? cb : 0, kAer ? bB : 0u),
       Ag(kAer ? g_aer : tau, kAer ? cb : 0, kAer ? bB : 0u);
-  auto ld_bnd = [&](const CA_ &a, int l) -> V {
-    if constexpr (!kInc) return (V)0.0f;
+  auto ld_bnd = [&](const CA_ &a, int l) -> L {
+    if constexpr (!kInc) return (L)0.0f;
+    else if constexpr (kDual) return a.ld1(vb0, brow * (uint32_t)l);
     else if constexpr (NPL == 2 && kBandPair) {
       const float v = a.ld1(vb0, brow * (uint32_t)l);
       return (f2){v, v};
@@ -364,8 +404,9 @@ __global__ void __launch_bounds__(512, WAVES)
     if constexpr (kMask) return __float_as_uint(Mk.ld1(vm, mrow * (uint32_t)l));
     else return 0u;
   };
-  auto sel = [&](V v, uint32_t m) -> V {
-    if constexpr (kMask && NPL == 2) {
+  auto sel = [&](L v, uint32_t m) -> L {
+    if constexpr (kMask && kDual) return ((m >> msh) & 1u) ? v : 0.0f;
+    else if constexpr (kMask && NPL == 2) {
       const uint32_t b = m >> msh;
       return (f2){(b & 1u) ? v[0] : 0.0f, (b & 2u) ? v[1] : 0.0f};
     } else return v;
@@ -376,7 +417,10 @@ __global__ void __launch_bounds__(512, WAVES)
   const float mu0_inv = 1.0f / mu0;
   // j counts layers from the top (clamped to the last layer); the result is the array layer
   auto lay = [&](int j) { return top_at_1 ? min(j, nlay - 1) : nlay - 1 - min(j, nlay - 1); };
-  auto ld_col = [&](const float *p) -> V { return on ? *(const V *)(p + gc + (size_t)ngpt * icol) : (V)0.0f; };
+  auto ld_col = [&](const float *p) -> V {
+    if constexpr (kDual) return on ? (V)p[gc + (size_t)ngpt * icol] : (V)0.0f;
+    else return on ? *(const V *)(p + gc + (size_t)ngpt * icol) : (V)0.0f;
+  };
   const int top = top_at_1 ? 0 : nlay;
   // the surface albedo, spectrally constant (rrtmgp_rfmip_sw.F90:428-433), or the caller's per g-point
   const V alb_bc = on && bcf ? (V)bc.sfc_alb[icol] : (V)0.0f;
@@ -386,16 +430,19 @@ __global__ void __launch_bounds__(512, WAVES)
   // in LDS.  Round 6, C3: the solver alone -1.3 %; in the large clear-sky instance C5 steps +0.3 % (2 pairs), so not
   // there (profiles/r06/swearly_*.txt)
   constexpr int P1 = P1C * K;
+  // (kDual: t is the clear sky's optical depth and q the cloud's, selected; the all-sky depth is their sum)
   struct Buf1 {
-    V t[P1];
+    L t[P1];
+    L q[kDual ? P1 : 1];
   } A1, B1;
   auto load1 = [&](Buf1 &b, int c1) {
 #pragma unroll
     for (int p = 0; p < P1; p++) {
       const int l = lay(c1 * P1 + p);
-      b.t[p] = Ttau.template ldv<kCp.p1_ld>(vL, row * (uint32_t)l);
+      b.t[p] = ck_ld<kDual, kCp.p1_ld>(Ttau, vL, row * (uint32_t)l);
       if constexpr (kAer) b.t[p] += ld_bnd(At, l);
-      if constexpr (kMask) b.t[p] += sel(ld_bnd(Bt, l), ld_msk(l));
+      if constexpr (kDual) b.q[p] = sel(ld_bnd(Bt, l), ld_msk(l));
+      else if constexpr (kMask) b.t[p] += sel(ld_bnd(Bt, l), ld_msk(l));
       else if constexpr (kInc) b.t[p] += ld_bnd(Bt, l);
     }
   };
@@ -426,9 +473,10 @@ __global__ void __launch_bounds__(512, WAVES)
   // checkpoints the pass reads for it: fb the beam at the chunk's top (pass 2), ae / se the albedo and source at its
   // bottom (pass 3)
   struct Chunk {
-    V t[K], w[K], g[K], qt[K], qw[K], qg[K], tn[K], em[K], fb, ae, se;
+    L t[K], w[K], g[K], qt[K], qw[K], qg[K];
+    V tn[K], em[K], fb, ae, se;
     uint32_t qm[kMask ? K : 1];
-    V at[kAer ? K : 1], aw[kAer ? K : 1], ag[kAer ? K : 1];
+    L at[kAer ? K : 1], aw[kAer ? K : 1], ag[kAer ? K : 1];
   };
   // pass: 2 or 3 (a constant: it selects the streams' cache policies).  Pass 3's loads are all last uses; pass 2's are
   // the beam checkpoint's and, when pass 3 reads exp(-k tau) from its plane and so no tau, tau's
@@ -440,11 +488,11 @@ __global__ void __launch_bounds__(512, WAVES)
     for (int p = 0; p < K; p++) {
       const int l = lay(ck * K + p);
       const uint32_t s = row * (uint32_t)l;
-      ch.t[p] = Ttau.template ldv<cpT>(vL, s);
-      ch.tn[p] = kTn ? CT.template ldv<cp3>(vL, s) : (V)0.0f;
-      ch.em[p] = (kEmk && pass == 3) ? CE.template ldv<cp3>(vL, s) : (V)0.0f;
-      ch.w[p] = Tssa.template ldv<cp3>(vL, s);
-      ch.g[p] = kHasG ? Tg.template ldv<cp3>(vL, s) : (V)0.0f;
+      ch.t[p] = ck_ld<kDual, cpT>(Ttau, vL, s);
+      ch.tn[p] = kTn ? CT.template ldv<cp3>(vLp, rowW * (uint32_t)l) : (V)0.0f;
+      ch.em[p] = (kEmk && pass == 3) ? CE.template ldv<cp3>(vLp, rowW * (uint32_t)l) : (V)0.0f;
+      ch.w[p] = ck_ld<kDual, cp3>(Tssa, vL, s);
+      ch.g[p] = kHasG ? ck_ld<kDual, cp3>(Tg, vL, s) : (L)0.0f;
       if constexpr (kInc) {
         ch.qt[p] = ld_bnd(Bt, l);
         ch.qw[p] = ld_bnd(Bw, l);
@@ -456,25 +504,37 @@ __global__ void __launch_bounds__(512, WAVES)
           ch.ag[p] = ld_bnd(Ag, l);
         }
       } else {
-        ch.qt[p] = ch.qw[p] = ch.qg[p] = (V)0.0f;
+        ch.qt[p] = ch.qw[p] = ch.qg[p] = (L)0.0f;
       }
     }
     if constexpr (pass == 2) {
-      ch.fb = CW.template ldv<kCp.p2_last>(vW, row * (uint32_t)ck);
+      ch.fb = CW.template ldv<kCp.p2_last>(vW, rowW * (uint32_t)ck);
     } else {
-      const uint32_t sE = row * (uint32_t)min(ck + 1, nck);
+      const uint32_t sE = rowW * (uint32_t)min(ck + 1, nck);
       ch.ae = CW.template ldv<cp3>(vW, sA0 + sE);
       ch.se = CW.template ldv<cp3>(vW, sS0 + sE);
     }
   };
   // the (incremented) properties of layer p of a chunk
   auto props = [&](const Chunk &ch, int p, V &t, V &w, V &g0) {
-    t = ch.t[p];
-    w = ch.w[p];
-    g0 = kHasG ? ch.g[p] : (V)0.0f;
-    if constexpr (kAer) ck_inc(t, w, g0, ch.at[p], ch.aw[p], ch.ag[p]);
-    if constexpr (kMask) ck_inc(t, w, g0, sel(ch.qt[p], ch.qm[p]), sel(ch.qw[p], ch.qm[p]), sel(ch.qg[p], ch.qm[p]));
-    else if constexpr (kInc) ck_inc(t, w, g0, ch.qt[p], ch.qw[p], ch.qg[p]);
+    if constexpr (kDual) {
+      // .y: the gases (and the aerosol) alone; .x: those values, then the (selected) cloud
+      float ty = ch.t[p], wy = ch.w[p], gy = kHasG ? ch.g[p] : 0.0f;
+      if constexpr (kAer) ck_inc(ty, wy, gy, ch.at[p], ch.aw[p], ch.ag[p]);
+      float tx = ty, wx = wy, gx = gy;
+      ck_inc(tx, wx, gx, sel(ch.qt[p], ch.qm[kMask ? p : 0]), sel(ch.qw[p], ch.qm[kMask ? p : 0]),
+             sel(ch.qg[p], ch.qm[kMask ? p : 0]));
+      t = (V){tx, ty};
+      w = (V){wx, wy};
+      g0 = (V){gx, gy};
+    } else {
+      t = ch.t[p];
+      w = ch.w[p];
+      g0 = kHasG ? ch.g[p] : (V)0.0f;
+      if constexpr (kAer) ck_inc(t, w, g0, ch.at[p], ch.aw[p], ch.ag[p]);
+      if constexpr (kMask) ck_inc(t, w, g0, sel(ch.qt[p], ch.qm[p]), sel(ch.qw[p], ch.qm[p]), sel(ch.qg[p], ch.qm[p]));
+      else if constexpr (kInc) ck_inc(t, w, g0, ch.qt[p], ch.qw[p], ch.qg[p]);
+    }
   };
   // Each pass walks its chunks two at a time through two register buffers: the loads of the next chunk go to the other
   // buffer while this one is computed, so no copy waits for them at the end of the step.  body(buf, ck, valid)
@@ -514,16 +574,19 @@ __global__ void __launch_bounds__(512, WAVES)
       const int n = valid ? min(P1, nlay - c1 * P1) : 0;
       V arg[P1], Tn[P1];
 #pragma unroll
-      for (int p = 0; p < P1; p++) arg[p] = -b.t[p] * mu0_inv;
+      for (int p = 0; p < P1; p++) {
+        if constexpr (kDual) arg[p] = -(V){b.t[p] + b.q[p], b.t[p]} * mu0_inv;
+        else arg[p] = -b.t[p] * mu0_inv;
+      }
       exp_beam_batch(arg, Tn, etab);
       if constexpr (kTn) {
 #pragma unroll
         for (int p = 0; p < P1; p++)
-          CT.template stv<kCp.p1_st>(Tn[p], (on && p < n) ? vL : kBufOOB, row * (uint32_t)lay(c1 * P1 + p));
+          CT.template stv<kCp.p1_st>(Tn[p], (on && p < n) ? vLp : kBufOOB, rowW * (uint32_t)lay(c1 * P1 + p));
       }
 #pragma unroll
       for (int p = 0; p < P1; p++) {
-        if (p % K == 0) CW.template stv<kCp.p1_st>(Fd, (p < n) ? vWs : kBufOOB, row * (uint32_t)(c1 * P1C + p / K));
+        if (p % K == 0) CW.template stv<kCp.p1_st>(Fd, (p < n) ? vWs : kBufOOB, rowW * (uint32_t)(c1 * P1C + p / K));
         Fd = (p < n) ? Tn[p] * Fd : Fd;
       }
     };
@@ -532,8 +595,8 @@ __global__ void __launch_bounds__(512, WAVES)
   // ---- pass 2: bottom -> top adding; albedo / source checkpoint at every chunk top and at the surface ----
   V alb_b = bcf ? alb_bc : ld_col(alb_dif);
   V src_b = Fd * (bcf ? alb_bc : ld_col(alb_dir));
-  CW.template stv<kCp.p2_st>(alb_b, vWs, sA0 + row * (uint32_t)nck);
-  CW.template stv<kCp.p2_st>(src_b, vWs, sS0 + row * (uint32_t)nck);
+  CW.template stv<kCp.p2_st>(alb_b, vWs, sA0 + rowW * (uint32_t)nck);
+  CW.template stv<kCp.p2_st>(src_b, vWs, sS0 + rowW * (uint32_t)nck);
   {
     Chunk A, B;
     auto load2 = [&](Chunk &ch, int ck) { load_chunk(ch, ck, std::integral_constant<int, 2>{}); };
@@ -565,7 +628,7 @@ __global__ void __launch_bounds__(512, WAVES)
       if constexpr (kEmk) {
 #pragma unroll
         for (int p = 0; p < K; p++)
-          CE.template stv<kCp.p2_st>(em[p], (on && p < n) ? vL : kBufOOB, row * (uint32_t)lay(ck * K + p));
+          CE.template stv<kCp.p2_st>(em[p], (on && p < n) ? vLp : kBufOOB, rowW * (uint32_t)lay(ck * K + p));
       }
 #pragma unroll
       for (int p = K - 1; p >= 0; p--) {
@@ -575,8 +638,8 @@ __global__ void __launch_bounds__(512, WAVES)
         alb_b = (p < n) ? alb : alb_b;
         src_b = (p < n) ? src : src_b;
       }
-      CW.template stv<kCp.p2_st>(alb_b, valid && ck > 0 ? vWs : kBufOOB, sA0 + row * (uint32_t)ck);
-      CW.template stv<kCp.p2_st>(src_b, valid && ck > 0 ? vWs : kBufOOB, sS0 + row * (uint32_t)ck);
+      CW.template stv<kCp.p2_st>(alb_b, valid && ck > 0 ? vWs : kBufOOB, sA0 + rowW * (uint32_t)ck);
+      CW.template stv<kCp.p2_st>(src_b, valid && ck > 0 ? vWs : kBufOOB, sS0 + rowW * (uint32_t)ck);
     };
     if constexpr (AHEAD == 2) {
       Chunk C;
@@ -588,13 +651,24 @@ __global__ void __launch_bounds__(512, WAVES)
   // ---- pass 3: top -> bottom fluxes + ordered broadband sums ----
   // idle lanes (past the block's columns) store their ring values to one spare slot instead of branching around the
   // stores; slots past the last level (the last chunk's padding layers) are written and never read
-  float *const spare = smem + kExpTabFloats + (size_t)ncb * 3 * R * rs;
+  float *const spare = smem + kExpTabFloats + (size_t)ncr * 3 * R * rs;
   // level `lev` (array index) of the g-point outputs
   auto put = [&](V up, V dif, V dir, int r, int lev, bool valid) {
     const V dn = kGpt ? dif + dir : dif;  // kGpt: the total, rounded once ("flux_dn is total", :665-666)
-    *(V *)(on ? &ring[(size_t)r * rs + g] : spare) = up;
-    *(V *)(on ? &ring[((size_t)R + r) * rs + g] : spare) = dn;
-    *(V *)(on ? &ring[((size_t)2 * R + r) * rs + g] : spare) = dir;
+    if constexpr (kDual) {
+      // sky s of g-point g in ring s (idle lanes: the spare slot's two floats)
+      const size_t o2 = on ? (size_t)3 * R * rs : 1;
+      float *const pu = on ? &ring[(size_t)r * rs + g] : spare;
+      float *const pd = on ? &ring[((size_t)R + r) * rs + g] : spare;
+      float *const pr = on ? &ring[((size_t)2 * R + r) * rs + g] : spare;
+      pu[0] = up.x, pu[o2] = up.y;
+      pd[0] = dn.x, pd[o2] = dn.y;
+      pr[0] = dir.x, pr[o2] = dir.y;
+    } else {
+      *(V *)(on ? &ring[(size_t)r * rs + g] : spare) = up;
+      *(V *)(on ? &ring[((size_t)R + r) * rs + g] : spare) = dn;
+      *(V *)(on ? &ring[((size_t)2 * R + r) * rs + g] : spare) = dir;
+    }
     if constexpr (kGpt) {
       if (on && valid) {
         const size_t o = (size_t)g + (size_t)ngpt * ((size_t)lev + (size_t)nlev * icol);
@@ -608,12 +682,12 @@ __global__ void __launch_bounds__(512, WAVES)
     // kBand: the by-band sums bo.up / bo.dn / bo.dir in the same barrier window; the ring keeps diffuse and direct
     // apart (the broadband bits do not move) and the band walk forms dif + dir itself (band_flush)
     const BandOut *pb = kBand ? &bo : nullptr;
-    if (kCkFlushLanes && (ngpt & 3) == 0 && 3 * ncb * n * 4 <= (int)blockDim.x)
-      ring_flush_sw_lanes<R, kGpt, kBand>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up,
-                                          flux_dn, flux_dir, rs, slot0, pb);
+    if (kCkFlushLanes && (ngpt & 3) == 0 && 3 * ncr * n * 4 <= (int)blockDim.x)
+      ring_flush_sw_lanes<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, ncol,
+                                                 flux_up, flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir);
     else
-      ring_flush_sw<R, kGpt, kBand>(smem + kExpTabFloats, ncb, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up, flux_dn,
-                                    flux_dir, rs, slot0, pb);
+      ring_flush_sw<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up,
+                                           flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir);
   };
   // the ring holds M = R / K chunks; the block flushes it when it is full (a barrier, the ordered sums, a barrier).
   // (Staggering the blocks' flush phases, so that blocks sharing a CU flush at different chunks, measured equal, round
@@ -700,8 +774,12 @@ bool sw_ck_small(const rrtmgpnn_context *ctx, int ngpt, int ncol, bool has_g, bo
 // workspace floats of the checkpointed kernel (sized for the smaller of the chunk lengths, so it holds either
 // instance) plus the planes of the instance that runs: small-grid clear sky, large-grid clear sky (NN: g = NULL, no
 // increment, no g-point outputs) or all sky (inc)
-size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool inc, bool nn, bool planes)
+// dual: the clear + all-sky instances' checkpoints and planes, a pair per g-point each
+size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool inc, bool nn, bool planes, bool dual)
 {
+  if (dual)
+    return 2 * sw_2stream_ck_ws_floats(ngpt, nlay, ncol, false, true, false, false, false) +
+           (planes ? (size_t)2 * ((int)kCkTnDual + (int)kCkEmkDual) * ngpt * nlay * ncol : 0);
   const int np = small  ? (int)kCkTnSmall + (int)kCkEmkSmall
                  : !planes ? 0
                  : nn     ? (int)kCkTnNN + (int)kCkEmkNN
@@ -741,10 +819,53 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
                        p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tb, sb, gb, (float *)ws,
                        p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits,
-                       ex.aer_tau, ex.aer_ssa, ex.aer_g);
+                       ex.aer_tau, ex.aer_ssa, ex.aer_g, nullptr, nullptr, nullptr);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
+  if (ex.clr_up) {
+    // clear-sky beside all-sky fluxes (rrtmgpnn_sw_solver_2stream_clr_all): the dual instances, one column per block,
+    // one g-point per lane, two rings; {gas g} x {mask} x {aerosol}, with the planes of kCkTnDual / kCkEmkDual or, when
+    // that workspace did not fit, without
+    if (!bands || !ex.clr_dn || !ex.clr_dir)
+      return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: the clear + all-sky instances need the fused band increment and "
+                                         "all three clear-sky outputs");
+    if (bb || ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: clear + all-sky fluxes with by-band or g-point outputs");
+    if (ex.aer_tau && (!ex.aer_ssa || !ex.aer_g))
+      return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
+    auto god = [&](auto kern) -> int {
+      const int threads = (ngpt + 63) / 64 * 64;
+      const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)2 * 3 * kCkRing * ck_ring_stride(ngpt) + 4);
+      if (lds > 64 * 1024)
+        if (int rc = raise_lds_limit((const void *)kern)) return rc;
+      hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, 1,
+                         p.inc_flux, p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tau_bnd, ssa_bnd,
+                         g_bnd, (float *)ws, p.flux_up, p.flux_dn, p.flux_dir, nullptr, nullptr, nullptr, bcd, bo,
+                         ex.mask_bits, ex.aer_tau, ex.aer_ssa, ex.aer_g, ex.clr_up, ex.clr_dn, ex.clr_dir);
+      RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel (clear + all sky)");
+      return RRTMGPNN_OK;
+    };
+    constexpr int W = kCkWaves, P = kCkP1;
+    const bool m = ex.mask_bits != nullptr, a = ex.aer_tau != nullptr;
+#define RRTMGPNN_DUAL_(G, M, A, T, E) \
+  sw_2stream_ck_kernel<G, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, M, A, true>
+#define RRTMGPNN_DUAL_GO_(T, E)                                        \
+  do {                                                                 \
+    if (g && m && a) return god(RRTMGPNN_DUAL_(true, true, true, T, E));    \
+    if (g && m) return god(RRTMGPNN_DUAL_(true, true, false, T, E));        \
+    if (g && a) return god(RRTMGPNN_DUAL_(true, false, true, T, E));        \
+    if (g) return god(RRTMGPNN_DUAL_(true, false, false, T, E));            \
+    if (m && a) return god(RRTMGPNN_DUAL_(false, true, true, T, E));        \
+    if (m) return god(RRTMGPNN_DUAL_(false, true, false, T, E));            \
+    if (a) return god(RRTMGPNN_DUAL_(false, false, true, T, E));            \
+    return god(RRTMGPNN_DUAL_(false, false, false, T, E));                  \
+  } while (0)
+    if (planes && (kCkTnDual || kCkEmkDual)) RRTMGPNN_DUAL_GO_(kCkTnDual, kCkEmkDual);
+    RRTMGPNN_DUAL_GO_(false, false);
+#undef RRTMGPNN_DUAL_GO_
+#undef RRTMGPNN_DUAL_
+  }
   if (ex.aer_tau) {
     // aerosols in front of the (masked) cloud increment (rrtmgpnn_solver_request_aerosol): the band-pair layout only,
     // with the all-sky instances' transmittance plane or, when that workspace did not fit, without it (the same bits)

@@ -266,10 +266,13 @@ __device__ __forceinline__ float combine4(const float *p) { return ((p[0] + p[1]
 // stride: floats per ring row (ngpt, or ngpt padded so that the rows the flush threads walk together fall in different
 // LDS banks)
 // kBand: also the by-band sums (band_flush), the down value formed as dif + dir per g-point unless kTotal
-template <int R, bool kTotal = false, bool kBand = false>
+// kSkies (the dual clear + all-sky instances, ncb = 2): the two "columns" of the ring are the two skies of column icol0
+// -- ring column 0 stores to o_up / o_dn / o_dir, ring column 1 to c_up / c_dn / c_dir, both at column icol0
+template <int R, bool kTotal = false, bool kBand = false, bool kSkies = false>
 __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n, int lev0, int dl, int ngpt, int nlev,
                                               int icol0, int ncol, float *o_up, float *o_dn, float *o_dir,
-                                              int stride = 0, int slot0 = 0, const BandOut *bo = nullptr)
+                                              int stride = 0, int slot0 = 0, const BandOut *bo = nullptr,
+                                              float *c_up = nullptr, float *c_dn = nullptr, float *c_dir = nullptr)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -301,9 +304,10 @@ __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n,
       if (dn && !kTotal) for (int i = 0; i < ngpt; i++) s0 = s0 + (r[i] + r2[i]);
       else    for (int i = 0; i < ngpt; i++) s0 = s0 + r[i];
     }
-    const int icol = icol0 + c;
+    const int icol = kSkies ? icol0 : icol0 + c;
     if (icol < ncol) {
       float *o = q == 0 ? o_up : (q == 1 ? o_dn : o_dir);
+      if constexpr (kSkies) o = c == 0 ? o : (q == 0 ? c_up : (q == 1 ? c_dn : c_dir));
       o[lev0 + s * dl + (size_t)nlev * icol] = ((s0 + s1) + s2) + s3;
     }
   }
@@ -323,11 +327,13 @@ __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n,
 // (the SW launchers refuse more before launching)
 constexpr int kFlushLanesMaxCols = 4;
 
-template <int R, bool kTotal = false, bool kBand = false>
+// kSkies: as ring_flush_sw's
+template <int R, bool kTotal = false, bool kBand = false, bool kSkies = false>
 __device__ __forceinline__ void ring_flush_sw_lanes(const float *ring, int ncb, int n, int lev0, int dl, int ngpt,
                                                     int nlev, int icol0, int ncol, float *o_up, float *o_dn,
                                                     float *o_dir, int stride, int slot0 = 0,
-                                                    const BandOut *bo = nullptr)
+                                                    const BandOut *bo = nullptr, float *c_up = nullptr,
+                                                    float *c_dn = nullptr, float *c_dir = nullptr)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -354,9 +360,10 @@ __device__ __forceinline__ void ring_flush_sw_lanes(const float *ring, int ncb, 
     }
     // the quad's partials p0..p3 sit in lanes j = 0..3 of consecutive threads (per_q is a multiple of 4)
     const float p1 = __shfl_down(sum, 1, 4), p2 = __shfl_down(sum, 2, 4), p3 = __shfl_down(sum, 3, 4);
-    const int icol = icol0 + c;
+    const int icol = kSkies ? icol0 : icol0 + c;
     if (j == 0 && icol < ncol) {
       float *o = q == 0 ? o_up : (q == 1 ? o_dn : o_dir);
+      if constexpr (kSkies) o = c == 0 ? o : (q == 0 ? c_up : (q == 1 ? c_dn : c_dir));
       o[lev0 + (dl > 0 ? sl : -sl) + (size_t)nlev * icol] = ((sum + p1) + p2) + p3;  // dl = +-1
     }
   }

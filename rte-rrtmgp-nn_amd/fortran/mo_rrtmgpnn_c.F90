@@ -17,6 +17,8 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_compute_heating_rate
   public :: c_rrtmgpnn_lw_solver_noscat_planck_clr_all, c_rrtmgpnn_context_set_lw_clr_all
   public :: c_rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica
+  public :: c_rrtmgpnn_sw_solver_2stream_clr_all, c_rrtmgpnn_sw_solver_2stream_rfmip_clr_all
+  public :: c_rrtmgpnn_context_set_sw_clr_all
   public :: c_rrtmgpnn_lw_solver_1rescl_planck_inc
   public :: c_rrtmgpnn_lw_solver_noscat_gpt, c_rrtmgpnn_lw_solver_noscat_planck_gpt, c_rrtmgpnn_sw_solver_2stream_gpt
   public :: c_rrtmgpnn_lw_solver_1rescl_gpt, c_rrtmgpnn_lw_solver_2stream_gpt, c_rrtmgpnn_sw_solver_noscat_gpt
@@ -179,6 +181,32 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx
       integer(c_int), value :: mode
+    end function
+    ! clear-sky beside all-sky SW fluxes of the same columns (the dual checkpointed kernel, or two launches)
+    integer(c_int) function c_rrtmgpnn_context_set_sw_clr_all(ctx, mode) bind(C, name="rrtmgpnn_context_set_sw_clr_all")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: mode
+    end function
+    integer(c_int) function c_rrtmgpnn_sw_solver_2stream_clr_all(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, &
+        inc_flux_dif, tau, ssa, g, nbnd, band_lims_gpt, tau_bnd, ssa_bnd, g_bnd, mu0, sfc_alb_dir_gpt, &
+        sfc_alb_dif_gpt, flux_up, flux_dn, flux_dir, flux_up_clr, flux_dn_clr, flux_dir_clr) &
+        bind(C, name="rrtmgpnn_sw_solver_2stream_clr_all")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, inc_flux, inc_flux_dif, tau, ssa, g, tau_bnd, ssa_bnd, g_bnd, mu0, sfc_alb_dir_gpt, &
+                            sfc_alb_dif_gpt, flux_up, flux_dn, flux_dir, flux_up_clr, flux_dn_clr, flux_dir_clr
+      integer(c_int), value :: ngpt, nlay, ncol, top_at_1, nbnd
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
+    end function
+    integer(c_int) function c_rrtmgpnn_sw_solver_2stream_rfmip_clr_all(ctx, ngpt, nlay, ncol, top_at_1, solar_source, &
+        tsi, sfc_alb, sza, tau, ssa, g, nbnd, band_lims_gpt, tau_bnd, ssa_bnd, g_bnd, toa_flux, sfc_alb_gpt, mu0, &
+        flux_up, flux_dn, flux_dir, flux_up_clr, flux_dn_clr, flux_dir_clr) &
+        bind(C, name="rrtmgpnn_sw_solver_2stream_rfmip_clr_all")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, solar_source, tsi, sfc_alb, sza, tau, ssa, g, tau_bnd, ssa_bnd, g_bnd, toa_flux, &
+                            sfc_alb_gpt, mu0, flux_up, flux_dn, flux_dir, flux_up_clr, flux_dn_clr, flux_dir_clr
+      integer(c_int), value :: ngpt, nlay, ncol, top_at_1, nbnd
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
     end function
     integer(c_int) function c_rrtmgpnn_sw_solver_noscat(ctx, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir) &
         bind(C, name="rrtmgpnn_sw_solver_noscat")

@@ -86,6 +86,9 @@ SIGNATURES = {
     "rrtmgpnn_sw_solver_2stream_inc": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_int, P(c_int), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                c_vp]),
+    "rrtmgpnn_context_set_sw_clr_all": (c_int, [c_vp, c_int]),
+    "rrtmgpnn_sw_solver_2stream_clr_all": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                   c_int, P(c_int)] + [c_vp] * 12),
     "rrtmgpnn_lw_solver_1rescl": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, P(c_float), P(c_float)]
                                   + [c_vp] * 10),
     "rrtmgpnn_lw_solver_1rescl_planck_inc": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, P(c_float),
@@ -141,6 +144,8 @@ SIGNATURES = {
     "rrtmgpnn_sw_boundary_rfmip": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_sw_solver_2stream_rfmip": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7
                                          + [c_int, P(c_int)] + [c_vp] * 9),
+    "rrtmgpnn_sw_solver_2stream_rfmip_clr_all": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7
+                                                 + [c_int, P(c_int)] + [c_vp] * 12),
     "rrtmgpnn_file_open": (c_int, [c_char_p, P(c_vp)]),
     "rrtmgpnn_file_close": (c_int, [c_vp]),
     "rrtmgpnn_file_nvars": (c_int, [c_vp, P(c_int)]),

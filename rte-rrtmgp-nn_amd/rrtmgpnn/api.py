@@ -95,6 +95,10 @@ class Context:
         """0: the clear + all-sky LW entry as the library chooses; 1: the dual kernel; 2: two launches (bit-identical)."""
         check(_lib.lib().rrtmgpnn_context_set_lw_clr_all(self.h, int(mode)), "context_set_lw_clr_all")
 
+    def set_sw_clr_all(self, mode):
+        """0: the clear + all-sky SW entries as the library chooses; 1: the dual kernel; 2: two launches (bit-identical)."""
+        check(_lib.lib().rrtmgpnn_context_set_sw_clr_all(self.h, int(mode)), "context_set_sw_clr_all")
+
     def close(self):
         """Destroy the context now (its workspace and buffer pool); the handle is unusable afterwards."""
         h, self.h = getattr(self, "h", None), None
@@ -124,6 +128,12 @@ def set_lw_clr_all_default(mode):
     """How rrtmgpnn_lw_solver_noscat_planck_clr_all runs on every context not set itself: 0 the library's choice, 1 the
     dual kernel, 2 the clear and the incremented kernel back to back (bit-identical fluxes; tests force each)."""
     check(_lib.lib().rrtmgpnn_context_set_lw_clr_all(None, int(mode)), "context_set_lw_clr_all")
+
+
+def set_sw_clr_all_default(mode):
+    """How rrtmgpnn_sw_solver_2stream_clr_all and _rfmip_clr_all run on every context not set itself: 0 the library's
+    choice, 1 the dual kernel, 2 the all-sky and the clear launch back to back (bit-identical fluxes; tests force each)."""
+    check(_lib.lib().rrtmgpnn_context_set_sw_clr_all(None, int(mode)), "context_set_sw_clr_all")
 
 
 def context(device=None):

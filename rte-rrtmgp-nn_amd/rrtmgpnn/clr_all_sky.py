@@ -47,6 +47,8 @@ AEROSOL_REQUEST = True
 # the fused LW scattering route may be taken (False: always gas optics into 2str properties, [draw_samples,] increment
 # and the rescaled solver)
 LW_SCAT_FUSED = True
+# rte_sw may take both SW flux sets from one call of rrtmgpnn_sw_solver_2stream_clr_all (False: always the two solves)
+SW_CLR_ALL_FUSED = True
 
 
 def aerosol_by_request(aer_props, optical_props, kind):
@@ -257,7 +259,12 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
     then the all-sky solve on cloud_props (by band) sampled per g-point.  With mask_bits, 2str clouds on k_dist's
     bands, even ngpt and broadband-only all-sky fluxes that is the library's masked fused solve
     (rrtmgpnn_solver_request_cloud_mask + rrtmgpnn_sw_solver_2stream_inc: the increment switched per g-point as the
-    properties are read); every other case runs draw_samples and increment first, which needs cloud_mask."""
+    properties are read); every other case runs draw_samples and increment first, which needs cloud_mask.
+
+    One call (SW_CLR_ALL_FUSED): with 2str clouds by band on k_dist's bands and extents, ngpt even and at most 256, both
+    flux objects broadband-only and desired and the albedos per g-point, both solves are one call of
+    rrtmgpnn_sw_solver_2stream_clr_all -- masked (mask_bits) or not, aer_props by request where they qualify and
+    incremented first otherwise: the same flux objects, bit for bit.  Every other case keeps the sequence above."""
     ncol, nlay = tuple(p_lay.shape)
     ngpt, nband = k_dist.get_ngpt(), k_dist.get_nband()
     e = ""
@@ -310,6 +317,42 @@ def rte_sw(k_dist, gas_concs, p_lay, t_lay, p_lev, mu0, sfc_alb_dir, sfc_alb_dif
                  and all(_shape(a) == (ncol, ngpt) for a in albs))
     f = lambda t: t if t is not None else torch.empty((ncol, nlay + 1), dtype=torch.float32, device=dev)  # noqa: E731
     lims = int_array(k_dist.band_lims_gpt.ravel())
+    broadband = lambda fl: (fl.are_desired() and not fl.are_desired_gpt()  # noqa: E731
+                            and not (isinstance(fl, FluxesByBand) and fl.are_desired_byband()))
+    one_call = (SW_CLR_ALL_FUSED and (not masked or mask_bits is not None)
+                and isinstance(optical_props, OpticalProps2str) and isinstance(cloud_props, OpticalProps2str)
+                and ngpt % 2 == 0 and ngpt <= 256
+                and cloud_props.bands_are_equal(optical_props) and not cloud_props.gpoints_are_equal(optical_props)
+                and cloud_props.get_ngpt() == nband
+                and (cloud_props.get_ncol(), cloud_props.get_nlay()) == (ncol, nlay)
+                and broadband(allsky_fluxes) and broadband(clrsky_fluxes)
+                and all(_shape(a) == (ncol, ngpt) for a in albs))
+    if one_call:
+        # aerosols by request where the solver's aerosol instances take them (band-pair layout: mode 2 of
+        # rrtmgpnn_context_set_sw_clr_all runs the single-sky aerosol instance), incremented into the gas properties
+        # otherwise; the gas g is read only in that second case
+        by_req = (AEROSOL_REQUEST and aerosol_by_request(aer_props, optical_props, OpticalProps2str)
+                  and all((int(lo) - 1) % 2 == 0 for lo in k_dist.band_lims_gpt[:, 0]))
+        if aer_props is not None and not by_req:
+            e = aer_props.increment(optical_props)
+            if e:
+                return e
+        up, dn, dr = f(allsky_fluxes.flux_up), f(allsky_fluxes.flux_dn), f(allsky_fluxes.flux_dn_dir)
+        upc, dnc, drc = f(clrsky_fluxes.flux_up), f(clrsky_fluxes.flux_dn), f(clrsky_fluxes.flux_dn_dir)
+        if by_req:
+            cloud_sampling.arm_aerosol(ctx, aer_props)
+        if mask_bits is not None:
+            cloud_sampling.arm_cloud_mask(ctx, ngpt, mask_bits)
+        check(_lib.lib().rrtmgpnn_sw_solver_2stream_clr_all(
+            ctx.h, ngpt, nlay, ncol, int(top_at_1), _p(toa_flux), None, _p(optical_props.tau), _p(optical_props.ssa),
+            None if (by_req or aer_props is None) else _p(optical_props.g), nband, lims, _p(cloud_props.tau),
+            _p(cloud_props.ssa), _p(cloud_props.g), _p(mu0), _p(albs[0]), _p(albs[1]), _p(up), _p(dn), _p(dr), _p(upc),
+            _p(dnc), _p(drc)), "sw_solver_2stream_clr_all")
+        if allsky_fluxes.flux_net is not None:
+            torch.sub(dn, up, out=allsky_fluxes.flux_net)
+        if clrsky_fluxes.flux_net is not None:
+            torch.sub(dnc, upc, out=clrsky_fluxes.flux_net)
+        return ""
     # aerosols by request: the masked fused solve is taken and the clear fluxes are broadband ones as well
     # (band-pair layout: the solver's aerosol instances need every band to start at an odd 1-based g-point)
     aer_req = (fused and AEROSOL_REQUEST and aerosol_by_request(aer_props, optical_props, OpticalProps2str)

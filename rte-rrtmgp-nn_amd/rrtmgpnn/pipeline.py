@@ -152,6 +152,10 @@ class ClearSkyStep:
     class layer's sequence.  "clrsky": True / "byband": True: also the clear-sky fluxes of the same columns / the by-band
     fluxes of a byband=True step under the sampled clouds, not the two together; the clrsky= and byband= arguments
     themselves are refused with mcica.
+    sw_dual (fused steps with clear-sky outputs): the SW chain's two solver launches are one call of
+    rrtmgpnn_sw_solver_2stream_rfmip_clr_all (sw_solver; no sw_solver_clr), which the context's
+    rrtmgpnn_context_set_sw_clr_all mode runs as the dual kernel or as the two launches; the same ten flux arrays, bit
+    for bit.  Refused without clear-sky outputs, with sw=False, fused=False or byband.
     jacobian: the step also owns lw_up_jac (ncol, nlay+1), the Jacobian of lw_up with respect to the surface
     temperature (rte_lw's flux_up_Jac), requested from the LW solver call; refused with byband, clrsky and their mcica
     keys.
@@ -163,8 +167,15 @@ class ClearSkyStep:
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
-                 clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False):
+                 clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False):
         self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica, aerosols, jacobian)
+        self.sw_dual = bool(sw_dual)
+        if self.sw_dual:
+            bad = [w for w, on in (("no clear-sky outputs (clrsky=True or mcica's 'clrsky')", not self.clrsky),
+                                   ("sw=False", not sw), ("fused=False", not fused), ("byband", self.byband)) if on]
+            if bad:
+                raise ValueError("sw_dual=True with %s is not supported: the clear + all-sky SW entry serves the fused "
+                                 "SW chain of a step with clear-sky outputs, broadband only" % ", ".join(bad))
         self.jacobian = bool(jacobian)
         self.lw_scattering = bool(lw_scattering)
         if self.lw_scattering:
@@ -629,7 +640,7 @@ class ClearSkyStep:
                 name, L.rrtmgpnn_sw_solver_2stream_rfmip,
                 (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("solar_source", "tsi", "sfc_alb", "sza")
                 + p("tau_sw", "ssa_sw") + (None,) + inc + p("toa", "alb", "mu0", *out))
-            return [
+            head = [
                 ("predict_nn_sw", L.rrtmgpnn_gas_optics_sw_nn,
                  (c, ncol, nlay, self.ng_sw, self.nx_sw) + p("play", "tlay", "plev") + h2o
                  + (self._g_sw, self._nd_sw, self._nets_sw) + ch.props),
@@ -638,6 +649,16 @@ class ClearSkyStep:
                 *self._clouds_in(ch),
                 *self._request(ch),
                 *self._aerosol_request(ch),
+            ]
+            if self.sw_dual:
+                # both flux sets from one call (rrtmgpnn_sw_solver_2stream_rfmip_clr_all): the same requests ahead of
+                # it, the clear outputs behind the all-sky ones
+                return head + [(
+                    "sw_solver", L.rrtmgpnn_sw_solver_2stream_rfmip_clr_all,
+                    (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("solar_source", "tsi", "sfc_alb", "sza")
+                    + p("tau_sw", "ssa_sw") + (None,) + band_inc
+                    + p("toa", "alb", "mu0", "sw_up", "sw_dn", "sw_dir", "sw_up_clr", "sw_dn_clr", "sw_dir_clr"))]
+            return head + [
                 solver("sw_solver", band_inc, "sw_up", "sw_dn", "sw_dir"),
                 # clear-sky fluxes: one more solver launch on the SW chain, on the gas optics' own properties (the fused
                 # solver leaves tau / ssa as they were).  Through the same entry without an increment: the
