@@ -67,6 +67,17 @@ int rrtmgpnn_context_set_sw_kernel(rrtmgpnn_context *ctx, int mode);
  * masked twins: 0 is mode 1 there too, measured 21 % faster than mode 2 at 10 000 x 60 columns.
  * ctx == NULL sets the default of every context not set itself. */
 int rrtmgpnn_context_set_lw_clr_all(rrtmgpnn_context *ctx, int mode);
+/* MI355X tuning, no reference counterpart: how rrtmgpnn_lw_solver_1rescl_planck_clr_all produces its two flux sets.
+ * 1: the dual kernel, one launch of the fused rescaled solver in which a lane also carries the clear radiance (down in
+ * the first pass, up in the second), reading tau, pfrac, the band rows and the mask word and building the Planck table
+ * once (one angle; several angles take mode 2).  2: rrtmgpnn_lw_solver_noscat_planck[_inc] for the clear set, then the
+ * single rescaled instance for the all-sky set.  0 (default): mode 1 -- at 10 000 x 60 columns, 256 g-points, under a
+ * sampled mask it took 1.829 ms against mode 2's 1.976 ms (7.5 %; sample spreads 0.047 and 0.030 ms) and with the
+ * aerosol 1.835 against 2.064 ms (11.1 %; spreads 0.024 and 0.025 ms); at 1800 x 60 3.8 % and 9.8 % (DESIGN.md
+ * section 3, profiles/lw_scat_dual_ab.txt).  Where the dual kernel's LDS would not fit, mode 1 takes the two launches.
+ * Bit-identical fluxes either way.  Any other value is RRTMGPNN_ERR_ARGUMENT.  ctx == NULL sets the default of every
+ * context not set itself. */
+int rrtmgpnn_context_set_lw_scat_clr_all(rrtmgpnn_context *ctx, int mode);
 /* MI355X tuning, no reference counterpart: how rrtmgpnn_sw_solver_2stream_clr_all and
  * rrtmgpnn_sw_solver_2stream_rfmip_clr_all produce their two flux sets.
  * 0 (default): mode 2 -- at 10 000 x 60 columns the dual kernel's gain over the two launches (1.3-1.8 % in four runs)
@@ -370,6 +381,32 @@ int rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          const int *band_lims_gpt, float temp_ref_min, float totplnk_delta,
                                          const float *totplnk, int emis_by_band, const float *sfc_emis,
                                          float *flux_up, float *flux_dn);
+/* Clear-sky beside all-sky LW fluxes for scattering clouds, with aerosols: rte_lw of
+ * extensions/mo_rrtmgp_clr_all_sky.F90:146-172 (clear sky = gases + aerosols, all sky = that + clouds) where the clouds
+ * are two-stream and rte_lw therefore takes the rescaled solver (rte/mo_rte_lw.F90:372-387).  The arguments of
+ * rrtmgpnn_lw_solver_1rescl_planck_inc in its order, then flux_up_clr, flux_dn_clr ((nlay+1, ncol) DEVICE, required).
+ * Requests it honours: rrtmgpnn_solver_request_cloud_mask, which switches the cloud in the all-sky set only, and a 1scl
+ * rrtmgpnn_solver_request_aerosol (ssa_aer and g_aer NULL) on the call's bands and extents, which goes into both sets:
+ * inc_2stream_by_1scalar_bybnd (rte/kernels/mo_optical_props_kernels.F90:426-484 holds it and the two-stream increment
+ * that follows), i.e. tau + tau_aer(b) with ssa = g = +0, before the cloud: (tau + tau_aer) + tau_bnd, two separately
+ * rounded adds.
+ * flux_up_clr / flux_dn_clr: bit for bit rrtmgpnn_lw_solver_noscat_planck on the same arguments, with an aerosol
+ * rrtmgpnn_lw_solver_noscat_planck_inc with tau_aer as its band increment (the rescaled solve of a 1scl atmosphere is the
+ * no-scattering one).  flux_up / flux_dn: bit for bit rrtmgpnn_lw_solver_1rescl_planck_inc under the same mask request,
+ * with an aerosol rrtmgpnn_increment_bybnd twice (aerosol, then cloud) and rrtmgpnn_lw_solver_1rescl.
+ * Refused with RRTMGPNN_ERR_ARGUMENT and a message naming this entry, every request cleared: a by-band request
+ * (separate or paired), a flux-Jacobian request, a 2str aerosol, mask or aerosol extents that are not the call's, NULL
+ * band or clear-sky arrays; ngpt > 256 is RRTMGPNN_ERR_UNSUPPORTED.  ncol == 0 is OK.  How the two sets are produced:
+ * rrtmgpnn_context_set_lw_scat_clr_all.  Operand bounds and workspace as rrtmgpnn_lw_solver_1rescl_planck_inc (the two
+ * launches of mode 2 share the context workspace in stream order).  No reference counterpart as one call. */
+int rrtmgpnn_lw_solver_1rescl_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
+                                             int nmus, const float *Ds, const float *weights, const float *inc_flux,
+                                             const float *tau, const float *tau_bnd, const float *ssa_bnd,
+                                             const float *g_bnd, const float *pfrac, int nbnd, int nPlanckTemp,
+                                             const float *tlay, const float *tlev, const float *tsfc, int sfc_lay,
+                                             const int *band_lims_gpt, float temp_ref_min, float totplnk_delta,
+                                             const float *totplnk, int emis_by_band, const float *sfc_emis,
+                                             float *flux_up, float *flux_dn, float *flux_up_clr, float *flux_dn_clr);
 /* rte_lw(..., use_2stream=.true.): lw_solver_2stream (rte/kernels/mo_rte_solver_kernels.F90:426-486) with
  * lw_two_stream (:1018-1069), lw_source_2str (:1112-1162) and adding (:1526-1637).  inc_flux (ngpt, ncol) is a flux
  * (NULL: zero); the layer sources are not used (as in the reference).  Broadband sums are sequential over g

@@ -38,6 +38,7 @@ extern int g_sw_kernel_default;  // rrtmgpnn_context_set_sw_kernel(NULL, mode)
 extern int g_mlp_kernel_default;  // rrtmgpnn_context_set_mlp_kernel(NULL, mode)
 extern int g_lw_clr_all_default;  // rrtmgpnn_context_set_lw_clr_all(NULL, mode)
 extern int g_sw_clr_all_default;  // rrtmgpnn_context_set_sw_clr_all(NULL, mode)
+extern int g_lw_scat_clr_all_default;  // rrtmgpnn_context_set_lw_scat_clr_all(NULL, mode)
 // Raise a kernel's dynamic-LDS limit to 160 KiB on the current device, once per (kernel, device): a function
 // attribute is per device, so a second GPU of the same process gets its own call.  Thread-safe; after the first
 // call for a (kernel, device) pair it makes no HIP call (hipGraph captures stay attribute-free).
@@ -132,6 +133,7 @@ struct rrtmgpnn_context {
   int mlp_kernel = -1;  // LW network tiling: 0 32x32x2 where instantiated, 1 16x16x4, -1 the library default
   int lw_clr_all = -1;  // clear + all-sky LW entry: 0 default, 1 the dual kernel, 2 two launches, -1 the library default
   int sw_clr_all = -1;  // clear + all-sky SW entries: the same modes
+  int lw_scat_clr_all = -1;  // clear + all-sky LW entry for scattering clouds: the same modes
   // rrtmgpnn_context_get_mlp_path: the kernel of this context's last network launch (kind, A's and B's (K1S, H1T, H2T),
   // flags), written by the launchers
   int mlp_path[8] = {0};
@@ -350,7 +352,11 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNosca
 // the rescaled solver on the fused-Planck path, tau incremented in-kernel by the band-resolved 2str set
 // (in.tau_bnd, ssa_bnd, g_bnd), which ex.mask_bits (or null) switches per g-point; broadband fluxes only
 int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in,
-                               const float *ssa_bnd, const float *g_bnd);
+                               const float *ssa_bnd, const float *g_bnd, float *flux_up_clr = nullptr,
+                               float *flux_dn_clr = nullptr);
+int launch_lw_rescl_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex, bool dual, const LwNoscat &p,
+                                   const LwPlanckIn &in, const float *ssa_bnd, const float *g_bnd, float *flux_up_clr,
+                                   float *flux_dn_clr);
 int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,
                       const float *inc_flux, const float *tau, const float *ssa, const float *g,
                       const float *lev_source, const float *sfc_emis, const float *sfc_source, float *flux_up,

@@ -257,15 +257,58 @@ static_assert(kScatPf >= 1 && kScatRing % kScatPf == 0, "prefetch depth must div
 struct RsIn {
   float t, y, yn, tb, wb, gb;
   uint32_t m;
+  float ta;  // kAer
 };
 
-template <bool kMask, int kPF>
+// the no-scattering layer of the clear radiance (kDual): lw_noscat_kernel's step, expression for expression, so the
+// clear fluxes carry the bits of rrtmgpnn_lw_solver_noscat_planck[_inc] (rs_layer with ssa = g = 0 gives the same
+// values wherever tau * D <= 2^126; this one also shares that kernel's division)
+struct NsLayer {
+  float trans, sdn, sup;
+};
+
+__device__ __forceinline__ NsLayer ns_layer(float tau, float D, float lay, float lev_l, float lev_lp1,
+                                            const uint64_t *etab)
+{
+  const float tau_thresh = sqrtf(FLT_EPSILON);
+  NsLayer r;
+  const float t = tau * D;
+  const float T = solver_exp_neg(-t, etab);
+  const float fact = (t > tau_thresh) ? solver_div(1.0f - T, t) - T : t * (0.5f - 1.0f / 3.0f * t);
+  r.trans = T;
+  r.sdn = (1.0f - T) * lev_lp1 + 2.0f * fact * (lay - lev_lp1);
+  r.sup = (1.0f - T) * lev_l + 2.0f * fact * (lay - lev_l);
+  return r;
+}
+
+// the arguments of the kAer / kDual instances only: the others' argument list is the one they had
+template <bool kOn>
+struct ScatDualArgs {};
+template <>
+struct ScatDualArgs<true> {
+  const float *tau_aer;              // kAer: (nbnd, nlay, ncol)
+  float *flux_up_clr, *flux_dn_clr;  // kDual: (nlay+1, ncol)
+};
+
+// kAer (rrtmgpnn_lw_solver_1rescl_planck_clr_all with an aerosol request): a second, unmasked band increment tau_aer
+// (nbnd, nlay, ncol) in front of the cloud's -- inc_2stream_by_1scalar_bybnd, which leaves ssa = g = +0 and
+// tau + tau_aer(band), then inc_2str with the cloud: two separately rounded adds, (tau + tau_aer) + tau_cld.  One more
+// band value per prefetched layer, read as tau_bnd is (same band offset, its own column base).  The mask never
+// switches it.
+//
+// kDual (one angle; the same entry in mode 1): clear-sky fluxes (gases [+ aerosols], no scattering) beside the all-sky
+// ones from one read of tau, pfrac, the band rows and the mask word and one Planck table (rte_lw of
+// extensions/mo_rrtmgp_clr_all_sky.F90:146-172).  Each lane carries the clear radiance of t_clr = tau [+ tau_aer]
+// through ns_layer: down in pass 1, up in pass 2; pass 3 has nothing to add for it.  The clear values are staged in a
+// second ring ([2][kScatRing][ngpt]: 0 = all-sky, 1 = clear) and reduced to part planes 2 (up) and 3 (dn): clear down
+// by pass 1's own flushes (the all-sky radiance stages nothing there), clear up beside all-sky up by pass 2's.
+template <bool kMask, int kPF, bool kAer, bool kDual>
 __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
     int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang, const float *__restrict__ inc_flux,
     const float *__restrict__ tau, const float *__restrict__ pfrac, const float *__restrict__ tau_bnd,
     const float *__restrict__ ssa_bnd, const float *__restrict__ g_bnd, const float *__restrict__ emis, LwPlanck pl,
     BandArgs bands, const uint32_t *__restrict__ cmask, float *__restrict__ ws, float *__restrict__ flux_up,
-    float *__restrict__ flux_dn)
+    float *__restrict__ flux_dn, ScatDualArgs<kAer || kDual> da)
 {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
@@ -274,10 +317,11 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
   const int nlev = nlay + 1, nbnd = bands.nbnd, brow = 2 * nlay + 1;
   uint64_t *etab = (uint64_t *)(smem + kExpTabOff);
   float *btab = smem + kExpTabFloats;
-  float *ring = btab + lw_btab_floats(nbnd, nlay);  // [kScatRing][ngpt]
-  float *part = ring + (size_t)kScatRing * ngpt;    // [2][nlev][4]: 0 = dn, 1 = up
+  float *ring = btab + lw_btab_floats(nbnd, nlay);  // [kScatRing][ngpt]; kDual: [2][kScatRing][ngpt]
+  // [2][nlev][4]: 0 = dn, 1 = up; kDual: [4][nlev][4]: and 2 = clear up, 3 = clear dn
+  float *part = ring + (size_t)(kDual ? 2 : 1) * kScatRing * ngpt;
   load_exp_table(etab);
-  const bool multi = ang.nmus > 1;
+  const bool multi = !kDual && ang.nmus > 1;
   float *W = ws + (size_t)(multi ? 3 : 1) * nlev * ngpt * icol, *acc_base = W + (size_t)nlev * ngpt;
   auto X = [&](int l) { return (size_t)gc + (size_t)ngpt * l; };
   // column-local descriptors (rte_device.hpp): the layer offset is an SGPR, the lane's offset a VGPR
@@ -289,6 +333,9 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
   const size_t cb = (size_t)nbnd * nlay * icol;
   const ColArr Ttb(tau_bnd, cb, irow * nlay), Twb(ssa_bnd, cb, irow * nlay), Tgb(g_bnd, cb, irow * nlay);
   const ColArr Tmsk(kMask ? (const float *)cmask : tau, kMask ? (size_t)nw * nlay * icol : 0, mrow * nlay);
+  const float *aer_base = tau;
+  if constexpr (kAer) aer_base = da.tau_aer;
+  const ColArr Taer(aer_base, kAer ? cb : 0, irow * nlay);
   auto load = [&](int l) {
     RsIn d;
     d.t = Ttau.ld(vg, row * (uint32_t)l);
@@ -298,6 +345,7 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
     d.wb = Twb.ld(vb, irow * (uint32_t)l);
     d.gb = Tgb.ld(vb, irow * (uint32_t)l);
     d.m = kMask ? __float_as_uint(Tmsk.ld(vm, mrow * (uint32_t)l)) : 0u;
+    d.ta = kAer ? Taer.ld(vb, irow * (uint32_t)l) : 0.0f;
     return d;
   };
   const float ysfc = Tpf.ld(vg, row * (uint32_t)(pl.sfc_lay - 1));
@@ -338,14 +386,147 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
   auto layer = [&](const RsIn &d, int l, float D) {
     const bool cld = !kMask || (d.m & mbit) != 0;
     float t = d.t, w = 0.0f, gq = 0.0f;
+    if constexpr (kAer) t = d.t + d.ta;
     inc_2str(t, w, gq, cld ? d.tb : 0.0f, cld ? d.wb : 0.0f, cld ? d.gb : 0.0f);
     return rs_layer(t, w, gq, D, d.y * bl[l], d.y * bl[nlay + l], d.yn * bl[nlay + l + 1], etab);
+  };
+  // kDual: the clear layer, from the same operands
+  auto layer_clr = [&](const RsIn &d, int l, float D) {
+    float t = d.t;
+    if constexpr (kAer) t = d.t + d.ta;
+    return ns_layer(t, D, d.y * bl[l], d.y * bl[nlay + l], d.yn * bl[nlay + l + 1], etab);
   };
   const int top = top_at_1 ? 0 : nlay, sfcl = top_at_1 ? nlay : 0, dl_dn = top_at_1 ? 1 : -1;
   auto lay_dn = [&](int j) { return top_at_1 ? j : nlay - 1 - j; };  // j-th layer from the top
   auto lay_up = [&](int j) { return top_at_1 ? nlay - 1 - j : j; };  // j-th layer from the surface
   float *pdn = part, *pup = part + (size_t)nlev * 4;
 
+  if constexpr (kDual) {
+    // One angle.  The loops below are the single instance's with the clear radiance beside the all-sky one; kept apart
+    // from them so that the single instances compile from the text they had.  A COPY: a change to the prefetch, the
+    // workspace reads or the flush windows of the three passes after this block belongs here too, and the other way.
+    float *const ring_clr = ring + (size_t)kScatRing * ngpt;
+    float *const pup_clr = part + (size_t)2 * nlev * 4, *const pdn_clr = part + (size_t)3 * nlev * 4;
+    const float D = ang.D[0];
+    const float fac = (ngpt & 3) == 0 ? 2.0f * kPi * ang.w[0] : 1.0f;  // quirk B-5 as noscat
+    auto put = [&](float v, int r) {
+      if (on) ring[(size_t)r * ngpt + g] = v;
+    };
+    auto put_clr = [&](float v, int r) {
+      if (on) ring_clr[(size_t)r * ngpt + g] = v;
+    };
+    // the clear ring alone (pass 1), both rings (pass 2: part planes 1 and 2), the all-sky ring alone (pass 3)
+    auto flush_clr_dn = [&](int n, int lev0, int dl) {
+      ring_flush<kScatRing>(ring_clr, pdn_clr, 1, n, lev0, dl, ngpt, nlev, false);
+    };
+    auto flush_up = [&](int n, int lev0, int dl) { ring_flush<kScatRing>(ring, pup, 2, n, lev0, dl, ngpt, nlev, false); };
+    auto flush_dn = [&](int n, int lev0, int dl) { ring_flush<kScatRing>(ring, pdn, 1, n, lev0, dl, ngpt, nlev, false); };
+    RsIn pf[kPF];
+    float pw[kPF];
+    // 1: down, no scattering: the all-sky radiance with the rescaled optics into W, the clear one into its ring
+    const float I0 = inc / (2.0f * kPi * ang.w[0]);
+    float I = I0, Ic = I0;
+    if (on) W[X(top)] = I;
+#pragma unroll
+    for (int p = 0; p < kPF; p++) pf[p] = load(lay_dn(min(p, nlay - 1)));
+    put_clr(fac * Ic, 0);
+    flush_clr_dn(1, top, 1);
+    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
+#pragma unroll
+      for (int s = 0; s < kScatRing; s++) {
+        const int j = j0 + s, p = s % kPF, l = lay_dn(min(j, nlay - 1));
+        const RsIn d = pf[p];
+        pf[p] = load(lay_dn(min(j + kPF, nlay - 1)));
+        if (j < nlay) {
+          const RsLayer r = layer(d, l, D);
+          I = r.trans * I + r.sdn;
+          if (on) W[X(top_at_1 ? l + 1 : l)] = I;
+          const NsLayer c = layer_clr(d, l, D);
+          Ic = c.trans * Ic + c.sdn;
+          put_clr(fac * Ic, s);
+        }
+      }
+      flush_clr_dn(min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
+    }
+    // surface reflection and emission
+    float U = I * (1.0f - e) + e * ss;
+    float Uc = Ic * (1.0f - e) + e * ss;
+    if (on) W[X(sfcl)] = U;
+    put(fac * U, 0);
+    put_clr(fac * Uc, 0);
+    flush_up(1, sfcl, 1);
+    // 2: up
+    auto ltop_of = [&](int l) { return top_at_1 ? l : l + 1; };
+#pragma unroll
+    for (int p = 0; p < kPF; p++) {
+      const int l = lay_up(min(p, nlay - 1));
+      pf[p] = load(l);
+      pw[p] = W[X(ltop_of(l))];
+    }
+    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
+#pragma unroll
+      for (int s = 0; s < kScatRing; s++) {
+        const int j = j0 + s, p = s % kPF, l = lay_up(min(j, nlay - 1)), ltop = ltop_of(l);
+        const RsIn d = pf[p];
+        const float wd = pw[p];
+        {
+          const int ln = lay_up(min(j + kPF, nlay - 1));
+          pf[p] = load(ln);
+          pw[p] = W[X(ltop_of(ln))];
+        }
+        if (j < nlay) {
+          const RsLayer r = layer(d, l, D);
+          const float adj = r.Cn * (r.An * wd - r.trans * r.sdn - r.sup);
+          U = r.trans * U + r.sup + adj;
+          if (on) W[X(ltop)] = U;
+          put(fac * U, s);
+          const NsLayer c = layer_clr(d, l, D);
+          Uc = c.trans * Uc + c.sup;
+          put_clr(fac * Uc, s);
+        }
+      }
+      flush_up(min(kScatRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
+    }
+    // 3: down again, the all-sky radiance only
+    I = I0;
+    put(fac * I, 0);
+#pragma unroll
+    for (int p = 0; p < kPF; p++) {
+      const int l = lay_dn(min(p, nlay - 1));
+      pf[p] = load(l);
+      pw[p] = W[X(l)];
+    }
+    flush_dn(1, top, 1);
+    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
+#pragma unroll
+      for (int s = 0; s < kScatRing; s++) {
+        const int j = j0 + s, p = s % kPF, l = lay_dn(min(j, nlay - 1));
+        const RsIn d = pf[p];
+        const float wu = pw[p];
+        {
+          const int ln = lay_dn(min(j + kPF, nlay - 1));
+          pf[p] = load(ln);
+          pw[p] = W[X(ln)];
+        }
+        if (j < nlay) {
+          const RsLayer r = layer(d, l, D);
+          const float adj = r.Cn * (r.An * wu - r.trans * r.sup - r.sdn);
+          I = r.trans * I + r.sdn + adj;
+          put(fac * I, s);
+        }
+      }
+      flush_dn(min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
+    }
+    for (int l = g; l < nlev; l += blockDim.x) {
+      flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
+      flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
+      da.flux_dn_clr[l + (size_t)nlev * icol] = combine4(pdn_clr + 4 * l);
+      da.flux_up_clr[l + (size_t)nlev * icol] = combine4(pup_clr + 4 * l);
+    }
+    return;
+  }
+
+  // (the three passes below have a copy in the kDual block above: keep the two in step)
   for (int imu = 0; imu < ang.nmus; imu++) {
     const float D = ang.D[imu];
     const float fac = (multi || (ngpt & 3) == 0) ? 2.0f * kPi * ang.w[imu] : 1.0f;  // quirk B-5 as noscat
@@ -636,23 +817,35 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNosca
   return RRTMGPNN_OK;
 }
 
+// lw_rescl_planck_inc_kernel's LDS in bytes; dual: two rings, four part planes
+static size_t lw_rescl_planck_lds(int nbnd, int nlay, int ngpt, bool dual)
+{
+  return sizeof(float) * (kExpTabFloats + lw_btab_floats(nbnd, nlay) + (size_t)(dual ? 2 : 1) * kScatRing * ngpt +
+                          (size_t)(dual ? 4 : 2) * (nlay + 1) * 4);
+}
+
 // in.tau_bnd, ssa_bnd, g_bnd: the band-resolved two-stream increment; ex.mask_bits, or null: the McICA mask that
-// switches it.  No other extras have an instance (the entry refuses them).
+// switches it; ex.aer_tau, or null: the 1scl aerosol in front of it (from the _clr_all entry only: _1rescl_planck_inc
+// refuses the request).  flux_up_clr / flux_dn_clr set (both; one angle): the dual instance.  No other extras have an
+// instance (the entries refuse them).
 int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in,
-                               const float *ssa_bnd, const float *g_bnd)
+                               const float *ssa_bnd, const float *g_bnd, float *flux_up_clr, float *flux_dn_clr)
 {
   const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol, nmus = p.nmus;
   if (ncol == 0) return RRTMGPNN_OK;
   if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
   if (ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
-  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.aer_tau || ex.lw_Ds)
+  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.lw_Ds)
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): broadband fluxes only");
+  const bool dual = flux_up_clr != nullptr;
+  if (dual && (!flux_dn_clr || nmus != 1))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): the dual instance runs one "
+                                          "angle and writes both clear-sky arrays");
   LwAngles a{};
   a.nmus = nmus;
   for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
   const int threads = (ngpt + 63) / 64 * 64;
-  const size_t lds = sizeof(float) * (kExpTabFloats + lw_btab_floats(in.bands.nbnd, nlay) + (size_t)kScatRing * ngpt +
-                                      (size_t)2 * (nlay + 1) * 4);
+  const size_t lds = lw_rescl_planck_lds(in.bands.nbnd, nlay, ngpt, dual);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
   void *ws = nullptr;
   const int planes = nmus > 1 ? 3 : 1;  // the shared radn_dn / radn_up plane, and the two angle accumulators
@@ -660,12 +853,68 @@ int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, co
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
                        p.tau, in.pfrac, in.tau_bnd, ssa_bnd, g_bnd, p.sfc_emis, in.pl, in.bands, ex.mask_bits,
-                       (float *)ws, p.flux_up, p.flux_dn);
+                       (float *)ws, p.flux_up, p.flux_dn, ScatDualArgs<false>{});
   };
-  if (ex.mask_bits) go(lw_rescl_planck_inc_kernel<true, kScatPf>);
-  else              go(lw_rescl_planck_inc_kernel<false, kScatPf>);
+  // the kAer / kDual instances, with their own arguments
+  auto go2 = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
+                       p.tau, in.pfrac, in.tau_bnd, ssa_bnd, g_bnd, p.sfc_emis, in.pl, in.bands, ex.mask_bits,
+                       (float *)ws, p.flux_up, p.flux_dn, ScatDualArgs<true>{ex.aer_tau, flux_up_clr, flux_dn_clr});
+  };
+  const bool m = ex.mask_bits != nullptr, aer = ex.aer_tau != nullptr;
+  if (dual) {
+    if (aer && m)  go2(lw_rescl_planck_inc_kernel<true, kScatPf, true, true>);
+    else if (aer)  go2(lw_rescl_planck_inc_kernel<false, kScatPf, true, true>);
+    else if (m)    go2(lw_rescl_planck_inc_kernel<true, kScatPf, false, true>);
+    else           go2(lw_rescl_planck_inc_kernel<false, kScatPf, false, true>);
+  } else if (aer) {
+    if (m) go2(lw_rescl_planck_inc_kernel<true, kScatPf, true, false>);
+    else   go2(lw_rescl_planck_inc_kernel<false, kScatPf, true, false>);
+  } else {
+    if (m) go(lw_rescl_planck_inc_kernel<true, kScatPf, false, false>);
+    else   go(lw_rescl_planck_inc_kernel<false, kScatPf, false, false>);
+  }
   RRTMGPNN_LAUNCH_CHECK("lw_rescl_planck_inc_kernel");
   return RRTMGPNN_OK;
+}
+
+// rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 for scattering clouds (rte/mo_rte_lw.F90:372-387): clear-sky
+// fluxes of tau [+ ex.aer_tau] without scattering, all-sky fluxes of that incremented by the (masked) two-stream cloud
+// through the rescaled solver.  dual (one angle only, and where the dual instance's LDS fits: it holds one more ring and
+// two more part planes than the single one, so at large nlay x nbnd the two launches still serve): one launch of the
+// dual instance; otherwise the no-scattering launcher (the aerosol as its increment) and the non-dual instance back to
+// back on the context's stream.  Identical bits either way.  The mask belongs to the all-sky launch only.  The all-sky
+// launcher's limits and workspace are checked before the clear launch is issued, so a refused call writes nothing.
+int launch_lw_rescl_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex, bool dual, const LwNoscat &p,
+                                   const LwPlanckIn &in, const float *ssa_bnd, const float *g_bnd, float *flux_up_clr,
+                                   float *flux_dn_clr)
+{
+  if (p.ncol == 0) return RRTMGPNN_OK;
+  if (dual && p.nmus == 1 && lw_rescl_planck_lds(in.bands.nbnd, p.nlay, p.ngpt, true) <= 64 * 1024)
+    return launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd, flux_up_clr, flux_dn_clr);
+  // what launch_lw_rescl_planck_inc would refuse, ahead of the clear launch
+  if (p.nmus < 1 || p.nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
+  if (p.ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
+  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.lw_Ds)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): broadband fluxes only");
+  if (lw_rescl_planck_lds(in.bands.nbnd, p.nlay, p.ngpt, false) > 64 * 1024)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
+  {
+    // the larger of the two launches' workspaces (the clear launch accumulates in two planes with several angles)
+    void *ws = nullptr;
+    const int planes = p.nmus > 1 ? 3 : 1;
+    if (int rc = ctx->workspace(sizeof(float) * planes * (size_t)p.ngpt * (p.nlay + 1) * p.ncol, &ws)) return rc;
+  }
+  SolverExtras clear_ex = ex;
+  clear_ex.mask_bits = nullptr;
+  clear_ex.aer_tau = nullptr;
+  LwNoscat clear = p;
+  clear.flux_up = flux_up_clr;
+  clear.flux_dn = flux_dn_clr;
+  LwPlanckIn clear_in = in;
+  clear_in.tau_bnd = ex.aer_tau;
+  if (int rc = launch_lw_noscat_planck(ctx, clear_ex, clear, clear_in)) return rc;
+  return launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd, nullptr, nullptr);
 }
 
 int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,

@@ -11,12 +11,14 @@
 ! band cloud optical depth read once, both flux sets from one kernel with one angle) when the cloud properties are
 ! 1scl and defined by band on the k-distribution's bands, gas optics left the Planck sources unformed
 ! (ty_source_func_lw%planck_deferred), and both flux objects want broadband up / down fluxes only.  With 2str clouds
-! (LW scattering: the rescaled solver) in the same situation and no aerosols it takes the fused scattering route: gas
-! optics into a 1scl object (no ssa / g arrays), the clear solve rrtmgpnn_lw_solver_noscat_planck (the rescaled solver
-! with ssa = g = 0 is the no-scattering one, bit for bit) and the all-sky solve rrtmgpnn_lw_solver_1rescl_planck_inc,
-! which increments tau by the two-stream band cloud as it reads it.  Every other case -- 2str clouds with aerosols,
-! clouds on g-points, g-point, by-band or net outputs -- runs the two solves with mo_rte_lw's rte_lw.  rte_sw always
-! runs the two solves.
+! (LW scattering: the rescaled solver) in the same situation, without aerosols or with aerosols of the fused kind, it
+! takes the fused scattering route: gas optics into a 1scl object (no ssa / g arrays), the clear solve
+! rrtmgpnn_lw_solver_noscat_planck (the rescaled solver with ssa = g = 0 is the no-scattering one, bit for bit) and the
+! all-sky solve rrtmgpnn_lw_solver_1rescl_planck_inc, which increments tau by the two-stream band cloud as it reads it;
+! with the aerosols one call of rrtmgpnn_lw_solver_1rescl_planck_clr_all under the aerosol request gives both sets, the
+! clear sky gases + aerosols.  Every other case -- 2str
+! clouds with other aerosols, clouds on g-points, g-point, by-band or net outputs -- runs the two solves with
+! mo_rte_lw's rte_lw.  rte_sw always runs the two solves.
 !
 ! aer_props: where rte_lw takes the dual entry and the aerosols are of the fused kind (1scl, defined by band on the
 ! k-distribution's bands, the same ncol and nlay), they are not added to the g-point array by aer_props%increment but
@@ -74,7 +76,7 @@ contains
     class(ty_optical_props_arry), allocatable :: optical_props
     type(ty_source_func_lw) :: sources
     integer :: ncol, nlay, ngpt, nband, nmus
-    logical :: top_at_1, dual, aer_req, scat
+    logical :: top_at_1, dual, aer_req, scat, aer_scat
 
     error_msg = ""
     ncol  = size(p_lay, 2)
@@ -105,12 +107,21 @@ contains
     if (len_trim(error_msg) > 0) return
     nmus = 1
     if (present(n_gauss_angles)) nmus = n_gauss_angles
-    ! scattering clouds by band, no aerosols, broadband fluxes: the gas atmosphere stays 1scl (its ssa and g are the
-    ! solver's literal zeros, never arrays)
+    ! scattering clouds by band, broadband fluxes, no aerosols or aerosols of the fused kind (1scl, by band on the
+    ! k-distribution's bands, the call's extents: they go to the solver as its aerosol request): the gas atmosphere stays
+    ! 1scl (its ssa and g are the solver's literal zeros, never arrays)
     scat = .false.
+    aer_scat = .false.
+    if (present(aer_props)) then
+      select type (aer_props)
+      class is (ty_optical_props_1scl)
+        aer_scat = aer_props%bands_are_equal(optical_props) .and. .not. aer_props%gpoints_are_equal(optical_props) .and. &
+                   aer_props%get_ngpt() == nband .and. aer_props%get_ncol() == ncol .and. aer_props%get_nlay() == nlay
+      end select
+    end if
     select type (cloud_props)
     class is (ty_optical_props_2str)
-      scat = .not. present(aer_props) .and. cloud_props%bands_are_equal(optical_props) .and. &
+      scat = (.not. present(aer_props) .or. aer_scat) .and. cloud_props%bands_are_equal(optical_props) .and. &
              .not. cloud_props%gpoints_are_equal(optical_props) .and. cloud_props%get_ngpt() == nband .and. &
              cloud_props%get_ncol() == ncol .and. cloud_props%get_nlay() == nlay .and. &
              broadband_only(allsky_fluxes) .and. broadband_only(clrsky_fluxes) .and. nmus >= 1 .and. nmus <= 4 .and. &
@@ -162,7 +173,8 @@ contains
                   aer_props%get_ngpt() == nband .and. aer_props%get_ncol() == ncol .and. aer_props%get_nlay() == nlay
       end select
     end if
-    if (present(aer_props) .and. .not. aer_req) error_msg = aer_props%increment(optical_props)
+    if (present(aer_props) .and. .not. aer_req .and. .not. (scat .and. aer_scat)) &
+      error_msg = aer_props%increment(optical_props)
     if (error_msg /= '') return
     if (dual) then
       error_msg = allsky_fluxes%check_extents(nlay + 1, ncol)
@@ -234,8 +246,9 @@ contains
       call dev_release(d_up); call dev_release(d_dn); call dev_release(d_upc); call dev_release(d_dnc)
     end subroutine solve_dual
 
-    ! scattering clouds: the clear solve of tau by the no-scattering fused-Planck entry, then the all-sky solve by the
-    ! rescaled one, which increments (tau, 0, 0) by the cloud's (tau, ssa, g)(band) as it reads tau
+    ! scattering clouds: the clear solve of tau without scattering and the all-sky solve by the rescaled solver, which
+    ! increments (tau, 0, 0) by the cloud's (tau, ssa, g)(band) as it reads tau; with aerosols of the fused kind both
+    ! from rrtmgpnn_lw_solver_1rescl_planck_clr_all under the aerosol request, tau + tau_aer(band) in both sets
     subroutine solve_scat()
       integer(c_long_long) :: ng, nv, nc
       integer(c_int), allocatable :: lims(:,:)
@@ -253,22 +266,46 @@ contains
       d_tlay = dev_present(sources%pk_tlay, size(sources%pk_tlay, kind=c_long_long), PRESENT_READ)
       d_tlev = dev_present(sources%pk_tlev, size(sources%pk_tlev, kind=c_long_long), PRESENT_READ)
       d_tsfc = dev_present(sources%pk_tsfc, size(sources%pk_tsfc, kind=c_long_long), PRESENT_READ)
-      error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
-                    merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
-                    d_tau, d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
-                    sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_upc, d_dnc), &
-                    "rte_lw: lw_solver_noscat (clear sky)")
-      select type (cloud_props)
-      class is (ty_optical_props_2str)
-        if (error_msg == '') &
-        error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+      if (aer_scat) then
+        ! aerosols: armed for the solver call below, which clears it whatever it returns; both flux sets from the one
+        ! entry, the clear sky gases + aerosols
+        select type (aer_props)
+        class is (ty_optical_props_1scl)
+          error_msg = rrtmgpnn_check(c_rrtmgpnn_solver_request_aerosol(rrtmgpnn_ctx(), nband, nlay, ncol, &
+                        dev_present(aer_props%tau, nc, PRESENT_READ), c_null_ptr, c_null_ptr), &
+                        "rte_lw: solver_request_aerosol")
+        end select
+        select type (cloud_props)
+        class is (ty_optical_props_2str)
+          if (error_msg == '') &
+          error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_planck_clr_all(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                        merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
+                        d_tau, dev_present(cloud_props%tau, nc, PRESENT_READ), &
+                        dev_present(cloud_props%ssa, nc, PRESENT_READ), dev_present(cloud_props%g, nc, PRESENT_READ), &
+                        d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
+                        sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_up, d_dn, d_upc, &
+                        d_dnc), "rte_lw: lw_solver_1rescl (clear + all sky, scattering clouds, aerosols)")
+        end select
+      else
+        ! no aerosols: the clear solve by the no-scattering fused-Planck entry, then the all-sky solve by the rescaled
+        ! one (the same bits as the one entry gives)
+        error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
                       merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
-                      d_tau, dev_present(cloud_props%tau, nc, PRESENT_READ), &
-                      dev_present(cloud_props%ssa, nc, PRESENT_READ), dev_present(cloud_props%g, nc, PRESENT_READ), &
-                      d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
-                      sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_up, d_dn), &
-                      "rte_lw: lw_solver_1rescl (all sky, scattering clouds)")
-      end select
+                      d_tau, d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
+                      sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_upc, d_dnc), &
+                      "rte_lw: lw_solver_noscat (clear sky)")
+        select type (cloud_props)
+        class is (ty_optical_props_2str)
+          if (error_msg == '') &
+          error_msg = rrtmgpnn_check(c_rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_ctx(), ngpt, nlay, ncol, &
+                        merge(1_c_int, 0_c_int, top_at_1), nmus, gauss_Ds(1:nmus, nmus), gauss_wts(1:nmus, nmus), d_inc, &
+                        d_tau, dev_present(cloud_props%tau, nc, PRESENT_READ), &
+                        dev_present(cloud_props%ssa, nc, PRESENT_READ), dev_present(cloud_props%g, nc, PRESENT_READ), &
+                        d_pf, nband, sources%pk_ntemp, d_tlay, d_tlev, d_tsfc, sources%pk_sfc_lay, lims, &
+                        sources%pk_tmin, sources%pk_tdelta, sources%pk_totplnk, 1_c_int, d_emis, d_up, d_dn), &
+                        "rte_lw: lw_solver_1rescl (all sky, scattering clouds)")
+        end select
+      end if
       if (error_msg == '') then
         call dev_copy_out(allsky_fluxes%flux_up, d_up, nv)
         call dev_copy_out(allsky_fluxes%flux_dn, d_dn, nv)

@@ -20,6 +20,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_sw_solver_2stream_clr_all, c_rrtmgpnn_sw_solver_2stream_rfmip_clr_all
   public :: c_rrtmgpnn_context_set_sw_clr_all
   public :: c_rrtmgpnn_lw_solver_1rescl_planck_inc
+  public :: c_rrtmgpnn_lw_solver_1rescl_planck_clr_all, c_rrtmgpnn_context_set_lw_scat_clr_all
   public :: c_rrtmgpnn_lw_solver_noscat_gpt, c_rrtmgpnn_lw_solver_noscat_planck_gpt, c_rrtmgpnn_sw_solver_2stream_gpt
   public :: c_rrtmgpnn_lw_solver_1rescl_gpt, c_rrtmgpnn_lw_solver_2stream_gpt, c_rrtmgpnn_sw_solver_noscat_gpt
   public :: c_rrtmgpnn_solver_request_byband, c_rrtmgpnn_sum_byband
@@ -176,6 +177,25 @@ module mo_rrtmgpnn_c
       real(c_float), dimension(*), intent(in) :: Ds, weights
       integer(c_int), dimension(*), intent(in) :: band_lims_gpt
       real(c_float), value :: temp_ref_min, totplnk_delta
+    end function
+    ! ... with the clear-sky fluxes (gases [+ a requested 1scl aerosol], no scattering) beside the all-sky ones
+    integer(c_int) function c_rrtmgpnn_lw_solver_1rescl_planck_clr_all(ctx, ngpt, nlay, ncol, top_at_1, nmus, Ds, &
+        weights, inc_flux, tau, tau_bnd, ssa_bnd, g_bnd, pfrac, nbnd, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, &
+        band_lims_gpt, temp_ref_min, totplnk_delta, totplnk, emis_by_band, sfc_emis, flux_up, flux_dn, flux_up_clr, &
+        flux_dn_clr) bind(C, name="rrtmgpnn_lw_solver_1rescl_planck_clr_all")
+      import :: c_int, c_ptr, c_float
+      type(c_ptr), value :: ctx, inc_flux, tau, tau_bnd, ssa_bnd, g_bnd, pfrac, tlay, tlev, tsfc, totplnk, sfc_emis, &
+                            flux_up, flux_dn, flux_up_clr, flux_dn_clr
+      integer(c_int), value :: ngpt, nlay, ncol, top_at_1, nmus, nbnd, nPlanckTemp, sfc_lay, emis_by_band
+      real(c_float), dimension(*), intent(in) :: Ds, weights
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
+      real(c_float), value :: temp_ref_min, totplnk_delta
+    end function
+    integer(c_int) function c_rrtmgpnn_context_set_lw_scat_clr_all(ctx, mode) &
+        bind(C, name="rrtmgpnn_context_set_lw_scat_clr_all")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: mode
     end function
     integer(c_int) function c_rrtmgpnn_context_set_lw_clr_all(ctx, mode) bind(C, name="rrtmgpnn_context_set_lw_clr_all")
       import :: c_int, c_ptr

@@ -95,6 +95,11 @@ SIGNATURES = {
                                                      P(c_float), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                                                      c_vp, c_vp, c_vp, c_int, P(c_int), c_float, c_float, c_vp, c_int,
                                                      c_vp, c_vp, c_vp]),
+    "rrtmgpnn_lw_solver_1rescl_planck_clr_all": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, P(c_float),
+                                                         P(c_float), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                                                         c_vp, c_vp, c_vp, c_int, P(c_int), c_float, c_float, c_vp,
+                                                         c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_context_set_lw_scat_clr_all": (c_int, [c_vp, c_int]),
     "rrtmgpnn_lw_solver_2stream": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 9),
     "rrtmgpnn_sw_solver_2stream": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_vp, c_vp, c_vp]),

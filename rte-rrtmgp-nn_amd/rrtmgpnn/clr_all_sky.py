@@ -11,12 +11,14 @@ rte_lw takes the library's dual entry (rrtmgpnn_lw_solver_noscat_planck_clr_all:
 band cloud optical depth read once, both flux sets from one kernel with one angle) when the cloud properties are
 1scl and defined by band on k_dist's bands and both flux objects want broadband up / down fluxes only; gas optics then
 leaves the Planck sources unformed and the kernel forms them.  With 2str clouds (LW scattering: the rescaled solver) in
-the same situation and no aerosols it takes the fused scattering route: gas optics into a 1scl object (no ssa / g
-arrays), the clear solve rrtmgpnn_lw_solver_noscat_planck (the rescaled solver with ssa = g = 0 is the no-scattering
-one, bit for bit) and the all-sky solve rrtmgpnn_lw_solver_1rescl_planck_inc, the cloud mask armed when mask_bits is
-given; LW_SCAT_FUSED = False keeps the sequence below (the comparison route).  Every other case -- 2str clouds with
-aerosols, clouds on g-points, g-point or by-band outputs -- runs the two solves with api.rte_lw.  rte_sw always runs two
-solves.
+the same situation, without aerosols or with aerosols of the fused kind (aerosol_by_request: 1scl, by band, same
+extents), it takes the fused scattering route: gas optics into a 1scl object (no ssa / g arrays) and one call of
+rrtmgpnn_lw_solver_1rescl_planck_clr_all, the cloud mask armed when mask_bits is given and the aerosols armed as its
+aerosol request: clear sky = gases [+ aerosols] without scattering (the rescaled solver with ssa = g = 0 is the
+no-scattering one, bit for bit), all sky = that + the clouds, the same bits as the sequence; the context's
+rrtmgpnn_context_set_lw_scat_clr_all mode decides one dual launch or two.  LW_SCAT_FUSED = False keeps the sequence
+below (the comparison route).  Every other case -- 2str clouds with other aerosols, clouds on g-points, g-point or
+by-band outputs -- runs the two solves with api.rte_lw.
 
 mask_bits= / cloud_mask= (both functions; not in the reference's interface) make the all-sky solve a McICA one: the band
 cloud is sampled per g-point by a mask from cloud_sampling.sampled_mask_*.  Where rte_lw would take the dual entry it
@@ -51,13 +53,15 @@ LW_SCAT_FUSED = True
 SW_CLR_ALL_FUSED = True
 
 
-def aerosol_by_request(aer_props, optical_props, kind):
+def aerosol_by_request(aer_props, optical_props, kind, extents=None):
     """Are these aerosols of the fused kind for a solve on optical_props -- `kind` (OpticalProps1scl for the LW,
-    OpticalProps2str for the SW), defined by band (ngpt == nband) on optical_props' bands, the same (ncol, nlay)?"""
+    OpticalProps2str for the SW), defined by band (ngpt == nband) on optical_props' bands, the same (ncol, nlay)?
+    extents: (ncol, nlay) of an optical_props that is initialised but holds no arrays yet."""
     return (aer_props is not None and isinstance(aer_props, kind) and isinstance(optical_props, kind)
             and aer_props.bands_are_equal(optical_props) and aer_props.get_ngpt() == optical_props.get_nband()
             and not aer_props.gpoints_are_equal(optical_props)
-            and (aer_props.get_ncol(), aer_props.get_nlay()) == (optical_props.get_ncol(), optical_props.get_nlay()))
+            and (aer_props.get_ncol(), aer_props.get_nlay())
+            == (extents or (optical_props.get_ncol(), optical_props.get_nlay())))
 
 
 def _shape(a):
@@ -176,12 +180,19 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
                and _broadband_only(allsky_fluxes) and _broadband_only(clrsky_fluxes) and 1 <= nmu <= 4
                and _shape(sfc_emis) == (ncol, nband) and (not masked or mask_bits is not None))
     dual = fusable and isinstance(optical_props, OpticalProps1scl)
-    scat = fusable and LW_SCAT_FUSED and isinstance(optical_props, OpticalProps2str) and aer_props is None
+    scat = fusable and LW_SCAT_FUSED and isinstance(optical_props, OpticalProps2str)
+    aer_scat = False
     if scat:
         # the gas atmosphere stays 1scl: its ssa and g are the solver's literal zeros, never arrays
-        optical_props, e = _init_like(cloud_props, k_dist, "lw", OpticalProps1scl)
+        gas_1scl, e = _init_like(cloud_props, k_dist, "lw", OpticalProps1scl)
         if e:
             return e
+        # aerosols of the fused kind ride the clear + all-sky entry as its aerosol request; any other kind keeps the
+        # materialising sequence
+        aer_scat = AEROSOL_REQUEST and aerosol_by_request(aer_props, gas_1scl, OpticalProps1scl, (ncol, nlay))
+        scat = aer_props is None or aer_scat
+        if scat:
+            optical_props = gas_1scl
     e = _alloc(optical_props, ncol, nlay, dev)
     if e:
         return e
@@ -202,13 +213,16 @@ def rte_lw(k_dist, gas_concs, p_lay, t_lay, p_lev, t_sfc, sfc_emis, cloud_props,
         tail = (_p(sources.lay_source), nband, k_dist.get_nPlanckTemp(), _p(tlay_d), _p(tlev_d), _p(tsfc_d), sfc_lay,
                 int_array(k_dist.band_lims_gpt.ravel()), k_dist.temp_ref_min, k_dist.totplnk_delta, _p(k_dist.totplnk),
                 1, _p(emis))
-        check(_lib.lib().rrtmgpnn_lw_solver_noscat_planck(*head, *tail, _p(clrsky_fluxes.flux_up),
-                                                          _p(clrsky_fluxes.flux_dn)), "lw_solver_noscat_planck")
+        # clear sky = gases [+ aerosols], all sky = that + the (sampled) clouds, from one entry; the context's
+        # rrtmgpnn_context_set_lw_scat_clr_all mode decides one launch or two
         if masked:
             cloud_sampling.arm_cloud_mask(ctx, ngpt, mask_bits)
-        check(_lib.lib().rrtmgpnn_lw_solver_1rescl_planck_inc(
+        if aer_scat:
+            cloud_sampling.arm_aerosol(ctx, aer_props)
+        check(_lib.lib().rrtmgpnn_lw_solver_1rescl_planck_clr_all(
             *head, _p(cloud_props.tau), _p(cloud_props.ssa), _p(cloud_props.g), *tail, _p(allsky_fluxes.flux_up),
-            _p(allsky_fluxes.flux_dn)), "lw_solver_1rescl_planck_inc")
+            _p(allsky_fluxes.flux_dn), _p(clrsky_fluxes.flux_up), _p(clrsky_fluxes.flux_dn)),
+            "lw_solver_1rescl_planck_clr_all")
         return ""
     aer_req = dual and AEROSOL_REQUEST and aerosol_by_request(aer_props, optical_props, OpticalProps1scl)
     if aer_props is not None and not aer_req:

@@ -74,6 +74,12 @@ in-kernel.  mcica= arms the cloud mask for it as for the absorbing clouds; clrsk
 rrtmgpnn_lw_solver_noscat_planck launch for the clear set ahead of it (the rescaled solver without scattering is the
 no-scattering one, bit for bit).  Not with fused=False, byband, mcica["byband"], jacobian or aerosols, for which the
 entry has no instances.  Off (the default), nothing of the step changes.
+
+lw_dual=True (with lw_scattering=True and clear-sky outputs): the LW chain's solver call is
+rrtmgpnn_lw_solver_1rescl_planck_clr_all, which gives both flux sets, and no lw_solver_clr is issued;
+rrtmgpnn_context_set_lw_scat_clr_all decides one dual launch or two.  aerosols= is then accepted beside lw_scattering:
+lw_aerosol is armed right before the solver (clear sky = gases + aerosols), and set_aerosols works between replays.  Not
+without lw_scattering or clear-sky outputs, nor with fused=False, byband, jacobian or mcica["byband"].
 """
 
 from types import SimpleNamespace
@@ -167,7 +173,20 @@ class ClearSkyStep:
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
-                 clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False):
+                 clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False,
+                 lw_dual=False):
+        self.lw_dual = bool(lw_dual)
+        if self.lw_dual:
+            # (ahead of the other option checks, so that the refusal names this option)
+            bad = [w for w, on in (("lw_scattering=False", not lw_scattering),
+                                   ("no clear-sky outputs (clrsky=True or mcica's 'clrsky')",
+                                    not (clrsky or (mcica is not None and mcica.get("clrsky")))),
+                                   ("fused=False", not fused), ("byband", bool(byband)), ("jacobian", bool(jacobian)),
+                                   ("mcica['byband']", mcica is not None and bool(mcica.get("byband")))) if on]
+            if bad:
+                raise ValueError("lw_dual=True with %s is not supported: the clear + all-sky LW entry for scattering "
+                                 "clouds serves the fused LW chain of an lw_scattering step with clear-sky outputs, "
+                                 "broadband only" % ", ".join(bad))
         self._resolve_options(fused, clouds, sw, sw_priority, byband, clrsky, mcica, aerosols, jacobian)
         self.sw_dual = bool(sw_dual)
         if self.sw_dual:
@@ -180,7 +199,7 @@ class ClearSkyStep:
         self.lw_scattering = bool(lw_scattering)
         if self.lw_scattering:
             bad = [w for w, on in (("fused=False", not fused), ("byband", self.byband), ("jacobian", self.jacobian),
-                                   ("aerosols", self.aerosols), ("no clouds", clouds is None)) if on]
+                                   ("aerosols", self.aerosols and not self.lw_dual), ("no clouds", clouds is None)) if on]
             if bad:
                 raise ValueError("lw_scattering=True with %s is not supported: the fused rescaled LW solve takes band "
                                  "clouds (clouds=) and gives broadband fluxes only" % ", ".join(bad))
@@ -590,7 +609,7 @@ class ClearSkyStep:
     def _lw_clear_scattering(self):
         """An lw_scattering step's clear launch (clrsky): the no-scattering fused-Planck entry on the gas optical depth,
         issued ahead of the cloud-mask request, which belongs to the all-sky launch."""
-        if not (self.lw_scattering and self.clrsky):
+        if not (self.lw_scattering and self.clrsky) or self.lw_dual:  # (lw_dual: both sets from the one solver call)
             return []
         return [("lw_solver_clr", self.L.rrtmgpnn_lw_solver_noscat_planck,
                  self._lw_planck_args((), "lw_up_clr", "lw_dn_clr"))]
@@ -602,6 +621,13 @@ class ClearSkyStep:
         from one call of the dual entry (_clr_all), whose McICA twin takes the packed mask as its last argument instead
         of a request."""
         L, p = self.L, self._p
+        if self.lw_dual:
+            # scattering clouds with clear-sky outputs from one entry: the mask request (all-sky set only) and the
+            # aerosol request (both sets) stand right before it; rrtmgpnn_context_set_lw_scat_clr_all decides one
+            # launch or two
+            return ("lw_solver", L.rrtmgpnn_lw_solver_1rescl_planck_clr_all,
+                    self._lw_planck_args(("cld_tau_lw", "cld_ssa_lw", "cld_g_lw"), "lw_up", "lw_dn")
+                    + p("lw_up_clr", "lw_dn_clr"))
         if self.lw_scattering:
             # scattering clouds: the rescaled solver with the two-stream band increment (a McICA step's mask is armed
             # by request, with or without clear-sky fluxes)
