@@ -245,6 +245,42 @@ int rrtmgpnn_gas_optics_sw_nn(rrtmgpnn_context *ctx, int ncol, int nlay, int ngp
                               const float *tlay, const float *plev, const float *vmr_h2o,
                               const float *const *gas_conc, const int *gas_ndims,
                               const rrtmgpnn_network *const *nets, float *tau, float *ssa, float *g);
+/* compute_bc (extensions/mo_compute_bc.F90): the upper boundary condition from one thin isothermal layer between the gas
+ * optics' minimum pressure press_min and the model's top.  flux_bc (ngpt, ncol) DEVICE is the spectrally resolved
+ * downward flux at that layer's bottom: the inc_flux of the solver entries.  At most three launches: the one-layer
+ * problem gathered as :108-140 build it (top_lay = top_at_1 ? 1 : nlay; tlay1 = tlev1(1:2) = tsfc1 = tlay(top_lay);
+ * plev1 = (press_min, plev(top_lay + 1)) -- literally, so with top_at_1 the layer overlaps the model's top layer,
+ * SURVEY.md quirk B-15; play1 = 0.5f * (plev1(1) + plev1(2)); each gas at top_lay), the in-kernel-input gas optics of
+ * rrtmgpnn_gas_optics_lw_nn / _sw_nn at nlay = 1, and the layer's solve at its bottom level.  The one-layer arrays, tau
+ * and pfrac / ssa live in the context workspace; no source array and no (ngpt, 2, ncol) flux array exists.  Networks
+ * without an in-kernel instance take the gas-optics entries' three-kernel fallback.
+ * Arguments as rrtmgpnn_gas_optics_*_nn (gas_conc / gas_ndims HOST arrays, the rest DEVICE; play is not read: the
+ * orientation is top_at_1) and rrtmgpnn_lw_solver_noscat_planck (band_lims_gpt, Ds, weights HOST; totplnk DEVICE).
+ * nlay >= 1, nmus 1..4, SW ngpt even; RRTMGPNN_ERR_ARGUMENT with a message otherwise; ncol == 0 is OK.  Requests armed
+ * on the context (rrtmgpnn_solver_request_*) are left for the next solver call.
+ * PRESSURES are device arrays, so the reference's check "pressures are too close to (or less than) min in gas optics"
+ * (plev(:, top_lay) <= press_min + 2 spacing(press_min), :110-114) is the class layers' part (rrtmgpnn/compute_bc.py,
+ * fortran/mo_compute_bc.F90, ClearSkyStep), not this entry's.
+ * LW: Planck sources as rrtmgpnn_compute_planck_source_nn's at nlay = 1 with tlev = tsfc = tlay; per angle
+ * lw_source_noscat's source_dn and the transport from a zero incident radiance.  UNITS: with nmus == 1 and
+ * as_flux == 0 flux_bc is the reference's own array, a RADIANCE (rte_lw's one-angle g-point output, quirk B-5; the
+ * reference always calls rte_lw with one angle); as_flux != 0 multiplies by the solver's 2.0f * pi * weights[0], which
+ * is what inc_flux means.  With nmus > 1 flux_bc is the angle-summed flux either way.  tau * D <= 2^126 as for every
+ * rrtmgpnn_lw_solver_noscat* entry.
+ * SW: tau = tau_abs + tau_ray as rrtmgpnn_predict_nn_sw forms it; flux_bc is sw_solver_2stream's direct beam at the
+ * layer's bottom, (solar_source(g) * mu0) * exp(-tau / mu0) with that kernel's operations; solar_source (ngpt) and
+ * mu0 (ncol) DEVICE. */
+int rrtmgpnn_compute_bc_lw(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs, int top_at_1,
+                           float press_min, const float *play, const float *plev, const float *tlay,
+                           const float *vmr_h2o, const float *const *gas_conc, const int *gas_ndims,
+                           const rrtmgpnn_network *const *nets, int nnets, int nbnd, int nPlanckTemp,
+                           const int *band_lims_gpt, float temp_ref_min, float totplnk_delta, const float *totplnk,
+                           int nmus, const float *Ds, const float *weights, int as_flux, float *flux_bc);
+int rrtmgpnn_compute_bc_sw(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs, int top_at_1,
+                           float press_min, const float *play, const float *plev, const float *tlay,
+                           const float *vmr_h2o, const float *const *gas_conc, const int *gas_ndims,
+                           const rrtmgpnn_network *const *nets, const float *solar_source, const float *mu0,
+                           float *flux_bc);
 /* Generic MLP forward (network_type%output_sgemm_flat, neural/mod_network.F90:273-354):
  * out(ny, nbatch) = net(x(nx, nbatch)), last-layer activation applied, no post-processing.  Any network
  * rrtmgpnn_network_create accepts with hidden widths <= 256 (RRTMGPNN_ERR_UNSUPPORTED beyond): the 16x16x4 MFMA

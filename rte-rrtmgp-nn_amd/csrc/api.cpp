@@ -911,6 +911,132 @@ int rrtmgpnn_gas_optics_sw_nn(rrtmgpnn_context *ctx, int ncol, int nlay, int ngp
   return rrtmgpnn_predict_nn_sw(ctx, ncol, nlay, ngpt, ninputs, x, cd, nets, tau, ssa, g);
 }
 
+// ---- compute_bc (extensions/mo_compute_bc.F90) ----
+// The one-layer problem in the context workspace, one allocation for the whole call: the gathered arrays
+// (launch_bc_inputs), the layer's tau and second network output (pfrac / ssa), (ngpt, ncol) each, and room for the
+// three-kernel fallback's nn_inputs and col_dry.  `in` comes back describing that layer (nlay = 1): 2-D gases point at
+// their gathered columns, a 1-D profile at its element top_lay, a scalar where it was.
+struct BcLayer {
+  MlpInputs in;
+  const float *tlay1;
+  float *tau, *second, *x, *cd;
+};
+
+static int bc_layer(const char *who, rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs, int top_at_1,
+                    float press_min, const float *play, const float *plev, const float *tlay, const float *vmr_h2o,
+                    const float *const *gas_conc, const int *gas_ndims, const rrtmgpnn_network *net, BcLayer &b)
+{
+  if (int rc = fused_inputs(who, net, ninputs, nlay, play, tlay, plev, vmr_h2o, gas_conc, gas_ndims, b.in)) return rc;
+  const int top_lay = top_at_1 ? 1 : nlay;
+  BcGather src{};
+  src.p[src.n++] = vmr_h2o;
+  int slot[kMaxInputs] = {0};
+  for (int k = 2; k < ninputs; k++) {
+    if (!b.in.gas.p[k] || b.in.gas.nd[k] != 2) continue;
+    int s = 0;
+    while (s < src.n && src.p[s] != b.in.gas.p[k]) s++;
+    if (s == src.n) src.p[src.n++] = b.in.gas.p[k];
+    slot[k] = s;
+  }
+  auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };  // the networks store 16 bytes at a time
+  const size_t n_in = pad4(bc_inputs_floats(ncol, src.n)), n_g = pad4((size_t)ngpt * ncol);
+  void *ws = nullptr;
+  if (int rc = ctx->workspace(sizeof(float) * (n_in + 2 * n_g + (size_t)ncol * (ninputs + 1)), &ws)) return rc;
+  float *w = (float *)ws;
+  if (int rc = launch_bc_inputs(ctx, ncol, nlay, top_lay, press_min, plev, tlay, src, w)) return rc;
+  const float *gas1 = w + 4 * (size_t)ncol;
+  b.in.play = w;
+  b.in.tlay = b.tlay1 = w + ncol;
+  b.in.plev = w + 2 * (size_t)ncol;
+  b.in.h2o = gas1;
+  b.in.nlay = 1;
+  for (int k = 2; k < ninputs; k++) {
+    if (!b.in.gas.p[k]) continue;
+    if (b.in.gas.nd[k] == 2) b.in.gas.p[k] = gas1 + (size_t)slot[k] * ncol;
+    else if (b.in.gas.nd[k] == 1) b.in.gas.p[k] += top_lay - 1;
+  }
+  b.tau = w + n_in;
+  b.second = b.tau + n_g;
+  b.x = b.second + n_g;
+  b.cd = b.x + (size_t)ncol * ninputs;
+  return RRTMGPNN_OK;
+}
+
+// the gas-optics entries' three-kernel fallback on the one-layer problem (its room is part of bc_layer's allocation)
+static int bc_fallback(rrtmgpnn_context *ctx, int ncol, int ninputs, const BcLayer &b)
+{
+  std::vector<float> mm(2 * ninputs);
+  for (int k = 0; k < ninputs; k++) { mm[k] = b.in.mn[k]; mm[ninputs + k] = b.in.mx[k]; }
+  if (int rc = launch_nn_inputs(ctx, ncol, 1, ninputs, b.in.play, b.in.tlay, b.in.gas, mm.data(), b.x)) return rc;
+  return launch_col_dry(ctx, ncol, 1, b.in.h2o, b.in.plev, b.cd);
+}
+
+int rrtmgpnn_compute_bc_lw(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs, int top_at_1,
+                           float press_min, const float *play, const float *plev, const float *tlay,
+                           const float *vmr_h2o, const float *const *gas_conc, const int *gas_ndims,
+                           const rrtmgpnn_network *const *nets, int nnets, int nbnd, int nPlanckTemp,
+                           const int *band_lims_gpt, float temp_ref_min, float totplnk_delta, const float *totplnk,
+                           int nmus, const float *Ds, const float *weights, int as_flux, float *flux_bc)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!nets || !nets[0] || !totplnk || !Ds || !weights || !flux_bc || ncol < 0 || ngpt < 1 ||
+      (nnets != 1 && nnets != 2) || nPlanckTemp < 2 || !(totplnk_delta > 0.0f))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "compute_bc_lw: bad argument");
+  if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "compute_bc_lw: nmus must be 1..4");
+  BandArgs bands;
+  if (int rc = band_args(nbnd, band_lims_gpt, ngpt, bands)) return rc;
+  if (int rc = bands_cover(bands, ngpt)) return rc;
+  const rrtmgpnn_network *A = nets[0], *B = nnets == 2 ? nets[1] : nullptr;
+  if (nnets == 2 && (!B || B->dims[0] != ninputs || A->dims[A->nlayers] != ngpt || B->dims[B->nlayers] != ngpt))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "compute_bc_lw: network sizes do not match (ninputs, ngpt)");
+  if (nnets == 2 && !A->has_out_scaling())
+    return fail(RRTMGPNN_ERR_ARGUMENT, "output_sgemm_tau: NN output scaling coefficients missing");
+  BcLayer b;
+  if (int rc = bc_layer("compute_bc_lw", ctx, ncol, nlay, ngpt, ninputs, top_at_1, press_min, play, plev, tlay,
+                        vmr_h2o, gas_conc, gas_ndims, A, b))
+    return rc;
+  if (ncol == 0) return RRTMGPNN_OK;
+  int rc = nnets == 2 ? launch_mlp(ctx, MLP_LW_PAIR, A, B, ncol, ngpt, nullptr, nullptr, b.tau, b.second, nullptr, &b.in)
+                      : RRTMGPNN_ERR_UNSUPPORTED;
+  if (rc == RRTMGPNN_ERR_UNSUPPORTED) {
+    if ((rc = bc_fallback(ctx, ncol, ninputs, b))) return rc;
+    rc = rrtmgpnn_predict_nn_lw(ctx, ncol, 1, ngpt, ninputs, b.x, b.cd, nets, nnets, b.tau, b.second);
+  }
+  if (rc) return rc;
+  const LwPlanck pl{b.tlay1, b.tlay1, b.tlay1, totplnk, nPlanckTemp, 1, 0, temp_ref_min, totplnk_delta};
+  return launch_bc_flux_lw(ctx, ngpt, ncol, b.tau, b.second, b.tlay1, pl, bands, nmus, Ds, weights, as_flux != 0,
+                           flux_bc);
+}
+
+int rrtmgpnn_compute_bc_sw(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs, int top_at_1,
+                           float press_min, const float *play, const float *plev, const float *tlay,
+                           const float *vmr_h2o, const float *const *gas_conc, const int *gas_ndims,
+                           const rrtmgpnn_network *const *nets, const float *solar_source, const float *mu0,
+                           float *flux_bc)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!nets || !nets[0] || !solar_source || !mu0 || !flux_bc || ncol < 0 || ngpt < 1)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "compute_bc_sw: bad argument");
+  if (ngpt % 2) return fail(RRTMGPNN_ERR_ARGUMENT, "compute_bc_sw: ngpt must be even");
+  const rrtmgpnn_network *A = nets[0], *B = nets[1];
+  if (!B || B->dims[0] != ninputs || A->dims[A->nlayers] != ngpt || B->dims[B->nlayers] != ngpt ||
+      !A->has_out_scaling() || !B->has_out_scaling())
+    return fail(RRTMGPNN_ERR_ARGUMENT, "compute_bc_sw: absorption / Rayleigh networks missing or inconsistent");
+  BcLayer b;
+  if (int rc = bc_layer("compute_bc_sw", ctx, ncol, nlay, ngpt, ninputs, top_at_1, press_min, play, plev, tlay,
+                        vmr_h2o, gas_conc, gas_ndims, A, b))
+    return rc;
+  if (ncol == 0) return RRTMGPNN_OK;
+  // tau = tau_abs + tau_ray as predict_nn_sw forms it; ssa is the pair kernel's second output and is not read
+  int rc = launch_mlp(ctx, MLP_SW_PAIR, A, B, ncol, ngpt, nullptr, nullptr, b.tau, b.second, nullptr, &b.in);
+  if (rc == RRTMGPNN_ERR_UNSUPPORTED) {
+    if ((rc = bc_fallback(ctx, ncol, ninputs, b))) return rc;
+    rc = rrtmgpnn_predict_nn_sw(ctx, ncol, 1, ngpt, ninputs, b.x, b.cd, nets, b.tau, b.second, nullptr);
+  }
+  if (rc) return rc;
+  return launch_bc_flux_sw(ctx, ngpt, ncol, b.tau, solar_source, mu0, flux_bc);
+}
+
 int rrtmgpnn_predict_nn_sw(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs, const float *nn_inputs,
                            const float *col_dry, const rrtmgpnn_network *const *nets, float *tau, float *ssa, float *g)
 {

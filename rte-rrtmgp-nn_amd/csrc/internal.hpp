@@ -363,6 +363,22 @@ int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, i
                       float *flux_dn);
 int launch_expand(rrtmgpnn_context *ctx, int nband, int ngpt, int ncol, const BandArgs &bands, const float *in,
                   float *out);
+// kernels_bc.hip (rrtmgpnn_compute_bc_lw / _sw): the one-layer problem of extensions/mo_compute_bc.F90 and its solve
+// the 2-D (nlay, ncol) arrays whose top-layer values the gather copies: the gases and the h2o vmr of get_col_dry
+constexpr int kBcMaxGather = kMaxInputs + 1;
+struct BcGather {
+  const float *p[kBcMaxGather];
+  int n;
+};
+// out: play1 (ncol), tlay1 (ncol), plev1 (2, ncol), then src.n arrays of (ncol); top_lay 1-based
+constexpr size_t bc_inputs_floats(int ncol, int ngather) { return (size_t)ncol * (4 + ngather); }
+int launch_bc_inputs(rrtmgpnn_context *ctx, int ncol, int nlay, int top_lay, float press_min, const float *plev,
+                     const float *tlay, const BcGather &src, float *out);
+int launch_bc_flux_lw(rrtmgpnn_context *ctx, int ngpt, int ncol, const float *tau, const float *pfrac,
+                      const float *tlay1, const LwPlanck &pl, const BandArgs &bands, int nmus, const float *Ds,
+                      const float *wts, int as_flux, float *flux_bc);
+int launch_bc_flux_sw(rrtmgpnn_context *ctx, int ngpt, int ncol, const float *tau, const float *solar_source,
+                      const float *mu0, float *flux_bc);
 // kernels_fluxes.hip: sum_byband of a g-point array (ngpt, nlev, ncol) into (nbnd, nlev, ncol)
 int launch_sum_byband(rrtmgpnn_context *ctx, int ngpt, long long nrow, const BandArgs &bands, const float *gpt_flux,
                       float *bnd_flux);

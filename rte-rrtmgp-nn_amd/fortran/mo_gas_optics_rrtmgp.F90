@@ -22,7 +22,8 @@ module mo_gas_optics_rrtmgp
   implicit none
   private
 
-  integer, parameter :: MAX_INPUTS = 32
+  integer, parameter, public :: MAX_INPUTS = 32
+  public :: gas_inputs  ! (mo_compute_bc builds the same argument lists)
 
   type, extends(ty_optical_props), public :: ty_gas_optics_rrtmgp
     real(wp) :: press_ref_min = 0._wp, press_ref_max = 110000._wp

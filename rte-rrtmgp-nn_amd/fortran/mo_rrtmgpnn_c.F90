@@ -15,6 +15,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_gas_optics_lw_nn, c_rrtmgpnn_gas_optics_sw_nn, c_rrtmgpnn_lw_solver_noscat_planck, &
             c_rrtmgpnn_sw_solver_noscat
   public :: c_rrtmgpnn_compute_heating_rate
+  public :: c_rrtmgpnn_compute_bc_lw, c_rrtmgpnn_compute_bc_sw
   public :: c_rrtmgpnn_lw_solver_noscat_planck_clr_all, c_rrtmgpnn_context_set_lw_clr_all
   public :: c_rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica
   public :: c_rrtmgpnn_sw_solver_2stream_clr_all, c_rrtmgpnn_sw_solver_2stream_rfmip_clr_all
@@ -127,6 +128,26 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, play, tlay, plev, vmr_h2o, tau, ssa, g
       integer(c_int), value :: ncol, nlay, ngpt, ninputs
+      type(c_ptr), dimension(*), intent(in) :: gas_conc, nets
+      integer(c_int), dimension(*), intent(in) :: gas_ndims
+    end function
+    integer(c_int) function c_rrtmgpnn_compute_bc_lw(ctx, ncol, nlay, ngpt, ninputs, top_at_1, press_min, play, plev, &
+        tlay, vmr_h2o, gas_conc, gas_ndims, nets, nnets, nbnd, nPlanckTemp, band_lims_gpt, temp_ref_min, totplnk_delta, &
+        totplnk, nmus, Ds, weights, as_flux, flux_bc) bind(C, name="rrtmgpnn_compute_bc_lw")
+      import :: c_int, c_ptr, c_float
+      type(c_ptr), value :: ctx, play, plev, tlay, vmr_h2o, totplnk, flux_bc
+      integer(c_int), value :: ncol, nlay, ngpt, ninputs, top_at_1, nnets, nbnd, nPlanckTemp, nmus, as_flux
+      real(c_float), value :: press_min, temp_ref_min, totplnk_delta
+      type(c_ptr), dimension(*), intent(in) :: gas_conc, nets
+      integer(c_int), dimension(*), intent(in) :: gas_ndims, band_lims_gpt
+      real(c_float), dimension(*), intent(in) :: Ds, weights
+    end function
+    integer(c_int) function c_rrtmgpnn_compute_bc_sw(ctx, ncol, nlay, ngpt, ninputs, top_at_1, press_min, play, plev, &
+        tlay, vmr_h2o, gas_conc, gas_ndims, nets, solar_source, mu0, flux_bc) bind(C, name="rrtmgpnn_compute_bc_sw")
+      import :: c_int, c_ptr, c_float
+      type(c_ptr), value :: ctx, play, plev, tlay, vmr_h2o, solar_source, mu0, flux_bc
+      integer(c_int), value :: ncol, nlay, ngpt, ninputs, top_at_1
+      real(c_float), value :: press_min
       type(c_ptr), dimension(*), intent(in) :: gas_conc, nets
       integer(c_int), dimension(*), intent(in) :: gas_ndims
     end function

@@ -75,6 +75,14 @@ rrtmgpnn_lw_solver_noscat_planck launch for the clear set ahead of it (the resca
 no-scattering one, bit for bit).  Not with fused=False, byband, mcica["byband"], jacobian or aerosols, for which the
 entry has no instances.  Off (the default), nothing of the step changes.
 
+upper_bc=True: the step owns lw_inc_flux (ncol, ngpt_lw), the downward LW flux at the model's top from one thin
+isothermal layer between the gas optics' minimum pressure and that top (extensions/mo_compute_bc.F90), formed every
+step by rrtmgpnn_compute_bc_lw (flux units, the step's nmus) at the head of the LW chain and passed as inc_flux to
+whichever LW solver entry the other options select, fused or not.  The reference's pressure check runs on the host
+arrays at construction and in inputs_for (ValueError with the reference's message): the unmodified RFMIP columns, whose
+top level is the minimum pressure itself, are refused.  Every option set takes it; the SW chain is untouched (the _rfmip
+solver forms its own incident flux).  Off (the default), nothing of the step changes.
+
 lw_dual=True (with lw_scattering=True and clear-sky outputs): the LW chain's solver call is
 rrtmgpnn_lw_solver_1rescl_planck_clr_all, which gives both flux sets, and no lw_solver_clr is issued;
 rrtmgpnn_context_set_lw_scat_clr_all decides one dual launch or two.  aerosols= is then accepted beside lw_scattering:
@@ -105,7 +113,8 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
 # lw_jacobian: a jacobian=True step's request, host-only too; lw_aerosol / sw_aerosol: an aerosols= step's requests
 # beside clouds, host-only)
 # (lw_solver_clr: an lw_scattering step's clear launch, ahead of the mask request its all-sky launch consumes)
-FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
+# (lw_upper_bc: an upper_bc=True step's boundary flux, at the head of the LW chain)
+FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "lw_upper_bc", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
                "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
                "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_solver"]
 
@@ -125,7 +134,11 @@ def issue_order(calls, fused, lw_after=""):
             raise ValueError("lw_after: %r is not a call of this fused step's SW chain" % lw_after)
         cut = names.index(lw_after)
         head = [c for i, c in enumerate(calls) if c[0] in SW_CHAIN and i <= cut]
-        calls = head + [c for c in calls if c not in head]
+        # an upper_bc=True step's boundary flux depends on no network: issued on the LW stream ahead of the gate it runs
+        # beside the SW chain's head, and the LW network stays the first call behind the gate (at C3 the option added
+        # 0.099 ms to the step so, 0.125 ms with the call behind the gate: DESIGN.md section 3)
+        pre = [c for c in calls if c[0] == "lw_upper_bc"]
+        calls = pre + head + [c for c in calls if c not in head and c not in pre]
     return calls
 
 
@@ -174,8 +187,9 @@ class ClearSkyStep:
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
                  clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False,
-                 lw_dual=False):
+                 lw_dual=False, upper_bc=False):
         self.lw_dual = bool(lw_dual)
+        self.upper_bc = bool(upper_bc)
         if self.lw_dual:
             # (ahead of the other option checks, so that the refusal names this option)
             bad = [w for w, on in (("lw_scattering=False", not lw_scattering),
@@ -329,6 +343,9 @@ class ClearSkyStep:
         f_sw = f if sw else (lambda *s: f(*s).zero_())  # an LW-only step's SW fluxes are zero
         self.lw_up, self.lw_dn = f(ncol, nlay + 1), f(ncol, nlay + 1)
         self.sw_up, self.sw_dn, self.sw_dir = (f_sw(ncol, nlay + 1) for _ in range(3))
+        if self.upper_bc:
+            self._upper_bc_check(prob)
+            self.lw_inc_flux = f(ncol, self.ng_lw)
         if self.jacobian:
             self.lw_up_jac = f(ncol, nlay + 1)
         if self.clrsky:
@@ -339,6 +356,14 @@ class ClearSkyStep:
             if sw:
                 self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (
                     f(ncol, nlay + 1, self.kd_sw["nband"]) for _ in range(3))
+
+    def _upper_bc_check(self, prob):
+        """compute_bc's pressure check (extensions/mo_compute_bc.F90:110-114) on a host problem's plev(:, top_lay)."""
+        from .compute_bc import pressure_check
+        top = 0 if prob["top_at_1"] else prob["nlay"] - 1
+        e = pressure_check(np.asarray(prob["plev"])[:, top], self.kd_lw["press_ref_min"][0])
+        if e:
+            raise ValueError(e)
 
     def _allocate_aerosols(self, aerosols):
         """An aerosols= step's band properties, step-owned: the solver calls hold their addresses."""
@@ -557,6 +582,7 @@ class ClearSkyStep:
             # compute_nn_inputs + get_col_dry + predict_nn_lw in one kernel (rrtmgpnn_gas_optics_lw_nn): the network
             # inputs and column amounts are formed in-kernel and never stored (same bits as the three calls)
             return [
+                *self._upper_bc_call(),
                 ("predict_nn_lw", L.rrtmgpnn_gas_optics_lw_nn,
                  (c, ncol, nlay, self.ng_lw, self.nx_lw) + p("play", "tlay", "plev") + h2o
                  + (self._g_lw, self._nd_lw, self._nets_lw, len(self.lw_nets)) + p("tau_lw", "lay_src")),
@@ -573,10 +599,11 @@ class ClearSkyStep:
             self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"]))
         solver = lambda name, up, dn: (  # noqa: E731
             name, L.rrtmgpnn_lw_solver_noscat,
-            (c, self.ng_lw, nlay, ncol, self.top_at_1, self.nmus, self._Ds, self._W, None)
+            (c, self.ng_lw, nlay, ncol, self.top_at_1, self.nmus, self._Ds, self._W) + p("lw_inc_flux")
             + p("tau_lw", "lay_src", "lev_src", "emis_gpt", "sfc_src", up, dn))
         clouds = self._clouds_in(ch)
         return [
+            *self._upper_bc_call(),
             ("nn_inputs_lw", L.rrtmgpnn_compute_nn_inputs,
              (c, ncol, nlay, self.nx_lw) + p("play", "tlay") + (self._g_lw, self._nd_lw, self.lw_nets[0]) + p("x_lw")),
             ("predict_nn_lw", L.rrtmgpnn_predict_nn_lw,
@@ -597,11 +624,24 @@ class ClearSkyStep:
             solver("lw_solver", "lw_up", "lw_dn"),
         ]
 
+    def _upper_bc_call(self):
+        """An upper_bc=True step's boundary flux into lw_inc_flux, the inc_flux of the chain's solver calls: in flux
+        units (as_flux = 1) at the step's angles."""
+        if not self.upper_bc:
+            return []
+        kd = self.kd_lw
+        return [("lw_upper_bc", self.L.rrtmgpnn_compute_bc_lw,
+                 (self.ctx.h, self.ncol, self.nlay, self.ng_lw, self.nx_lw, self.top_at_1, float(kd["press_ref_min"][0]))
+                 + self._p("play", "plev", "tlay") + (self.gases["h2o"].data_ptr(),)
+                 + (self._g_lw, self._nd_lw, self._nets_lw, len(self.lw_nets), self.nb_lw, kd["nPlanckTemp"],
+                    self._lims_lw, float(kd["temp_ref_min"][0]), float(kd["totplnk_delta"]))
+                 + self._p("totplnk") + (self.nmus, self._Ds, self._W, 1) + self._p("lw_inc_flux"))]
+
     def _lw_planck_args(self, inc, up, dn):
         """The arguments of a fused-Planck LW entry: `inc` the names of its band increment's arrays."""
         p = self._p
-        return (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W, None) \
-            + p("tau_lw", *inc, "lay_src") \
+        return (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W) \
+            + p("lw_inc_flux", "tau_lw", *inc, "lay_src") \
             + (self.nb_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") \
             + (self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"])) \
             + p("totplnk") + (1,) + p("sfc_emis", up, dn)
@@ -633,8 +673,8 @@ class ClearSkyStep:
             # by request, with or without clear-sky fluxes)
             return ("lw_solver", L.rrtmgpnn_lw_solver_1rescl_planck_inc,
                     self._lw_planck_args(("cld_tau_lw", "cld_ssa_lw", "cld_g_lw"), "lw_up", "lw_dn"))
-        args = (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W, None) \
-            + p("tau_lw") + (p("cld_tau_lw") if self.allsky else p("aer_tau_lw") if self.aerosols else ()) \
+        args = (self.ctx.h, self.ng_lw, self.nlay, self.ncol, self.top_at_1, self.nmus, self._Ds, self._W) \
+            + p("lw_inc_flux", "tau_lw") + (p("cld_tau_lw") if self.allsky else p("aer_tau_lw") if self.aerosols else ()) \
             + p("lay_src") \
             + (self.nb_lw, self.kd_lw["nPlanckTemp"]) + p("tlay", "tlev", "tsfc") \
             + (self.sfc_lay, self._lims_lw, float(self.kd_lw["temp_ref_min"][0]), float(self.kd_lw["totplnk_delta"])) \
@@ -1024,6 +1064,8 @@ class ClearSkyStep:
         into this step's inputs before each replay)."""
         if prob["ncol"] != self.ncol or prob["nlay"] != self.nlay or list(prob["gases"]) != self._gas_names:
             raise ValueError("inputs_for: block shape differs from the step's")
+        if self.upper_bc:
+            self._upper_bc_check(prob)
         return self._inputs(prob, clouds if self.allsky else None)
 
     def io_tensors(self):
