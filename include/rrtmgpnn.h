@@ -118,6 +118,24 @@ int rrtmgpnn_context_set_mlp_kernel(rrtmgpnn_context *ctx, int mode);
 #define RRTMGPNN_MLP_PATH_MFMA32  2
 #define RRTMGPNN_MLP_PATH_MFMA16  3
 int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8]);
+/* Which solver kernel instance served this context's last solver launch (the rrtmgpnn_lw_solver_* and
+ * rrtmgpnn_sw_solver_* entries and the steps built on them), for tests of the dispatch.  path[0]: the kernel family, 0
+ * before the first launch, 1 lw_noscat_kernel, 2 sw_2stream_ck_kernel, 3 lw_rescl_planck_inc_kernel, 4 lw_rescl_kernel,
+ * 5 sw_2stream_kernel, 6 sw_2stream_x2_kernel (lw_2stream_kernel and sw_noscat_kernel, one flag each, record nothing).
+ * path[1]: the instance's compile-time options, an OR of the family's bits:
+ *   1 lw_noscat_kernel: 1 fused Planck sources, 2 band increment, 4 several angles or g-point outputs, 8 by-band
+ *     outputs, 16 clear beside all sky (dual), 32 cloud mask, 64 the mask as the wave's scalar pair, 128 Jacobian,
+ *     256 aerosol;
+ *   2 sw_2stream_ck_kernel: 1 gas g, 2 band increment, 4 g-point outputs, 8 transmittance plane, 16 exp(-k tau) plane,
+ *     32 band-pair increment, 64 by-band outputs, 128 cloud mask, 256 aerosol, 512 clear beside all sky (dual),
+ *     1024 the small-grid instance;
+ *   3 lw_rescl_planck_inc_kernel: 1 cloud mask, 2 aerosol, 4 clear beside all sky (dual);
+ *   4 lw_rescl_kernel: 1 by-band outputs, 2 Jacobian;
+ *   5 sw_2stream_kernel, 6 sw_2stream_x2_kernel: 1 gas g, 2 band increment, 4 g-point outputs, 8 by-band outputs.
+ * path[2]: the launches the call made in these families, 2 where a clear + all-sky entry ran its two launches (path[0]
+ * and path[1] are then the second's).  path[3]: the number of instances the family is compiled for; an options value
+ * outside that list is refused with RRTMGPNN_ERR_UNSUPPORTED.  A call that launches nothing leaves the path as it was. */
+int rrtmgpnn_context_get_solver_path(rrtmgpnn_context *ctx, int path[4]);
 /* MI355X tuning, no reference counterpart: the gas-optics networks launched on this context use at most `cus` CUs'
  * worth of resident blocks (0, the default: every CU).  For a host that runs the LW and SW chains side by side on two
  * streams: an LW network confined to part of the chip leaves the other CUs to the SW solver from its start (each LW

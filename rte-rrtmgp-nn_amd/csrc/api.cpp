@@ -536,6 +536,14 @@ int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8])
   return RRTMGPNN_OK;
 }
 
+int rrtmgpnn_context_get_solver_path(rrtmgpnn_context *ctx, int path[4])
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!path) return fail(RRTMGPNN_ERR_ARGUMENT, "null path");
+  for (int i = 0; i < 4; i++) path[i] = ctx->solver_path[i];
+  return RRTMGPNN_OK;
+}
+
 int rrtmgpnn_context_set_stream(rrtmgpnn_context *ctx, void *hip_stream)
 {
   if (int rc = check_ctx(ctx)) return rc;
@@ -1406,6 +1414,7 @@ static int sw_clr_all_requests(const char *entry, rrtmgpnn_context *ctx, int ngp
 static int sw_clr_all_launch(rrtmgpnn_context *ctx, SolverExtras &ex, const Sw2Stream &p, const SwBc *bc,
                              float *flux_up_clr, float *flux_dn_clr, float *flux_dir_clr)
 {
+  if (p.ncol == 0) return RRTMGPNN_OK;
   const int mode0 = ctx->sw_clr_all >= 0 ? ctx->sw_clr_all : g_sw_clr_all_default;
   const int mode = mode0 == 0 ? kSwClrAllDefaultMode : mode0;
   if (mode == 1 && sw_ck_selected(ctx, p.ngpt)) {
@@ -1428,7 +1437,7 @@ static int sw_clr_all_launch(rrtmgpnn_context *ctx, SolverExtras &ex, const Sw2S
     pc.bands = nullptr;
     pc.tau_bnd = pc.ssa_bnd = pc.g_bnd = nullptr;
   }
-  return launch_sw_2stream(ctx, exc, pc, bc);
+  return ctx->second_solver_launch(launch_sw_2stream(ctx, exc, pc, bc));
 }
 
 static int sw_clr_all_shape(const char *entry, int ngpt, int nbnd)

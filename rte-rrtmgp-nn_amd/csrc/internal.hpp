@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -142,6 +143,20 @@ struct rrtmgpnn_context {
     const int p[8] = {kind, ak, ah1, ah2, bk, bh1, bh2, flags};
     for (int i = 0; i < 8; i++) mlp_path[i] = p[i];
   }
+  // rrtmgpnn_context_get_solver_path: the kernel of this context's last solver launch (family, options value, launches
+  // of the call, instances in the family's list), written by the launchers (launch_listed below)
+  int solver_path[4] = {0};
+  void set_solver_path(int family, uint32_t options, int listed)
+  {
+    const int p[4] = {family, (int)options, 1, listed};
+    for (int i = 0; i < 4; i++) solver_path[i] = p[i];
+  }
+  // the two-launch fallbacks of the clear + all-sky calls: the status of the second launch, counted when it went out
+  int second_solver_launch(int rc)
+  {
+    if (rc == RRTMGPNN_OK) solver_path[2] = 2;
+    return rc;
+  }
   // rrtmgpnn_solver_request_byband: armed for the next solver call on this context, which clears it
   struct BybandRequest {
     bool armed = false;
@@ -247,6 +262,50 @@ struct rrtmgpnn_cloud_optics {
 };
 
 namespace rrtmgpnn {
+// The solver kernels' compile-time options.  Each kernel family takes one options value, an OR of its bits below, and
+// turns it back into its named constexpr flags in its first lines.  A launcher has three parts: a select_* function
+// that maps the call (its extras and argument struct) to the options value or to a refusal, one list of the options
+// values the family compiles (SolverInstances), and launch_listed, which walks that list and hands the matching
+// instance to the launcher's generic lambda.  rrtmgpnn_context_get_solver_path reports (family, options) of the last
+// launch; include/rrtmgpnn.h documents these values, tests/test_gpu_solver_dispatch.py holds them to the table.
+enum SolverFamily {
+  kSolverNone = 0,
+  kSolverLwNoscat = 1,     // lw_noscat_kernel (kernels_rte.hip)
+  kSolverSwCk = 2,         // sw_2stream_ck_kernel (kernels_sw_ck.hip)
+  kSolverLwResclInc = 3,   // lw_rescl_planck_inc_kernel (kernels_lw_scat.hip)
+  kSolverLwRescl = 4,      // lw_rescl_kernel (kernels_lw_scat.hip)
+  kSolverSw2Stream = 5,    // sw_2stream_kernel (kernels_rte.hip)
+  kSolverSwX2 = 6          // sw_2stream_x2_kernel (kernels_sw_x2.hip)
+};
+// lw_noscat_kernel
+constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand = 8, kLwOptDual = 16, kLwOptMask = 32,
+                   kLwOptMaskS = 64, kLwOptJac = 128, kLwOptAer = 256;
+// sw_2stream_ck_kernel; kSwCkSmall: the small-grid set of chunk length, ring, wave floor, lane type and prefetch
+// (kCk*Small, VSmall), else the default set
+constexpr uint32_t kSwCkHasG = 1, kSwCkInc = 2, kSwCkGpt = 4, kSwCkTn = 8, kSwCkEmk = 16, kSwCkBandPair = 32,
+                   kSwCkBand = 64, kSwCkMask = 128, kSwCkAer = 256, kSwCkDual = 512, kSwCkSmall = 1024;
+// lw_rescl_planck_inc_kernel
+constexpr uint32_t kScatOptMask = 1, kScatOptAer = 2, kScatOptDual = 4;
+// lw_rescl_kernel
+constexpr uint32_t kResclOptBand = 1, kResclOptJac = 2;
+// sw_2stream_kernel and sw_2stream_x2_kernel (the latter has no g-point instances)
+constexpr uint32_t kSwOptHasG = 1, kSwOptInc = 2, kSwOptGpt = 4, kSwOptBand = 8;
+
+// the options values a family compiles, and no others
+template <uint32_t... Os>
+struct SolverInstances {};
+// go(std::integral_constant<uint32_t, O>) launches the family's instance O and returns its status; an options value
+// that is not listed has no instance.  The launch that went out is recorded in the context
+template <uint32_t... Os, class Go>
+int launch_listed(rrtmgpnn_context *ctx, SolverFamily family, SolverInstances<Os...>, uint32_t o, Go &&go)
+{
+  int rc = RRTMGPNN_OK;
+  const bool listed = ((o == Os && ((rc = go(std::integral_constant<uint32_t, Os>{})), true)) || ...);
+  if (!listed) return fail(RRTMGPNN_ERR_UNSUPPORTED, "solver: no instance is compiled for the options of this call");
+  if (rc == RRTMGPNN_OK) ctx->set_solver_path(family, o, (int)sizeof...(Os));
+  return rc;
+}
+
 // kernels_clouds.hip
 struct BandArgs;
 int launch_cloud_optics(rrtmgpnn_context *ctx, const rrtmgpnn_cloud_optics *co, int ncol, int nlay, const float *clwp,

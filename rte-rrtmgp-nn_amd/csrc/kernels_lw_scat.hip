@@ -53,7 +53,9 @@ __device__ __forceinline__ RsLayer rs_layer(float tau, float ssal, float g, floa
 // the upward flux with respect to the surface temperature: J = e * sfc_jac at the surface, J = trans * J with the
 // rescaled transmittance in pass 2 (:1761, 1782), staged in a second ring beside the up values (or, several angles,
 // a third accumulator plane) and summed as flux_up is.  No downward Jacobian (:1743-1745).
-template <bool kBand = false, bool kJac = false>
+//
+// O: the instance's options, an OR of the kResclOpt* bits (internal.hpp), named again in the first lines
+template <uint32_t O>
 __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                                        const float *__restrict__ inc_flux,
                                                        const float *__restrict__ tau, const float *__restrict__ ssa,
@@ -65,6 +67,7 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
                                                        BandOut bo, const float *__restrict__ sfc_jac,
                                                        float *__restrict__ flux_jac)
 {
+  constexpr bool kBand = (O & kResclOptBand) != 0, kJac = (O & kResclOptJac) != 0;
   static_assert(!kJac || !kBand, "the Jacobian instance has no by-band outputs");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
@@ -302,14 +305,18 @@ struct ScatDualArgs<true> {
 // through ns_layer: down in pass 1, up in pass 2; pass 3 has nothing to add for it.  The clear values are staged in a
 // second ring ([2][kScatRing][ngpt]: 0 = all-sky, 1 = clear) and reduced to part planes 2 (up) and 3 (dn): clear down
 // by pass 1's own flushes (the all-sky radiance stages nothing there), clear up beside all-sky up by pass 2's.
-template <bool kMask, int kPF, bool kAer, bool kDual>
+//
+// O: the instance's options, an OR of the kScatOpt* bits (internal.hpp), named again in the first lines
+template <uint32_t O>
 __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
     int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang, const float *__restrict__ inc_flux,
     const float *__restrict__ tau, const float *__restrict__ pfrac, const float *__restrict__ tau_bnd,
     const float *__restrict__ ssa_bnd, const float *__restrict__ g_bnd, const float *__restrict__ emis, LwPlanck pl,
     BandArgs bands, const uint32_t *__restrict__ cmask, float *__restrict__ ws, float *__restrict__ flux_up,
-    float *__restrict__ flux_dn, ScatDualArgs<kAer || kDual> da)
+    float *__restrict__ flux_dn, ScatDualArgs<(O & (kScatOptAer | kScatOptDual)) != 0> da)
 {
+  constexpr bool kMask = (O & kScatOptMask) != 0, kAer = (O & kScatOptAer) != 0, kDual = (O & kScatOptDual) != 0;
+  constexpr int kPF = kScatPf;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int icol = blockIdx.x, g = threadIdx.x;
   const bool on = g < ngpt;
@@ -774,6 +781,9 @@ __global__ void __launch_bounds__(256) lw_2stream_kernel(int ngpt, int nlay, int
   }
 }
 
+// The instances lw_rescl_kernel is compiled for
+using LwResclInstances = SolverInstances<0u, kResclOptBand, kResclOptJac>;
+
 int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *ssa, const float *g,
                     const float *lay_source, const float *lev_source, const float *sfc_source)
 {
@@ -801,20 +811,17 @@ int launch_lw_rescl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNosca
   if (ex.byband() && ex.gpt_up)
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: by-band and g-point outputs in one call (rrtmgpnn_sum_byband "
                                           "reduces g-point fluxes)");
-  if (jac)
-    hipLaunchKernelGGL((lw_rescl_kernel<false, true>), dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol,
-                       p.top_at_1, a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source,
-                       (float *)ws, p.flux_up, p.flux_dn, nullptr, nullptr, BandOut{}, ex.sfc_jac, ex.jac_up);
-  else if (ex.byband())
-    hipLaunchKernelGGL(lw_rescl_kernel<true>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1,
-                       a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
-                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, band_out(ex), nullptr, nullptr);
-  else
-    hipLaunchKernelGGL(lw_rescl_kernel<false>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1,
-                       a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source, (float *)ws,
-                       p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, BandOut{}, nullptr, nullptr);
-  RRTMGPNN_LAUNCH_CHECK("lw_rescl_kernel");
-  return RRTMGPNN_OK;
+  // by band, or the Jacobian (never both, and the Jacobian without g-point outputs: refused above)
+  const bool bb = ex.byband();
+  const uint32_t options = jac ? kResclOptJac : (bb ? kResclOptBand : 0u);
+  return launch_listed(ctx, kSolverLwRescl, LwResclInstances{}, options, [&](auto oc) -> int {
+    hipLaunchKernelGGL(lw_rescl_kernel<decltype(oc)::value>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay,
+                       ncol, p.top_at_1, a, p.inc_flux, p.tau, ssa, g, lay_source, lev_source, p.sfc_emis, sfc_source,
+                       (float *)ws, p.flux_up, p.flux_dn, ex.gpt_up, ex.gpt_dn, bb ? band_out(ex) : BandOut{},
+                       ex.sfc_jac, ex.jac_up);
+    RRTMGPNN_LAUNCH_CHECK("lw_rescl_kernel");
+    return RRTMGPNN_OK;
+  });
 }
 
 // lw_rescl_planck_inc_kernel's LDS in bytes; dual: two rings, four part planes
@@ -823,6 +830,11 @@ static size_t lw_rescl_planck_lds(int nbnd, int nlay, int ngpt, bool dual)
   return sizeof(float) * (kExpTabFloats + lw_btab_floats(nbnd, nlay) + (size_t)(dual ? 2 : 1) * kScatRing * ngpt +
                           (size_t)(dual ? 4 : 2) * (nlay + 1) * 4);
 }
+
+// The instances lw_rescl_planck_inc_kernel is compiled for: {mask} x {aerosol} x {dual}
+using LwResclIncInstances =
+    SolverInstances<0u, kScatOptMask, kScatOptAer, kScatOptAer | kScatOptMask, kScatOptDual, kScatOptDual | kScatOptMask,
+                    kScatOptDual | kScatOptAer, kScatOptDual | kScatOptAer | kScatOptMask>;
 
 // in.tau_bnd, ssa_bnd, g_bnd: the band-resolved two-stream increment; ex.mask_bits, or null: the McICA mask that
 // switches it; ex.aer_tau, or null: the 1scl aerosol in front of it (from the _clr_all entry only: _1rescl_planck_inc
@@ -850,32 +862,18 @@ int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, co
   void *ws = nullptr;
   const int planes = nmus > 1 ? 3 : 1;  // the shared radn_dn / radn_up plane, and the two angle accumulators
   if (int rc = ctx->workspace(sizeof(float) * planes * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
-                       p.tau, in.pfrac, in.tau_bnd, ssa_bnd, g_bnd, p.sfc_emis, in.pl, in.bands, ex.mask_bits,
-                       (float *)ws, p.flux_up, p.flux_dn, ScatDualArgs<false>{});
-  };
-  // the kAer / kDual instances, with their own arguments
-  auto go2 = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
-                       p.tau, in.pfrac, in.tau_bnd, ssa_bnd, g_bnd, p.sfc_emis, in.pl, in.bands, ex.mask_bits,
-                       (float *)ws, p.flux_up, p.flux_dn, ScatDualArgs<true>{ex.aer_tau, flux_up_clr, flux_dn_clr});
-  };
-  const bool m = ex.mask_bits != nullptr, aer = ex.aer_tau != nullptr;
-  if (dual) {
-    if (aer && m)  go2(lw_rescl_planck_inc_kernel<true, kScatPf, true, true>);
-    else if (aer)  go2(lw_rescl_planck_inc_kernel<false, kScatPf, true, true>);
-    else if (m)    go2(lw_rescl_planck_inc_kernel<true, kScatPf, false, true>);
-    else           go2(lw_rescl_planck_inc_kernel<false, kScatPf, false, true>);
-  } else if (aer) {
-    if (m) go2(lw_rescl_planck_inc_kernel<true, kScatPf, true, false>);
-    else   go2(lw_rescl_planck_inc_kernel<false, kScatPf, true, false>);
-  } else {
-    if (m) go(lw_rescl_planck_inc_kernel<true, kScatPf, false, false>);
-    else   go(lw_rescl_planck_inc_kernel<false, kScatPf, false, false>);
-  }
-  RRTMGPNN_LAUNCH_CHECK("lw_rescl_planck_inc_kernel");
-  return RRTMGPNN_OK;
+  const uint32_t options = (ex.mask_bits ? kScatOptMask : 0u) | (ex.aer_tau ? kScatOptAer : 0u) | (dual ? kScatOptDual : 0u);
+  return launch_listed(ctx, kSolverLwResclInc, LwResclIncInstances{}, options, [&](auto oc) -> int {
+    constexpr uint32_t O = decltype(oc)::value;
+    // the kAer / kDual instances have their own arguments behind the others' list
+    ScatDualArgs<(O & (kScatOptAer | kScatOptDual)) != 0> da{};
+    if constexpr ((O & (kScatOptAer | kScatOptDual)) != 0) da = {ex.aer_tau, flux_up_clr, flux_dn_clr};
+    hipLaunchKernelGGL(lw_rescl_planck_inc_kernel<O>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol,
+                       p.top_at_1, a, p.inc_flux, p.tau, in.pfrac, in.tau_bnd, ssa_bnd, g_bnd, p.sfc_emis, in.pl,
+                       in.bands, ex.mask_bits, (float *)ws, p.flux_up, p.flux_dn, da);
+    RRTMGPNN_LAUNCH_CHECK("lw_rescl_planck_inc_kernel");
+    return RRTMGPNN_OK;
+  });
 }
 
 // rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 for scattering clouds (rte/mo_rte_lw.F90:372-387): clear-sky
@@ -914,7 +912,7 @@ int launch_lw_rescl_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex
   LwPlanckIn clear_in = in;
   clear_in.tau_bnd = ex.aer_tau;
   if (int rc = launch_lw_noscat_planck(ctx, clear_ex, clear, clear_in)) return rc;
-  return launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd, nullptr, nullptr);
+  return ctx->second_solver_launch(launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd, nullptr, nullptr));
 }
 
 int launch_lw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, int ngpt, int nlay, int ncol, int top_at_1,

@@ -199,8 +199,10 @@ static constexpr int kLwMaxG = 256, kSwMaxG = 256;  // g-points per column block
 // adds (the sum of the two increments, or the other order, gives other float32 values).  One more band value per
 // prefetched layer, read as ld_inc reads the cloud's.  The mask never touches it.  With kDual the clear radiance takes
 // ta * D: the clear sky is gases plus aerosols (:155-157).
-template <bool kFused, bool kInc, int kPF, bool kMulti, bool kBand = false, bool kDual = false, bool kMask = false,
-          bool kMaskS = false, bool kJac = false, bool kAer = false>
+//
+// O: the instance's options, an OR of the kLwOpt* bits (internal.hpp), named again in the first lines; the prefetch
+// depth follows kFused
+template <uint32_t O>
 __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top_at_1, LwAngles ang,
                                            const float *__restrict__ inc_flux, const float *__restrict__ tau,
                                            const float *__restrict__ lay, const float *__restrict__ lev,
@@ -211,6 +213,10 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
                                            const uint32_t *__restrict__ cmask, const float *__restrict__ sfc_jac,
                                            float *__restrict__ flux_jac, const float *__restrict__ tau_aer)
 {
+  constexpr bool kFused = (O & kLwOptFused) != 0, kInc = (O & kLwOptInc) != 0, kMulti = (O & kLwOptMulti) != 0;
+  constexpr bool kBand = (O & kLwOptBand) != 0, kDual = (O & kLwOptDual) != 0, kMask = (O & kLwOptMask) != 0;
+  constexpr bool kMaskS = (O & kLwOptMaskS) != 0, kJac = (O & kLwOptJac) != 0, kAer = (O & kLwOptAer) != 0;
+  constexpr int kPF = kFused ? kLwfPf : kLwPf;
   constexpr int kR = kDual ? kRingDual : kRing;  // levels staged per flush
   // kJac with one angle: the down pass' chunk, the up pass' (two rings), and the ring's rows
   constexpr bool kJac1 = kJac && !kMulti;
@@ -656,13 +662,60 @@ __global__ void LW_BOUNDS lw_noscat_kernel(int ngpt, int nlay, int ncol, int top
   }
 }
 
+// The instances lw_noscat_kernel is compiled for: {one angle, several} x {broadband, by band, Jacobian} on source
+// arrays, on the fused Planck sources and on those with the band increment; the rest need the last
+constexpr uint32_t kLwOptFI = kLwOptFused | kLwOptInc;
+using LwNoscatInstances = SolverInstances<
+    0u, kLwOptMulti, kLwOptBand, kLwOptBand | kLwOptMulti, kLwOptJac, kLwOptJac | kLwOptMulti,
+    kLwOptFused, kLwOptFused | kLwOptMulti, kLwOptFused | kLwOptBand, kLwOptFused | kLwOptBand | kLwOptMulti,
+    kLwOptFused | kLwOptJac, kLwOptFused | kLwOptJac | kLwOptMulti,
+    kLwOptFI, kLwOptFI | kLwOptMulti, kLwOptFI | kLwOptBand, kLwOptFI | kLwOptBand | kLwOptMulti, kLwOptFI | kLwOptJac,
+    kLwOptFI | kLwOptJac | kLwOptMulti,
+    // clear beside all sky (one angle): plain, masked by the lane's word or the wave's pair, and their aerosol twins
+    kLwOptFI | kLwOptDual, kLwOptFI | kLwOptDual | kLwOptMask, kLwOptFI | kLwOptDual | kLwOptMask | kLwOptMaskS,
+    kLwOptFI | kLwOptDual | kLwOptAer, kLwOptFI | kLwOptDual | kLwOptAer | kLwOptMask,
+    kLwOptFI | kLwOptDual | kLwOptAer | kLwOptMask | kLwOptMaskS,
+    // aerosol + (masked) cloud
+    kLwOptFI | kLwOptAer, kLwOptFI | kLwOptAer | kLwOptMulti, kLwOptFI | kLwOptAer | kLwOptMask,
+    kLwOptFI | kLwOptAer | kLwOptMask | kLwOptMulti,
+    // masked cloud: broadband, by band, Jacobian
+    kLwOptFI | kLwOptMask, kLwOptFI | kLwOptMask | kLwOptMulti, kLwOptFI | kLwOptMask | kLwOptBand,
+    kLwOptFI | kLwOptMask | kLwOptBand | kLwOptMulti, kLwOptFI | kLwOptMask | kLwOptJac,
+    kLwOptFI | kLwOptMask | kLwOptJac | kLwOptMulti>;
+
+// The instance a call runs (its options value), or the refusal; launch_lw_impl has checked the extras against each
+// other before.  fused / inc: the Planck sources are formed in-kernel / tau takes the band increment; dual: the clear
+// beside the all-sky fluxes
+static int select_lw_noscat(const SolverExtras &ex, const LwNoscat &p, bool fused, bool inc, bool dual, uint32_t *options)
+{
+  const bool gpt = ex.gpt_up != nullptr, mask = ex.mask_bits != nullptr, multi = p.nmus > 1 || gpt;
+  uint32_t o = (fused ? kLwOptFused : 0u) | (inc ? kLwOptInc : 0u) | (mask ? kLwOptMask : 0u) |
+               (ex.aer_tau ? kLwOptAer : 0u);
+  if (dual) {
+    // McICA beside clear-sky: the wave-uniform pair where every wave is full and the pair can be read as one 8-byte
+    // scalar, the per-lane word otherwise
+    o |= kLwOptDual;
+    if (mask && p.ngpt % 64 == 0 && (reinterpret_cast<uintptr_t>(ex.mask_bits) & 7u) == 0) o |= kLwOptMaskS;
+  } else if (ex.aer_tau) {
+    // aerosols in front of the (masked) cloud increment: one angle or several, with or without the mask
+    o |= multi ? kLwOptMulti : 0u;
+  } else {
+    // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask)
+    if (mask && !(fused && inc)) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: a cloud mask needs the fused band increment");
+    if (mask && (gpt || ex.lw_Ds))
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: a cloud mask with g-point outputs or lw_Ds");
+    o |= (multi ? kLwOptMulti : 0u) | (ex.jac_up ? kLwOptJac : (ex.byband() ? kLwOptBand : 0u));
+  }
+  *options = o;
+  return RRTMGPNN_OK;
+}
+
 // lay_source / lev_source / sfc_source: the unfused path's sources (kFused: formed in-kernel from `in`).
 // up_clr / dn_clr (both or neither; kFused && kInc, one angle, no extras but the mask): the dual instance, clear-sky
 // fluxes beside the all-sky ones
-template <bool kFused, bool kInc>
-static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *lay_source,
-                          const float *lev_source, const float *sfc_source, const LwPlanckIn &in,
-                          float *up_clr = nullptr, float *dn_clr = nullptr)
+static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, bool fused, bool inc,
+                          const float *lay_source, const float *lev_source, const float *sfc_source,
+                          const LwPlanckIn &in, float *up_clr = nullptr, float *dn_clr = nullptr)
 {
   const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol, nmus = p.nmus;
   if (ncol == 0) return RRTMGPNN_OK;
@@ -674,7 +727,7 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   const bool gpt = ex.gpt_up != nullptr;
   const bool bb = ex.byband();
   const bool dual = up_clr != nullptr;
-  if (dual && (!kFused || !kInc || nmus != 1 || gpt || bb || ex.lw_Ds || !dn_clr))
+  if (dual && (!fused || !inc || nmus != 1 || gpt || bb || ex.lw_Ds || !dn_clr))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: the dual instance is the one-angle fused-Planck path without extras");
   if (bb && ex.bnd_dir) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: bnd_flux_dn_dir is not a longwave output");
   if (bb && gpt)
@@ -684,12 +737,12 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   const bool jac = ex.jac_up != nullptr;
   if (jac && (gpt || bb || dual))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: the flux Jacobian comes without g-point, by-band or clear-sky outputs");
-  if (jac && (ex.sfc_jac == nullptr) != kFused)
+  if (jac && (ex.sfc_jac == nullptr) != fused)
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: the flux Jacobian needs sfc_source_Jac with source arrays, and none "
                                        "with the fused Planck sources");
   // the aerosol increment in front of the fused one (rrtmgpnn_solver_request_aerosol)
   const bool aer = ex.aer_tau != nullptr;
-  if (aer && (!kFused || !kInc))
+  if (aer && (!fused || !inc))
     return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: an aerosol increment needs the fused band increment behind it");
   // (Not reachable through the C ABI as it stands: the entries that take the request have no g-point or lw_Ds
   // arguments and refuse a by-band or Jacobian request beside it themselves.  Kept so that the launcher never runs an
@@ -708,7 +761,7 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
   const int ring_rows = dual ? 2 * kRingDual : ((jac && !multi) ? std::max(kRing, 2 * kRingDual) : kRing);
   size_t lds = sizeof(float) * (kExpTabFloats + (size_t)ring_rows * lw_ring_stride(ngpt) +
                                 (size_t)(dual ? 4 : ((jac && !multi) ? 3 : 2)) * (nlay + 1) * 4);
-  if (kFused) lds += sizeof(float) * lw_btab_floats(in.bands.nbnd, nlay, jac);
+  if (fused) lds += sizeof(float) * lw_btab_floats(in.bands.nbnd, nlay, jac);
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: too many layers for LDS partials");
   // per-g accumulators: the caller's g-point arrays, or (several angles) the context workspace
   float *gdn = ex.gpt_dn, *gup = ex.gpt_up;
@@ -723,98 +776,33 @@ static int launch_lw_impl(rrtmgpnn_context *ctx, const SolverExtras &ex, const L
     gup = gdn + nv;
     gcs = planes * nv;
   }
-  constexpr int PF = kFused ? kLwfPf : kLwPf;
   const BandOut bo = bb ? band_out(ex) : BandOut{};
-  auto go = [&](auto kern) {
-    const float *src = kFused ? in.pfrac : lay_source;
-    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, a, p.inc_flux,
-                       p.tau, src, kFused ? src : lev_source, p.sfc_emis, sfc_source, in.pl, in.bands,
-                       kInc ? in.tau_bnd : nullptr, gdn, gup, gcs, p.flux_up, p.flux_dn, bo, ex.mask_bits, ex.sfc_jac,
-                       ex.jac_up, ex.aer_tau);
-  };
-  if constexpr (kFused && kInc) {
-    if (dual) {
-      gdn = dn_clr;
-      gup = up_clr;
-      if (aer) {
-        // the dual instances' aerosol twins: the clear set is gases plus aerosols
-        if (ex.mask_bits && ngpt % 64 == 0 && (reinterpret_cast<uintptr_t>(ex.mask_bits) & 7u) == 0)
-          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, true, false, true>);
-        else if (ex.mask_bits)
-          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, false, false, true>);
-        else
-          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, false, false, false, true>);
-        RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual, aerosol)");
-        return RRTMGPNN_OK;
-      }
-      if (ex.mask_bits) {
-        // McICA beside clear-sky: the wave-uniform pair where every wave is full and the pair can be read as one
-        // 8-byte scalar, the per-lane word otherwise
-        if (ngpt % 64 == 0 && (reinterpret_cast<uintptr_t>(ex.mask_bits) & 7u) == 0)
-          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, true>);
-        else
-          go(lw_noscat_kernel<kFused, kInc, PF, false, false, true, true, false>);
-        RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual, masked)");
-        return RRTMGPNN_OK;
-      }
-      go(lw_noscat_kernel<kFused, kInc, PF, false, false, true>);
-      RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (dual)");
-      return RRTMGPNN_OK;
-    }
+  if (dual) {
+    gdn = dn_clr;
+    gup = up_clr;
   }
-  if constexpr (kFused && kInc) {
-    if (aer) {
-      // aerosols in front of the (masked) cloud increment: one angle or several, with or without the mask
-      if (ex.mask_bits && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true, false, false, true>);
-      else if (ex.mask_bits)     go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true, false, false, true>);
-      else if (multi)            go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, false, false, false, true>);
-      else                       go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, false, false, false, true>);
-      RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (aerosol)");
-      return RRTMGPNN_OK;
-    }
-  }
-  if (ex.mask_bits) {
-    // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask)
-    if constexpr (kFused && kInc) {
-      if (gpt || ex.lw_Ds)
-        return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw solver: a cloud mask with g-point outputs or lw_Ds");
-      if (jac) {
-        if (multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true, false, true>);
-        else       go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true, false, true>);
-        RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (masked, Jacobian)");
-        return RRTMGPNN_OK;
-      }
-      // bb: the masked by-band twins (rrtmgpnn_solver_request_byband_mcica)
-      if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true, false, true>);
-      else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true, false, true>);
-      else if (multi)  go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, true>);
-      else             go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, true>);
-      RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel (masked)");
-      return RRTMGPNN_OK;
-    } else {
-      return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: a cloud mask needs the fused band increment");
-    }
-  }
-  if (jac && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, false, false, false, false, true>);
-  else if (jac)    go(lw_noscat_kernel<kFused, kInc, PF, false, false, false, false, false, true>);
-  else if (bb && multi) go(lw_noscat_kernel<kFused, kInc, PF, true, true>);
-  else if (bb)     go(lw_noscat_kernel<kFused, kInc, PF, false, true>);
-  else if (multi)  go(lw_noscat_kernel<kFused, kInc, PF, true>);
-  else             go(lw_noscat_kernel<kFused, kInc, PF, false>);
-  RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel");
-  return RRTMGPNN_OK;
+  uint32_t options = 0;
+  if (int rc = select_lw_noscat(ex, p, fused, inc, dual, &options)) return rc;
+  return launch_listed(ctx, kSolverLwNoscat, LwNoscatInstances{}, options, [&](auto oc) -> int {
+    const float *src = fused ? in.pfrac : lay_source;
+    hipLaunchKernelGGL(lw_noscat_kernel<decltype(oc)::value>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay,
+                       ncol, p.top_at_1, a, p.inc_flux, p.tau, src, fused ? src : lev_source, p.sfc_emis, sfc_source,
+                       in.pl, in.bands, inc ? in.tau_bnd : nullptr, gdn, gup, gcs, p.flux_up, p.flux_dn, bo,
+                       ex.mask_bits, ex.sfc_jac, ex.jac_up, ex.aer_tau);
+    RRTMGPNN_LAUNCH_CHECK("lw_noscat_kernel");
+    return RRTMGPNN_OK;
+  });
 }
 
 int launch_lw_noscat(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const float *lay_source,
                      const float *lev_source, const float *sfc_source)
 {
-  return launch_lw_impl<false, false>(ctx, ex, p, lay_source, lev_source, sfc_source, LwPlanckIn{});
+  return launch_lw_impl(ctx, ex, p, false, false, lay_source, lev_source, sfc_source, LwPlanckIn{});
 }
 
 int launch_lw_noscat_planck(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, const LwPlanckIn &in)
 {
-  if (in.tau_bnd) return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
-  return launch_lw_impl<true, false>(ctx, ex, p, nullptr, nullptr, nullptr, in);
+  return launch_lw_impl(ctx, ex, p, true, in.tau_bnd != nullptr, nullptr, nullptr, nullptr, in);
 }
 
 // rte_lw of extensions/mo_rrtmgp_clr_all_sky.F90:146-172 on the fused-Planck path: clear-sky fluxes from tau, all-sky
@@ -825,8 +813,9 @@ int launch_lw_noscat_planck(rrtmgpnn_context *ctx, const SolverExtras &ex, const
 int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex, bool dual, const LwNoscat &p,
                                     const LwPlanckIn &in, float *flux_up_clr, float *flux_dn_clr)
 {
+  if (p.ncol == 0) return RRTMGPNN_OK;
   if (dual && p.nmus == 1)
-    return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in, flux_up_clr, flux_dn_clr);
+    return launch_lw_impl(ctx, ex, p, true, true, nullptr, nullptr, nullptr, in, flux_up_clr, flux_dn_clr);
   SolverExtras clear_ex = ex;
   clear_ex.mask_bits = nullptr;
   LwNoscat clear = p;
@@ -838,11 +827,11 @@ int launch_lw_noscat_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &e
     clear_ex.aer_tau = nullptr;
     LwPlanckIn clear_in = in;
     clear_in.tau_bnd = ex.aer_tau;
-    if (int rc = launch_lw_impl<true, true>(ctx, clear_ex, clear, nullptr, nullptr, nullptr, clear_in)) return rc;
-    return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
+    if (int rc = launch_lw_impl(ctx, clear_ex, clear, true, true, nullptr, nullptr, nullptr, clear_in)) return rc;
+    return ctx->second_solver_launch(launch_lw_impl(ctx, ex, p, true, true, nullptr, nullptr, nullptr, in));
   }
-  if (int rc = launch_lw_impl<true, false>(ctx, clear_ex, clear, nullptr, nullptr, nullptr, in)) return rc;
-  return launch_lw_impl<true, true>(ctx, ex, p, nullptr, nullptr, nullptr, in);
+  if (int rc = launch_lw_impl(ctx, clear_ex, clear, true, false, nullptr, nullptr, nullptr, in)) return rc;
+  return ctx->second_solver_launch(launch_lw_impl(ctx, ex, p, true, true, nullptr, nullptr, nullptr, in));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -935,7 +924,8 @@ __device__ __forceinline__ SwCoef sw_two_stream(float tau, float w0, float g, fl
 // takes the checkpointed kernel's g-point instance.
 // kBand: also the by-band fluxes bo.up / bo.dn / bo.dir (ty_fluxes_byband, (nbnd, nlay+1, ncol)), summed from the ring
 // rows in the flush's barrier window; the total down value is dif + dir, rounded once per g-point (band_flush).
-template <bool kHasG, bool kInc, int kPF, bool kGpt = false, bool kBand = false>
+// O: the instance's options, an OR of the kSwOpt* bits (internal.hpp), named again in the first lines
+template <uint32_t O>
 __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int top_at_1,
                                             const float *__restrict__ inc_flux, const float *__restrict__ inc_dif,
                                             const float *__restrict__ tau, const float *__restrict__ ssa,
@@ -948,6 +938,9 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
                                             float *__restrict__ gpt_up, float *__restrict__ gpt_dn,
                                             float *__restrict__ gpt_dir, BandOut bo)
 {
+  constexpr bool kHasG = (O & kSwOptHasG) != 0, kInc = (O & kSwOptInc) != 0, kGpt = (O & kSwOptGpt) != 0;
+  constexpr bool kBand = (O & kSwOptBand) != 0;
+  constexpr int kPF = kSwPf;
   static_assert(kRingSw % kPF == 0, "prefetch depth must divide the ring");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int nlev = nlay + 1;
@@ -1136,6 +1129,12 @@ __global__ void SW_BOUNDS sw_2stream_kernel(int ngpt, int nlay, int ncol, int to
   }
 }
 
+// The instances sw_2stream_kernel is compiled for: {gas g} x {increment} x {broadband, by band}, and g-point outputs
+// without the increment
+using Sw2StreamInstances =
+    SolverInstances<0u, kSwOptHasG, kSwOptInc, kSwOptInc | kSwOptHasG, kSwOptBand, kSwOptBand | kSwOptHasG,
+                    kSwOptBand | kSwOptInc, kSwOptBand | kSwOptInc | kSwOptHasG, kSwOptGpt, kSwOptGpt | kSwOptHasG>;
+
 bool sw_ck_selected(const rrtmgpnn_context *ctx, int ngpt)
 {
   const int mode = ctx->sw_kernel >= 0 ? ctx->sw_kernel : g_sw_kernel_default;
@@ -1227,25 +1226,17 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
   if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: too many layers for LDS partials");
   const BandArgs nob{};
   const BandOut bo = bb ? band_out(ex) : BandOut{};
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, p.inc_flux,
-                       p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, inc ? *p.bands : nob,
-                       inc ? p.tau_bnd : nullptr, inc ? p.ssa_bnd : nullptr, inc ? p.g_bnd : nullptr, (float *)ws,
-                       p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bo);
-  };
-  // <kHasG, kInc, kPF, kGpt, kBand>
-  if (bb && inc && g) go(sw_2stream_kernel<true, true, kSwPf, false, true>);
-  else if (bb && inc) go(sw_2stream_kernel<false, true, kSwPf, false, true>);
-  else if (bb && g)   go(sw_2stream_kernel<true, false, kSwPf, false, true>);
-  else if (bb)        go(sw_2stream_kernel<false, false, kSwPf, false, true>);
-  else if (gpt && g)  go(sw_2stream_kernel<true, false, kSwPf, true>);
-  else if (gpt)       go(sw_2stream_kernel<false, false, kSwPf, true>);
-  else if (inc && g)  go(sw_2stream_kernel<true, true, kSwPf>);
-  else if (inc)       go(sw_2stream_kernel<false, true, kSwPf>);
-  else if (g)         go(sw_2stream_kernel<true, false, kSwPf>);
-  else                go(sw_2stream_kernel<false, false, kSwPf>);
-  RRTMGPNN_LAUNCH_CHECK("sw_2stream_kernel");
-  return RRTMGPNN_OK;
+  // by-band outputs come with or without the increment; g-point outputs without (refused above)
+  const uint32_t options = (g ? kSwOptHasG : 0u) | (inc ? kSwOptInc : 0u) | (bb ? kSwOptBand : (gpt ? kSwOptGpt : 0u));
+  return launch_listed(ctx, kSolverSw2Stream, Sw2StreamInstances{}, options, [&](auto oc) -> int {
+    hipLaunchKernelGGL(sw_2stream_kernel<decltype(oc)::value>, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay,
+                       ncol, p.top_at_1, p.inc_flux, p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif,
+                       inc ? *p.bands : nob, inc ? p.tau_bnd : nullptr, inc ? p.ssa_bnd : nullptr,
+                       inc ? p.g_bnd : nullptr, (float *)ws, p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn,
+                       ex.gpt_dir, bo);
+    RRTMGPNN_LAUNCH_CHECK("sw_2stream_kernel");
+    return RRTMGPNN_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------

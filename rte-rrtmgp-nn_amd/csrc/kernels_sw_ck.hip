@@ -294,11 +294,20 @@ constexpr SwCkCp kCpSwOther = {};
 // 8 g bytes), the planes ((2 ngpt, nlay, ncol) each) and the ring ([2 skies][3][R][rs], the footprint of two columns)
 // are per sky; one flush window reduces both (ring_flush_sw*'s kSkies) and stores sky 1 to clr_up / clr_dn / clr_dir.
 // kBandPair is not used: one g-point has one band whatever the limits are.
-template <bool kHasG, bool kInc, int K, bool kGpt = false, int R = kCkRing,
-          int WAVES = (!kHasG && !kInc && !kGpt) ? kCkWavesNN : kCkWaves, bool kTn = false,
-          class V = f2, bool kEmk = false, bool kBandPair = false, int P1C = kCkP1, int AHEAD = 1,
-          bool kBand = false, bool kMask = false, bool kAer = false, bool kDual = false>
-__global__ void __launch_bounds__(512, WAVES)
+// The workspace planes (kSwCkTn | kSwCkEmk) of each instance family, from the constants above
+constexpr uint32_t sw_ck_planes(bool tn, bool emk) { return (tn ? kSwCkTn : 0u) | (emk ? kSwCkEmk : 0u); }
+constexpr uint32_t kSwCkPlanesNN = sw_ck_planes(kCkTnNN, kCkEmkNN), kSwCkPlanesInc = sw_ck_planes(kCkTnInc, kCkEmkInc),
+                   kSwCkPlanesDual = sw_ck_planes(kCkTnDual, kCkEmkDual),
+                   kSwCkPlanesSmall = sw_ck_planes(kCkTnSmall, kCkEmkSmall);
+// waves per SIMD of instance O: the small-grid floor, the large-grid clear-sky NN instance's, or the others'
+constexpr int sw_ck_waves(uint32_t O)
+{
+  return (O & kSwCkSmall) ? kCkWavesSmall : ((O & (kSwCkHasG | kSwCkInc | kSwCkGpt)) == 0 ? kCkWavesNN : kCkWaves);
+}
+
+// O: the instance's options, an OR of the kSwCk* bits (internal.hpp), named again in the first lines
+template <uint32_t O>
+__global__ void __launch_bounds__(512, sw_ck_waves(O))
     sw_2stream_ck_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
                          const float *__restrict__ ssa, const float *__restrict__ gg, const float *__restrict__ mu0p,
@@ -311,6 +320,14 @@ __global__ void __launch_bounds__(512, WAVES)
                          const float *__restrict__ ssa_aer, const float *__restrict__ g_aer,
                          float *__restrict__ clr_up, float *__restrict__ clr_dn, float *__restrict__ clr_dir)
 {
+  constexpr bool kHasG = (O & kSwCkHasG) != 0, kInc = (O & kSwCkInc) != 0, kGpt = (O & kSwCkGpt) != 0;
+  constexpr bool kTn = (O & kSwCkTn) != 0, kEmk = (O & kSwCkEmk) != 0, kBandPair = (O & kSwCkBandPair) != 0;
+  constexpr bool kBand = (O & kSwCkBand) != 0, kMask = (O & kSwCkMask) != 0, kAer = (O & kSwCkAer) != 0;
+  constexpr bool kDual = (O & kSwCkDual) != 0, kSmall = (O & kSwCkSmall) != 0;
+  // chunk length, ring levels, wave floor, pass-1 chunks per step and prefetch distance: the small-grid set or the default
+  constexpr int K = kSmall ? kCkKSmall : kCkK, R = kSmall ? kCkRingSmall : kCkRing, WAVES = sw_ck_waves(O);
+  constexpr int P1C = kSmall ? kCkP1Small : kCkP1, AHEAD = kSmall ? kCkAheadSmall : 1;
+  using V = std::conditional_t<kSmall, VSmall, f2>;
   static_assert(R % K == 0, "the flux ring must hold whole chunks");
   static_assert(!kDual || (kInc && sizeof(V) == 8 && !kGpt && !kBand && !kBandPair),
                 "the dual instances: two skies of one g-point per lane, broadband outputs");
@@ -791,38 +808,54 @@ size_t sw_2stream_ck_ws_floats(int ngpt, int nlay, int ncol, bool small, bool in
   return (size_t)ngpt * ncol * (nck + 2 * (nck + 1)) + tn;
 }
 
-// ngpt even and <= 256
-int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws, bool planes,
-                         const SwBcDev *bc)
+// The instances sw_2stream_ck_kernel is compiled for, family by family (select_sw_ck below names the calls they serve)
+using SwCkInstances = SolverInstances<
+    // clear + all sky from one launch: {gas g} x {mask} x {aerosol}, with the dual family's planes and without
+    kSwCkDual | kSwCkInc | kSwCkPlanesDual, kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkHasG,
+    kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkMask, kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkMask | kSwCkHasG,
+    kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkAer, kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkAer | kSwCkHasG,
+    kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkMask | kSwCkAer,
+    kSwCkDual | kSwCkInc | kSwCkPlanesDual | kSwCkMask | kSwCkAer | kSwCkHasG,
+    kSwCkDual | kSwCkInc, kSwCkDual | kSwCkInc | kSwCkHasG, kSwCkDual | kSwCkInc | kSwCkMask,
+    kSwCkDual | kSwCkInc | kSwCkMask | kSwCkHasG, kSwCkDual | kSwCkInc | kSwCkAer,
+    kSwCkDual | kSwCkInc | kSwCkAer | kSwCkHasG, kSwCkDual | kSwCkInc | kSwCkMask | kSwCkAer,
+    kSwCkDual | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkHasG,
+    // aerosol + (masked) cloud, band pair: {gas g} x {mask}, with the all-sky planes and without
+    kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkPlanesInc, kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkPlanesInc | kSwCkHasG,
+    kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkPlanesInc | kSwCkMask,
+    kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkPlanesInc | kSwCkMask | kSwCkHasG,
+    kSwCkAer | kSwCkInc | kSwCkBandPair, kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkHasG,
+    kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkMask, kSwCkAer | kSwCkInc | kSwCkBandPair | kSwCkMask | kSwCkHasG,
+    // masked cloud: {gas g} x {band pair}, by band (no planes), with the all-sky planes and without
+    kSwCkMask | kSwCkInc | kSwCkBand, kSwCkMask | kSwCkInc | kSwCkBand | kSwCkHasG,
+    kSwCkMask | kSwCkInc | kSwCkBand | kSwCkBandPair, kSwCkMask | kSwCkInc | kSwCkBand | kSwCkBandPair | kSwCkHasG,
+    kSwCkMask | kSwCkInc | kSwCkPlanesInc, kSwCkMask | kSwCkInc | kSwCkPlanesInc | kSwCkHasG,
+    kSwCkMask | kSwCkInc | kSwCkPlanesInc | kSwCkBandPair, kSwCkMask | kSwCkInc | kSwCkPlanesInc | kSwCkBandPair | kSwCkHasG,
+    kSwCkMask | kSwCkInc, kSwCkMask | kSwCkInc | kSwCkHasG, kSwCkMask | kSwCkInc | kSwCkBandPair,
+    kSwCkMask | kSwCkInc | kSwCkBandPair | kSwCkHasG,
+    // g-point outputs
+    kSwCkGpt, kSwCkGpt | kSwCkHasG,
+    // by band: the small-grid instance, the increment ({gas g} x {band pair}) and the clear sky, all without planes
+    kSwCkBand | kSwCkSmall | kSwCkPlanesSmall, kSwCkBand | kSwCkInc, kSwCkBand | kSwCkInc | kSwCkHasG,
+    kSwCkBand | kSwCkInc | kSwCkBandPair, kSwCkBand | kSwCkInc | kSwCkBandPair | kSwCkHasG, kSwCkBand,
+    kSwCkBand | kSwCkHasG,
+    // the increment: {gas g} x {band pair}, with the all-sky planes and without
+    kSwCkInc | kSwCkPlanesInc, kSwCkInc | kSwCkPlanesInc | kSwCkHasG, kSwCkInc | kSwCkPlanesInc | kSwCkBandPair,
+    kSwCkInc | kSwCkPlanesInc | kSwCkBandPair | kSwCkHasG, kSwCkInc, kSwCkInc | kSwCkHasG, kSwCkInc | kSwCkBandPair,
+    kSwCkInc | kSwCkBandPair | kSwCkHasG,
+    // clear sky: with a gas g; the small-grid instance; the large-grid NN instance with its planes and without
+    kSwCkHasG, kSwCkSmall | kSwCkPlanesSmall, kSwCkPlanesNN, 0u>;
+
+// The instance a call runs (its options value), or the refusal.  planes: the workspace with the instance family's
+// planes was allocated (launch_sw_2stream's fallback runs the plane-free twins: the same bits); small: sw_ck_small()
+static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes, bool small, uint32_t *options)
 {
-  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
-  const float *const g = p.g, *const tau_bnd = p.tau_bnd, *const ssa_bnd = p.ssa_bnd, *const g_bnd = p.g_bnd;
   const BandArgs *const bands = p.bands;
-  const int ncb2 = 2 * (ngpt / 2) <= 512 ? 2 : 1;  // two columns per block where 512 lanes hold them
-  const BandArgs nob{};
-  const BandArgs &b = bands ? *bands : nob;
-  const SwBcDev nobc{};  // tsi == NULL: the caller's inc_flux, mu0 and albedos
-  const SwBcDev &bcd = bc ? *bc : nobc;
-  const bool bb = ex.byband();
-  const BandOut bo = bb ? band_out(ex) : BandOut{};
-  // npl g-points per lane, ncb columns per block
-  auto go = [&](auto kern, const float *tb, const float *sb, const float *gb, int ring = kCkRing, int npl = 2) -> int {
-    const int ncb = npl == 2 ? ncb2 : columns_per_block(ngpt);
-    if (ncb > kFlushLanesMaxCols)  // the flush's lane -> column map (ring_flush_sw_lanes) covers at most 4 columns
-      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: more columns per block than the ordered flush maps");
-    const int threads = (ncb * (ngpt / npl) + 63) / 64 * 64;
-    const dim3 grid((ncol + ncb - 1) / ncb), block(threads);
-    const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)ncb * 3 * ring * ck_ring_stride(ngpt) + 4);  // + spare
-    if (lds > 160 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: LDS ring exceeds 160 KiB");
-    if (lds > 64 * 1024)
-      if (int rc = raise_lds_limit((const void *)kern)) return rc;
-    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
-                       p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tb, sb, gb, (float *)ws,
-                       p.flux_up, p.flux_dn, p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits,
-                       ex.aer_tau, ex.aer_ssa, ex.aer_g, nullptr, nullptr, nullptr);
-    RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel");
-    return RRTMGPNN_OK;
-  };
+  const bool bb = ex.byband(), gpt = ex.gpt_up || ex.gpt_dn || ex.gpt_dir;
+  // kBandPair: every band of the increment starts at an even (0-based) g-point
+  bool pair = bands != nullptr;
+  for (int i = 0; bands && i < bands->nbnd; i++) pair = pair && ((bands->lims[2 * i] - 1) % 2 == 0);
+  uint32_t o = (p.g ? kSwCkHasG : 0u) | (bands ? kSwCkInc : 0u) | (ex.mask_bits ? kSwCkMask : 0u);
   if (ex.clr_up) {
     // clear-sky beside all-sky fluxes (rrtmgpnn_sw_solver_2stream_clr_all): the dual instances, one column per block,
     // one g-point per lane, two rings; {gas g} x {mask} x {aerosol}, with the planes of kCkTnDual / kCkEmkDual or, when
@@ -830,43 +863,12 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
     if (!bands || !ex.clr_dn || !ex.clr_dir)
       return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: the clear + all-sky instances need the fused band increment and "
                                          "all three clear-sky outputs");
-    if (bb || ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
+    if (bb || gpt)
       return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: clear + all-sky fluxes with by-band or g-point outputs");
     if (ex.aer_tau && (!ex.aer_ssa || !ex.aer_g))
       return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
-    auto god = [&](auto kern) -> int {
-      const int threads = (ngpt + 63) / 64 * 64;
-      const size_t lds = sizeof(float) * (kExpTabFloats + (size_t)2 * 3 * kCkRing * ck_ring_stride(ngpt) + 4);
-      if (lds > 64 * 1024)
-        if (int rc = raise_lds_limit((const void *)kern)) return rc;
-      hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, 1,
-                         p.inc_flux, p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tau_bnd, ssa_bnd,
-                         g_bnd, (float *)ws, p.flux_up, p.flux_dn, p.flux_dir, nullptr, nullptr, nullptr, bcd, bo,
-                         ex.mask_bits, ex.aer_tau, ex.aer_ssa, ex.aer_g, ex.clr_up, ex.clr_dn, ex.clr_dir);
-      RRTMGPNN_LAUNCH_CHECK("sw_2stream_ck_kernel (clear + all sky)");
-      return RRTMGPNN_OK;
-    };
-    constexpr int W = kCkWaves, P = kCkP1;
-    const bool m = ex.mask_bits != nullptr, a = ex.aer_tau != nullptr;
-#define RRTMGPNN_DUAL_(G, M, A, T, E) \
-  sw_2stream_ck_kernel<G, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, M, A, true>
-#define RRTMGPNN_DUAL_GO_(T, E)                                        \
-  do {                                                                 \
-    if (g && m && a) return god(RRTMGPNN_DUAL_(true, true, true, T, E));    \
-    if (g && m) return god(RRTMGPNN_DUAL_(true, true, false, T, E));        \
-    if (g && a) return god(RRTMGPNN_DUAL_(true, false, true, T, E));        \
-    if (g) return god(RRTMGPNN_DUAL_(true, false, false, T, E));            \
-    if (m && a) return god(RRTMGPNN_DUAL_(false, true, true, T, E));        \
-    if (m) return god(RRTMGPNN_DUAL_(false, true, false, T, E));            \
-    if (a) return god(RRTMGPNN_DUAL_(false, false, true, T, E));            \
-    return god(RRTMGPNN_DUAL_(false, false, false, T, E));                  \
-  } while (0)
-    if (planes && (kCkTnDual || kCkEmkDual)) RRTMGPNN_DUAL_GO_(kCkTnDual, kCkEmkDual);
-    RRTMGPNN_DUAL_GO_(false, false);
-#undef RRTMGPNN_DUAL_GO_
-#undef RRTMGPNN_DUAL_
-  }
-  if (ex.aer_tau) {
+    o |= kSwCkDual | (ex.aer_tau ? kSwCkAer : 0u) | (planes ? kSwCkPlanesDual : 0u);
+  } else if (ex.aer_tau) {
     // aerosols in front of the (masked) cloud increment (rrtmgpnn_solver_request_aerosol): the band-pair layout only,
     // with the all-sky instances' transmittance plane or, when that workspace did not fit, without it (the same bits)
     if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: an aerosol increment needs the fused band increment behind it");
@@ -874,156 +876,75 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
       return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
     // (as in launch_lw_impl: not reachable through the C ABI as it stands -- the two entries have no g-point arguments
     // and refuse a by-band request beside the aerosol themselves, and launch_sw_2stream checks both again)
-    if (bb || ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
+    if (bb || gpt)
       return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment with by-band or g-point outputs");
-    for (int i = 0; i < b.nbnd; i++)
-      if ((b.lims[2 * i] - 1) % 2 != 0)
-        return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment needs every band to start at an odd "
-                                              "(1-based) g-point, the band-pair layout");
-    constexpr int W = kCkWaves, P = kCkP1;
-    constexpr bool T = kCkTnInc, E = kCkEmkInc;
-    const bool m = ex.mask_bits != nullptr;
-    if (!planes) {
-      if (g && m)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      if (g)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, false, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      if (m)
-        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, false, true>,
-                tau_bnd, ssa_bnd, g_bnd);
-    }
-    if (g && m)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (g)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, false, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (m)
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, false, true>, tau_bnd,
-              ssa_bnd, g_bnd);
-  }
-  if (ex.mask_bits) {
-    // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask), as the instances below
+    if (!pair)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment needs every band to start at an odd "
+                                            "(1-based) g-point, the band-pair layout");
+    o |= kSwCkAer | kSwCkBandPair | (planes ? kSwCkPlanesInc : 0u);
+  } else if (ex.mask_bits) {
+    // McICA: the masked twins of the fused increment (rrtmgpnn_solver_request_cloud_mask); by band
+    // (rrtmgpnn_solver_request_byband_mcica) without workspace planes, as the unmasked by-band instances
     if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
-    if (ex.gpt_up || ex.gpt_dn || ex.gpt_dir)
-      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask with g-point outputs");
-    bool pair = true;
-    for (int i = 0; i < b.nbnd; i++) pair = pair && ((b.lims[2 * i] - 1) % 2 == 0);
-    constexpr int W = kCkWaves, P = kCkP1;
-    constexpr bool T = kCkTnInc, E = kCkEmkInc;
-    if (bb) {
-      // by-band under the mask (rrtmgpnn_solver_request_byband_mcica): the masked twins of the by-band all-sky
-      // instances below, without workspace planes (the same bits as the others)
-      if (pair && g)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      if (pair)
-        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      if (g)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true, true>,
-                tau_bnd, ssa_bnd, g_bnd);
-    }
-    if (!planes) {
-      if (pair && g)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      if (pair)
-        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, false, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      if (g)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, false, true>,
-                  tau_bnd, ssa_bnd, g_bnd);
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, false, true>,
-                tau_bnd, ssa_bnd, g_bnd);
-    }
-    if (pair && g)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (pair)
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true, P, 1, false, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (g)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, false, P, 1, false, true>, tau_bnd,
-              ssa_bnd, g_bnd);
-  }
-  if (ex.gpt_up || ex.gpt_dn || ex.gpt_dir) {  // ty_fluxes_flexible g-point outputs: all three (launch_sw_2stream)
+    if (gpt) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: a cloud mask with g-point outputs");
+    o |= (pair ? kSwCkBandPair : 0u) | (bb ? kSwCkBand : (planes ? kSwCkPlanesInc : 0u));
+  } else if (gpt) {  // ty_fluxes_flexible g-point outputs: all three (launch_sw_2stream)
     if (bands) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: g-point outputs with a fused increment");
-    if (g) return go(sw_2stream_ck_kernel<true, false, kCkK, true>, nullptr, nullptr, nullptr);
-    return go(sw_2stream_ck_kernel<false, false, kCkK, true>, nullptr, nullptr, nullptr);
-  }
-  if (bb) {
+    o |= kSwCkGpt;
+  } else if (bb) {
     // by-band instances: the small-grid clear-sky instance where it applies (as without the request), else the
-    // large-grid forms without workspace planes (the same bits as the others), the band-pair and the general
-    // increment, with and without g
-    if (!g && !bands && sw_ck_small(ctx, ngpt, ncol, false, false, false))
-      return go(sw_2stream_ck_kernel<false, false, kCkKSmall, false, kCkRingSmall, kCkWavesSmall, kCkTnSmall, VSmall,
-                                     kCkEmkSmall, false, kCkP1Small, kCkAheadSmall, true>,
-                nullptr, nullptr, nullptr, kCkRingSmall, (int)(sizeof(VSmall) / sizeof(float)));
-    bool pair = bands != nullptr;
-    for (int i = 0; bands && i < b.nbnd; i++) pair = pair && ((b.lims[2 * i] - 1) % 2 == 0);
-    constexpr int W = kCkWaves;
-    constexpr int P = kCkP1;
-    if (pair && g)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (pair)
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true, P, 1, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (bands && g)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true>, tau_bnd,
-                ssa_bnd, g_bnd);
-    if (bands)
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true>,
-                tau_bnd, ssa_bnd, g_bnd);
-    if (g)
-      return go(sw_2stream_ck_kernel<true, false, kCkK, false, kCkRing, W, false, f2, false, false, P, 1, true>, nullptr,
-                nullptr, nullptr);
-    return go(sw_2stream_ck_kernel<false, false, kCkK, false, kCkRing, kCkWavesNN, false, f2, false, false, P, 1, true>,
-              nullptr, nullptr, nullptr);
+    // large-grid forms without workspace planes (the same bits as the others)
+    o |= kSwCkBand | (small ? kSwCkSmall | kSwCkPlanesSmall : 0u) | (pair ? kSwCkBandPair : 0u);
+  } else if (bands) {
+    o |= (pair ? kSwCkBandPair : 0u) | (planes ? kSwCkPlanesInc : 0u);
+  } else if (!p.g) {
+    // the small-grid instance when the clear-sky grid fits in one round of resident waves, else the NN instance
+    o |= small ? kSwCkSmall | kSwCkPlanesSmall : (planes ? kSwCkPlanesNN : 0u);
   }
-  if (bands) {
-    bool pair = true;  // every band starts at an even (0-based) g-point
-    for (int i = 0; i < b.nbnd; i++) pair = pair && ((b.lims[2 * i] - 1) % 2 == 0);
-    constexpr int W = kCkWaves;
-    constexpr bool T = kCkTnInc, E = kCkEmkInc;
-    if (!planes) {  // the workspace planes did not fit (launch_sw_2stream's fallback): the same bits, recomputed
-      if (pair && g)
-        return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, false, f2, false, true>, tau_bnd, ssa_bnd,
-                  g_bnd);
-      if (pair)
-        return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, false, f2, false, true>, tau_bnd, ssa_bnd,
-                  g_bnd);
-      if (g) return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W>, tau_bnd, ssa_bnd, g_bnd);
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W>, tau_bnd, ssa_bnd, g_bnd);
-    }
-    if (pair && g)
-      return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E, true>, tau_bnd, ssa_bnd, g_bnd);
-    if (pair)
-      return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E, true>, tau_bnd, ssa_bnd, g_bnd);
-    if (g) return go(sw_2stream_ck_kernel<true, true, kCkK, false, kCkRing, W, T, f2, E>, tau_bnd, ssa_bnd, g_bnd);
-    return go(sw_2stream_ck_kernel<false, true, kCkK, false, kCkRing, W, T, f2, E>, tau_bnd, ssa_bnd, g_bnd);
-  }
-  if (g) return go(sw_2stream_ck_kernel<true, false, kCkK>, nullptr, nullptr, nullptr);
-  // the small-grid instance when the clear-sky grid fits in one round of resident waves (2 g-points per lane, 16
-  // waves per CU)
-  if (sw_ck_small(ctx, ngpt, ncol, false, false, false))
-    return go(sw_2stream_ck_kernel<false, false, kCkKSmall, false, kCkRingSmall, kCkWavesSmall, kCkTnSmall, VSmall,
-                                   kCkEmkSmall, false, kCkP1Small, kCkAheadSmall>,
-              nullptr, nullptr, nullptr, kCkRingSmall, (int)(sizeof(VSmall) / sizeof(float)));
-  if (!planes) return go(sw_2stream_ck_kernel<false, false, kCkK, false, kCkRing, kCkWavesNN>, nullptr, nullptr, nullptr);
-  return go(sw_2stream_ck_kernel<false, false, kCkK, false, kCkRing, kCkWavesNN, kCkTnNN, f2, kCkEmkNN>, nullptr,
-            nullptr, nullptr);
+  *options = o;
+  return RRTMGPNN_OK;
+}
+
+// ngpt even and <= 256
+int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws, bool planes,
+                         const SwBcDev *bc)
+{
+  const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
+  const BandArgs nob{};
+  const BandArgs &b = p.bands ? *p.bands : nob;
+  const SwBcDev nobc{};  // tsi == NULL: the caller's inc_flux, mu0 and albedos
+  const SwBcDev &bcd = bc ? *bc : nobc;
+  const bool gpt = ex.gpt_up || ex.gpt_dn || ex.gpt_dir;
+  const BandOut bo = ex.byband() ? band_out(ex) : BandOut{};
+  uint32_t options = 0;
+  if (int rc = select_sw_ck(ex, p, planes, sw_ck_small(ctx, ngpt, ncol, p.g != nullptr, p.bands != nullptr, gpt), &options))
+    return rc;
+  return launch_listed(ctx, kSolverSwCk, SwCkInstances{}, options, [&](auto oc) -> int {
+    constexpr uint32_t O = decltype(oc)::value;
+    constexpr bool kDual = (O & kSwCkDual) != 0, kInc = (O & kSwCkInc) != 0;
+    constexpr int ring = (O & kSwCkSmall) ? kCkRingSmall : kCkRing;
+    // npl g-points per lane, ncb columns per block (two where 512 lanes hold them); the dual instances: one g-point
+    // per lane, one column per block, a ring per sky
+    constexpr int npl = kDual ? 1 : ((O & kSwCkSmall) ? (int)(sizeof(VSmall) / sizeof(float)) : 2);
+    const int ncb = kDual ? 1 : (npl == 2 ? (2 * (ngpt / 2) <= 512 ? 2 : 1) : columns_per_block(ngpt));
+    if (ncb > kFlushLanesMaxCols)  // the flush's lane -> column map (ring_flush_sw_lanes) covers at most 4 columns
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: more columns per block than the ordered flush maps");
+    const int threads = (ncb * (ngpt / npl) + 63) / 64 * 64;
+    const dim3 grid((ncol + ncb - 1) / ncb), block(threads);
+    const size_t lds =
+        sizeof(float) * (kExpTabFloats + (size_t)(kDual ? 2 : ncb) * 3 * ring * ck_ring_stride(ngpt) + 4);  // + spare
+    if (lds > 160 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: LDS ring exceeds 160 KiB");
+    const auto kern = sw_2stream_ck_kernel<O>;
+    if (lds > 64 * 1024)
+      if (int rc = raise_lds_limit((const void *)kern)) return rc;
+    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
+                       p.inc_flux_dif, p.tau, p.ssa, p.g, p.mu0, p.alb_dir, p.alb_dif, b, kInc ? p.tau_bnd : nullptr,
+                       kInc ? p.ssa_bnd : nullptr, kInc ? p.g_bnd : nullptr, (float *)ws, p.flux_up, p.flux_dn,
+                       p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits, ex.aer_tau, ex.aer_ssa,
+                       ex.aer_g, ex.clr_up, ex.clr_dn, ex.clr_dir);
+    RRTMGPNN_LAUNCH_CHECK(kDual ? "sw_2stream_ck_kernel (clear + all sky)" : "sw_2stream_ck_kernel");
+    return RRTMGPNN_OK;
+  });
 }
 
 }  // namespace rrtmgpnn

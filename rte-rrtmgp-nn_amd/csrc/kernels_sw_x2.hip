@@ -104,7 +104,9 @@ constexpr int kSw2Ring = 6;  // levels staged per ordered flush (2, 4, 8 were 2-
 
 // kBand: also the by-band fluxes bo.up / bo.dn / bo.dir (ty_fluxes_byband, (nbnd, nlay+1, ncol)), summed from the ring
 // rows in the flush's barrier window (band_flush, rte_device.hpp)
-template <bool kHasG, bool kInc, int kPF, bool kBand = false>
+// O: the instance's options, an OR of the kSwOpt* bits (internal.hpp), named again in the first lines; the prefetch
+// depth follows them (kSw2Pf*)
+template <uint32_t O>
 __global__ void __launch_bounds__(512, kSw2Waves)
     sw_2stream_x2_kernel(int ngpt, int nlay, int ncol, int top_at_1, int ncb, const float *__restrict__ inc_flux,
                          const float *__restrict__ inc_dif, const float *__restrict__ tau,
@@ -114,6 +116,8 @@ __global__ void __launch_bounds__(512, kSw2Waves)
                          const float *__restrict__ g_bnd, float *__restrict__ ws, float *__restrict__ flux_up,
                          float *__restrict__ flux_dn, float *__restrict__ flux_dir, BandOut bo)
 {
+  constexpr bool kHasG = (O & kSwOptHasG) != 0, kInc = (O & kSwOptInc) != 0, kBand = (O & kSwOptBand) != 0;
+  constexpr int kPF = kHasG ? kSw2Pf : (kInc ? kSw2PfInc : kSw2PfNoG);
   static_assert(kSw2Ring % kPF == 0, "prefetch depth must divide the ring");
   constexpr bool kRc = kInc ? kSw2RecompInc : kSw2Recomp;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -304,11 +308,15 @@ __global__ void __launch_bounds__(512, kSw2Waves)
 // layer planes (ngpt x nlay x ncol floats) the x2 kernel needs after its 4 level planes: none
 size_t sw_2stream_x2_layer_planes(bool) { return 0; }
 
+// The instances sw_2stream_x2_kernel is compiled for: {gas g} x {increment} x {broadband, by band}
+using SwX2Instances =
+    SolverInstances<0u, kSwOptHasG, kSwOptInc, kSwOptInc | kSwOptHasG, kSwOptBand, kSwOptBand | kSwOptHasG,
+                    kSwOptBand | kSwOptInc, kSwOptBand | kSwOptInc | kSwOptHasG>;
+
 // ngpt even and <= 256; workspace: 4 level planes + sw_2stream_x2_layer_planes(inc) layer planes
 int launch_sw_2stream_x2(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw2Stream &p, void *ws)
 {
   const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol;
-  const float *const g = p.g, *const tau_bnd = p.tau_bnd, *const ssa_bnd = p.ssa_bnd, *const g_bnd = p.g_bnd;
   const BandArgs *const bands = p.bands;
   // Columns per block: 2 (224 g-points: 224 lanes in 4 waves, 32 idle, a 32 KB ring).  Four columns fill 7 waves
   // exactly and were 5 % faster alone at C4, but in the overlapped step the smaller blocks share the CUs better with
@@ -320,29 +328,22 @@ int launch_sw_2stream_x2(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
   const BandArgs nob{};
   const BandArgs &b = bands ? *bands : nob;
   const dim3 grid((ncol + ncb - 1) / ncb), block(threads);
-  constexpr int PF = kSw2Pf, PFN = kSw2PfNoG, PFI = kSw2PfInc;
-  const bool bb = ex.byband();
-  const BandOut bo = bb ? band_out(ex) : BandOut{};
-  auto go = [&](auto kern, const float *tb, const float *sb, const float *gb) -> int {
+  const BandOut bo = ex.byband() ? band_out(ex) : BandOut{};
+  const uint32_t options = (p.g ? kSwOptHasG : 0u) | (bands ? kSwOptInc : 0u) | (ex.byband() ? kSwOptBand : 0u);
+  return launch_listed(ctx, kSolverSwX2, SwX2Instances{}, options, [&](auto oc) -> int {
+    constexpr uint32_t O = decltype(oc)::value;
+    constexpr bool kInc = (O & kSwOptInc) != 0;
+    const auto kern = sw_2stream_x2_kernel<O>;
     // rings past 64 KiB (4 columns of 224 g-points: 64.5 KiB) need the dynamic-LDS limit raised (per device)
     if (lds > 64 * 1024)
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
-                       p.inc_flux_dif, p.tau, p.ssa, g, p.mu0, p.alb_dir, p.alb_dif, b, tb, sb, gb, (float *)ws,
-                       p.flux_up, p.flux_dn, p.flux_dir, bo);
+                       p.inc_flux_dif, p.tau, p.ssa, p.g, p.mu0, p.alb_dir, p.alb_dif, b, kInc ? p.tau_bnd : nullptr,
+                       kInc ? p.ssa_bnd : nullptr, kInc ? p.g_bnd : nullptr, (float *)ws, p.flux_up, p.flux_dn,
+                       p.flux_dir, bo);
     RRTMGPNN_LAUNCH_CHECK("sw_2stream_x2_kernel");
     return RRTMGPNN_OK;
-  };
-  if (bb) {
-    if (bands && g) return go(sw_2stream_x2_kernel<true, true, PF, true>, tau_bnd, ssa_bnd, g_bnd);
-    if (bands) return go(sw_2stream_x2_kernel<false, true, PFI, true>, tau_bnd, ssa_bnd, g_bnd);
-    if (g) return go(sw_2stream_x2_kernel<true, false, PF, true>, nullptr, nullptr, nullptr);
-    return go(sw_2stream_x2_kernel<false, false, PFN, true>, nullptr, nullptr, nullptr);
-  }
-  if (bands && g) return go(sw_2stream_x2_kernel<true, true, PF>, tau_bnd, ssa_bnd, g_bnd);
-  if (bands) return go(sw_2stream_x2_kernel<false, true, PFI>, tau_bnd, ssa_bnd, g_bnd);
-  if (g) return go(sw_2stream_x2_kernel<true, false, PF>, nullptr, nullptr, nullptr);
-  return go(sw_2stream_x2_kernel<false, false, PFN>, nullptr, nullptr, nullptr);
+  });
 }
 
 }  // namespace rrtmgpnn
