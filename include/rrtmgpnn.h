@@ -331,7 +331,11 @@ int rrtmgpnn_compute_planck_source_nn(rrtmgpnn_context *ctx, int ncol, int nlay,
  * with _planck_inc and _planck_clr_all, tau is the incremented optical depth).  Beyond it the layer source's (1 - T) / (tau * D) is
  * taken as 0 where the reference has ~3e-39, and a tau * D that overflows to inf makes the column's fluxes nan where
  * the reference's are finite.  The shortened division that causes this saves 1.2 - 2.3 % of the solver's time
- * (DESIGN.md section 3); tests/test_gpu_solver_edges.py holds both sides of the bound.  The SW solvers have no such
+ * (DESIGN.md section 3); tests/test_gpu_solver_edges.py holds both sides of the bound for each of these entries (the
+ * fused ones with the band increment, both modes of rrtmgpnn_context_set_lw_clr_all, the McICA mask and lw_Ds), and for
+ * the clear-sky set of rrtmgpnn_lw_solver_1rescl_planck_clr_all, which carries the same bound.  Where the Planck level
+ * sources beside the layer are not zero (every fused-Planck entry) a finite tau * D beyond 2^126 was still bitwise: the
+ * flushed quotient is absorbed; a product that overflows to inf is nan there too.  The SW solvers have no such
  * bound: tau, ssa, g and mu0 over their whole float range (tau up to 2e38, ssa down to 1e-45, mu0 down to FLT_MIN) were
  * bitwise. */
 int rrtmgpnn_lw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
@@ -402,7 +406,12 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ng
 /* rte_lw on two-stream optical properties, default branch (rte/mo_rte_lw.F90:372-387): lw_solver_noscat_GaussQuad
  * with do_rescaling -- tau scaled by (1 - ssa + ssa(1-g)/2), a no-scattering pass down, then
  * lw_transport_1rescl up and down again with the adjustment terms (rte/kernels/mo_rte_solver_kernels.F90:209-233,
- * 1729-1795).  Arguments as rrtmgpnn_lw_solver_noscat plus ssa, g (ngpt, nlay, ncol). */
+ * 1729-1795).  Arguments as rrtmgpnn_lw_solver_noscat plus ssa, g (ngpt, nlay, ncol).
+ * OPERAND DOMAIN: ssa (1 + g) / 2 < 1 (the scaling 1 - ssa + ssa (1 - g) / 2 must not vanish, as in the reference); no
+ * bound on tau: the rescaled layer divides plainly, and tau up to 3e38 (tau * D * scaling overflowing to inf included),
+ * ssa from 1e-45 to 1 and g from -0.4 to 1 were the reference's bit for bit, as were rrtmgpnn_lw_solver_1rescl_gpt, the
+ * flux Jacobian, rrtmgpnn_lw_solver_1rescl_planck_inc and rrtmgpnn_lw_solver_2stream[_gpt] on the same operands
+ * (tests/test_gpu_solver_edges.py). */
 int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
                               const float *Ds, const float *weights, const float *inc_flux, const float *tau,
                               const float *ssa, const float *g, const float *lay_source, const float *lev_source,
@@ -452,7 +461,11 @@ int rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
  * (separate or paired), a flux-Jacobian request, a 2str aerosol, mask or aerosol extents that are not the call's, NULL
  * band or clear-sky arrays; ngpt > 256 is RRTMGPNN_ERR_UNSUPPORTED.  ncol == 0 is OK.  How the two sets are produced:
  * rrtmgpnn_context_set_lw_scat_clr_all.  Operand bounds and workspace as rrtmgpnn_lw_solver_1rescl_planck_inc (the two
- * launches of mode 2 share the context workspace in stream order).  No reference counterpart as one call. */
+ * launches of mode 2 share the context workspace in stream order).  OPERAND BOUND of the clear-sky set, in either mode:
+ * that of the rrtmgpnn_lw_solver_noscat* entries, (tau [+ tau_aer]) * D <= 2^126 -- the clear radiance is the
+ * no-scattering step with its shortened division, so a product that overflows to inf gives nan in flux_up_clr /
+ * flux_dn_clr where the reference is finite, while the all-sky set of the same call, which divides plainly, stays the
+ * reference's (tests/test_gpu_solver_edges.py holds both).  No reference counterpart as one call. */
 int rrtmgpnn_lw_solver_1rescl_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
                                              int nmus, const float *Ds, const float *weights, const float *inc_flux,
                                              const float *tau, const float *tau_bnd, const float *ssa_bnd,

@@ -11,6 +11,11 @@ direct 0.46, LW up 0.006, down 0.092 (fused Planck: 0.015 / 0.09); eps branch 48
 exp(-tau/mu0) underflowed 636, 0 < ssa < 2^-100 240, subnormal nonzero fluxes > 3000.  The zero shares are those of the
 problem as built (incident diffuse flux present in two thirds of the columns); the GPU test's runs without any
 diffuse flux compare more zeros (up 0.31) on top of these.
+
+The scattering and fused LW solvers (build_lw_scat, 1224 columns): every reference finite; zeros 0.044-0.051 of the up
+and down fluxes together (two-stream without incident flux 0.094; flux_up_Jac below 0.10 outside the emissivity-0
+columns, where it is 0 by definition); 0.82-0.87 of the columns change when the edge (ssa, g) gives way to the
+background pair (flux_up_Jac 0.65-0.69), 0.82-0.85 when the lit mask bit is flipped; the census of the last test.
 """
 import numpy as np
 import pytest
@@ -170,3 +175,213 @@ def test_lw_census_both_sides_of_tau_thresh_for_every_secant(lw):
     sharp = np.array([c.lev == 0 and c.src >= 1 for c in lw["cases"]])
     assert (sharp & lw["beyond_2p126"]).sum() >= 4 and (sharp & lw["in_domain"]).sum() >= 50
     assert set(lw["lit"] % 4) == {0, 1, 2, 3} and set(lw["layer"]) == set(range(E.NLAY))
+
+
+# ---- the scattering and fused LW solvers (solver_edges.build_lw_scat) --------------------------------------------------
+@pytest.fixture(scope="module")
+def scat():
+    return E.build_lw_scat()
+
+
+NMUS = (1, 3)
+FUSED = [(nmus, masked, aer, by_band) for nmus in NMUS for masked in (False, True) for aer in (False, True)
+         for by_band in (False,)] + [(1, True, False, True), (1, True, True, True)]
+
+
+def _scat_references(orc, top_at_1):
+    """Every reference the GPU file compares with on build_lw_scat(): name -> flux arrays."""
+    for n in NMUS:
+        yield "1rescl nmus%d" % n, E.ref_rescl(orc, top_at_1, n)
+        yield "1rescl_gpt nmus%d" % n, E.ref_rescl(orc, top_at_1, n, gpt=True)
+    for with_inc in (True, False):
+        for gpt in (False, True):
+            yield "2stream inc=%s gpt=%s" % (with_inc, gpt), E.ref_2stream(orc, top_at_1, with_inc, gpt)
+    for nmus, masked, aer, by_band in FUSED:
+        yield ("fused nmus%d masked=%s aer=%s emis_by_band=%s" % (nmus, masked, aer, by_band),
+               E.ref_fused(orc, top_at_1, nmus, masked, aer, by_band)[:4])
+
+
+def _noscat_fused_references(orc, top_at_1):
+    for kind in ("inc", "masked", "clear", "gpt"):
+        yield "noscat fused " + kind, E.ref_noscat_fused(orc, top_at_1, 1, kind)[:2 if kind != "gpt" else 4]
+
+
+def _changed_share(a, b):
+    """Share of the columns in which any flux of the lists a and b differs."""
+    n = a[0].shape[0]
+    diff = np.zeros(n, bool)
+    for x, y in zip(a, b):
+        diff[E.mismatch_columns(x, y)] = True
+    return float(diff.mean())
+
+
+@pytest.mark.parametrize("top_at_1", [True, False])
+def test_lw_scat_references_are_finite_and_not_mostly_zero(orc, scat, top_at_1):
+    """Conditions 1 and 2.  The share of exact zeros is taken over the up and down fluxes of a reference together (the
+    g-point arrays apart: all but one g-point of them are zero by design).  flux_up_Jac is apart too: a third of the
+    columns have emissivity 0 (LW_EMIS), where J = emis * sfc_source_Jac is exactly 0 at every level; its cap holds on
+    the other columns."""
+    for what, arrs in list(_scat_references(orc, top_at_1)) + list(_noscat_fused_references(orc, top_at_1)):
+        for a in arrs:
+            assert np.isfinite(a).all(), what
+        share = _zero_share(np.concatenate([a.ravel() for a in arrs[:2]]))
+        print("%s top_at_1=%s: share of exact zeros %.3f (cap 0.10)" % (what, top_at_1, share))
+        assert share <= 0.10, "%s: share of exact zeros %.3f exceeds 0.10" % (what, share)
+        if len(arrs) == 4 and "fused" in what and "noscat" not in what:  # the clear set of the dual entry
+            share = _zero_share(np.concatenate([a.ravel() for a in arrs[2:]]))
+            print("%s clear set: share of exact zeros %.3f (cap 0.10)" % (what, share))
+            assert share <= 0.10, "%s clear set: share of exact zeros %.3f exceeds 0.10" % (what, share)
+    lit_emis = scat["edge"]["tau"] * 0 + np.array([c.emis for c in scat["cases"]], F)
+    for n in NMUS:
+        jac = E.ref_rescl_jac(orc, top_at_1, n)
+        assert np.isfinite(jac).all()
+        assert not jac[lit_emis == 0].any()
+        share = _zero_share(jac[lit_emis > 0])
+        print("flux_up_Jac nmus%d top_at_1=%s: share of exact zeros %.3f where emis > 0 (cap 0.10)" % (n, top_at_1, share))
+        assert share <= 0.10, "flux_up_Jac nmus%d: share of exact zeros %.3f exceeds 0.10" % (n, share)
+
+
+@pytest.mark.parametrize("top_at_1", [True, False])
+def test_lw_scat_broadband_is_the_lit_gpoint(orc, scat, top_at_1):
+    """Condition 3: the unlit g-points carry exactly +-0 and the broadband flux is the lit g-point's term bit for bit --
+    with three angles and in the two-stream solver the g-point flux itself, with one angle fac * radiance (quirk B-5)."""
+    p = scat
+    c = np.arange(p["ncol"])
+    fac1 = F(2) * F(np.pi) * F(0.5)
+    io = E.ref_fused(orc, top_at_1, 3, True, True)[4]
+    lay, lev, sfc = E.planck_sources(orc, p, top_at_1)
+    for a in (lay, lev):  # a zero Planck fraction leaves the unlit g-points without any source
+        a = a.copy()
+        a[c, :, p["lit"]] = 0
+        assert not a.any()
+    runs = [("1rescl nmus1", E.ref_rescl(orc, top_at_1, 1, gpt=True), fac1),
+            ("1rescl nmus3", E.ref_rescl(orc, top_at_1, 3, gpt=True), None),
+            ("2stream", E.ref_2stream(orc, top_at_1, True, gpt=True), None),
+            ("fused masked aer nmus3", orc.lw_solver(io[0], lay, lev, p["emis"], sfc, top_at_1, 3, inc_flux=p["inc"],
+                                                     ssa=io[1], g=io[2], gpt=True), None)]
+    plain = {"1rescl nmus1": E.ref_rescl(orc, top_at_1, 1), "1rescl nmus3": E.ref_rescl(orc, top_at_1, 3),
+             "2stream": E.ref_2stream(orc, top_at_1, True), "fused masked aer nmus3": E.ref_fused(orc, top_at_1, 3, True, True)}
+    for what, (up, dn, gu, gd), fac in runs:
+        for name, bb, gp, bb_plain in (("up", up, gu, plain[what][0]), ("dn", dn, gd, plain[what][1])):
+            term = gp[c, :, p["lit"]]
+            np.testing.assert_array_equal(bb, term if fac is None else fac * term, err_msg="%s %s" % (what, name))
+            np.testing.assert_array_equal(bb_plain, bb, err_msg="%s %s" % (what, name))
+            unlit = gp.copy()
+            unlit[c, :, p["lit"]] = 0
+            assert not unlit.any(), (what, name)
+
+
+@pytest.mark.parametrize("top_at_1", [True, False])
+def test_lw_scat_edge_operands_show_in_the_fluxes(orc, scat, top_at_1):
+    """Condition 4: at least half of the columns change their fluxes when the edge layer's (ssa, g) -- for the fused
+    references the edge band operands -- is replaced by the background pair, and when the lit mask bit is flipped."""
+    p = scat
+    shares = {}
+    w, q = E.with_background_pair(p)
+    for n in NMUS:
+        other = orc.lw_solver(p["tau"], p["lay"], p["lev"], p["emis"], p["sfc"], top_at_1, n, inc_flux=p["inc"], ssa=w, g=q)
+        shares["1rescl nmus%d" % n] = _changed_share(E.ref_rescl(orc, top_at_1, n), other)
+        import lw_jacobian_ref as J
+        other = J.zero_source_flux_up(orc, p["tau"], p["emis"], p["sjac"], top_at_1, n, ssa=w, g=q)
+        emis = np.array([c.emis for c in p["cases"]], F) > 0  # with emissivity 0 the Jacobian is 0 whatever the layer
+        shares["flux_up_Jac nmus%d (emis > 0)" % n] = _changed_share([E.ref_rescl_jac(orc, top_at_1, n)[emis]], [other[emis]])
+    for with_inc in (True, False):
+        other = orc.lw_solver_2stream(p["tau"], w, q, p["lev"], p["emis"], p["sfc"], top_at_1, p["inc"] if with_inc else None)
+        shares["2stream inc=%s" % with_inc] = _changed_share(E.ref_2stream(orc, top_at_1, with_inc), other)
+    wb, gb = E.with_background_pair(p, "ssa_bnd", "g_bnd")
+    lay, lev, sfc = E.planck_sources(orc, p, top_at_1)
+    for nmus, masked, aer, by_band in FUSED:
+        if by_band:
+            continue
+        ref = E.ref_fused(orc, top_at_1, nmus, masked, aer)
+        io = E.fused_props(orc, p, masked, aer, cloud=[p["tau_bnd"], wb, gb])
+        other = orc.lw_solver(io[0], lay, lev, p["emis"], sfc, top_at_1, nmus, inc_flux=p["inc"], ssa=io[1], g=io[2])
+        name = "fused nmus%d masked=%s aer=%s" % (nmus, masked, aer)
+        if masked:  # the edge operands reach the kernel in the columns whose lit bit is set
+            lit = p["edge"]["bit"]
+            shares[name + " (lit bit set)"] = _changed_share([a[lit] for a in ref[:2]], [a[lit] for a in other])
+            io = E.fused_props(orc, p, True, aer, mask=E.flipped_lit_mask(p))
+            other = orc.lw_solver(io[0], lay, lev, p["emis"], sfc, top_at_1, nmus, inc_flux=p["inc"], ssa=io[1], g=io[2])
+            shares[name + ", lit bit flipped"] = _changed_share(ref[:2], other)
+        else:
+            shares[name] = _changed_share(ref[:2], other)
+    for what, share in shares.items():
+        print("%s top_at_1=%s: %.3f of the columns change (at least 0.5)" % (what, top_at_1, share))
+    for what, share in shares.items():
+        assert share >= 0.5, "%s: only %.3f of the columns change their fluxes" % (what, share)
+
+
+def test_lw_scat_census_of_the_edge_layers(scat):
+    """Condition 5, in float32 with the kernels' operation order: every value-dependent path of rs_layer, l2_layer and
+    the in-kernel increments is reached by at least 20 columns."""
+    p, e = scat, scat["edge"]
+    census = {}
+    wb, scale, cn = E.scale_tau(e["ssa"], e["g"])
+    with np.errstate(over="ignore"):
+        for D in E.rescl_secants():
+            t = (e["tau"] * F(D)) * scale
+            for name, sel in (("scaleTau != 1", scale != 1), ("scaleTau == 1 (ssa == 0)", e["ssa"] == 0)):
+                census["D=%.4f %s, t <= thresh" % (D, name)] = int((sel & (t <= E.TAU_THRESH)).sum())
+                census["D=%.4f %s, t > thresh" % (D, name)] = int((sel & (t > E.TAU_THRESH)).sum())
+            # the switch itself: the columns built for a pair of THRESH_PAIRS sit one float either side of it
+            forced = np.zeros(p["ncol"], bool)
+            for w, g in E.THRESH_PAIRS:
+                lo, hi = E.tau_at_thresh(D, E.scale_tau(w, g)[1])
+                forced |= (e["ssa"] == w) & (e["g"] == g) & ((e["tau"] == lo) | (e["tau"] == hi))
+            census["D=%.4f one float below the switch" % D] = int((forced & (t <= E.TAU_THRESH)).sum())
+            census["D=%.4f one float above the switch" % D] = int((forced & (t > E.TAU_THRESH)).sum())
+    census["Cn == 0"], census["Cn > 0"] = int((cn == 0).sum()), int((cn > 0).sum())
+    census["l2: tau <= 1e-8"], census["l2: tau > 1e-8"] = int((e["tau"] <= F(1e-8)).sum()), int((e["tau"] > F(1e-8)).sum())
+    k2, emk, em2k = E.l2_terms(e["tau"], e["ssa"], e["g"])
+    census["l2: k_min clamp active (w0 == 1)"] = int(((k2 < E.K_MIN) & (e["ssa"] == 1)).sum())
+    census["l2: em2k == 0 with emk > 0"] = int(((em2k == 0) & (emk > 0)).sum())
+    census["l2: emk == 0"] = int((emk == 0).sum())
+    for aer in (False, True):
+        with np.errstate(over="ignore"):
+            t1 = e["gas_tau"] + e["aer"] if aer else e["gas_tau"]
+            tau12, _, _, scat12 = E.inc_2str_gas(t1, e["tau"], e["ssa"], e["g"])
+        census["inc_2str aer=%s: max(eps, tauscat12) bites" % aer] = int((scat12 < E.EPS_INC).sum())
+        census["inc_2str aer=%s: max(eps, tau12) bites" % aer] = int((tau12 < E.EPS_INC).sum())
+        census["inc_2str aer=%s: t1 == 0 with t2 == 0" % aer] = int(((t1 == 0) & (e["tau"] == 0)).sum())
+        census["inc_2str aer=%s: t1 == 0 with t2 > 0" % aer] = int(((t1 == 0) & (e["tau"] > 0)).sum())
+    census["lit mask bit set"], census["lit mask bit clear"] = int(e["bit"].sum()), int((~e["bit"]).sum())
+    census["tau_aer == 0"], census["tau_aer > 0"] = int((e["aer"] == 0).sum()), int((e["aer"] > 0).sum())
+    print(census)
+    for what, n in census.items():
+        # with the aerosol in front t1 is tau_gas + tau_aer, zero in a third of the columns above: 8 where 24 were
+        assert n >= (8 if "aer=True" in what else 20), (what, n)
+    # the edge values are where the kernels read them
+    c = np.arange(p["ncol"])
+    b = p["band_of"][p["lit"]]
+    for k, kb in (("tau", "tau_bnd"), ("ssa", "ssa_bnd"), ("g", "g_bnd"), ("aer", "tau_aer")):
+        np.testing.assert_array_equal(p[kb][c, p["layer"], b], e[k])
+    np.testing.assert_array_equal(p["mask"][c, p["layer"], p["lit"]], e["bit"])
+    assert not any(w == 1 and g == 1 for w, g in E.SCAT_PAIRS) and len(E.SCAT_PAIRS) == 59
+    assert {(float(x.ssa), float(x.g)) for x in p["cases"]} >= {(float(w), float(g)) for w, g in E.SCAT_PAIRS}
+    assert set(p["lit"] % 4) == {0, 1, 2, 3} and set(p["layer"]) == set(range(E.NLAY))
+    # the three floats around l2_layer's branch, each with its 24 columns
+    for t in E.TAUS_1E8:
+        assert (e["tau"] == t).sum() >= 20
+
+
+def test_lw_scat_domain_classes_have_columns(orc, scat):
+    """Every class the GPU file compares has at least 20 columns (it asserts so itself; here without a device)."""
+    p, e = scat, scat["edge"]
+    qs = {"1rescl nmus%d" % n: E.classes(p, e["tau"], E.scale_tau(e["ssa"], e["g"])[1], E.gauss_ds(n)) for n in NMUS}
+    for nmus, masked, aer, _ in FUSED:
+        ref = E.ref_fused(orc, True, nmus, masked, aer)
+        io = ref[4]
+        scale = E.scale_tau(E.edge_values(p, io[1]), E.edge_values(p, io[2]))[1]
+        qs["fused %d %s %s all" % (nmus, masked, aer)] = E.classes(p, E.edge_values(p, io[0]), scale, E.gauss_ds(nmus))
+        qs["fused %d %s %s clr" % (nmus, masked, aer)] = E.classes(p, E.edge_values(p, ref[5]), None, E.gauss_ds(nmus))
+    for what, q in qs.items():
+        n = (int(q["in_domain"].sum()), int((~q["in_domain"] & ~q["beyond_2p126"]).sum()), int(q["beyond_2p126"].sum()))
+        assert min(n) >= 20, (what, n)
+        assert not (q["in_domain"] & q["beyond_2p126"]).any()
+    q = E.classes(p, e["tau"])
+    assert q["in_domain"].sum() >= 20 and (~q["in_domain"]).sum() >= 20
+    pl = E.build_lw()
+    for kind in ("inc", "masked", "clear"):
+        q = E.classes(pl, E.edge_values(pl, E.ref_noscat_fused(orc, True, 1, kind)[2]), None, E.gauss_ds(1))
+        n = (int(q["in_domain"].sum()), int((~q["in_domain"] & ~q["beyond_2p126"]).sum()), int(q["beyond_2p126"].sum()))
+        assert min(n) >= 20, (kind, n)
