@@ -96,8 +96,13 @@ int rrtmgpnn_context_set_lw_scat_clr_all(rrtmgpnn_context *ctx, int mode);
 int rrtmgpnn_context_set_sw_clr_all(rrtmgpnn_context *ctx, int mode);
 /* MI355X tuning, no reference counterpart: the MFMA tiling of the gas-optics networks (rrtmgpnn_predict_nn_lw/_sw,
  * rrtmgpnn_gas_optics_lw_nn/_sw_nn).  0 (default): v_mfma_f32_32x32x2_f32 tiles where an instance exists for the
- * networks (the shipped LW g256 pair, LW g128 single model and SW g224 pair, softsign/softsign/linear, ngpt a
- * multiple of 32, 16-byte aligned outputs), 16x16x4 otherwise.  1: 16x16x4 tiles.
+ * networks, 16x16x4 otherwise.  1: 16x16x4 tiles.  The 32x32x2 instances, each for its own ngpt, with
+ * softsign/softsign/linear and 16-byte aligned outputs, with and without the inputs formed in-kernel (the fused
+ * entries): the LW g256 pair 18-58-58-256 + 18-16-16-256, the SW g224 pair 7-16-16-224 twice, the LW g128 single model
+ * 18-64-64-256, and the reduced-resolution 2021 set, the LW g128 pair 18-72-72-128 + 18-24-24-128 and the SW g112 pair
+ * 7-32-32-112 twice (its last tile of 32 g-points holds 16).  Without an in-kernel-input instance (every 16x16x4 route
+ * of these three reduced-resolution sets) the fused entries run compute_nn_inputs, get_col_dry and the network kernel
+ * on context workspace.
  * Bit-identical outputs either way.  ctx == NULL sets the default of every context not set itself.
  * The 16x16x4 kernel is compiled for 3-layer networks [nx, h1, h2, ny] of these shapes, written (K1S, H1T, H2T) =
  * (ceil(nx/4), ceil(h1/16), ceil(h2/16)): (2,1,1), (2,2,2), (5,1,1), (5,2,2), (5,3,3), (5,4,4), (5,5,5), (5,8,8) --

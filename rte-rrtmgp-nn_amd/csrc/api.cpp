@@ -887,6 +887,11 @@ int rrtmgpnn_gas_optics_lw_nn(rrtmgpnn_context *ctx, int ncol, int nlay, int ngp
     if (!A->has_out_scaling()) return fail(RRTMGPNN_ERR_ARGUMENT, "output_sgemm_tau: NN output scaling coefficients missing");
     const int rc = launch_mlp(ctx, MLP_LW_PAIR, A, B, N, ngpt, nullptr, nullptr, tau, pfrac, nullptr, &in);
     if (rc != RRTMGPNN_ERR_UNSUPPORTED) return rc;
+  } else if (nets[0]->dims[nets[0]->nlayers] == 2 * ngpt && nets[0]->has_out_scaling()) {
+    // the single model: only the 32x32x2 kernel has an in-kernel-input instance (predict_nn_lw below reports a model
+    // that does not fit the call)
+    const int rc = launch_mlp32(ctx, MLP_LW_BOTH, nets[0], nullptr, N, ngpt, nullptr, nullptr, tau, pfrac, nullptr, &in);
+    if (rc != RRTMGPNN_ERR_UNSUPPORTED) return rc;
   }
   const float *x = nullptr, *cd = nullptr;
   if (int rc = fused_fallback(ctx, ncol, nlay, in, ninputs, &x, &cd)) return rc;

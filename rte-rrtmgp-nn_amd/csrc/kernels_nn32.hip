@@ -71,7 +71,7 @@ int pack_network32(rrtmgpnn_network *net)
 {
   if (net->nlayers != 3) return RRTMGPNN_OK;
   const int nx = net->dims[0], h1 = net->dims[1], h2 = net->dims[2], ny = net->dims[3];
-  if (nx > kMaxInputs || h1 > 64 || h2 > 64) return RRTMGPNN_OK;  // the 16x16x4 kernel covers the rest
+  if (nx > kMaxInputs || h1 > 96 || h2 > 96) return RRTMGPNN_OK;  // the 16x16x4 kernel covers the rest
   const int KS = (nx + 1) / 2, HT1 = (h1 + 31) / 32, N2 = (h1 + 1) / 2, HT2 = (h2 + 31) / 32, N3 = (h2 + 1) / 2,
             NGT = (ny + 31) / 32;
   const Img32 L = img32_layout(KS, HT1, N2, HT2, N3, NGT);
@@ -283,14 +283,19 @@ __device__ __forceinline__ void mlp32_hidden(const float *__restrict__ img, cons
 // code; profiles/r05/ab/u1_*.txt).  A/B knob: tools/ablations.py mlp_unroll.
 constexpr int kMlp32Threads = 512, kSwNT = 512, kSwWPE = 1;
 
-// A: (KS, AH1, AN2, AH2, AN3), B: (KS, BH1, BN2, BH2, BN3) -- B unused for MLP_LW_BOTH.  The host guarantees that the
-// g-tiles are full: ngpt = 32 NGT (LW pair) or 2 ngpt = 32 NGT (LW both).  Dynamic LDS: the weight images, then 32
-// floats per wave (the tile's column amounts, handed from the sample lanes to the row registers).
+// A: (KS, AH1, AN2, AH2, AN3), B: (KS, BH1, BN2, BH2, BN3) -- B unused for MLP_LW_BOTH.  GLAST: the g-points of the
+// last g-tile; the host guarantees ngpt = 32 (NGT - 1) + GLAST (the pairs) or 2 ngpt = 32 NGT (LW both).  GLAST < 32
+// (the SW g112 pair: 112 = 3 x 32 + 16): the images hold zeros for the g-points past ngpt (pack_network32), and the
+// lanes that own them in the last tile store nothing there (one 64-byte row segment instead of two) and divide by 1;
+// with GLAST = 32 none of that is compiled.  Dynamic LDS: the weight images, then 32 floats per wave (the tile's
+// column amounts, handed from the sample lanes to the row registers).
 template <int KS, int AH1, int AN2, int AH2, int AN3, int BH1, int BN2, int BH2, int BN3, int NGT, int MODE, bool XIN,
-          int NT = kMlp32Threads, int WPE = 1>
+          int NT = kMlp32Threads, int WPE = 1, int GLAST = 32>
 __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
 {
   constexpr bool kPair = MODE == MLP_LW_PAIR || MODE == MLP_SW_PAIR;
+  constexpr bool kPartial = GLAST < 32;
+  static_assert(GLAST >= 1 && GLAST <= 32 && (!kPartial || MODE == MLP_SW_PAIR), "a partial last g-tile: the SW pair");
   extern __shared__ floatx4 lds4[];
   const float *imgA = (const float *)lds4;
   const float *imgB = imgA + a.imgA_floats;
@@ -321,7 +326,7 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
         return h ? v1 : v0;
       };
       xv[0] = pair(0, a.tlay, nb4, o2, a.play, nb4, o2);
-      if constexpr (kMlpPackedIn && MODE == MLP_LW_PAIR) {
+      if constexpr (kMlpPackedIn && (MODE == MLP_LW_PAIR || MODE == MLP_LW_BOTH)) {
         // code c of input k: records (c == 3 ? batch : c == 2 ? layers : c) x 4 bytes; offset s*4 (2-D) or ilay*4
         auto gp = [&](int k) {
           const float *p = a.gas.p[k];
@@ -461,6 +466,8 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
       if constexpr (kPair) yB = mfma_chain_t<BN3>(iB + LB.l3, go, hB, lane);
       const int g = 32 * go + j;
       const float bA = iA[LA.b3 + g], sdA = iA[LA.sd + g], mnA = iA[LA.mn + g];
+      // kPartial: this lane's g-point of the last g-tile is past ngpt
+      const bool pad = kPartial && go == NGT - 1 && j >= GLAST;
       if constexpr (MODE == MLP_SW_PAIR) {
         // tau = tau_abs + tau_ray, ssa = tau_ray / tau, g = 0 (predict_nn_sw_blas with the combine,
         // rrtmgp/kernels/mo_gas_optics_kernels.F90:869-953; mo_gas_optics_rrtmgp.F90:560-567)
@@ -473,8 +480,8 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
           float tr = sdB * (yB[r] + bB);
           tr = tr + mnB;
           const float vray = pow8(tr) * cdr[r];
-          const float tot = vabs + vray, ssa = vray / tot;
-          const uint32_t off = vo[r] + 128u * go;
+          const float tot = vabs + vray, ssa = vray / (kPartial && pad ? 1.0f : tot);
+          const uint32_t off = kPartial && pad ? kOOB : vo[r] + 128u * go;
           o0.st<kCpNnSwSt>(tot, off);
           o1.st<kCpNnSwSt>(ssa, off);
         }
@@ -482,7 +489,7 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
         // one uniform branch per g-tile instead of a dropped store per element
         if (a.out2) {
 #pragma unroll
-          for (int r = 0; r < 16; r++) o2.st(0.0f, vo[r] + 128u * go);
+          for (int r = 0; r < 16; r++) o2.st(0.0f, kPartial && pad ? kOOB : vo[r] + 128u * go);
         }
       } else if constexpr (kPair) {
         const float bB = iB[LB.b3 + g];
@@ -520,10 +527,10 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
 constexpr int kOccDevices = 64;
 
 template <int KS, int AH1, int AN2, int AH2, int AN3, int BH1, int BN2, int BH2, int BN3, int NGT, int MODE, bool XIN,
-          int NT = kMlp32Threads, int WPE = 1>
+          int NT = kMlp32Threads, int WPE = 1, int GLAST = 32>
 static int launch32(rrtmgpnn_context *ctx, Mlp32Args &a)
 {
-  auto kern = mlp32_kernel<KS, AH1, AN2, AH2, AN3, BH1, BN2, BH2, BN3, NGT, MODE, XIN, NT, WPE>;
+  auto kern = mlp32_kernel<KS, AH1, AN2, AH2, AN3, BH1, BN2, BH2, BN3, NGT, MODE, XIN, NT, WPE, GLAST>;
   const size_t lds = sizeof(float) * ((size_t)(a.imgA_floats + (MODE != MLP_LW_BOTH ? a.imgB_floats : 0)) +
                                       32 * (NT / 64));
   if (lds > 160 * 1024) return RRTMGPNN_ERR_UNSUPPORTED;
@@ -566,8 +573,9 @@ static bool shape32(const rrtmgpnn_network *n, int KS, int HT1, int N2, int HT2,
          n->s32[4] == N3 && n->s32[5] == NGT;
 }
 
-// The LW modes on the 32x32x2 kernel for the shipped shapes with the shipped activations (softsign, softsign,
-// linear); RRTMGPNN_ERR_UNSUPPORTED (no error set) otherwise, and the caller runs the 16x16x4 kernel.
+// The LW and SW modes on the 32x32x2 kernel for the shapes listed at the end (the g256 / g224 models and the
+// reduced-resolution g128 / g112 ones) with their activations (softsign, softsign, linear);
+// RRTMGPNN_ERR_UNSUPPORTED (no error set) otherwise, and the caller runs the 16x16x4 kernel.
 int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A, const rrtmgpnn_network *B,
                  long long nbatch, int ngpt, const float *x, const float *col_dry, float *out0, float *out1,
                  float *out2, const MlpInputs *in)
@@ -593,9 +601,9 @@ int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A,
   a.ncol = in && in->nlay > 0 ? (int)(nbatch / in->nlay) : 0;
   // 16-byte stores, and every descriptor's range below kOOB
   auto al16 = [](const float *p) { return ((uintptr_t)p & 15) == 0; };
-  if (ngpt % 32 != 0 || !al16(out0) || !out1 || !al16(out1)) return RRTMGPNN_ERR_UNSUPPORTED;
-  if (A->s32[5] * 32 != (pair ? ngpt : 2 * ngpt) || (pair && B->s32[5] != A->s32[5]))
-    return RRTMGPNN_ERR_UNSUPPORTED;  // full g-tiles
+  if (ngpt % 4 != 0 || !al16(out0) || !out1 || !al16(out1)) return RRTMGPNN_ERR_UNSUPPORTED;
+  // the networks' outputs are the call's g-points; each instance below names the ngpt its g-tiles are compiled for
+  if (A->dims[3] != (pair ? ngpt : 2 * ngpt) || (pair && B->dims[3] != ngpt)) return RRTMGPNN_ERR_UNSUPPORTED;
   if ((unsigned long long)nbatch * 4ull * (unsigned long long)std::max(1, A->dims[0]) >= kMaxRecords ||
       32ull * 4ull * (unsigned long long)ngpt >= kMaxRecords)
     return RRTMGPNN_ERR_UNSUPPORTED;
@@ -618,19 +626,30 @@ int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A,
       const uint32_t code = !on ? 0u : (nd == 2 ? 3u : (nd == 1 ? 2u : 1u));
       a.gcode[k >> 4] |= code << (2 * (k & 15));
     }
-  if (mode == MLP_LW_PAIR && shape32(A, 9, 2, 29, 2, 29, 8) && shape32(B, 9, 1, 8, 1, 8, 8)) {
+  if (mode == MLP_LW_PAIR && ngpt == 256 && shape32(A, 9, 2, 29, 2, 29, 8) && shape32(B, 9, 1, 8, 1, 8, 8)) {
     // the shipped g256 pair: absorption 18-58-58-256, Planck fraction 18-16-16-256
     if (xin) return launch32<9, 2, 29, 2, 29, 1, 8, 1, 8, 8, MLP_LW_PAIR, true>(ctx, a);
     return launch32<9, 2, 29, 2, 29, 1, 8, 1, 8, 8, MLP_LW_PAIR, false>(ctx, a);
   }
-  if (mode == MLP_SW_PAIR && shape32(A, 4, 1, 8, 1, 8, 7) && shape32(B, 4, 1, 8, 1, 8, 7)) {
+  if (mode == MLP_SW_PAIR && ngpt == 224 && shape32(A, 4, 1, 8, 1, 8, 7) && shape32(B, 4, 1, 8, 1, 8, 7)) {
     // the shipped g224 pair: absorption and Rayleigh 7-16-16-224
     if (xin) return launch32<4, 1, 8, 1, 8, 1, 8, 1, 8, 7, MLP_SW_PAIR, true, kSwNT, kSwWPE>(ctx, a);
     return launch32<4, 1, 8, 1, 8, 1, 8, 1, 8, 7, MLP_SW_PAIR, false, kSwNT, kSwWPE>(ctx, a);
   }
-  if (mode == MLP_LW_BOTH && !xin && shape32(A, 9, 2, 32, 2, 32, 8)) {
-    // the shipped g128 single model: 18-64-64-256
+  if (mode == MLP_LW_BOTH && ngpt == 128 && shape32(A, 9, 2, 32, 2, 32, 8)) {
+    // the shipped g128 single model: 18-64-64-256; tau and pfrac split by whole g-tiles (4 + 4)
+    if (xin) return launch32<9, 2, 32, 2, 32, 1, 1, 1, 1, 8, MLP_LW_BOTH, true>(ctx, a);
     return launch32<9, 2, 32, 2, 32, 1, 1, 1, 1, 8, MLP_LW_BOTH, false>(ctx, a);
+  }
+  if (mode == MLP_LW_PAIR && ngpt == 128 && shape32(A, 9, 3, 36, 3, 36, 4) && shape32(B, 9, 1, 12, 1, 12, 4)) {
+    // the reduced-resolution g128 pair: absorption 18-72-72-128, Planck fraction 18-24-24-128
+    if (xin) return launch32<9, 3, 36, 3, 36, 1, 12, 1, 12, 4, MLP_LW_PAIR, true>(ctx, a);
+    return launch32<9, 3, 36, 3, 36, 1, 12, 1, 12, 4, MLP_LW_PAIR, false>(ctx, a);
+  }
+  if (mode == MLP_SW_PAIR && ngpt == 112 && shape32(A, 4, 1, 16, 1, 16, 4) && shape32(B, 4, 1, 16, 1, 16, 4)) {
+    // the reduced-resolution g112 pair: absorption and Rayleigh 7-32-32-112; the last g-tile holds 16 g-points
+    if (xin) return launch32<4, 1, 16, 1, 16, 1, 16, 1, 16, 4, MLP_SW_PAIR, true, kSwNT, kSwWPE, 16>(ctx, a);
+    return launch32<4, 1, 16, 1, 16, 1, 16, 1, 16, 4, MLP_SW_PAIR, false, kSwNT, kSwWPE, 16>(ctx, a);
   }
   return RRTMGPNN_ERR_UNSUPPORTED;
 }

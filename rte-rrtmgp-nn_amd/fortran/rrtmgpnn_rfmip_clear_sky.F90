@@ -8,6 +8,9 @@
 ! sources, and its own device context and stream (mo_rrtmgpnn_c), so blocks run concurrently on the GPU.
 !
 ! usage: rrtmgpnn_rfmip_clear_sky <problem.rbin> <output.rbin> <data_dir> [block_size] [nrepeat]
+!          [lw_absorption] [lw_planck_frac] [sw_absorption] [sw_rayleigh] [kdist_lw] [kdist_sw]
+!   arguments 6-11: paths that replace the four model files (netCDF or RBIN) and the two k-distribution tables
+!   (RBIN) of <data_dir>, e.g. the reduced-resolution g128 / g112 set; absent or "-": the file of <data_dir>.
 !   problem.rbin: play/tlay (ncol,nlay), plev/tlev (ncol,nlay+1), tsfc/sfc_emis/sfc_alb/mu0/tsi/usecol
 !   (ncol), gas_names (ngas,32) + vmr_<gas> (ncol,nlay), top_at_1 and n_gauss_angles (1).
 !   output.rbin:  lw_flux_up/dn, sw_flux_up/dn/dir (ncol,nlay+1), lw_heating_rate (ncol,nlay) [K/s].
@@ -89,12 +92,12 @@ program rrtmgpnn_rfmip_clear_sky
   ngas = size(gas_names)
   if (block_size <= 0) block_size = ncol
 
-  call nets_lw(1)%load_netcdf(trim(data_dir) // "/nn_lw_g256_abs.rbin")
-  call nets_lw(2)%load_netcdf(trim(data_dir) // "/nn_lw_g256_pfrac.rbin")
-  call nets_sw(1)%load_netcdf(trim(data_dir) // "/nn_sw_g224_abs.rbin")
-  call nets_sw(2)%load_netcdf(trim(data_dir) // "/nn_sw_g224_ray.rbin")
-  call stop_on_err(kdist_lw%load_rbin(trim(data_dir) // "/kdist_lw_g256.rbin", gas_names))
-  call stop_on_err(kdist_sw%load_rbin(trim(data_dir) // "/kdist_sw_g224.rbin", gas_names))
+  call nets_lw(1)%load_netcdf(data_file(6, "nn_lw_g256_abs.rbin"))
+  call nets_lw(2)%load_netcdf(data_file(7, "nn_lw_g256_pfrac.rbin"))
+  call nets_sw(1)%load_netcdf(data_file(8, "nn_sw_g224_abs.rbin"))
+  call nets_sw(2)%load_netcdf(data_file(9, "nn_sw_g224_ray.rbin"))
+  call stop_on_err(kdist_lw%load_rbin(data_file(10, "kdist_lw_g256.rbin"), gas_names))
+  call stop_on_err(kdist_sw%load_rbin(data_file(11, "kdist_sw_g224.rbin"), gas_names))
   call stop_on_err(kdist_sw%set_tsi(1361.0_wp))                  ! rrtmgp_rfmip_sw.F90:317
 
   allocate(lw_up(nlay + 1, ncol), lw_dn(nlay + 1, ncol), sw_up(nlay + 1, ncol), sw_dn(nlay + 1, ncol), &
@@ -257,4 +260,19 @@ contains
       error stop 1
     end if
   end subroutine stop_on_err
+
+  ! command argument n when given (and not "-"), else <data_dir>/<name>
+  function data_file(n, name) result(path)
+    integer, intent(in) :: n
+    character(len=*), intent(in) :: name
+    character(len=:), allocatable :: path
+    character(len=512) :: given
+    given = "-"
+    if (command_argument_count() >= n) call get_command_argument(n, given)
+    if (len_trim(given) == 0 .or. trim(given) == "-") then
+      path = trim(data_dir) // "/" // name
+    else
+      path = trim(given)
+    end if
+  end function data_file
 end program rrtmgpnn_rfmip_clear_sky

@@ -177,34 +177,14 @@ class RrtmgpNetwork:
         """neural/mod_network_rrtmgp.F90:58-122.  `filename` is the reference's netCDF model file (read natively,
         csrc/datafile.cpp) or its RBIN conversion."""
         from . import ncio
-        with ncio.DataFile(filename) as f:
-            if "nn_dimsize" in f:  # the netCDF model: nn_dim_input, nn_dimsize, nn_activation_char, ...
-                self.dims = [int(f.read("nn_input_coeffs_min").size)] + [int(v) for v in f.read("nn_dimsize")]
-                acts = ["linear", "softsign", "relu", "sigmoid", "hard_sigmoid", "tanh", "gaussian"]
-                self.activation = [acts.index(a) for a in f.strings("nn_activation_char")]
-                self.input_names = f.strings("nn_inputs_char") if "nn_inputs_char" in f else [""] * self.dims[0]
-                self.coeffs_input_min = f.read("nn_input_coeffs_min", np.float32)
-                self.coeffs_input_max = f.read("nn_input_coeffs_max", np.float32)
-                has_out = "nn_output_coeffs_mean" in f
-                self.coeffs_output_mean = f.read("nn_output_coeffs_mean", np.float32) if has_out else None
-                self.coeffs_output_std = f.read("nn_output_coeffs_std", np.float32) if has_out else None
-                m = {"dims": np.array(self.dims, np.int32), "activation": np.array(self.activation, np.int32),
-                     "input_names": rbin.chars(self.input_names), "input_min": self.coeffs_input_min,
-                     "input_max": self.coeffs_input_max}
-                for n in range(1, len(self.dims)):
-                    m["w%d" % n] = f.read("nn_weights_%d" % n, np.float32)
-                    m["b%d" % n] = f.read("nn_bias_%d" % n, np.float32)
-                if has_out:
-                    m["output_mean"], m["output_std"] = self.coeffs_output_mean, self.coeffs_output_std
-            else:
-                m = {v: f.read(v) for v in f.vars}
-                self.dims = [int(v) for v in m["dims"]]
-                self.activation = [int(v) for v in m["activation"]]
-                self.input_names = rbin.unchars(m["input_names"]) if "input_names" in m else [""] * self.dims[0]
-                self.coeffs_input_min = m["input_min"]
-                self.coeffs_input_max = m["input_max"]
-                self.coeffs_output_mean = m.get("output_mean")
-                self.coeffs_output_std = m.get("output_std")
+        m = ncio.read_model(filename)  # the netCDF model's variables under the RBIN model's keys
+        self.dims = [int(v) for v in m["dims"]]
+        self.activation = [int(v) for v in m["activation"]]
+        self.input_names = rbin.unchars(m["input_names"]) if "input_names" in m else [""] * self.dims[0]
+        self.coeffs_input_min = m["input_min"]
+        self.coeffs_input_max = m["input_max"]
+        self.coeffs_output_mean = m.get("output_mean")
+        self.coeffs_output_std = m.get("output_std")
         self.model = m
         ctx = context(self.device)
         h = _lib.c_vp()
@@ -591,9 +571,10 @@ class GasOpticsRRTMGP(OpticalProps):
     """ty_gas_optics_rrtmgp, NN branch.  The lookup-table branch needs the k-distribution files that are
     missing from the reference and is not provided."""
 
-    def load(self, which, device=None):
-        """Load the (surrogate) k-distribution tables, 'lw' (g256) or 'sw' (g224)."""
-        kd = data.load_kdist(which)
+    def load(self, which, device=None, ngpt=None):
+        """Load the (surrogate) k-distribution tables, 'lw' (g256) or 'sw' (g224); ngpt = 128 ('lw') / 112 ('sw'): the
+        reduced-resolution tables the 2021 networks go with (data.load_kdist)."""
+        kd = data.load_kdist(which, ngpt)
         e = self.init(kd["band_lims_wvn"], kd["band_lims_gpt"])
         if e:
             return e

@@ -34,12 +34,58 @@ def path(name):
 
 
 def load_model(name):
-    return rbin.read(path(name))
+    """A model dict (dims, activation, input_names, input_min / input_max, w1.., b1.., output_mean / output_std): a
+    shipped model by its key or file name, or the path of a model file, RBIN or the reference's netCDF (read natively,
+    ncio.read_model: the dict RrtmgpNetwork.load_netcdf holds)."""
+    p = path(name)
+    with open(p, "rb") as f:
+        magic = f.read(4)
+    if magic == b"RBIN":
+        return rbin.read(p)
+    from . import ncio
+    return ncio.read_model(p)
 
 
-def load_kdist(which):
-    """Surrogate k-distribution tables ('lw' -> g256, 'sw' -> g224); see tools/convert_reference_data.py."""
-    d = rbin.read(os.path.join(DATA_DIR, "kdist_lw_g256.rbin" if which == "lw" else "kdist_sw_g224.rbin"))
+KDIST_FILES = {"lw": "kdist_lw_g256.rbin", "sw": "kdist_sw_g224.rbin"}
+REDUCED_NGPT = {"lw": 128, "sw": 112}  # the 2021 networks' grids
+REDUCED_PER_BAND = 8
+
+
+def reduce_kdist(full):
+    """The reduced-resolution surrogate table of a full-resolution one (a dict in the file's variable order): every band
+    keeps its wavenumber limits and half its g-points, 8 per band; totplnk, temp_ref_min / max and press_ref_min are
+    copied; the SW solar source of a reduced g-point is the float32 sum of the two it replaces,
+    solar_source_112[8 b + i] = solar_source_224[16 b + 2 i] + solar_source_224[16 b + 2 i + 1].  Project-made like the
+    full tables, from them alone.  (The real g128 / g112 band limits are unequal; a host passes its own to
+    init(band_lims_wvn, band_lims_gpt).)"""
+    lims = np.asarray(full["band_lims_gpt"], np.int32)
+    if not ((lims[:, 1] - lims[:, 0] + 1) == 2 * REDUCED_PER_BAND).all():
+        raise ValueError("reduce_kdist: the full-resolution table does not have %d g-points in every band"
+                         % (2 * REDUCED_PER_BAND))
+    out = {}
+    for k, v in full.items():
+        if k == "band_lims_gpt":
+            lo = 1 + REDUCED_PER_BAND * np.arange(lims.shape[0], dtype=np.int32)
+            out[k] = np.stack([lo, lo + REDUCED_PER_BAND - 1], axis=1).astype(np.int32)
+        elif k == "solar_source":
+            s = np.asarray(v, np.float32)
+            out[k] = (s[0::2] + s[1::2]).astype(np.float32)
+        else:
+            out[k] = v.copy()
+    return out
+
+
+def load_kdist(which, ngpt=None):
+    """Surrogate k-distribution tables: 'lw' -> g256, 'sw' -> g224 (tools/convert_reference_data.py); ngpt = 128 (LW) /
+    112 (SW): the reduced-resolution tables of the 2021 networks, 8 g-points per band, derived from the full ones
+    (reduce_kdist; tools/make_reduced_kdist.py writes them as files for hosts that read files)."""
+    which = "lw" if which == "lw" else "sw"
+    if ngpt is not None and ngpt != REDUCED_NGPT[which]:
+        raise ValueError("load_kdist: no %s table with ngpt = %r (None, or the reduced grid: 128 for lw, 112 for sw)"
+                         % (which, ngpt))
+    d = rbin.read(os.path.join(DATA_DIR, KDIST_FILES[which]))
+    if ngpt is not None:
+        d = reduce_kdist(d)
     out = {k: v for k, v in d.items()}
     out["nband"] = int(d["band_lims_gpt"].shape[0])
     out["ngpt"] = int(d["band_lims_gpt"][-1, 1])

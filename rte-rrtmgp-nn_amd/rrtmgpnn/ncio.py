@@ -84,6 +84,34 @@ def read(path):
         return {v: f.read(v) for v in f.vars}
 
 
+MODEL_ACTIVATIONS = ["linear", "softsign", "relu", "sigmoid", "hard_sigmoid", "tanh", "gaussian"]
+
+
+def read_model(path):
+    """A network model file as the RBIN model's dict (dims, activation, input_names, input_min, input_max, w1.., b1..,
+    output_mean, output_std): the reference's netCDF model (neural/mod_network_rrtmgp.F90:58-122: nn_dimsize,
+    nn_activation_char, nn_inputs_char, nn_input_coeffs_*, nn_weights_n, nn_bias_n, nn_output_coeffs_*) mapped onto
+    those keys, or an RBIN conversion as it is.  The one mapping: RrtmgpNetwork.load_netcdf and data.load_model both
+    read through it."""
+    from . import rbin
+    with DataFile(path) as f:
+        if "nn_dimsize" not in f:
+            return {v: f.read(v) for v in f.vars}
+        dims = [int(f.read("nn_input_coeffs_min").size)] + [int(v) for v in f.read("nn_dimsize")]
+        names = f.strings("nn_inputs_char") if "nn_inputs_char" in f else [""] * dims[0]
+        m = {"dims": np.array(dims, np.int32),
+             "activation": np.array([MODEL_ACTIVATIONS.index(a) for a in f.strings("nn_activation_char")], np.int32),
+             "input_names": rbin.chars(names), "input_min": f.read("nn_input_coeffs_min", np.float32),
+             "input_max": f.read("nn_input_coeffs_max", np.float32)}
+        for n in range(1, len(dims)):
+            m["w%d" % n] = f.read("nn_weights_%d" % n, np.float32)
+            m["b%d" % n] = f.read("nn_bias_%d" % n, np.float32)
+        if "nn_output_coeffs_mean" in f:
+            m["output_mean"] = f.read("nn_output_coeffs_mean", np.float32)
+            m["output_std"] = f.read("nn_output_coeffs_std", np.float32)
+    return m
+
+
 # examples/rfmip-clear-sky/mo_rfmip_io.F90:323-358 (forcing_index = 1): chemical name -> RFMIP variable
 RFMIP_GASES = {"co2": "carbon_dioxide", "n2o": "nitrous_oxide", "ch4": "methane", "co": "carbon_monoxide",
                "ccl4": "carbon_tetrachloride", "cfc22": "hcfc22", "o2": "oxygen", "n2": "nitrogen",

@@ -187,7 +187,8 @@ class ClearSkyStep:
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
                  clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False,
-                 lw_dual=False, upper_bc=False):
+                 lw_dual=False, upper_bc=False, spectral=None):
+        lw_models, sw_models = self._resolve_spectral(spectral, lw_models, sw_models)
         self.lw_dual = bool(lw_dual)
         self.upper_bc = bool(upper_bc)
         if self.lw_dual:
@@ -231,6 +232,24 @@ class ClearSkyStep:
             self._finish(overlap, lw_after, sw_after, lw_net_cus, sw_net_cus)
         else:
             self._finish(False)
+
+    def _resolve_spectral(self, spectral, lw_models, sw_models):
+        """spectral=: the step's spectral configuration.  None: the shipped g256 / g224 tables and the models named by
+        lw_models / sw_models.  A dict selects the k-distribution tables by ngpt and loads the models from paths:
+        "ngpt_lw", "ngpt_sw" (data.load_kdist's ngpt; absent or None: the shipped tables), "lw_models" (absorption,
+        Planck fraction) or (single model,), "sw_models" (absorption, Rayleigh) -- model files, netCDF or RBIN."""
+        self._ngpt_lw = self._ngpt_sw = None
+        if spectral is None:
+            return lw_models, sw_models
+        unknown = set(spectral) - {"lw_models", "sw_models", "ngpt_lw", "ngpt_sw"}
+        if unknown:
+            raise ValueError("spectral: unknown keys %s" % sorted(unknown))
+        self._ngpt_lw, self._ngpt_sw = spectral.get("ngpt_lw"), spectral.get("ngpt_sw")
+        lw_models, sw_models = tuple(spectral.get("lw_models", lw_models)), tuple(spectral.get("sw_models", sw_models))
+        if len(lw_models) not in (1, 2) or len(sw_models) != 2:
+            raise ValueError("spectral: lw_models is (absorption, planck_frac) or (both,), sw_models (absorption, "
+                             "rayleigh)")
+        return lw_models, sw_models
 
     def _resolve_options(self, fused, clouds, sw, sw_priority, byband, clrsky, mcica, aerosols=None, jacobian=False):
         """Every option check, and the flags derived from the options, before any device object exists."""
@@ -281,7 +300,7 @@ class ClearSkyStep:
         self._streams, self._closed, self.graph, self.ctx2 = [], False, None, None
         self.ctx = ctx or Context(device, self._new_stream())
         L = self.L = _lib.lib()
-        self.kd_lw, self.kd_sw = data.load_kdist("lw"), data.load_kdist("sw")
+        self.kd_lw, self.kd_sw = data.load_kdist("lw", self._ngpt_lw), data.load_kdist("sw", self._ngpt_sw)
 
         def net(name):
             h = _lib.c_vp()
@@ -295,6 +314,12 @@ class ClearSkyStep:
         self.nx_lw, self.nx_sw = len(self.lw_names), len(self.sw_names)
         self.ng_lw, self.ng_sw = self.kd_lw["ngpt"], self.kd_sw["ngpt"]
         self.nb_lw = self.kd_lw["nband"]
+        for w, models, ng in (("lw", lw_models, self.ng_lw), ("sw", sw_models, self.ng_sw)):
+            for k, name in enumerate(models):  # a single LW model predicts tau and the Planck fraction: 2 ngpt outputs
+                ny = int(data.load_model(name)["dims"][-1])
+                if ny != (2 * ng if w == "lw" and len(models) == 1 else ng):
+                    raise ValueError("%s model %r has %d outputs, the %s k-distribution %d g-points"
+                                     % (w, name, ny, w, ng))
         if self.allsky:
             self.nb_sw = self.kd_sw["nband"]
             self.cloud_lw, self.cloud_sw = (self._cloud_optics(w, cloud_lut, icergh) for w in ("lw", "sw"))
