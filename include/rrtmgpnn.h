@@ -117,7 +117,7 @@ int rrtmgpnn_context_set_mlp_kernel(rrtmgpnn_context *ctx, int mode);
  * rrtmgpnn_gas_optics_lw_nn/_sw_nn), for tests of the dispatch: path[0] one of RRTMGPNN_MLP_PATH_* (NONE before the
  * first launch); for MFMA16 path[1..3] = the first network's (K1S, H1T, H2T), path[4..6] the second's (0 without one);
  * path[7] flag bits: 1 softsign/softsign/linear inlined, 2 output tile count compiled in, 4 inputs formed in-kernel,
- * 8 16-byte output stores. */
+ * 8 16-byte output stores, 16 the active-column count read from a device word (rrtmgpnn_gas_optics_sw_nn_active). */
 #define RRTMGPNN_MLP_PATH_NONE    0
 #define RRTMGPNN_MLP_PATH_GENERIC 1
 #define RRTMGPNN_MLP_PATH_MFMA32  2
@@ -136,7 +136,9 @@ int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8]);
  *     1024 the small-grid instance;
  *   3 lw_rescl_planck_inc_kernel: 1 cloud mask, 2 aerosol, 4 clear beside all sky (dual);
  *   4 lw_rescl_kernel: 1 by-band outputs, 2 Jacobian;
- *   5 sw_2stream_kernel, 6 sw_2stream_x2_kernel: 1 gas g, 2 band increment, 4 g-point outputs, 8 by-band outputs.
+ *   5 sw_2stream_kernel, 6 sw_2stream_x2_kernel: 1 gas g, 2 band increment, 4 g-point outputs, 8 by-band outputs;
+ *   7 sw_2stream_ck_kernel with the active-column count read from a device word
+ *     (rrtmgpnn_solver_request_active_columns): family 2's bits, and 2048 in every instance.
  * path[2]: the launches the call made in these families, 2 where a clear + all-sky entry ran its two launches (path[0]
  * and path[1] are then the second's).  path[3]: the number of instances the family is compiled for; an options value
  * outside that list is refused with RRTMGPNN_ERR_UNSUPPORTED.  A call that launches nothing leaves the path as it was. */
@@ -852,6 +854,55 @@ int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, 
  * Nothing is allocated and the pointers become kernel arguments, so an armed call can be captured in a hipGraph. */
 int rrtmgpnn_solver_request_aerosol(rrtmgpnn_context *ctx, int nbnd, int nlay, int ncol, const float *tau_aer,
                                     const float *ssa_aer, const float *g_aer);
+/* ---- daylit columns: device-side column compaction for the shortwave chain ----------------------------
+ * The RFMIP driver marks the columns where the sun is up (usecol, examples/rfmip-clear-sky/rrtmgp_rfmip_sw.F90:285-287),
+ * solves the others with mu0 = 1 (:433) and zeroes their fluxes afterwards (:456-463).  These entries compact a block
+ * to its daylit columns instead: plan, gather the inputs into dense arrays, run rrtmgpnn_gas_optics_sw_nn_active and an
+ * SW solver armed with rrtmgpnn_solver_request_active_columns on them, scatter the fluxes back with zeros at night.
+ * The number of daylit columns is one int (32 bits) in DEVICE memory that the kernels read: the host never sees it, so
+ * a hipGraph captured once serves any day / night pattern.  Every array argument is a DEVICE pointer; src[], dst[],
+ * dense[], out[] and row_floats[] themselves are HOST arrays.
+ *
+ * rrtmgpnn_daylit_plan (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): v (ncol); kind 0: column i is daylit iff
+ * v[i] < bound (the driver's form on the zenith angle, bound = 90 - 2 spacing(90)), kind 1: iff v[i] > bound (callers
+ * that hold mu0); a NaN is night under both.  idx (ncol): the daylit columns in increasing order, then the night columns
+ * in increasing order (a permutation of 0..ncol-1); slot (ncol): the dense position of a daylit column, -1 for a night
+ * column; nday: their count.  The order is stable: dense column j is the j-th daylit column.  In all five
+ * entries ncol == 0 launches nothing (nday is then left as it was). */
+int rrtmgpnn_daylit_plan(rrtmgpnn_context *ctx, int ncol, const float *v, int kind, float bound, int *idx, int *slot,
+                         int *nday);
+/* rrtmgpnn_gather_columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): one launch; for each of the narrays (1..16)
+ * arrays of row_floats[a] floats per column, row idx[j] of src[a] goes to row j of dst[a] for j < *nday.  Rows of dst at
+ * or past *nday are left as they were.  Rows need no alignment beyond a float's. */
+int rrtmgpnn_gather_columns(rrtmgpnn_context *ctx, int ncol, int narrays, const float *const *src, float *const *dst,
+                            const int *row_floats, const int *idx, const int *nday);
+/* rrtmgpnn_scatter_columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): one launch; for each of the narrays (1..6)
+ * arrays, column i of out[a] (row_floats[a], ncol) is row slot[i] of dense[a] where slot[i] >= 0 and zeros otherwise:
+ * the driver's zeroing of the unused columns.  It applies to flux_dir as well, which the driver leaves at its mu0 = 1
+ * value: here a night column's direct flux is 0. */
+int rrtmgpnn_scatter_columns(rrtmgpnn_context *ctx, int ncol, int narrays, const float *const *dense, float *const *out,
+                             const int *row_floats, const int *slot);
+/* rrtmgpnn_gas_optics_sw_nn on the first *nact columns of dense arrays (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463):
+ * the same arguments, ncol the allocated extent of every array, nact one DEVICE int with 0 <= *nact <= ncol.  Samples
+ * at or past nlay * (*nact) are neither read nor written.  Served by the in-kernel-input SW pairs of the 32x32x2 kernel
+ * (the g224 and g112 models) only: RRTMGPNN_ERR_UNSUPPORTED for any other networks, for ssa == NULL and under
+ * rrtmgpnn_context_set_mlp_kernel mode 1.  rrtmgpnn_context_get_mlp_path then reports flag bit 16. */
+int rrtmgpnn_gas_optics_sw_nn_active(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs,
+                                     const float *play, const float *tlay, const float *plev, const float *vmr_h2o,
+                                     const float *const *gas_conc, const int *gas_ndims,
+                                     const rrtmgpnn_network *const *nets, float *tau, float *ssa, float *g,
+                                     const int *nact);
+/* Ask this context's next solver call to solve the first *nact of its ncol columns only (rrtmgp_rfmip_sw.F90:285-287,
+ * 433, 456-463): nact one DEVICE int, 0 <= *nact <= ncol, read by the kernel.  Flux rows at or past *nact are not
+ * written.  Armed for one call, cleared by it whatever it returns; nact == NULL disarms.
+ * Honoured by rrtmgpnn_sw_solver_2stream, rrtmgpnn_sw_solver_2stream_inc and rrtmgpnn_sw_solver_2stream_rfmip on the
+ * checkpointed kernel (even ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), kernel family 7 of
+ * rrtmgpnn_context_get_solver_path: the instances of family 2 with option bit 2048, for g == NULL and without or with
+ * the band increment.  The instance and its workspace are chosen from ncol, as without the request.
+ * RRTMGPNN_ERR_ARGUMENT: every other solver entry, with a message naming the three; ncol other than the call's.
+ * RRTMGPNN_ERR_UNSUPPORTED: a by-band, cloud-mask, aerosol or Jacobian request beside it, g-point outputs, a gas g
+ * array, the other SW kernel modes, odd ngpt. */
+int rrtmgpnn_solver_request_active_columns(rrtmgpnn_context *ctx, int ncol, const int *nact);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */
 int rrtmgpnn_delta_scale_2str(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);

@@ -122,6 +122,7 @@ struct Requests {
   rrtmgpnn_context::CloudMaskRequest mask{};
   rrtmgpnn_context::JacobianRequest jac{};
   rrtmgpnn_context::AerosolRequest aer{};
+  rrtmgpnn_context::ActiveRequest act{};
 };
 
 static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
@@ -134,6 +135,8 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
   ctx->jacobian = rrtmgpnn_context::JacobianRequest{};
   rq.aer = ctx->aerosol;
   ctx->aerosol = rrtmgpnn_context::AerosolRequest{};
+  rq.act = ctx->active;
+  ctx->active = rrtmgpnn_context::ActiveRequest{};
   if (!ctx->byband.armed) return rq;
   const auto bb = ctx->byband;
   ctx->byband = rrtmgpnn_context::BybandRequest{};
@@ -149,6 +152,23 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
 // the entries without masked instances refuse an armed cloud mask
 static const char kNoMaskMsg[] = "solver_request_cloud_mask: this solver entry takes no cloud mask (the _planck_inc, "
                                  "_2stream_inc, _2stream_rfmip, _2stream_clr_all and _2stream_rfmip_clr_all entries do)";
+// ... and an armed active-column count (rrtmgpnn_solver_request_active_columns; rrtmgp_rfmip_sw.F90:285-287, 433,
+// 456-463): the three SW two-stream entries take it alone, on the call's ncol, into the call's extras
+static const char kNoActiveMsg[] = "solver_request_active_columns: this solver entry takes no active-column count (the "
+                                   "sw_solver_2stream, sw_solver_2stream_inc and sw_solver_2stream_rfmip entries do)";
+static int take_active(const char *entry, const Requests &rq, bool honour, int ncol, SolverExtras &ex)
+{
+  if (!rq.act.armed) return RRTMGPNN_OK;
+  if (!honour) return fail(RRTMGPNN_ERR_ARGUMENT, kNoActiveMsg);
+  const std::string e(entry);
+  if (rq.byband || rq.mask.armed || rq.aer.armed || rq.jac.armed)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an active-column count together with a by-band, cloud-mask, aerosol or "
+                                              "Jacobian request");
+  if (rq.act.ncol != ncol)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested active-column count's ncol is not this call's");
+  ex.nact = rq.act.nact;
+  return RRTMGPNN_OK;
+}
 // What an entry does with an armed Jacobian request (rrtmgpnn_solver_request_jacobian): the LW entries that read source
 // arrays need its sfc_source_Jac, the fused-Planck ones form it in-kernel and take none, every other entry refuses
 // (`refusal`, or a message naming the entry).  The extents are the call's; by-band outputs do not go with it.
@@ -211,9 +231,10 @@ static int jacobian_no_gpt(const char *entry, const SolverExtras &ex, const floa
 }
 
 static int take_byband(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
-                       JacMode jac = kJacRefuse, const char *jac_refusal = nullptr)
+                       JacMode jac = kJacRefuse, const char *jac_refusal = nullptr, bool active = false)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
+  if (int rc = take_active(entry, rq, active, ncol, ex)) return rc;
   if (rq.byband_rc) return rq.byband_rc;
   if (int rc = take_aerosol(entry, rq, kAerRefuse, 0, nlay, ncol, ex)) return rc;
   if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, kNoMaskMsg);
@@ -223,9 +244,10 @@ static int take_byband(const char *entry, rrtmgpnn_context *ctx, int ngpt, int n
 // the three that honour it, alone or paired with by-band outputs: the mask against the call's extents, then into the
 // call's extras
 static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
-                               JacMode jac = kJacRefuse, AerMode aer = kAerRefuse, int nbnd = 0)
+                               JacMode jac = kJacRefuse, AerMode aer = kAerRefuse, int nbnd = 0, bool active = false)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
+  if (int rc = take_active(entry, rq, active, ncol, ex)) return rc;
   if (rq.byband_rc) return rq.byband_rc;
   if (int rc = take_aerosol(entry, rq, aer, nbnd, nlay, ncol, ex)) return rc;
   if (int rc = take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex)) return rc;
@@ -248,6 +270,7 @@ static int refuse_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, i
                            SolverExtras &ex, const char *mask_msg)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
+  if (int rc = take_active(entry, rq, false, ncol, ex)) return rc;
   if (int rc = take_aerosol(entry, rq, kAerLw, nbnd, nlay, ncol, ex)) return rc;
   if (rq.byband)
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": by-band outputs are not available from this entry (the "
@@ -350,7 +373,9 @@ static int lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
 static int sw_2stream(rrtmgpnn_context *ctx, const Sw2Stream &p, float *gpt_up, float *gpt_dn, float *gpt_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband("sw_solver_2stream", ctx, p.ngpt, p.nlay, p.ncol, ex)) return rc;
+  if (int rc = take_byband("sw_solver_2stream", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacRefuse, nullptr, true)) return rc;
+  if (ex.nact && (gpt_up || gpt_dn || gpt_dir))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw_solver_2stream: an active-column count together with g-point outputs");
   if (int rc = check_ctx(ctx)) return rc;
   if (!p.inc_flux || !p.tau || !p.ssa || !p.mu0 || !p.alb_dir || !p.alb_dif || !p.flux_up || !p.flux_dn ||
       !p.flux_dir || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
@@ -924,6 +949,34 @@ int rrtmgpnn_gas_optics_sw_nn(rrtmgpnn_context *ctx, int ncol, int nlay, int ngp
   return rrtmgpnn_predict_nn_sw(ctx, ncol, nlay, ngpt, ninputs, x, cd, nets, tau, ssa, g);
 }
 
+// rrtmgpnn_gas_optics_sw_nn on the first *nact columns of dense arrays (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463: the
+// daylit columns of a compacted block).  A new entry, not a request: the gas-optics entries take none.  Only the two
+// active-count instances of the 32x32x2 kernel serve it; nothing else is tried
+int rrtmgpnn_gas_optics_sw_nn_active(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ninputs,
+                                     const float *play, const float *tlay, const float *plev, const float *vmr_h2o,
+                                     const float *const *gas_conc, const int *gas_ndims,
+                                     const rrtmgpnn_network *const *nets, float *tau, float *ssa, float *g,
+                                     const int *nact)
+{
+  static const char who[] = "gas_optics_sw_nn_active";
+  if (int rc = check_ctx(ctx)) return rc;
+  if (!nets || !nets[0] || !tau || !nact || ncol < 0 || ngpt < 1)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": bad argument");
+  MlpInputs in;
+  if (int rc = fused_inputs(who, nets[0], ninputs, nlay, play, tlay, plev, vmr_h2o, gas_conc, gas_ndims, in)) return rc;
+  static const char unsupported[] = ": only the in-kernel-input SW pairs of the 32x32x2 kernel (the g224 and g112 "
+                                    "models, ssa set, rrtmgpnn_context_set_mlp_kernel mode 0) read an active-column count";
+  if (!ssa) return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(who) + unsupported);
+  const rrtmgpnn_network *A = nets[0], *B = nets[1];
+  if (!B || B->dims[0] != ninputs || A->dims[A->nlayers] != ngpt || B->dims[B->nlayers] != ngpt ||
+      !A->has_out_scaling() || !B->has_out_scaling())
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": absorption / Rayleigh networks missing or inconsistent");
+  if (ncol == 0) return RRTMGPNN_OK;
+  const int rc = launch_mlp32(ctx, MLP_SW_PAIR, A, B, (long long)ncol * nlay, ngpt, nullptr, nullptr, tau, ssa, g, &in, nact);
+  if (rc == RRTMGPNN_ERR_UNSUPPORTED) return fail(rc, std::string(who) + unsupported);
+  return rc;
+}
+
 // ---- compute_bc (extensions/mo_compute_bc.F90) ----
 // The one-layer problem in the context workspace, one allocation for the whole call: the gathered arrays
 // (launch_bc_inputs), the layer's tau and second network output (pfrac / ssa), (ngpt, ncol) each, and room for the
@@ -1252,6 +1305,7 @@ int rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
   static const char kEntry[] = "lw_solver_1rescl_planck_inc";
   SolverExtras ex;
   const Requests rq = take_requests(ctx, ngpt, ex);
+  if (int rc = take_active(kEntry, rq, false, ncol, ex)) return rc;
   if (rq.byband)
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": by-band outputs are not available from this entry (the "
                                                              "lw_solver_1rescl entry has them, without a mask)");
@@ -1289,6 +1343,7 @@ int rrtmgpnn_lw_solver_1rescl_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
   static const char kEntry[] = "lw_solver_1rescl_planck_clr_all";
   SolverExtras ex;
   const Requests rq = take_requests(ctx, ngpt, ex);
+  if (int rc = take_active(kEntry, rq, false, ncol, ex)) return rc;
   if (rq.byband)
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": by-band outputs are not available from this entry (the "
                                                              "lw_solver_1rescl entry has them, without a mask)");
@@ -1372,7 +1427,7 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    float *flux_dn, float *flux_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd))
+  if (int rc = take_byband_or_mask("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd, true))
     return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !tau_bnd || !ssa_bnd || !g_bnd || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt ||
@@ -1402,6 +1457,7 @@ static int sw_clr_all_requests(const char *entry, rrtmgpnn_context *ctx, int ngp
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
   const std::string e(entry);
+  if (int rc = take_active(entry, rq, false, ncol, ex)) return rc;
   if (int rc = sw_clr_all_shape(entry, ngpt, nbnd)) return rc;
   if (rq.byband)
     return fail(RRTMGPNN_ERR_ARGUMENT, e + ": by-band outputs are not available from this entry (the sw_solver_2stream_inc "
@@ -1554,6 +1610,73 @@ int rrtmgpnn_solver_request_aerosol(rrtmgpnn_context *ctx, int nbnd, int nlay, i
   rq.ssa = ssa_aer;
   rq.g = g_aer;
   return RRTMGPNN_OK;
+}
+
+// rrtmgp_rfmip_sw.F90:285-287, 433, 456-463: the solver on the daylit columns of a compacted block
+int rrtmgpnn_solver_request_active_columns(rrtmgpnn_context *ctx, int ncol, const int *nact)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->active = rrtmgpnn_context::ActiveRequest{};
+  if (!nact) return RRTMGPNN_OK;  // nothing wanted: nothing armed
+  if (ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_active_columns: ncol < 0");
+  auto &rq = ctx->active;
+  rq.armed = true;
+  rq.ncol = ncol;
+  rq.nact = nact;
+  return RRTMGPNN_OK;
+}
+
+// rrtmgp_rfmip_sw.F90:285-287 (usecol), 433 (mu0 = 1 at night), 456-463 (the zeroing): kernels_daylit.hip
+int rrtmgpnn_daylit_plan(rrtmgpnn_context *ctx, int ncol, const float *v, int kind, float bound, int *idx, int *slot,
+                         int *nday)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (ncol < 0 || !nday || (ncol > 0 && (!v || !idx || !slot)))
+    return fail(RRTMGPNN_ERR_ARGUMENT, "daylit_plan: bad argument");
+  if (kind != 0 && kind != 1) return fail(RRTMGPNN_ERR_ARGUMENT, "daylit_plan: kind must be 0 (v < bound) or 1 (v > bound)");
+  if (ncol == 0) return RRTMGPNN_OK;
+  return launch_daylit_plan(ctx, ncol, v, kind, bound, idx, slot, nday);
+}
+
+static int column_table(const char *who, int ncol, int narrays, int max_arrays, const float *const *src,
+                        float *const *dst, const int *row_floats, ColumnTable &t)
+{
+  const std::string e(who);
+  if (ncol < 0 || !src || !dst || !row_floats) return fail(RRTMGPNN_ERR_ARGUMENT, e + ": bad argument");
+  if (narrays < 1 || narrays > max_arrays)
+    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": narrays must be 1.." + std::to_string(max_arrays));
+  t = ColumnTable{};
+  t.n = narrays;
+  for (int a = 0; a < narrays; a++) {
+    if (!src[a] || !dst[a] || row_floats[a] < 1 || (long long)row_floats[a] * 64 > 0x7fffffffLL)
+      return fail(RRTMGPNN_ERR_ARGUMENT, e + ": a null array or a row length out of range");
+    t.src[a] = src[a];
+    t.dst[a] = dst[a];
+    t.row[a] = row_floats[a];
+  }
+  return RRTMGPNN_OK;
+}
+
+// rrtmgp_rfmip_sw.F90:285-287, 433, 456-463
+int rrtmgpnn_gather_columns(rrtmgpnn_context *ctx, int ncol, int narrays, const float *const *src, float *const *dst,
+                            const int *row_floats, const int *idx, const int *nday)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ColumnTable t;
+  if (int rc = column_table("gather_columns", ncol, narrays, kDaylitMaxGather, src, dst, row_floats, t)) return rc;
+  if (!idx || !nday) return fail(RRTMGPNN_ERR_ARGUMENT, "gather_columns: bad argument");
+  return launch_gather_columns(ctx, ncol, t, idx, nday);
+}
+
+// rrtmgp_rfmip_sw.F90:285-287, 433, 456-463
+int rrtmgpnn_scatter_columns(rrtmgpnn_context *ctx, int ncol, int narrays, const float *const *dense, float *const *out,
+                             const int *row_floats, const int *slot)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ColumnTable t;
+  if (int rc = column_table("scatter_columns", ncol, narrays, kDaylitMaxScatter, dense, out, row_floats, t)) return rc;
+  if (!slot) return fail(RRTMGPNN_ERR_ARGUMENT, "scatter_columns: bad argument");
+  return launch_scatter_columns(ctx, ncol, t, slot);
 }
 
 int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
@@ -1953,7 +2076,7 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      float *flux_up, float *flux_dn, float *flux_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd))
+  if (int rc = take_byband_or_mask("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd, true))
     return rc;
   if (ex.mask_bits && nbnd <= 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream_rfmip: a cloud mask needs the band increment (nbnd > 0)");

@@ -83,6 +83,10 @@ struct SolverExtras {
   // launcher runs its dual instance, which solves the clear sky (the gases and the aerosol, never the fused band
   // increment) beside the all-sky problem; broadband outputs only
   float *clr_up = nullptr, *clr_dn = nullptr, *clr_dir = nullptr;
+  // rrtmgpnn_solver_request_active_columns: one device word, the number of columns (the first *nact of the call's ncol)
+  // the kernel solves; only the checkpointed SW launcher has such instances (kSolverSwCkActive), for g == NULL, without
+  // any of the above
+  const int *nact = nullptr;
 };
 
 // Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction (a kernel argument)
@@ -186,6 +190,12 @@ struct rrtmgpnn_context {
     int nbnd = 0, nlay = 0, ncol = 0;
     const float *tau = nullptr, *ssa = nullptr, *g = nullptr;
   } aerosol;
+  // rrtmgpnn_solver_request_active_columns: armed for the next solver call on this context, which clears it
+  struct ActiveRequest {
+    bool armed = false;
+    int ncol = 0;
+    const int *nact = nullptr;
+  } active;
   void *ws = nullptr;
   size_t ws_bytes = 0;
   bool ws_pinned = false;
@@ -275,7 +285,8 @@ enum SolverFamily {
   kSolverLwResclInc = 3,   // lw_rescl_planck_inc_kernel (kernels_lw_scat.hip)
   kSolverLwRescl = 4,      // lw_rescl_kernel (kernels_lw_scat.hip)
   kSolverSw2Stream = 5,    // sw_2stream_kernel (kernels_rte.hip)
-  kSolverSwX2 = 6          // sw_2stream_x2_kernel (kernels_sw_x2.hip)
+  kSolverSwX2 = 6,         // sw_2stream_x2_kernel (kernels_sw_x2.hip)
+  kSolverSwCkActive = 7    // sw_2stream_ck_kernel, the active-count instances (rrtmgpnn_solver_request_active_columns)
 };
 // lw_noscat_kernel
 constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand = 8, kLwOptDual = 16, kLwOptMask = 32,
@@ -283,7 +294,8 @@ constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand =
 // sw_2stream_ck_kernel; kSwCkSmall: the small-grid set of chunk length, ring, wave floor, lane type and prefetch
 // (kCk*Small, VSmall), else the default set
 constexpr uint32_t kSwCkHasG = 1, kSwCkInc = 2, kSwCkGpt = 4, kSwCkTn = 8, kSwCkEmk = 16, kSwCkBandPair = 32,
-                   kSwCkBand = 64, kSwCkMask = 128, kSwCkAer = 256, kSwCkDual = 512, kSwCkSmall = 1024;
+                   kSwCkBand = 64, kSwCkMask = 128, kSwCkAer = 256, kSwCkDual = 512, kSwCkSmall = 1024,
+                   kSwCkActive = 2048;  // the active-column count comes from a device word (family kSolverSwCkActive)
 // lw_rescl_planck_inc_kernel
 constexpr uint32_t kScatOptMask = 1, kScatOptAer = 2, kScatOptDual = 4;
 // lw_rescl_kernel
@@ -373,7 +385,7 @@ int pack_network(rrtmgpnn_network *net);
 int pack_network32(rrtmgpnn_network *net);
 int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A, const rrtmgpnn_network *B,
                  long long nbatch, int ngpt, const float *x, const float *col_dry, float *out0, float *out1,
-                 float *out2, const MlpInputs *in);
+                 float *out2, const MlpInputs *in, const int *nact = nullptr);
 // kernels_rte.hip
 int launch_planck_source(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int ntemp, const float *tlay,
                          const float *tlev, const float *tsfc, int sfc_lay, const BandArgs &bands,
@@ -438,6 +450,20 @@ int launch_bc_flux_lw(rrtmgpnn_context *ctx, int ngpt, int ncol, const float *ta
                       const float *wts, int as_flux, float *flux_bc);
 int launch_bc_flux_sw(rrtmgpnn_context *ctx, int ngpt, int ncol, const float *tau, const float *solar_source,
                       const float *mu0, float *flux_bc);
+// kernels_daylit.hip (rrtmgpnn_daylit_plan / _gather_columns / _scatter_columns): the daylit columns of a block, their
+// rows gathered into dense arrays, and the dense fluxes scattered back with zeros at night
+constexpr int kDaylitMaxGather = 16, kDaylitMaxScatter = 6;
+// n arrays of row[a] floats per column; gather: row idx[j] of src to row j of dst; scatter: row slot[i] of src to row i
+struct ColumnTable {
+  const float *src[kDaylitMaxGather];
+  float *dst[kDaylitMaxGather];
+  int row[kDaylitMaxGather];
+  int n;
+};
+int launch_daylit_plan(rrtmgpnn_context *ctx, int ncol, const float *v, int kind, float bound, int *idx, int *slot,
+                       int *nday);
+int launch_gather_columns(rrtmgpnn_context *ctx, int ncol, const ColumnTable &t, const int *idx, const int *nday);
+int launch_scatter_columns(rrtmgpnn_context *ctx, int ncol, const ColumnTable &t, const int *slot);
 // kernels_fluxes.hip: sum_byband of a g-point array (ngpt, nlev, ncol) into (nbnd, nlev, ncol)
 int launch_sum_byband(rrtmgpnn_context *ctx, int ngpt, long long nrow, const BandArgs &bands, const float *gpt_flux,
                       float *bnd_flux);

@@ -181,7 +181,12 @@ struct Buf {
 constexpr CachePolicy kCpNnLwSt = (CachePolicy)RRTMGPNN_CP_NN_LW_ST, kCpNnSwSt = (CachePolicy)RRTMGPNN_CP_NN_SW_ST;
 
 struct Mlp32Args {
-  const float *x;        // (nx, nbatch)
+  // x: (nx, nbatch), the network inputs.  The active-count instances (in-kernel inputs, so no x) find their device word
+  // here instead: the struct, and with it every other instance's kernel argument, keeps its layout
+  union {
+    const float *x;
+    const int *nact;
+  };
   const float *col_dry;  // (nbatch)
   float *out0, *out1, *out2;
   const float *imgA, *imgB;
@@ -289,13 +294,20 @@ constexpr int kMlp32Threads = 512, kSwNT = 512, kSwWPE = 1;
 // lanes that own them in the last tile store nothing there (one 64-byte row segment instead of two) and divide by 1;
 // with GLAST = 32 none of that is compiled.  Dynamic LDS: the weight images, then 32 floats per wave (the tile's
 // column amounts, handed from the sample lanes to the row registers).
+// ACTIVE (rrtmgpnn_gas_optics_sw_nn_active; in-kernel inputs only): the batch is the samples of the first *a.nact
+// columns, nact a device word read once -- the tile count, the last tile's valid rows and the past-the-batch tests use
+// nlay * nact; the arrays' record sizes stay those of the allocation (a.nbatch = nlay * ncol), so samples of columns at
+// or past nact that share the last tile are loaded (stale values of the dense arrays), computed and never stored.
 template <int KS, int AH1, int AN2, int AH2, int AN3, int BH1, int BN2, int BH2, int BN3, int NGT, int MODE, bool XIN,
-          int NT = kMlp32Threads, int WPE = 1, int GLAST = 32>
+          int NT = kMlp32Threads, int WPE = 1, int GLAST = 32, bool ACTIVE = false>
 __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
 {
   constexpr bool kPair = MODE == MLP_LW_PAIR || MODE == MLP_SW_PAIR;
   constexpr bool kPartial = GLAST < 32;
   static_assert(GLAST >= 1 && GLAST <= 32 && (!kPartial || MODE == MLP_SW_PAIR), "a partial last g-tile: the SW pair");
+  static_assert(!ACTIVE || XIN, "the active count takes the place of the input array's pointer");
+  int nbatch = a.nbatch;
+  if constexpr (ACTIVE) nbatch = a.nlay * min(max(*a.nact, 0), a.ncol);  // never past the allocation
   extern __shared__ floatx4 lds4[];
   const float *imgA = (const float *)lds4;
   const float *imgB = imgA + a.imgA_floats;
@@ -305,7 +317,7 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
   const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
   const int nx = a.nx, ngpt = a.ngpt;
-  const int ntiles = (a.nbatch + 31) / 32;
+  const int ntiles = (nbatch + 31) / 32;
   const int tstride = gridDim.x * nwaves;
   const uint32_t nb4 = 4u * (uint32_t)a.nbatch;
 
@@ -355,9 +367,9 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
       const Buf bh(a.h2o, nb4), bl(a.plev, 4u * (nlay + 1u) * (uint32_t)a.ncol);
       const uint32_t pl = 4u * (icol * (nlay + 1u) + ilay);
       xv[KS] = bh.ld(o2);
-      xv[KS + 1] = bl.ld(s < (uint32_t)a.nbatch ? pl : kOOB);
-      const float p1 = bl.ld(s < (uint32_t)a.nbatch ? pl + 4u : kOOB);
-      xv[KS + 2] = s < (uint32_t)a.nbatch ? p1 : 1.0f;
+      xv[KS + 1] = bl.ld(s < (uint32_t)nbatch ? pl : kOOB);
+      const float p1 = bl.ld(s < (uint32_t)nbatch ? pl + 4u : kOOB);
+      xv[KS + 2] = s < (uint32_t)nbatch ? p1 : 1.0f;
     } else {
       const Buf bx(a.x, nb4 * (uint32_t)nx);
 #pragma unroll
@@ -430,7 +442,7 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
     // wave-uniform by construction; readfirstlane lets the compiler keep the output descriptors in SGPRs (it treats
     // the loop index as divergent and would wrap every store in a waterfall loop)
     const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane(tile * 32);
-    const uint32_t nvalid = min(32u, (uint32_t)a.nbatch - s0);
+    const uint32_t nvalid = min(32u, (uint32_t)nbatch - s0);
     float cd;
     if constexpr (XIN) {
       cd = cd_in;
@@ -527,10 +539,10 @@ __global__ __launch_bounds__(NT, WPE) void mlp32_kernel(Mlp32Args a)
 constexpr int kOccDevices = 64;
 
 template <int KS, int AH1, int AN2, int AH2, int AN3, int BH1, int BN2, int BH2, int BN3, int NGT, int MODE, bool XIN,
-          int NT = kMlp32Threads, int WPE = 1, int GLAST = 32>
+          int NT = kMlp32Threads, int WPE = 1, int GLAST = 32, bool ACTIVE = false>
 static int launch32(rrtmgpnn_context *ctx, Mlp32Args &a)
 {
-  auto kern = mlp32_kernel<KS, AH1, AN2, AH2, AN3, BH1, BN2, BH2, BN3, NGT, MODE, XIN, NT, WPE, GLAST>;
+  auto kern = mlp32_kernel<KS, AH1, AN2, AH2, AN3, BH1, BN2, BH2, BN3, NGT, MODE, XIN, NT, WPE, GLAST, ACTIVE>;
   const size_t lds = sizeof(float) * ((size_t)(a.imgA_floats + (MODE != MLP_LW_BOTH ? a.imgB_floats : 0)) +
                                       32 * (NT / 64));
   if (lds > 160 * 1024) return RRTMGPNN_ERR_UNSUPPORTED;
@@ -563,7 +575,7 @@ static int launch32(rrtmgpnn_context *ctx, Mlp32Args &a)
   const long long grid = std::max<long long>(1, std::min<long long>(want, (long long)cus * per_cu));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, ctx->stream, a);
   RRTMGPNN_LAUNCH_CHECK("mlp32_kernel");
-  ctx->set_mlp_path(RRTMGPNN_MLP_PATH_MFMA32, 0, 0, 0, 0, 0, 0, 1 | 2 | (XIN ? 4 : 0) | 8);
+  ctx->set_mlp_path(RRTMGPNN_MLP_PATH_MFMA32, 0, 0, 0, 0, 0, 0, 1 | 2 | (XIN ? 4 : 0) | 8 | (ACTIVE ? 16 : 0));
   return RRTMGPNN_OK;
 }
 
@@ -578,11 +590,13 @@ static bool shape32(const rrtmgpnn_network *n, int KS, int HT1, int N2, int HT2,
 // RRTMGPNN_ERR_UNSUPPORTED (no error set) otherwise, and the caller runs the 16x16x4 kernel.
 int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A, const rrtmgpnn_network *B,
                  long long nbatch, int ngpt, const float *x, const float *col_dry, float *out0, float *out1,
-                 float *out2, const MlpInputs *in)
+                 float *out2, const MlpInputs *in, const int *nact)
 {
   const int kmode = ctx->mlp_kernel >= 0 ? ctx->mlp_kernel : g_mlp_kernel_default;
   if (kmode == 1 || (mode != MLP_LW_PAIR && mode != MLP_LW_BOTH && mode != MLP_SW_PAIR))
     return RRTMGPNN_ERR_UNSUPPORTED;
+  // an active-column count (a device word): the in-kernel-input SW pairs only, the two instances at the end
+  if (nact && (mode != MLP_SW_PAIR || !in || x)) return RRTMGPNN_ERR_UNSUPPORTED;
   const bool pair = mode != MLP_LW_BOTH;
   auto std_acts = [](const rrtmgpnn_network *n) {
     return n->act[0] == RRTMGPNN_ACT_SOFTSIGN && n->act[1] == RRTMGPNN_ACT_SOFTSIGN && n->act[2] == RRTMGPNN_ACT_LINEAR;
@@ -590,6 +604,7 @@ int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A,
   if (!A || !std_acts(A) || (pair && (!B || !std_acts(B)))) return RRTMGPNN_ERR_UNSUPPORTED;
   Mlp32Args a{};
   a.x = x; a.col_dry = col_dry; a.out0 = out0; a.out1 = out1; a.out2 = out2;
+  if (nact) a.nact = nact;  // (x is null then: the union's other member)
   a.imgA = A->d_packed32; a.imgA_floats = A->packed32_floats;
   a.imgB = pair ? B->d_packed32 : nullptr;
   a.imgB_floats = pair ? B->packed32_floats : 0;
@@ -633,6 +648,7 @@ int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A,
   }
   if (mode == MLP_SW_PAIR && ngpt == 224 && shape32(A, 4, 1, 8, 1, 8, 7) && shape32(B, 4, 1, 8, 1, 8, 7)) {
     // the shipped g224 pair: absorption and Rayleigh 7-16-16-224
+    if (nact) return launch32<4, 1, 8, 1, 8, 1, 8, 1, 8, 7, MLP_SW_PAIR, true, kSwNT, kSwWPE, 32, true>(ctx, a);
     if (xin) return launch32<4, 1, 8, 1, 8, 1, 8, 1, 8, 7, MLP_SW_PAIR, true, kSwNT, kSwWPE>(ctx, a);
     return launch32<4, 1, 8, 1, 8, 1, 8, 1, 8, 7, MLP_SW_PAIR, false, kSwNT, kSwWPE>(ctx, a);
   }
@@ -648,6 +664,7 @@ int launch_mlp32(rrtmgpnn_context *ctx, MlpMode mode, const rrtmgpnn_network *A,
   }
   if (mode == MLP_SW_PAIR && ngpt == 112 && shape32(A, 4, 1, 16, 1, 16, 4) && shape32(B, 4, 1, 16, 1, 16, 4)) {
     // the reduced-resolution g112 pair: absorption and Rayleigh 7-32-32-112; the last g-tile holds 16 g-points
+    if (nact) return launch32<4, 1, 16, 1, 16, 1, 16, 1, 16, 4, MLP_SW_PAIR, true, kSwNT, kSwWPE, 16, true>(ctx, a);
     if (xin) return launch32<4, 1, 16, 1, 16, 1, 16, 1, 16, 4, MLP_SW_PAIR, true, kSwNT, kSwWPE, 16>(ctx, a);
     return launch32<4, 1, 16, 1, 16, 1, 16, 1, 16, 4, MLP_SW_PAIR, false, kSwNT, kSwWPE, 16>(ctx, a);
   }

@@ -323,7 +323,18 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
   constexpr bool kHasG = (O & kSwCkHasG) != 0, kInc = (O & kSwCkInc) != 0, kGpt = (O & kSwCkGpt) != 0;
   constexpr bool kTn = (O & kSwCkTn) != 0, kEmk = (O & kSwCkEmk) != 0, kBandPair = (O & kSwCkBandPair) != 0;
   constexpr bool kBand = (O & kSwCkBand) != 0, kMask = (O & kSwCkMask) != 0, kAer = (O & kSwCkAer) != 0;
-  constexpr bool kDual = (O & kSwCkDual) != 0, kSmall = (O & kSwCkSmall) != 0;
+  constexpr bool kDual = (O & kSwCkDual) != 0, kSmall = (O & kSwCkSmall) != 0, kActive = (O & kSwCkActive) != 0;
+  static_assert(!kActive || (!kMask && !kAer && !kDual && !kGpt && !kBand && !kHasG),
+                "the active-count instances: clear sky or the fused increment, broadband outputs");
+  // kActive (rrtmgpnn_solver_request_active_columns): the block solves columns below *nact, a device word read here,
+  // before any barrier -- the word arrives in cmask's place (no instance has both a mask and a count), so every other
+  // instance keeps its arguments.  ncol stays the launch's in everything that lays out memory (the checkpoints pW, the
+  // planes); nca bounds the columns a block works on and the flush stores
+  int nca = ncol;
+  if constexpr (kActive) {
+    nca = min(max(*(const int *)cmask, 0), ncol);  // never past the allocation
+    if ((int)blockIdx.x * ncb >= nca) return;
+  }
   // chunk length, ring levels, wave floor, pass-1 chunks per step and prefetch distance: the small-grid set or the default
   constexpr int K = kSmall ? kCkKSmall : kCkK, R = kSmall ? kCkRingSmall : kCkRing, WAVES = sw_ck_waves(O);
   constexpr int P1C = kSmall ? kCkP1Small : kCkP1, AHEAD = kSmall ? kCkAheadSmall : 1;
@@ -342,7 +353,7 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
   using L = std::conditional_t<kDual, float, V>;  // what a lane loads of a layer's properties
   const int ncr = kDual ? 2 : ncb;  // rings in the block's LDS (kDual: ncb = 1, a ring per sky)
   const int nlev = nlay + 1, lanes = ngpt / NPL, nck = (nlay + K - 1) / K;
-  const int icol0 = blockIdx.x * ncb, nc = min(ncb, ncol - icol0);
+  const int icol0 = blockIdx.x * ncb, nc = min(ncb, nca - icol0);
   const int craw = (int)threadIdx.x / lanes;
   const bool on = craw < nc;
   const int c = on ? craw : nc - 1;
@@ -700,10 +711,10 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
     // apart (the broadband bits do not move) and the band walk forms dif + dir itself (band_flush)
     const BandOut *pb = kBand ? &bo : nullptr;
     if (kCkFlushLanes && (ngpt & 3) == 0 && 3 * ncr * n * 4 <= (int)blockDim.x)
-      ring_flush_sw_lanes<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, ncol,
+      ring_flush_sw_lanes<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, nca,
                                                  flux_up, flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir);
     else
-      ring_flush_sw<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, ncol, flux_up,
+      ring_flush_sw<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, nca, flux_up,
                                            flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir);
   };
   // the ring holds M = R / K chunks; the block flushes it when it is full (a barrier, the ordered sums, a barrier).
@@ -846,6 +857,15 @@ using SwCkInstances = SolverInstances<
     // clear sky: with a gas g; the small-grid instance; the large-grid NN instance with its planes and without
     kSwCkHasG, kSwCkSmall | kSwCkPlanesSmall, kSwCkPlanesNN, 0u>;
 
+// ... and with the active-column count read from a device word (rrtmgpnn_solver_request_active_columns), a family of
+// its own (kSolverSwCkActive): what a step on compacted daylit columns selects and no more -- the small-grid clear-sky
+// instance, the large-grid NN instance with its planes and without, and the fused increment ({band pair} x {the all-sky
+// plane}); no gas g
+using SwCkActiveInstances = SolverInstances<
+    kSwCkActive | kSwCkSmall | kSwCkPlanesSmall, kSwCkActive | kSwCkPlanesNN, kSwCkActive,
+    kSwCkActive | kSwCkInc | kSwCkBandPair | kSwCkPlanesInc, kSwCkActive | kSwCkInc | kSwCkBandPair,
+    kSwCkActive | kSwCkInc | kSwCkPlanesInc, kSwCkActive | kSwCkInc>;
+
 // The instance a call runs (its options value), or the refusal.  planes: the workspace with the instance family's
 // planes was allocated (launch_sw_2stream's fallback runs the plane-free twins: the same bits); small: sw_ck_small()
 static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes, bool small, uint32_t *options)
@@ -856,7 +876,17 @@ static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes,
   bool pair = bands != nullptr;
   for (int i = 0; bands && i < bands->nbnd; i++) pair = pair && ((bands->lims[2 * i] - 1) % 2 == 0);
   uint32_t o = (p.g ? kSwCkHasG : 0u) | (bands ? kSwCkInc : 0u) | (ex.mask_bits ? kSwCkMask : 0u);
-  if (ex.clr_up) {
+  if (ex.nact) {
+    // the daylit columns of a compacted block: the instance the same call would run without the count (chosen from the
+    // launch-time ncol: the host never sees the count), from the family's own list
+    if (ex.clr_up || ex.aer_tau || ex.mask_bits || bb || gpt)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count with clear-sky twins, aerosols, a cloud "
+                                            "mask, by-band or g-point outputs");
+    if (p.g)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count with a gas g array (g == NULL: the NN path)");
+    o |= kSwCkActive | (bands ? (pair ? kSwCkBandPair : 0u) | (planes ? kSwCkPlanesInc : 0u)
+                              : (small ? kSwCkSmall | kSwCkPlanesSmall : (planes ? kSwCkPlanesNN : 0u)));
+  } else if (ex.clr_up) {
     // clear-sky beside all-sky fluxes (rrtmgpnn_sw_solver_2stream_clr_all): the dual instances, one column per block,
     // one g-point per lane, two rings; {gas g} x {mask} x {aerosol}, with the planes of kCkTnDual / kCkEmkDual or, when
     // that workspace did not fit, without
@@ -919,7 +949,7 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
   uint32_t options = 0;
   if (int rc = select_sw_ck(ex, p, planes, sw_ck_small(ctx, ngpt, ncol, p.g != nullptr, p.bands != nullptr, gpt), &options))
     return rc;
-  return launch_listed(ctx, kSolverSwCk, SwCkInstances{}, options, [&](auto oc) -> int {
+  auto go = [&](auto oc) -> int {
     constexpr uint32_t O = decltype(oc)::value;
     constexpr bool kDual = (O & kSwCkDual) != 0, kInc = (O & kSwCkInc) != 0;
     constexpr int ring = (O & kSwCkSmall) ? kCkRingSmall : kCkRing;
@@ -940,11 +970,14 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
                        p.inc_flux_dif, p.tau, p.ssa, p.g, p.mu0, p.alb_dir, p.alb_dif, b, kInc ? p.tau_bnd : nullptr,
                        kInc ? p.ssa_bnd : nullptr, kInc ? p.g_bnd : nullptr, (float *)ws, p.flux_up, p.flux_dn,
-                       p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo, ex.mask_bits, ex.aer_tau, ex.aer_ssa,
-                       ex.aer_g, ex.clr_up, ex.clr_dn, ex.clr_dir);
+                       p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo,
+                       (O & kSwCkActive) ? (const uint32_t *)ex.nact : ex.mask_bits,  // the count word in the mask's place
+                       ex.aer_tau, ex.aer_ssa, ex.aer_g, ex.clr_up, ex.clr_dn, ex.clr_dir);
     RRTMGPNN_LAUNCH_CHECK(kDual ? "sw_2stream_ck_kernel (clear + all sky)" : "sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
-  });
+  };
+  if (ex.nact) return launch_listed(ctx, kSolverSwCkActive, SwCkActiveInstances{}, options, go);
+  return launch_listed(ctx, kSolverSwCk, SwCkInstances{}, options, go);
 }
 
 }  // namespace rrtmgpnn

@@ -28,6 +28,8 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_solver_request_byband_mcica
   public :: c_rrtmgpnn_solver_request_jacobian
   public :: c_rrtmgpnn_solver_request_aerosol
+  public :: c_rrtmgpnn_daylit_plan, c_rrtmgpnn_gather_columns, c_rrtmgpnn_scatter_columns, &
+            c_rrtmgpnn_gas_optics_sw_nn_active, c_rrtmgpnn_solver_request_active_columns
   public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
             c_rrtmgpnn_draw_samples
   public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
@@ -419,6 +421,45 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, tau_aer, ssa_aer, g_aer
       integer(c_int), value :: nbnd, nlay, ncol
+    end function
+    ! Daylit columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): a block compacted to the columns where the sun is up.
+    ! v, idx, slot, nday, nact and the arrays the tables name are device pointers; nday / nact is one int on the device
+    integer(c_int) function c_rrtmgpnn_daylit_plan(ctx, ncol, v, kind, bound, idx, slot, nday) &
+        bind(C, name="rrtmgpnn_daylit_plan")
+      import :: c_int, c_ptr, c_float
+      type(c_ptr), value :: ctx, v, idx, slot, nday
+      integer(c_int), value :: ncol, kind
+      real(c_float), value :: bound
+    end function
+    integer(c_int) function c_rrtmgpnn_gather_columns(ctx, ncol, narrays, src, dst, row_floats, idx, nday) &
+        bind(C, name="rrtmgpnn_gather_columns")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, idx, nday
+      integer(c_int), value :: ncol, narrays
+      type(c_ptr), dimension(*), intent(in) :: src, dst
+      integer(c_int), dimension(*), intent(in) :: row_floats
+    end function
+    integer(c_int) function c_rrtmgpnn_scatter_columns(ctx, ncol, narrays, dense, out, row_floats, slot) &
+        bind(C, name="rrtmgpnn_scatter_columns")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, slot
+      integer(c_int), value :: ncol, narrays
+      type(c_ptr), dimension(*), intent(in) :: dense, out
+      integer(c_int), dimension(*), intent(in) :: row_floats
+    end function
+    integer(c_int) function c_rrtmgpnn_gas_optics_sw_nn_active(ctx, ncol, nlay, ngpt, ninputs, play, tlay, plev, &
+        vmr_h2o, gas_conc, gas_ndims, nets, tau, ssa, g, nact) bind(C, name="rrtmgpnn_gas_optics_sw_nn_active")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, play, tlay, plev, vmr_h2o, tau, ssa, g, nact
+      integer(c_int), value :: ncol, nlay, ngpt, ninputs
+      type(c_ptr), dimension(*), intent(in) :: gas_conc, nets
+      integer(c_int), dimension(*), intent(in) :: gas_ndims
+    end function
+    integer(c_int) function c_rrtmgpnn_solver_request_active_columns(ctx, ncol, nact) &
+        bind(C, name="rrtmgpnn_solver_request_active_columns")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, nact
+      integer(c_int), value :: ncol
     end function
     ! the two requests above as a pair: by-band outputs of the next solver call under its McICA mask
     integer(c_int) function c_rrtmgpnn_solver_request_byband_mcica(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, &

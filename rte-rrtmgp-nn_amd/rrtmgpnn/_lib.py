@@ -157,6 +157,12 @@ SIGNATURES = {
                                          + [c_int, P(c_int)] + [c_vp] * 9),
     "rrtmgpnn_sw_solver_2stream_rfmip_clr_all": (c_int, [c_vp, c_int, c_int, c_int, c_int] + [c_vp] * 7
                                                  + [c_int, P(c_int)] + [c_vp] * 12),
+    "rrtmgpnn_daylit_plan": (c_int, [c_vp, c_int, c_vp, c_int, c_float, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_gather_columns": (c_int, [c_vp, c_int, c_int, P(c_vp), P(c_vp), P(c_int), c_vp, c_vp]),
+    "rrtmgpnn_scatter_columns": (c_int, [c_vp, c_int, c_int, P(c_vp), P(c_vp), P(c_int), c_vp]),
+    "rrtmgpnn_gas_optics_sw_nn_active": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, P(c_vp),
+                                                 P(c_int), P(c_vp), c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_solver_request_active_columns": (c_int, [c_vp, c_int, c_vp]),
     "rrtmgpnn_file_open": (c_int, [c_char_p, P(c_vp)]),
     "rrtmgpnn_file_close": (c_int, [c_vp]),
     "rrtmgpnn_file_nvars": (c_int, [c_vp, P(c_int)]),

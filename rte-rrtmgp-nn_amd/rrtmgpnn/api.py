@@ -1046,9 +1046,13 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
     return ""
 
 
-def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, fluxes, inc_flux_dif=None):
+def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, fluxes, inc_flux_dif=None, active=None):
     """rte/mo_rte_sw.F90:48-266 (fork: albedos per g-point (ncol, ngpt)).  1scl: the direct beam (sw_solver_noscat);
-    2str: sw_solver_2stream."""
+    2str: sw_solver_2stream.
+    active: a rrtmgpnn.daylit plan, or its count word (an int32 device tensor of one element): the arrays are dense
+    (daylit.gather) and only their first nday columns are solved (rrtmgpnn_solver_request_active_columns, armed right
+    ahead of the solver call); flux rows at or past the count are left as they are.  Two-stream, broadband fluxes,
+    atmos.g None."""
     if not fluxes.are_desired():
         return "rte_sw: no space allocated for fluxes"
     if not isinstance(atmos, (OpticalProps1scl, OpticalProps2str)):
@@ -1071,6 +1075,8 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
         e = _byband_checks(fluxes, ncol, nlay + 1, atmos.get_nband(), have_beam=True)
         if e:
             return e
+    if active is not None and (isinstance(atmos, OpticalProps1scl) or fluxes.are_desired_gpt()):
+        return "rte_sw: active columns go with the two-stream solver and broadband fluxes"
     if isinstance(atmos, OpticalProps1scl):
         # direct beam only (:213-222): apply_BC_factor + sw_solver_noscat; as in the reference only the direct flux
         # is written (flux_up / flux_dn / flux_net are left as they are)
@@ -1111,6 +1117,9 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
     else:
         if bb:
             _byband_arm(ctx, atmos, fluxes.bnd_flux_up, fluxes.bnd_flux_dn, fluxes.bnd_flux_dn_dir)
+        if active is not None:
+            word = getattr(active, "nday", active)
+            check(_lib.lib().rrtmgpnn_solver_request_active_columns(ctx.h, ncol, _p(word)), "solver_request_active_columns")
         check(_lib.lib().rrtmgpnn_sw_solver_2stream(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux),
                                                     _p(inc_flux_dif), _p(atmos.tau), _p(atmos.ssa), _p(atmos.g),
                                                     _p(mu0), _p(sfc_alb_dir_gpt), _p(sfc_alb_dif_gpt), _p(up),

@@ -88,6 +88,17 @@ rrtmgpnn_lw_solver_1rescl_planck_clr_all, which gives both flux sets, and no lw_
 rrtmgpnn_context_set_lw_scat_clr_all decides one dual launch or two.  aerosols= is then accepted beside lw_scattering:
 lw_aerosol is armed right before the solver (clear sky = gases + aerosols), and set_aerosols works between replays.  Not
 without lw_scattering or clear-sky outputs, nor with fused=False, byband, jacobian or mcica["byband"].
+
+daylit=True (fused, clear sky or overcast clouds=): the SW chain runs on the block's daylit columns only, as a host model
+does, in place of the RFMIP driver's mu0 = 1 solve of the night columns (rrtmgp_rfmip_sw.F90:433) -- and sw_up, sw_dn
+and sw_dir of the night columns are 0, the driver's zeroing (:456-463) applied to flux_dir as well.  The chain becomes
+rrtmgpnn_daylit_plan on sza; one rrtmgpnn_gather_columns of play, tlay, plev, the SW gases, sza, tsi, sfc_alb (and the
+cloud fields) into step-owned dense twins of full extent; rrtmgpnn_gas_optics_sw_nn_active; cloud optics and delta
+scaling on the dense cloud fields at full extent (rows past the count are stale and never read);
+rrtmgpnn_solver_request_active_columns and the _rfmip solver; rrtmgpnn_scatter_columns into sw_up / sw_dn / sw_dir.  The
+count of daylit columns is a device word that the network and the solver read, so a captured step follows the sun:
+set_sza() between replays, no recapture.  The LW chain is untouched.  Not with mcica, aerosols, clrsky, byband, sw_dual,
+fused=False, sw=False, capture_chains or run_blocks.  Off (the default), nothing of the step changes.
 """
 
 from types import SimpleNamespace
@@ -103,7 +114,8 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 # calls of the SW chain (issued on the second stream when overlapping)
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
             "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask",
-            "mcica_randoms_sw", "sw_mask_byband", "sw_aerosol", "increment_aer_sw"}
+            "mcica_randoms_sw", "sw_mask_byband", "sw_aerosol", "increment_aer_sw",
+            "daylit_plan", "daylit_gather", "sw_active", "daylit_scatter"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
@@ -114,9 +126,11 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
 # beside clouds, host-only)
 # (lw_solver_clr: an lw_scattering step's clear launch, ahead of the mask request its all-sky launch consumes)
 # (lw_upper_bc: an upper_bc=True step's boundary flux, at the head of the LW chain)
+# (daylit_plan / daylit_gather: a daylit=True step's compaction at the head of the SW chain; sw_active: its active-column
+# request, host-only, right before the solver; daylit_scatter: the fluxes back to their columns, behind it)
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "lw_upper_bc", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
-               "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "nn_inputs_sw", "cloud_optics_sw",
-               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_solver"]
+               "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "daylit_plan", "daylit_gather", "nn_inputs_sw", "cloud_optics_sw",
+               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_active", "sw_solver", "daylit_scatter"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -187,8 +201,18 @@ class ClearSkyStep:
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
                  clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False,
-                 lw_dual=False, upper_bc=False, spectral=None):
+                 lw_dual=False, upper_bc=False, spectral=None, daylit=False):
         lw_models, sw_models = self._resolve_spectral(spectral, lw_models, sw_models)
+        self.daylit = bool(daylit)
+        if self.daylit:
+            # (ahead of the other option checks, so that the refusal names this option)
+            bad = [w for w, on in (("mcica", mcica is not None), ("aerosols", aerosols is not None),
+                                   ("clrsky", bool(clrsky)), ("byband", bool(byband)), ("sw_dual", bool(sw_dual)),
+                                   ("fused=False", not fused), ("sw=False", not sw)) if on]
+            if bad:
+                raise ValueError("daylit=True with %s is not supported: the daylit-column SW chain is the fused clear-sky "
+                                 "or overcast one, broadband only (the active-count network and solver instances)"
+                                 % ", ".join(bad))
         self.lw_dual = bool(lw_dual)
         self.upper_bc = bool(upper_bc)
         if self.lw_dual:
@@ -381,6 +405,36 @@ class ClearSkyStep:
             if sw:
                 self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (
                     f(ncol, nlay + 1, self.kd_sw["nband"]) for _ in range(3))
+        if self.daylit:
+            self._allocate_daylit()
+
+    def _allocate_daylit(self):
+        """A daylit=True step's plan (idx, slot, the count word) and the dense twins of what its SW chain reads and
+        writes, all of full extent so that an all-day replay fits.  The twins start as copies: rows at or past the
+        count, which the full-extent cloud kernels still walk, always hold some column's values."""
+        ncol, dev = self.ncol, self.dev
+        self.day_idx, self.day_slot = (torch.zeros(ncol, dtype=torch.int32, device=dev) for _ in range(2))
+        self.nday = torch.zeros(1, dtype=torch.int32, device=dev)
+        names = ["play", "tlay", "plev"]
+        # the SW network's gases (inputs 3 on; every gas of the step is an (ncol, nlay) array) and get_col_dry's h2o
+        self._day_gases = [n for n in dict.fromkeys(["h2o"] + list(self.sw_names[2:])) if n in self.gases]
+        names += ["sza", "tsi", "sfc_alb"] + (["lwp", "iwp", "rel", "rei"] if self.allsky else [])
+        self._day_pairs = [(getattr(self, n), n) for n in names] + [(self.gases[n], "gas_" + n) for n in self._day_gases]
+        for t, n in self._day_pairs:
+            setattr(self, "d_" + n, t.clone())
+        self.d_sw_up, self.d_sw_dn, self.d_sw_dir = (torch.zeros_like(self.sw_up) for _ in range(3))
+        if len(self._day_pairs) > 16:
+            raise ValueError("daylit=True: more than 16 arrays to gather")
+
+    def set_sza(self, sza):
+        """Overwrite the step's solar zenith angles (degrees, (ncol)) between steps or graph replays; complete on
+        return.  A daylit=True step plans its daylit columns from them on the device every step: no recapture."""
+        torch.cuda.synchronize(self.dev)  # nothing in flight reads the angles
+        src = sza if isinstance(sza, torch.Tensor) else _t(sza, self.dev)
+        if tuple(src.shape) != tuple(self.sza.shape):
+            raise ValueError("set_sza: sza has shape %s, expected %s" % (tuple(src.shape), tuple(self.sza.shape)))
+        self.sza.copy_(src)
+        torch.cuda.synchronize(self.dev)
 
     def _upper_bc_check(self, prob):
         """compute_bc's pressure check (extensions/mo_compute_bc.F90:110-114) on a host problem's plev(:, top_lay)."""
@@ -720,6 +774,8 @@ class ClearSkyStep:
         h2o = (self.gases["h2o"].data_ptr(),)
         delta_scale = [("delta_scale_sw", L.rrtmgpnn_delta_scale_2str,
                         (c, ncol * nlay * self.nb_sw) + ch.cld + (None,))] if self.allsky else []
+        if self.daylit:
+            return self._sw_chain_daylit()
         if self.fused:
             # the boundary conditions and (all sky) clouds%increment(atmos) fused into the solver
             # (rrtmgpnn_sw_solver_2stream_rfmip; same bits as sw_boundary_rfmip + sw_solver_2stream[_inc])
@@ -775,6 +831,44 @@ class ClearSkyStep:
             *self._clouds_in(ch),
             *self._request(ch),
             solver("sw_solver", "sw_up", "sw_dn", "sw_dir"),
+        ]
+
+    def _sw_chain_daylit(self):
+        """A daylit=True step's SW chain (module docstring): the fused chain on dense twins of its inputs, between the
+        plan + gather at its head and the scatter at its end.  usecol = sza < 90 - 2 spacing(90)
+        (rrtmgp_rfmip_sw.F90:285-287), the bound the solver's own mu0 merge uses."""
+        L, c, ncol, nlay, p, ch = self.L, self.ctx.h, self.ncol, self.nlay, self._p, self._chain_sw
+        bound = float(np.float32(90.0) - np.float32(2.0) * data.spacing(90.0))
+        pairs = self._day_pairs
+        rows = [int(t[0].numel()) if t.dim() > 1 else 1 for t, _ in pairs]
+        # (ctypes arrays the captured calls point at: kept on the step)
+        self._day_src = ptr_array([t.data_ptr() for t, _ in pairs])
+        self._day_dst = ptr_array([getattr(self, "d_" + n).data_ptr() for _, n in pairs])
+        self._day_rows = int_array(rows)
+        self._day_dense = ptr_array(list(p("d_sw_up", "d_sw_dn", "d_sw_dir")))
+        self._day_out = ptr_array(list(p("sw_up", "sw_dn", "sw_dir")))
+        self._day_out_rows = int_array([nlay + 1] * 3)
+        dense_gas = {n: getattr(self, "d_gas_" + n) for n in self._day_gases}
+        g = [dense_gas.get(n) if k >= 2 else None for k, n in enumerate(self.sw_names)]
+        self._g_sw_day = ptr_array([t.data_ptr() if t is not None else None for t in g])
+        cld_in = p("d_lwp", "d_iwp", "d_rel", "d_rei")
+        band_inc = (self.nb_sw, self._lims_sw) + ch.cld if self.allsky else (0, None, None, None, None)
+        return [
+            ("daylit_plan", L.rrtmgpnn_daylit_plan, (c, ncol) + p("sza") + (0, bound) + p("day_idx", "day_slot", "nday")),
+            ("daylit_gather", L.rrtmgpnn_gather_columns,
+             (c, ncol, len(pairs), self._day_src, self._day_dst, self._day_rows) + p("day_idx", "nday")),
+            ("predict_nn_sw", L.rrtmgpnn_gas_optics_sw_nn_active,
+             (c, ncol, nlay, self.ng_sw, self.nx_sw) + p("d_play", "d_tlay", "d_plev", "d_gas_h2o")
+             + (self._g_sw_day, self._nd_sw, self._nets_sw) + ch.props + p("nday")),
+            *([("cloud_optics_sw", L.rrtmgpnn_cloud_optics_compute, (c, self.cloud_sw, ncol, nlay) + cld_in + ch.cld),
+               ("delta_scale_sw", L.rrtmgpnn_delta_scale_2str, (c, ncol * nlay * self.nb_sw) + ch.cld + (None,))]
+              if self.allsky else []),
+            ("sw_active", L.rrtmgpnn_solver_request_active_columns, (c, ncol) + p("nday")),
+            ("sw_solver", L.rrtmgpnn_sw_solver_2stream_rfmip,
+             (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("solar_source", "d_tsi", "d_sfc_alb", "d_sza")
+             + p("tau_sw", "ssa_sw") + (None,) + band_inc + p("toa", "alb", "mu0", "d_sw_up", "d_sw_dn", "d_sw_dir")),
+            ("daylit_scatter", L.rrtmgpnn_scatter_columns,
+             (c, ncol, 3, self._day_dense, self._day_out, self._day_out_rows) + p("day_slot")),
         ]
 
     def _finish(self, overlap, lw_after=None, sw_after=None, lw_net_cus=None, sw_net_cus=0):
@@ -1029,6 +1123,9 @@ class ClearSkyStep:
         between them."""
         if not (self.overlap and self.sw):
             raise ValueError("capture_chains: a step with its LW and SW chains on two streams")
+        if self.daylit:
+            raise ValueError("daylit=True with capture_chains / run_blocks is not supported: a stream of blocks re-runs "
+                             "one block, whose daylit columns do not change")
         self.step()  # warm-up outside capture
         torch.cuda.synchronize(self.dev)
         graphs = []
@@ -1049,6 +1146,9 @@ class ClearSkyStep:
         block b's join.  (A stream of distinct blocks needs each block's inputs and outputs in storage of its own;
         this one re-runs the step's block, whose results are the same every time.)  Ordered after the caller's
         current stream's work and before its later work."""
+        if self.daylit:
+            raise ValueError("daylit=True with capture_chains / run_blocks is not supported: a stream of blocks re-runs "
+                             "one block, whose daylit columns do not change")
         g_sw, g_lw = self.chain_graphs
         cur = torch.cuda.current_stream(self.dev)
         for s in (self.ctx2.stream, self.ctx.stream):
