@@ -15,6 +15,10 @@ message.  Nothing here is random.
 build_lw_scat() is the LW problem of the scattering and fused solvers (an edge (ssa, g) pair beside the edge tau, the
 same edge through band arrays, an aerosol and a packed mask); ref_* are the oracle references both test files share,
 computed once; classes() names the operand-domain classes of one run.
+
+build_sw_fused() is the SW problem of the fused entries (the band increment with a cloud mask and a 2str aerosol, clear
+beside all sky, by band, active columns): build_sw()'s cases with the edge as the cloud's band operand; ref_sw_fused() is
+its shared reference, classes_sw() its classes and tile() repeats a problem's columns for the large-grid instances.
 """
 import collections
 import functools
@@ -541,3 +545,133 @@ def ref_noscat_fused(orc, top_at_1, nmus, kind):
             tau = p["tau"]
         return orc.lw_solver(tau, lay, lev, p["emis"], sfc, top_at_1, nmus, inc_flux=p["inc"]) + (tau,)
     return _cached(("noscat_fused", top_at_1, nmus, kind), make)
+
+
+# ---- the fused SW solvers: band increment, cloud mask, aerosol, clear beside all sky, by band -------------------------
+SW_AER_TAUS = np.array([0, 1e-30, 0.1], F)
+SW_AER_SSAS = np.array([0, 0.9, 1], F)
+SW_AER_GS = np.array([0, 0.6], F)
+
+FusedSwCase = collections.namedtuple("FusedSwCase", SwCase._fields + ("gas_tau", "gas_ssa", "gas_g", "bit"))
+
+
+@functools.lru_cache(maxsize=None)
+def build_sw_fused():
+    """The SW problem of the fused entries, on build_sw()'s design and with its 1344 cases (edge (tau, ssa, g), mu0,
+    albedos, incident fluxes, lit g-point and edge layer), on the shipped SW bands (14 x 16, the band-pair layout).
+
+    The case's edge (tau, ssa, g) is the CLOUD's: tau_bnd / ssa_bnd / g_bnd hold it at (edge layer, lit g-point's band)
+    and cycle over INC_TAUS / INC_SSAS / INC_GS by column, layer and band elsewhere.  The gas tau and ssa at (edge layer,
+    lit g-point) cycle over {0, background, the case's edge value}, each on its own (all nine pairings occur); the gas
+    tau falls back to the background where tau_gas + tau_edge overflows to inf in float32 (2e38 + 2e38: the oracle's
+    own properties are inf there).  The gas g holds the case's g where the gas ssa is the edge ssa and 0 elsewhere.
+    The 2str aerosol cycles over SW_AER_TAUS / SW_AER_SSAS / SW_AER_GS by column, layer and band.  mask: alternating by
+    layer + g-point, except the lit bit at the edge layer, which is set in half the columns by a mix of the three case
+    indices (the column's parity alone would follow the ssa index: there are 12 of them)."""
+    from rrtmgpnn import data
+    b = build_sw()
+    lims = np.asarray(data.load_kdist("sw")["band_lims_gpt"], np.int32).reshape(-1, 2)
+    ncol, nlay, ngpt, nb = b["ncol"], b["nlay"], b["ngpt"], len(lims)
+    assert nb == INC_NBND and np.array_equal(lims, b["band_lims_gpt"])
+    band_of = np.zeros(ngpt, np.int64)
+    for ib, (lo, hi) in enumerate(lims):
+        band_of[lo - 1:hi] = ib
+    n_s, n_t = len(SSAS), len(TAUS)
+    tau = np.full((ncol, nlay, ngpt), BG_TAU, F)
+    ssa = np.full((ncol, nlay, ngpt), BG_SSA, F)
+    g = np.full((ncol, nlay, ngpt), BG_G, F)
+    ci, li, bi = np.meshgrid(np.arange(ncol), np.arange(nlay), np.arange(nb), indexing="ij")
+    tau_bnd = INC_TAUS[(ci + li + bi) % 4]
+    ssa_bnd = INC_SSAS[(ci // 4 + li + 2 * bi) % 4]
+    g_bnd = INC_GS[(ci + li // 2 + bi) % 3]
+    tau_aer = SW_AER_TAUS[(ci + 2 * li + bi) % 3]
+    ssa_aer = SW_AER_SSAS[(ci // 3 + li + bi) % 3]
+    g_aer = SW_AER_GS[(ci // 2 + li + bi) % 2]
+    mask = ((np.arange(nlay)[None, :, None] + np.arange(ngpt)[None, None, :]) % 2 == 0) & np.ones((ncol, 1, 1), bool)
+    cases = []
+    for c, x in enumerate(b["cases"]):
+        i_s, i_t, i_m = c % n_s, (c // n_s) % n_t, c // (n_s * n_t)
+        k_t, k_w = (i_s + i_m) % 3, (i_s // 3 + i_t + 2 * i_m) % 3
+        gas_tau = (F(0), BG_TAU, x.tau)[k_t]
+        with np.errstate(over="ignore"):
+            if np.isinf(gas_tau + x.tau):
+                gas_tau = BG_TAU
+        gas_ssa = (F(0), BG_SSA, x.ssa)[k_w]
+        gas_g = x.g if k_w == 2 else F(0)
+        case = FusedSwCase(*x, gas_tau=gas_tau, gas_ssa=gas_ssa, gas_g=gas_g, bit=(i_s // 2 + i_t // 2 + i_m) % 2 == 1)
+        cases.append(case)
+        ib = band_of[x.lit]
+        tau[c, x.layer, x.lit], ssa[c, x.layer, x.lit], g[c, x.layer, x.lit] = gas_tau, gas_ssa, gas_g
+        tau_bnd[c, x.layer, ib], ssa_bnd[c, x.layer, ib], g_bnd[c, x.layer, ib] = x.tau, x.ssa, x.g
+        mask[c, x.layer, x.lit] = case.bit
+    edge = {k: np.array([getattr(x, k) for x in cases], F) for k in ("tau", "ssa", "g", "mu0", "gas_tau", "gas_ssa", "gas_g")}
+    edge["bit"] = np.array([x.bit for x in cases])
+    p = {k: b[k] for k in ("ncol", "nlay", "ngpt", "mu0", "inc", "inc_dif", "alb_dir", "alb_dif", "lit", "layer")}
+    p.update({"nb": nb, "lims": lims, "band_of": band_of, "tau": tau, "ssa": ssa, "g": g, "mask": mask, "cases": cases,
+              "edge": edge, "describe": _describe(cases)})
+    for k, a in (("tau_bnd", tau_bnd), ("ssa_bnd", ssa_bnd), ("g_bnd", g_bnd), ("tau_aer", tau_aer), ("ssa_aer", ssa_aer),
+                 ("g_aer", g_aer)):
+        p[k] = np.ascontiguousarray(a, F)
+    return _freeze(p)
+
+
+def sw_fused_props(orc, p, masked=False, aer=False, with_g=True, cloud=None, mask=None):
+    """((tau, ssa, g) all sky, (tau, ssa, g) clear) of the composed oracle of the fused SW entries: increment_bybnd of
+    the gases by the 2str aerosol first (aer: both sets), then by the cloud (the all-sky set) -- masked: each band array
+    through mcica_ref.draw, at identity limits, as fused_props.  with_g False: the gas g is zero (the entries' g = NULL).
+    cloud / mask: others than the problem's."""
+    import mcica_ref as M
+    clear = (p["tau"], p["ssa"], p["g"] if with_g else np.zeros_like(p["g"]))
+    if aer:
+        clear = orc.increment_bybnd(p["lims"], clear, [p["tau_aer"], p["ssa_aer"], p["g_aer"]])
+    cloud = [p["tau_bnd"], p["ssa_bnd"], p["g_bnd"]] if cloud is None else cloud
+    if not masked:
+        return orc.increment_bybnd(p["lims"], clear, cloud), clear
+    mask = p["mask"] if mask is None else mask
+    return orc.increment_bybnd(_ident(p["ngpt"]), clear, [M.draw(mask, a, p["lims"]) for a in cloud]), clear
+
+
+def sw_fused_solve(orc, p, io, top_at_1, gpt=False):
+    return orc.sw_solver(*io, p["mu0"], p["inc"], p["alb_dir"], p["alb_dif"], top_at_1, inc_flux_dif=p["inc_dif"], gpt=gpt)
+
+
+def ref_sw_fused(orc, top_at_1, masked, aer, with_g, gpt=False):
+    """(all-sky fluxes, clear fluxes, all-sky (tau, ssa, g), clear (tau, ssa, g)) of the composed oracle on
+    build_sw_fused(); the flux tuples are (up, dn, dir), with gpt followed by the three g-point arrays."""
+    p = build_sw_fused()
+    io, clr = _cached(("sw_props", masked, aer, with_g), lambda: sw_fused_props(orc, p, masked, aer, with_g))
+    allsky = _cached(("sw_all", top_at_1, masked, aer, with_g, gpt), lambda: sw_fused_solve(orc, p, io, top_at_1, gpt))
+    clear = _cached(("sw_clr", top_at_1, aer, with_g, gpt), lambda: sw_fused_solve(orc, p, clr, top_at_1, gpt))
+    return allsky, clear, io, clr
+
+
+def classes_sw(p, tau_op, ssa_op):
+    """p with the operand-domain classes of one SW run, from the INCREMENTED operands at (edge layer, lit g-point):
+    in_domain is tau <= 1e4 and (ssa == 0 or ssa >= 2^-99), the domain the shortened divisions state; out_of_domain is
+    the rest."""
+    tau_op, ssa_op = np.asarray(tau_op, F), np.asarray(ssa_op, F)
+    return dict(p, in_domain=(tau_op <= F(1e4)) & ((ssa_op == 0) | (ssa_op >= F(2.0 ** -99))))
+
+
+def classes_sw_of(p, io):
+    return classes_sw(p, edge_values(p, io[0]), edge_values(p, io[1]))
+
+
+def with_background_cloud(p):
+    """Copies of the cloud band arrays with the background triple at every (edge layer, lit band)."""
+    c, ib = np.arange(p["ncol"]), p["band_of"][p["lit"]]
+    out = [p[k].copy() for k in ("tau_bnd", "ssa_bnd", "g_bnd")]
+    for a, v in zip(out, (BG_TAU, BG_SSA, BG_G)):
+        a[c, p["layer"], ib] = v
+    return out
+
+
+def tile(p, n):
+    """The problem with its columns repeated n times (column c of tile k is column k * ncol + c)."""
+    ncol = p["ncol"]
+    q = {k: (np.concatenate([v] * n, axis=0) if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == ncol
+             and k not in ("lims", "band_of") else v) for k, v in p.items()}
+    q["ncol"], q["cases"], q["tiles"] = n * ncol, list(p["cases"]) * n, n
+    q["edge"] = {k: np.concatenate([v] * n) for k, v in p["edge"].items()}
+    q["describe"] = _describe(q["cases"])
+    return _freeze(q)

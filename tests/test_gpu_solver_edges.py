@@ -33,6 +33,28 @@ clear radiance, the incremented tau for the fused entries).  What an MI355X gave
 The rescaled layer divides plainly and the two-stream layer has no shortened division: neither has a bound on tau.  The
 two classes that differ are the stated bound of the no-scattering step (include/rrtmgpnn.h) and strict xfails below; no
 kernel was changed.
+
+The fused SW solvers (solver_edges.build_sw_fused: build_sw()'s 1344 cases with the edge (tau, ssa, g) as the CLOUD's band
+operand, gas operands of 0 / the background / the edge itself, a 2str aerosol and a mask whose lit bit is set in half the
+columns; classes by the INCREMENTED operands at the edge layer's lit g-point: in_domain tau <= 1e4 and ssa == 0 or
+ssa >= 2^-99, out_of_domain the rest).  Every call asserts the instance rrtmgpnn_context_get_solver_path reports.  What
+an MI355X gave, columns differing per class (in_domain / out_of_domain), both orientations, gas g and g = NULL alike:
+  sw_solver_2stream_inc, no request / cloud mask / aerosol / aerosol + mask    0 of 1006-1148 / 0 of 196-338; inputs unchanged
+  sw_solver_2stream_clr_all, mode 1 (dual) and mode 2, {mask} x {aerosol}      all-sky set as above; clear set 0 of
+    1238-1265 / 0 of 79-106
+  solver_request_byband on sw_solver_2stream (build_sw(), SW kernels 1, 2 and 3) and on sw_solver_2stream_inc,
+    solver_request_byband_mcica on sw_solver_2stream_inc: 0 / 0; the lit band is the broadband flux bit for bit, every
+    other band +-0, the broadband outputs those of the call without the request
+  the large grid (two tiles, 2688 columns): sw_solver_2stream with g = NULL (the NN instance and its planes),
+    sw_solver_2stream_inc plain and with aerosol + mask, mode 1 of _clr_all with aerosol + mask: 0 / 0 in every tile
+  solver_request_active_columns with counts 0, ncol - 1 and ncol on sw_solver_2stream (small and tiled) and
+    sw_solver_2stream_inc: 0 / 0 below the count, the prefill at and past it
+  the plane-free twins (RRTMGPNN_SW_NO_PLANES=1, a child process) on the large-grid list: 0 / 0, no plane bit in a path
+No class differs, so the SW entries state no operand bound and no kernel was changed.
+Three one-line breaks of csrc/kernels_sw_ck.hip, each built and run once against the SW files of the suite as it was and
+then against the tests below: sel()'s dual branch returning 1e-38f for a clear bit (before: all pass; below: 13 fail, the
+masked dual runs), load1's aerosol add dropping tau_aer < 1e-25 (before: all pass; below: 40 fail, every aerosol run),
+ck_inc's eps at 2 FLT_MIN (before: 3 of test_sw_2stream_inc_edges fail already; below: 135 fail).
 """
 import functools
 
@@ -590,3 +612,337 @@ def test_lw_noscat_fused_edges(dev, orc, top_at_1, entry, mode, domain):
     for kind, arrs, names in sets:
         up, dn, tau = E.ref_noscat_fused(orc, top_at_1, 1, kind)
         _compare(E.classes(p, E.edge_values(p, tau), None, E.gauss_ds(1)), domain, zip(arrs, (up, dn), names))
+
+
+# ---- the fused SW solvers (inputs: solver_edges.build_sw_fused) -----------------------------------------------------------
+import ctypes  # noqa: E402
+import os  # noqa: E402
+import subprocess  # noqa: E402
+import sys  # noqa: E402
+
+import byband_ref as BR  # noqa: E402
+from test_gpu_solver_dispatch import (CK_AER, CK_BAND, CK_DUAL, CK_EMK, CK_G, CK_INC, CK_MASK, CK_PAIR, CK_SMALL,  # noqa: E402
+                                      CK_TN, PL_DUAL, PL_INC, PL_NN, PL_SMALL, SW_1, SW_BAND, SW_CK, SW_G, SW_X2)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SW_CK_ACTIVE, CK_ACTIVE = 7, 2048  # rrtmgpnn_context_get_solver_path: family 7, family 2's bits and 2048
+WITH_G = pytest.mark.parametrize("with_g", [True, False], ids=["g", "nog"])
+SW_DOMAIN = pytest.mark.parametrize("domain", DOMAINS)
+REQUESTS = pytest.mark.parametrize("masked,aer", [(False, False), (True, False), (False, True), (True, True)],
+                                   ids=["plain", "mask", "aer", "aer-mask"])
+SW_IN = ("inc", "inc_dif", "tau", "ssa", "g", "mu0", "alb_dir", "alb_dif")
+SW_BANDS = ("tau_bnd", "ssa_bnd", "g_bnd")
+SW_AER = ("tau_aer", "ssa_aer", "g_aer")
+FLUX = ("up", "dn", "dir")
+
+
+def _solver_path(ctx):
+    from rrtmgpnn import _lib
+    out = (ctypes.c_int * 4)()
+    _lib.check(_lib.lib().rrtmgpnn_context_get_solver_path(ctx, out), "context_get_solver_path")
+    return list(out)
+
+
+def expected_sw_path(entry, with_g, masked=False, aer=False, mode=None, byband=False, active=False, large=False,
+                     planes=True, kernel=3):
+    """[family, options, launches] of one call on the shipped bands (the band-pair layout).  planes False: under
+    RRTMGPNN_SW_NO_PLANES=1, where only the small-grid instance keeps its planes."""
+    pl = (lambda bits: bits) if planes else (lambda bits: 0)
+    g = CK_G if with_g else 0
+    clear = g if with_g else (pl(PL_NN) if large else CK_SMALL | PL_SMALL)  # rrtmgpnn_sw_solver_2stream on the gases
+    inc = CK_INC | CK_PAIR | g
+    if active:
+        return [SW_CK_ACTIVE, CK_ACTIVE | (inc | pl(PL_INC) if entry == "inc" else clear), 1]
+    if entry == "clr_all":
+        if mode == 1:
+            return [SW_CK, CK_DUAL | CK_INC | pl(PL_DUAL) | g | (CK_MASK if masked else 0) | (CK_AER if aer else 0), 1]
+        return [SW_CK, inc | pl(PL_INC) if aer else clear, 2]  # the all-sky launch, then the clear one
+    if entry == "inc":
+        return [SW_CK, inc | (CK_MASK if masked else 0) | (CK_AER if aer else 0) | (CK_BAND if byband else pl(PL_INC)), 1]
+    if kernel in (1, 2):
+        return [SW_1 if kernel == 1 else SW_X2, (SW_G if with_g else 0) | (SW_BAND if byband else 0), 1]
+    if byband:
+        return [SW_CK, CK_BAND | (CK_G if with_g else CK_SMALL | PL_SMALL if not large else 0), 1]
+    return [SW_CK, clear, 1]
+
+
+def run_swf(dev, p, name, top_at_1, entry, with_g=True, masked=False, aer=False, mode=None, byband=None, nact=None,
+            cols=None):
+    """One call on the problem p (build_sw_fused(), a tiling of it, or build_sw() for entry "plain"): entry "plain"
+    rrtmgpnn_sw_solver_2stream on the gases, "inc" rrtmgpnn_sw_solver_2stream_inc, "clr_all" _clr_all under
+    mode `mode` of rrtmgpnn_context_set_sw_clr_all (set as the default and restored); masked / aer: the cloud-mask and 2str aerosol requests; byband "plain"
+    rrtmgpnn_solver_request_byband, "mcica" rrtmgpnn_solver_request_byband_mcica (with the mask); nact: the
+    active-column count.  -> {"out": [up, dn, dir(, up_clr, dn_clr, dir_clr)], "bnd": [...], "path": [...]}; name: the
+    key of the device copies, which the entries only read (cols: a column subset, copied for the call)."""
+    from rrtmgpnn import _lib
+    from rrtmgpnn._lib import check, int_array
+    from rrtmgpnn.api import context
+    keys = SW_IN + (SW_BANDS if entry != "plain" else ()) + (SW_AER if aer else ())
+    d = _dev_of(name, p, keys, dev) if cols is None else {k: T(p[k][cols], dev) for k in keys}
+    if (masked or byband == "mcica") and "bits" not in d:
+        d["bits"] = _bits(p["mask"] if cols is None else p["mask"][cols], dev)
+    ncol, nlay, ngpt = d["tau"].shape
+    lims = np.asarray(p["lims"] if "lims" in p else p["band_lims_gpt"], np.int32).reshape(-1, 2)
+    nb, lims_c = len(lims), int_array(lims.ravel())
+    outs = [nan(dev, ncol, nlay + 1) for _ in range(6 if entry == "clr_all" else 3)]
+    bnd = [nan(dev, ncol, nlay + 1, nb) for _ in range(3)] if byband else []
+    L, ctx = _lib.lib(), context(0).h
+    head = [ctx, ngpt, nlay, ncol, int(top_at_1), P(d["inc"]), P(d["inc_dif"]), P(d["tau"]), P(d["ssa"]),
+            P(d["g"]) if with_g else None]
+    bands = [nb, lims_c] + [P(d[k]) for k in SW_BANDS] if entry != "plain" else []
+    tail = [P(d["mu0"]), P(d["alb_dir"]), P(d["alb_dif"])] + [P(t) for t in outs]
+    word = torch.full((1,), nact, dtype=torch.int32, device=dev) if nact is not None else None
+    try:
+        if mode is not None:  # the default of the contexts not set themselves: a context set once stays set
+            check(L.rrtmgpnn_context_set_sw_clr_all(None, mode), "context_set_sw_clr_all")
+        if byband == "mcica":
+            check(L.rrtmgpnn_solver_request_byband_mcica(ctx, nb, lims_c, *[P(t) for t in bnd], ngpt, nlay, ncol,
+                                                         P(d["bits"])), "solver_request_byband_mcica")
+        elif byband:
+            check(L.rrtmgpnn_solver_request_byband(ctx, nb, lims_c, *[P(t) for t in bnd]), "solver_request_byband")
+        if masked and byband != "mcica":
+            check(L.rrtmgpnn_solver_request_cloud_mask(ctx, ngpt, nlay, ncol, P(d["bits"])), "solver_request_cloud_mask")
+        if aer:
+            check(L.rrtmgpnn_solver_request_aerosol(ctx, nb, nlay, ncol, *[P(d[k]) for k in SW_AER]),
+                  "solver_request_aerosol")
+        if word is not None:
+            check(L.rrtmgpnn_solver_request_active_columns(ctx, ncol, P(word)), "solver_request_active_columns")
+        fn = {"plain": L.rrtmgpnn_sw_solver_2stream, "inc": L.rrtmgpnn_sw_solver_2stream_inc,
+              "clr_all": L.rrtmgpnn_sw_solver_2stream_clr_all}[entry]
+        check(fn(*head, *bands, *tail), "sw_solver_2stream (%s)" % entry)
+        torch.cuda.synchronize()
+    finally:
+        if mode is not None:
+            check(L.rrtmgpnn_context_set_sw_clr_all(None, 0), "context_set_sw_clr_all")
+    return {"out": [t.cpu().numpy() for t in outs], "bnd": [t.cpu().numpy() for t in bnd], "path": _solver_path(ctx)}
+
+
+def _inputs_unchanged(name, p):
+    """The device copies the entries were given still hold the problem's bits."""
+    for k, t in _dev_arrays[name].items():
+        if k in p:
+            np.testing.assert_array_equal(t.cpu().numpy().view(np.uint32), np.asarray(p[k], np.float32).view(np.uint32),
+                                          err_msg="the call changed its input " + k)
+
+
+@SW_DOMAIN
+@REQUESTS
+@WITH_G
+@ORIENT
+def test_sw_2stream_inc_fused_edges(dev, orc, top_at_1, with_g, masked, aer, domain):
+    """rrtmgpnn_sw_solver_2stream_inc with no request, a cloud mask, a 2str aerosol and both: the edge reaches ck_inc as
+    the CLOUD operand (selected to literal zeros where the lit bit is clear) on gas operands of 0, the background and the
+    edge itself, behind a second ck_inc of the aerosol; against increment_bybnd (aerosol, then the drawn cloud) and
+    sw_solver.  The inputs are left as they were."""
+    p = E.build_sw_fused()
+
+    def run():
+        r = run_swf(dev, p, "swf", top_at_1, "inc", with_g, masked, aer)
+        _inputs_unchanged("swf", p)
+        return r
+    r = _once(("swf_inc", top_at_1, with_g, masked, aer), run)
+    assert r["path"][:3] == expected_sw_path("inc", with_g, masked, aer), r["path"]
+    want, _, io, _ = E.ref_sw_fused(orc, top_at_1, masked, aer, with_g)
+    _compare(E.classes_sw_of(p, io), domain, zip(r["out"], want, FLUX))
+
+
+@pytest.mark.parametrize("which", ["all", "clr"])
+@SW_DOMAIN
+@REQUESTS
+@WITH_G
+@pytest.mark.parametrize("mode", [1, 2], ids=["dual", "two"])
+@ORIENT
+def test_sw_2stream_clr_all_edges(dev, orc, top_at_1, mode, with_g, masked, aer, domain, which):
+    """rrtmgpnn_sw_solver_2stream_clr_all in both modes: in mode 1 the dual kernel, whose .x sky is ck_inc of the .y
+    sky's values by the selected cloud and whose pass 1 carries the two optical depths apart; the all-sky set against the
+    single entry's reference, the clear set against sw_solver on the gases (incremented by the aerosol).  Each set is
+    classed by its own incremented operands."""
+    p = E.build_sw_fused()
+    r = _once(("swf_clr_all", top_at_1, mode, with_g, masked, aer),
+              lambda: run_swf(dev, p, "swf", top_at_1, "clr_all", with_g, masked, aer, mode=mode))
+    assert r["path"][:3] == expected_sw_path("clr_all", with_g, masked, aer, mode=mode), r["path"]
+    allsky, clear, io, clr = E.ref_sw_fused(orc, top_at_1, masked, aer, with_g)
+    if which == "all":
+        _compare(E.classes_sw_of(p, io), domain, zip(r["out"][:3], allsky, FLUX))
+    else:
+        _compare(E.classes_sw_of(p, clr), domain, zip(r["out"][3:], clear, ("up_clr", "dn_clr", "dir_clr")))
+
+
+def _check_byband(q, domain, r, plain, gpt_ref, lims, lit_band):
+    """The by-band outputs against sum_byband of the oracle's g-point fluxes; the lit band holds the broadband flux bit
+    for bit and every other band +-0; the broadband outputs are those of the call without the request."""
+    cols = _cols(q, domain)
+    c = np.arange(q["ncol"])
+    for got, bb, bb_plain, gp, what in zip(r["bnd"], r["out"], plain, gpt_ref, FLUX):
+        E.assert_bitwise(bb, bb_plain, q, what + " against the call without the request")
+        E.assert_bitwise(got, BR.sum_byband(gp, lims), q, "bnd_" + what, cols)
+        E.assert_bitwise(got[c, :, lit_band], bb, q, "bnd_%s at the lit band against the broadband flux" % what, cols)
+        rest = got.copy()
+        rest[c, :, lit_band] = 0
+        E.assert_bitwise(rest, np.zeros_like(rest), q, "bnd_%s outside the lit band" % what, cols)
+
+
+@SW_DOMAIN
+@WITH_G
+@ORIENT
+def test_sw_2stream_byband_edges(dev, sw_kernel, top_at_1, with_g, domain):
+    """rrtmgpnn_solver_request_byband on rrtmgpnn_sw_solver_2stream, build_sw()'s problem on each SW kernel (g = NULL on
+    the columns whose edge g is 0): the by-band flush of the one-per-lane, two-per-lane and checkpointed kernels."""
+    p = E.build_sw()
+    sub = np.arange(p["ncol"]) if with_g else p["g0"]
+    key = ("sw_bb", sw_kernel, top_at_1, with_g)
+    r = _once(key, lambda: run_swf(dev, p, "sw", top_at_1, "plain", with_g, byband="plain", cols=sub))
+    plain = _once(key + ("plain",), lambda: run_swf(dev, p, "sw", top_at_1, "plain", with_g, cols=sub))
+    assert r["path"][:3] == expected_sw_path("plain", with_g, byband=True, kernel=sw_kernel), r["path"]
+    ref = sw_reference(top_at_1, True, gpt=True)
+    q = dict(p, ncol=len(sub), in_domain=p["in_domain"][sub], describe=lambda ids: p["describe"](sub[np.asarray(ids)]))
+    lit_band = (p["lit"] // 16)[sub]
+    _check_byband(q, domain, r, plain["out"], [a[sub] for a in ref[3:]], p["band_lims_gpt"], lit_band)
+    for got, want, what in zip(r["out"], ref[:3], FLUX):
+        E.assert_bitwise(got, want[sub], q, what, _cols(q, domain))
+
+
+@SW_DOMAIN
+@pytest.mark.parametrize("masked", [False, True], ids=["byband", "byband_mcica"])
+@WITH_G
+@ORIENT
+def test_sw_2stream_inc_byband_edges(dev, orc, top_at_1, with_g, masked, domain):
+    """rrtmgpnn_solver_request_byband and rrtmgpnn_solver_request_byband_mcica on rrtmgpnn_sw_solver_2stream_inc: the
+    by-band instances of the checkpointed kernel (no planes), plain and masked."""
+    p = E.build_sw_fused()
+    r = _once(("swf_inc_bb", top_at_1, with_g, masked),
+              lambda: run_swf(dev, p, "swf", top_at_1, "inc", with_g, masked, byband="mcica" if masked else "plain"))
+    plain = _once(("swf_inc", top_at_1, with_g, masked, False),
+                  lambda: run_swf(dev, p, "swf", top_at_1, "inc", with_g, masked))
+    assert r["path"][:3] == expected_sw_path("inc", with_g, masked, byband=True), r["path"]
+    ref, _, io, _ = E.ref_sw_fused(orc, top_at_1, masked, False, with_g, gpt=True)
+    q = E.classes_sw_of(p, io)
+    _check_byband(q, domain, r, plain["out"], ref[3:], p["lims"], p["band_of"][p["lit"]])
+    for got, want, what in zip(r["out"], ref[:3], FLUX):
+        E.assert_bitwise(got, want, q, what, _cols(q, domain))
+
+
+# ---- the large grid: ncol * ngpt / 2 past 64 * 16 * CUs ------------------------------------------------------------------
+def _tiles():
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    p = E.build_sw_fused()
+    return 64 * 16 * cus // (p["ncol"] * (p["ngpt"] // 2)) + 1
+
+
+# (name, entry, masked, aer, mode): rrtmgpnn_sw_solver_2stream with g = NULL (the NN instance with its planes), _inc plain
+# and with mask + aerosol, mode 1 of _clr_all with mask + aerosol
+LARGE_RUNS = [("plain", "plain", False, False, None), ("inc", "inc", False, False, None),
+              ("inc-aer-mask", "inc", True, True, None), ("dual-aer-mask", "clr_all", True, True, 1)]
+LARGE_CASES = [(n, e, m, a, mo, g) for n, e, m, a, mo in LARGE_RUNS for g in ((False,) if e == "plain" else (True, False))]
+LARGE = pytest.mark.parametrize("name,entry,masked,aer,mode,with_g", LARGE_CASES,
+                                ids=["%s-%s" % (c[0], "g" if c[5] else "nog") for c in LARGE_CASES])
+
+
+def _large_reference(orc, top_at_1, entry, masked, aer, with_g):
+    """[(flux triple, its (tau, ssa, g))] of the untiled problem: "plain" solves the gases (the clear set)."""
+    allsky, clear, io, clr = E.ref_sw_fused(orc, top_at_1, masked, aer, with_g)
+    return {"plain": [(clear, clr)], "inc": [(allsky, io)], "clr_all": [(allsky, io), (clear, clr)]}[entry]
+
+
+def _compare_tiles(p, n, domain, got, sets, upto=None):
+    """Every tile of the outputs against the untiled reference; upto: only the rows below it (the others: the prefill)."""
+    for k, (want, props) in enumerate(sets):
+        q = E.classes_sw_of(p, props)
+        cols = _cols(q, domain)
+        for t in range(n):
+            rows = cols if upto is None else cols[cols + t * p["ncol"] < upto]
+            if upto is not None and upto >= (t + 1) * p["ncol"]:
+                assert rows.size >= 20
+            if not rows.size:  # a tile at or past the count: only the prefill, checked below
+                continue
+            for x, y, what in zip(got[3 * k:3 * k + 3], want, FLUX):
+                E.assert_bitwise(x[t * p["ncol"]:(t + 1) * p["ncol"]], y, q, "%s, tile %d, set %d" % (what, t, k), rows)
+    if upto is not None:
+        for x in got:
+            assert np.isnan(x[upto:]).all(), "rows at or past the active-column count were written"
+
+
+@SW_DOMAIN
+@LARGE
+@ORIENT
+def test_sw_fused_edges_on_the_large_grid(dev, orc, top_at_1, name, entry, masked, aer, mode, with_g, domain):
+    """The same cases tiled past the small-grid bound: the large-grid NN instance (chunk 3, ring 9, its transmittance and
+    exp(-k tau) planes written in pass 2 and read in pass 3) and the all-sky and dual instances at more than one round of
+    blocks; every tile against the untiled reference."""
+    p, n = E.build_sw_fused(), _tiles()
+    assert n * p["ncol"] <= 2688
+    r = _once(("swf_large", top_at_1, name, with_g),
+              lambda: run_swf(dev, E.tile(p, n), "swf_tiled", top_at_1, entry, with_g, masked, aer, mode=mode))
+    assert r["path"][:3] == expected_sw_path(entry, with_g, masked, aer, mode=mode, large=True), r["path"]
+    _compare_tiles(p, n, domain, r["out"], _large_reference(orc, top_at_1, entry, masked, aer, with_g))
+
+
+# ---- active columns ------------------------------------------------------------------------------------------------------
+@SW_DOMAIN
+@pytest.mark.parametrize("count", ["zero", "below_block", "all"])
+@pytest.mark.parametrize("entry,large", [("plain", False), ("inc", False), ("plain", True)],
+                         ids=["plain", "inc", "plain-large"])
+@ORIENT
+def test_sw_fused_edges_on_active_columns(dev, orc, top_at_1, entry, large, count, domain):
+    """rrtmgpnn_solver_request_active_columns (family 7, g = NULL) with counts 0, one below a block boundary (ncol is a
+    multiple of every block's column count: the last block's last column is inactive) and ncol: rows below the count
+    are the reference's, rows at or past it keep their prefill."""
+    p = E.build_sw_fused()
+    n = _tiles() if large else 1
+    ncol = n * p["ncol"]
+    assert ncol % 4 == 0
+    nact = {"zero": 0, "below_block": ncol - 1, "all": ncol}[count]
+    r = _once(("swf_active", top_at_1, entry, large, count),
+              lambda: run_swf(dev, E.tile(p, n) if large else p, "swf_tiled" if large else "swf", top_at_1, entry, False,
+                              nact=nact))
+    assert r["path"][:3] == expected_sw_path(entry, False, active=True, large=large), r["path"]
+    _compare_tiles(p, n, domain, r["out"], _large_reference(orc, top_at_1, entry, False, False, False), upto=nact)
+
+
+# ---- the plane-free twins: a child process with RRTMGPNN_SW_NO_PLANES=1 -------------------------------------------------
+def child_main(ref_npz):
+    """The large-grid list once, in a process started with RRTMGPNN_SW_NO_PLANES=1: every tile and both domain classes
+    against the references of the file, and no plane bit in any path."""
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    ref = np.load(ref_npz)
+    p, n = E.build_sw_fused(), _tiles()
+    tiled = E.tile(p, n)
+    for top_at_1 in (True, False):
+        for name, entry, masked, aer, mode, with_g in LARGE_CASES:
+            r = run_swf(dev, tiled, "swf_tiled", top_at_1, entry, with_g, masked, aer, mode=mode)
+            want = expected_sw_path(entry, with_g, masked, aer, mode=mode, large=True, planes=False)
+            assert r["path"][:3] == want and not r["path"][1] & (CK_TN | CK_EMK), (name, with_g, r["path"], want)
+            tag = "%s/%d/%d" % (name, with_g, top_at_1)
+            for k in range(len(r["out"]) // 3):
+                q = dict(p, in_domain=ref["%s/in_domain%d" % (tag, k)])
+                for domain in DOMAINS:
+                    cols = _cols(q, domain)
+                    for t in range(n):
+                        for x, what in zip(r["out"][3 * k:3 * k + 3], FLUX):
+                            E.assert_bitwise(x[t * p["ncol"]:(t + 1) * p["ncol"]], ref["%s/%s%d" % (tag, what, k)], q,
+                                             "%s %s, tile %d, set %d" % (tag, what, t, k), cols)
+            print("%-24s family %d options %4d launches %d" % ((tag,) + tuple(r["path"][:3])))
+
+
+def test_sw_fused_edges_plane_free_twins(dev, orc, tmp_path):
+    """The instances that recompute instead of reading workspace planes give the same bits at the edges."""
+    assert "RRTMGPNN_SW_NO_PLANES" not in os.environ
+    p = E.build_sw_fused()
+    ref = {}
+    for top_at_1 in (True, False):
+        for name, entry, masked, aer, mode, with_g in LARGE_CASES:
+            for k, (want, props) in enumerate(_large_reference(orc, top_at_1, entry, masked, aer, with_g)):
+                tag = "%s/%d/%d" % (name, with_g, top_at_1)
+                ref["%s/in_domain%d" % (tag, k)] = E.classes_sw_of(p, props)["in_domain"]
+                for a, what in zip(want, FLUX):
+                    ref["%s/%s%d" % (tag, what, k)] = a
+    path = str(tmp_path / "ref.npz")
+    np.savez(path, **ref)
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import test_gpu_solver_edges as G; G.child_main(%r)"
+            % (os.path.join(ROOT, "tests"), os.path.join(ROOT, "rte-rrtmgp-nn_amd"), os.path.join(ROOT, "oracle"), path))
+    env = dict(os.environ, RRTMGPNN_SW_NO_PLANES="1")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert len(r.stdout.strip().splitlines()) == 2 * len(LARGE_CASES)

@@ -16,6 +16,17 @@ The scattering and fused LW solvers (build_lw_scat, 1224 columns): every referen
 and down fluxes together (two-stream without incident flux 0.094; flux_up_Jac below 0.10 outside the emissivity-0
 columns, where it is 0 by definition); 0.82-0.87 of the columns change when the edge (ssa, g) gives way to the
 background pair (flux_up_Jac 0.65-0.69), 0.82-0.85 when the lit mask bit is flipped; the census of the last test.
+
+The fused SW solvers (build_sw_fused, 1344 columns; {mask} x {aerosol} x {gas g, g = NULL} x both orientations): every
+reference and every incremented property finite (the gas tau falls back to the background in the 28 columns where
+2e38 + 2e38 would be inf); zero shares all sky up 0.25-0.26, down 0.21, direct 0.48, masked 0.18-0.19 / 0.14-0.15 /
+0.43-0.44, clear 0.12 / 0.08 / 0.38-0.39 (caps 0.30 / 0.30 / 0.55); the background cloud triple changes 0.95-0.96 of
+the columns without a mask and of the bit-set columns under it, the flipped lit bit 0.58-0.60; census (no mask -
+masked): eps branch 313 - 280, k_min clamp 143 - 101, 0 < ssa < 2^-100 136 - 83, tau12 > 0 with tauscat12 < 3 FLT_MIN
+328, incremented tau > 1e4 224, tau12 == 0 with the lit bit set 28 and clear 28 (all the case grid holds: 84 columns
+have an edge tau of 0, the gas tau is 0 in two thirds of them and the bit halves those); the lit bit set and clear
+with every edge tau in at least 42 columns, every edge ssa 40, every mu0 96; classes in_domain / out_of_domain: all sky
+1006-1148 / 196-338, clear 1238-1265 / 79-106.
 """
 import numpy as np
 import pytest
@@ -385,3 +396,151 @@ def test_lw_scat_domain_classes_have_columns(orc, scat):
         q = E.classes(pl, E.edge_values(pl, E.ref_noscat_fused(orc, True, 1, kind)[2]), None, E.gauss_ds(1))
         n = (int(q["in_domain"].sum()), int((~q["in_domain"] & ~q["beyond_2p126"]).sum()), int(q["beyond_2p126"].sum()))
         assert min(n) >= 20, (kind, n)
+
+
+# ---- the fused SW solvers (solver_edges.build_sw_fused) -----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def swf():
+    return E.build_sw_fused()
+
+
+SW_SETS = [(masked, aer, with_g) for masked in (False, True) for aer in (False, True) for with_g in (True, False)]
+
+
+def _lit_only(p, flux, what):
+    """flux: (up, dn, dir, gpt_up, gpt_dn, gpt_dir).  The broadband flux is the lit g-point's, the others are +-0."""
+    c = np.arange(p["ncol"])
+    for name, bb, gp in zip(("up", "dn", "dir"), flux[:3], flux[3:]):
+        np.testing.assert_array_equal(bb, gp[c, :, p["lit"]], err_msg="%s %s" % (what, name))
+        unlit = gp.copy()
+        unlit[c, :, p["lit"]] = 0
+        assert not unlit.any(), (what, name)
+
+
+@pytest.mark.parametrize("top_at_1", [True, False])
+def test_sw_fused_references_are_finite_lit_only_and_not_mostly_zero(orc, swf, top_at_1):
+    """Finite everywhere ({mask} x {aerosol} x {gas g, g = NULL}, the all-sky and the clear sets, the incremented
+    properties); zero shares up <= 0.30, down <= 0.30, direct <= 0.55; the broadband flux is the lit g-point's flux bit for
+    bit and every unlit g-point is exactly zero, under the mask and with the aerosol too."""
+    p = swf
+    for masked, aer, with_g in SW_SETS:
+        allsky, clear, io, clr = E.ref_sw_fused(orc, top_at_1, masked, aer, with_g, gpt=True)
+        plain = E.ref_sw_fused(orc, top_at_1, masked, aer, with_g)
+        what = "masked=%s aer=%s g=%s top_at_1=%s" % (masked, aer, with_g, top_at_1)
+        for a in allsky + clear + tuple(io) + tuple(clr) + plain[0] + plain[1]:
+            assert np.isfinite(a).all(), what
+        for name, flux, flux_plain in (("all sky", allsky, plain[0]), ("clear", clear, plain[1])):
+            _lit_only(p, flux, what + " " + name)
+            for x, y in zip(flux[:3], flux_plain):
+                np.testing.assert_array_equal(x, y, err_msg=what + " " + name)
+            shares = [_zero_share(a) for a in flux[:3]]
+            print("SW fused %s %s: share of exact zeros up %.3f down %.3f direct %.3f (caps 0.30 0.30 0.55)"
+                  % (what, name, *shares))
+            for s, cap in zip(shares, (0.30, 0.30, 0.55)):
+                assert s <= cap, (what, name, shares)
+
+
+def _changed(a, b, cols=None):
+    n = a[0].shape[0]
+    diff = np.zeros(n, bool)
+    for x, y in zip(a, b):
+        diff[E.mismatch_columns(x, y)] = True
+    return float(diff.mean() if cols is None else diff[cols].mean())
+
+
+@pytest.mark.parametrize("top_at_1", [True, False])
+def test_sw_fused_edge_operands_show_in_the_fluxes(orc, swf, top_at_1):
+    """The edge cloud triple gives way to the background triple: at least 0.8 of the columns change without a mask, at
+    least 0.8 of the bit-set columns under it; the lit bit flipped: at least 0.5 of the columns."""
+    p = swf
+    bit = p["edge"]["bit"]
+    bg = E.with_background_cloud(p)
+    shares = {}
+    for aer in (False, True):
+        for with_g in (True, False):
+            t = "aer=%s g=%s" % (aer, with_g)
+            ref = E.ref_sw_fused(orc, top_at_1, False, aer, with_g)[0]
+            other = E.sw_fused_solve(orc, p, E.sw_fused_props(orc, p, False, aer, with_g, cloud=bg)[0], top_at_1)
+            shares["background cloud, no mask, " + t] = (_changed(ref, other), 0.8)
+            ref = E.ref_sw_fused(orc, top_at_1, True, aer, with_g)[0]
+            other = E.sw_fused_solve(orc, p, E.sw_fused_props(orc, p, True, aer, with_g, cloud=bg)[0], top_at_1)
+            shares["background cloud, masked, bit-set columns, " + t] = (_changed(ref, other, bit), 0.8)
+            assert _changed(ref, other, ~bit) == 0  # a clear bit switches either triple off
+            other = E.sw_fused_solve(orc, p, E.sw_fused_props(orc, p, True, aer, with_g, mask=E.flipped_lit_mask(p))[0],
+                                     top_at_1)
+            shares["lit bit flipped, " + t] = (_changed(ref, other), 0.5)
+    for what, (share, least) in shares.items():
+        print("SW fused top_at_1=%s %s: %.3f of the columns change (at least %.1f)" % (top_at_1, what, share, least))
+    for what, (share, least) in shares.items():
+        assert share >= least, "%s: only %.3f of the columns change their fluxes" % (what, share)
+
+
+def test_sw_fused_census_of_the_incremented_edge_operands(orc, swf):
+    """In float32, from the oracle's incremented properties at (edge layer, lit g-point), gas g present: every
+    value-dependent path of sw_two_stream and of the band increment is reached by at least 50 columns, without and under
+    the mask.  The two rows on tau12 == 0 are bounded by the case grid itself: tau12 = tau_gas + tau_cloud is zero only
+    in the 84 columns whose edge tau is 0, the gas tau is 0 in two thirds of them (the cycle {0, background, edge}) and
+    the lit bit halves those: 28 and 28, which is what they must hold."""
+    p, e = swf, swf["edge"]
+    census = {}
+    for masked in (False, True):
+        io = E.ref_sw_fused(orc, True, masked, False, True)[2]
+        t, w, q = (E.edge_values(p, a) for a in io)
+        tag = "masked" if masked else "no mask"
+        census["eps branch, " + tag] = int(E.in_eps_branch(w, q, e["mu0"]).sum())
+        census["k_min clamp, " + tag] = int((E.sw_k(w, q)[1] < E.K_MIN).sum())
+        census["0 < ssa < 2^-100, " + tag] = int(((w > 0) & (w < F(2.0 ** -100))).sum())
+    with np.errstate(over="ignore", under="ignore"):
+        tau12 = e["gas_tau"] + e["tau"]
+        scat12 = e["gas_tau"] * e["gas_ssa"] + e["tau"] * e["ssa"]
+    grid = {"tau12 == 0, bit set": int(((tau12 == 0) & e["bit"]).sum()),
+            "tau12 == 0, bit clear": int(((tau12 == 0) & ~e["bit"]).sum())}
+    census["tau12 > 0 and tauscat12 < 3 FLT_MIN"] = int(((tau12 > 0) & (scat12 < E.EPS_INC)).sum())
+    census["incremented tau > 1e4"] = int((E.edge_values(p, E.ref_sw_fused(orc, True, False, False, True)[2][0]) > F(1e4)).sum())
+    print(census, grid)
+    for what, n in census.items():
+        assert n >= 50, (what, n)
+    assert grid == {"tau12 == 0, bit set": 28, "tau12 == 0, bit clear": 28}
+    # the lit bit is spread over every edge tau, edge ssa and mu0
+    spread = {}
+    for k in ("tau", "ssa", "mu0"):
+        vals = np.unique(e[k])
+        spread[k] = min(min(int(((e[k] == v) & e["bit"]).sum()), int(((e[k] == v) & ~e["bit"]).sum())) for v in vals)
+    print("least columns of one edge value with the lit bit set / clear:", spread)
+    assert set(np.unique(e["tau"])) == set(E.TAUS) and set(np.unique(e["ssa"])) >= set(E.SSAS)  # + the resonant 0.3
+    for k, n in spread.items():
+        assert n >= 20, (k, n)
+    assert abs(int(e["bit"].sum()) - p["ncol"] // 2) <= 24
+    # gas tau and gas ssa cycle independently: all nine pairings of {0, background, edge}
+    kt = np.select([e["gas_tau"] == 0, e["gas_tau"] == E.BG_TAU], [0, 1], 2)
+    kw = np.select([e["gas_ssa"] == 0, e["gas_ssa"] == E.BG_SSA], [0, 1], 2)
+    pairs = np.bincount(3 * kt + kw, minlength=9)
+    print("gas (tau, ssa) pairings:", pairs)
+    assert pairs.min() >= 50
+    # the edge values are where the kernels read them
+    c, b = np.arange(p["ncol"]), p["band_of"][p["lit"]]
+    for k, kb in (("tau", "tau_bnd"), ("ssa", "ssa_bnd"), ("g", "g_bnd")):
+        np.testing.assert_array_equal(p[kb][c, p["layer"], b], e[k])
+    for k in ("tau", "ssa", "g"):
+        np.testing.assert_array_equal(E.edge_values(p, p[k]), e["gas_" + k])
+    np.testing.assert_array_equal(E.edge_values(p, p["mask"]), e["bit"])
+    with np.errstate(over="ignore"):
+        assert np.isfinite(e["gas_tau"] + e["tau"]).all()
+    assert (p["lims"][:, 0] % 2 == 1).all() and p["nb"] == 14  # the band-pair layout
+
+
+def test_sw_fused_domain_classes_have_columns(orc, swf):
+    """Every class the GPU file compares holds at least 20 columns (it asserts so itself; here without a device), and the
+    tiled problem repeats the columns."""
+    p = swf
+    for masked, aer, with_g in SW_SETS:
+        _, _, io, clr = E.ref_sw_fused(orc, True, masked, aer, with_g)
+        for name, props in (("all sky", io), ("clear", clr)):
+            q = E.classes_sw_of(p, props)
+            n = (int(q["in_domain"].sum()), int((~q["in_domain"]).sum()))
+            print("SW fused masked=%s aer=%s g=%s %s: in_domain %d, out_of_domain %d" % (masked, aer, with_g, name, *n))
+            assert min(n) >= 20, (masked, aer, with_g, name, n)
+    t = E.tile(p, 2)
+    assert t["ncol"] == 2 * p["ncol"] and t["tau"].shape[0] == t["ncol"] and t["lims"].shape == p["lims"].shape
+    np.testing.assert_array_equal(t["tau_bnd"][p["ncol"]:], p["tau_bnd"])
+    np.testing.assert_array_equal(t["mask"][:p["ncol"]], p["mask"])
