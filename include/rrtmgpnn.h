@@ -645,7 +645,9 @@ int rrtmgpnn_cloud_optics_compute(rrtmgpnn_context *ctx, const rrtmgpnn_cloud_op
                                   float *tau, float *ssa, float *g);
 /* ty_optical_props_arry%increment of g-point properties (ngpt, nlay, ncol) by band-resolved ones
  * (nband, nlay, ncol) (rte/mo_optical_props.F90:882-1023, inc_*_bybnd).  ssa_io == NULL: 1scl target;
- * ssa_in == NULL: 1scl increment.  band_lims_gpt HOST (2, nband). */
+ * ssa_in == NULL: 1scl increment.  band_lims_gpt HOST (2, nband).  A g-point in no band is left untouched; limits
+ * that overlap are RRTMGPNN_ERR_ARGUMENT (the reference would increment such a g-point once per band; the kernel
+ * gives a g-point one band), here and in every fused entry that takes a band increment. */
 int rrtmgpnn_increment_bybnd(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt, int nband, const int *band_lims_gpt,
                              float *tau_io, float *ssa_io, float *g_io, const float *tau_in, const float *ssa_in,
                              const float *g_in);

@@ -100,9 +100,21 @@ static int band_args(int nbnd, const int *lims, int ngpt, BandArgs &b)
   return RRTMGPNN_OK;
 }
 
-// the fused increments give every g-point a band: refuse band limits that leave one out
+// The kernels give a g-point the FIRST band that holds it and increment it once; the reference's inc_*_bybnd loop over
+// the bands and increment it once per band that holds it.  Overlapping limits would differ silently: refuse them.
+static int bands_disjoint(const BandArgs &b)
+{
+  for (int i = 0; i < b.nbnd; i++)
+    for (int k = i + 1; k < b.nbnd; k++)
+      if (b.lims[2 * i] <= b.lims[2 * k + 1] && b.lims[2 * k] <= b.lims[2 * i + 1])
+        return fail(RRTMGPNN_ERR_ARGUMENT, "band limits overlap: a g-point may lie in one band only");
+  return RRTMGPNN_OK;
+}
+
+// the fused increments give every g-point exactly one band: refuse band limits that overlap or leave one out
 static int bands_cover(const BandArgs &b, int ngpt)
 {
+  if (int rc = bands_disjoint(b)) return rc;
   for (int g = 1; g <= ngpt; g++) {
     bool in = false;
     for (int i = 0; i < b.nbnd && !in; i++) in = g >= b.lims[2 * i] && g <= b.lims[2 * i + 1];
@@ -2012,11 +2024,14 @@ int rrtmgpnn_increment_bybnd(rrtmgpnn_context *ctx, int ncol, int nlay, int ngpt
                              float *tau_io, float *ssa_io, float *g_io, const float *tau_in, const float *ssa_in,
                              const float *g_in)
 {
+  // the band limits are judged before the context, so that the refusals need no device (a gap is allowed here: such
+  // a g-point is left untouched)
+  BandArgs b;
+  if (int rc = band_args(nband, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_disjoint(b)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!tau_io || !tau_in || ncol < 0 || nlay < 0 || ngpt < 1 || (ssa_io && !g_io) || (ssa_in && !g_in))
     return fail(RRTMGPNN_ERR_ARGUMENT, "increment: bad argument");
-  BandArgs b;
-  if (int rc = band_args(nband, band_lims_gpt, ngpt, b)) return rc;
   return launch_increment_bybnd(ctx, ncol, nlay, ngpt, &b, tau_io, ssa_io, g_io, tau_in, ssa_in, g_in);
 }
 
