@@ -322,7 +322,19 @@ int rrtmgpnn_network_forward(rrtmgpnn_context *ctx, const rrtmgpnn_network *net,
                              const float *x, float *out);
 /* compute_Planck_source_nn (rrtmgp/kernels/mo_gas_optics_kernels.F90:615-683).  sfc_lay 1-based.
  * band_lims_gpt: HOST (2,nbnd) 1-based.  totplnk: DEVICE (nPlanckTemp, nbnd).
- * pfrac is overwritten with lay_source. */
+ * pfrac is overwritten with lay_source.
+ * BAND LIMITS must give every g-point exactly one band: limits that overlap or leave a g-point out are
+ * RRTMGPNN_ERR_ARGUMENT, here and in every fused-Planck solver entry (rrtmgpnn_lw_solver_noscat_planck[_gpt / _inc /
+ * _clr_all / _clr_all_mcica], rrtmgpnn_lw_solver_1rescl_planck_*) and in rrtmgpnn_compute_bc_lw, whether or not the
+ * call has a band increment or a by-band emissivity: the reference leaves lev_source undefined and pfrac untouched at
+ * a g-point outside every band and multiplies pfrac once per band at one in several, where the kernels' band lookup
+ * would give band 0 and the first band (as rrtmgpnn_increment_bybnd states for the increments).
+ * TEMPERATURES outside the table follow interpolate1D (:1024-1043) literally, bit for bit (tests/planck_edges.py):
+ * with val0 = (T - temp_ref_min) / totplnk_delta the index is clamped to the table but the fraction is val0 - int(val0)
+ * with int() truncating toward zero, so T = temp_ref_max returns the LAST BUT ONE table value, T above it extrapolates
+ * the last interval by the fractional part alone, T <= temp_ref_min - totplnk_delta on a knot returns the first value
+ * and between knots extrapolates the first interval with a negative fraction, and sfc_source_Jac is 0 wherever tsfc
+ * and tsfc + 1 share an index and a fraction (tsfc = temp_ref_max - 1 with totplnk_delta 1). */
 int rrtmgpnn_compute_planck_source_nn(rrtmgpnn_context *ctx, int ncol, int nlay, int nbnd, int ngpt,
                                       int nPlanckTemp, const float *tlay, const float *tlev, const float *tsfc,
                                       int sfc_lay, const int *band_lims_gpt, float temp_ref_min,
@@ -354,7 +366,8 @@ int rrtmgpnn_lw_solver_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int nco
  * + lw_solver_noscat_GaussQuad in one kernel.  Takes the Planck fraction (what predict_nn_lw writes into
  * lay_source) instead of lay/lev/sfc sources, forms every source in-kernel with the same products as
  * rrtmgpnn_compute_planck_source_nn, and never stores them: fluxes are bit-identical to
- * compute_planck_source_nn followed by lw_solver_noscat.  band_lims_gpt HOST (2,nbnd); totplnk DEVICE.
+ * compute_planck_source_nn followed by lw_solver_noscat.  band_lims_gpt HOST (2,nbnd), every g-point in exactly one
+ * band (rrtmgpnn_compute_planck_source_nn's rule); totplnk DEVICE.
  * emis_by_band == 0: sfc_emis is (ngpt, ncol) per g-point; 1: (nbnd, ncol) by band, as rte_lw takes it, expanded
  * in-kernel (expand, rte/mo_rte_lw.F90:429-447: the same values, no band-to-g-point array in HBM). */
 int rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,

@@ -318,7 +318,8 @@ static int lw_noscat(rrtmgpnn_context *ctx, const LwNoscat &p, const float *lay_
 }
 
 // the fused-Planck entries' arguments: `inc` needs tau_bnd, `more` is what else the entry needs; then the bands into
-// `in`, which cover every g-point where each g-point's band is looked up (the increment, by-band emissivity)
+// `in`, which give every g-point exactly one band: the Planck source itself looks each g-point's band up, and the
+// reference leaves a g-point outside every band undefined and multiplies one in two bands twice
 static int planck_args(const char *entry, const LwNoscat &p, LwPlanckIn &in, int nbnd, const int *band_lims_gpt,
                        bool inc, bool more = true)
 {
@@ -328,8 +329,7 @@ static int planck_args(const char *entry, const LwNoscat &p, LwPlanckIn &in, int
       pl.ntemp < 2 || pl.sfc_lay < 1 || pl.sfc_lay > p.nlay || !(pl.tdelta > 0.0f))
     return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": bad argument");
   if (int rc = band_args(nbnd, band_lims_gpt, p.ngpt, in.bands)) return rc;
-  if (inc || pl.emis_by_band) return bands_cover(in.bands, p.ngpt);
-  return RRTMGPNN_OK;
+  return bands_cover(in.bands, p.ngpt);
 }
 
 static int lw_noscat_planck(rrtmgpnn_context *ctx, const LwNoscat &p, LwPlanckIn &in, int nbnd,
@@ -1158,6 +1158,7 @@ int rrtmgpnn_compute_planck_source_nn(rrtmgpnn_context *ctx, int ncol, int nlay,
     return fail(RRTMGPNN_ERR_ARGUMENT, "compute_planck_source_nn: bad argument");
   BandArgs b;
   if (int rc = band_args(nbnd, band_lims_gpt, ngpt, b)) return rc;
+  if (int rc = bands_cover(b, ngpt)) return rc;
   return launch_planck_source(ctx, ncol, nlay, ngpt, nPlanckTemp, tlay, tlev, tsfc, sfc_lay, b, temp_ref_min,
                               totplnk_delta, totplnk, sfc_source, sfc_source_Jac, pfrac, lev_source);
 }

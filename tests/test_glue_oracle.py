@@ -8,7 +8,9 @@ unconditionally and cannot be built here, so the glue is pinned by
     RFMIP expt 1 (column 0 below) and printed five fluxes to two decimals.  The SW harness of that probe used a
     flat solar_source (one value for every g-point, renormalised to the column's TSI), not the 5778 K blackbody
     surrogate the build ships: with a flat source the restatement reproduces all five printed values;
-  * operation-by-operation restatements in numpy float32 of the Fortran expressions (tlev, the "both" split).
+  * operation-by-operation restatements in numpy float32 of the Fortran expressions (tlev, the "both" split); the
+    Planck source's own (interpolate1D and compute_Planck_source_nn, at every table and temperature edge, with a
+    float64 reference beside it) is planck_edges.planck_source_f32, held in tests/test_planck_edges_host.py.
 """
 import numpy as np
 import pytest
