@@ -138,7 +138,11 @@ int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8]);
  *   4 lw_rescl_kernel: 1 by-band outputs, 2 Jacobian;
  *   5 sw_2stream_kernel, 6 sw_2stream_x2_kernel: 1 gas g, 2 band increment, 4 g-point outputs, 8 by-band outputs;
  *   7 sw_2stream_ck_kernel with the active-column count read from a device word
- *     (rrtmgpnn_solver_request_active_columns): family 2's bits, and 2048 in every instance.
+ *     (rrtmgpnn_solver_request_active_columns): family 2's bits, and 2048 in every instance;
+ *   8 sw_2stream_ck_kernel with that count beside a cloud mask and / or an aerosol (the requests armed together):
+ *     family 2's bits, 2048 and 2 in every instance, with 128, 256 or both -- the masked cloud with and without the
+ *     band-pair layout, the aerosol (band pair only) in front of the masked or the unmasked cloud, each with the
+ *     transmittance plane and without.
  * path[2]: the launches the call made in these families, 2 where a clear + all-sky entry ran its two launches (path[0]
  * and path[1] are then the second's).  path[3]: the number of instances the family is compiled for; an options value
  * outside that list is refused with RRTMGPNN_ERR_UNSUPPORTED.  A call that launches nothing leaves the path as it was. */
@@ -769,6 +773,32 @@ int rrtmgpnn_sampled_mask_max_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nl
 int rrtmgpnn_sampled_mask_exp_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const unsigned int *rng,
                                          const float *cloud_frac, const float *overlap_param,
                                          unsigned char *cloud_mask, unsigned int *mask_bits);
+/* The four packed masks above for a block compacted to its daylit columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463):
+ * idx (ncol) and nact (one DEVICE int) are rrtmgpnn_daylit_plan's idx and nday.  Dense column j < min(max(*nact, 0), ncol)
+ * is source column i = idx[j]: its cloud_frac, overlap_param and, on the array route, randoms are read at column i in
+ * place (nothing is gathered: all three keep their full extents), and the seeded route's counter word is col0 + i, so a
+ * column has the same clouds whether the block is compacted or not.  The words go to row j of a dense mask_bits
+ * (nw, nlay, ncol), what rrtmgpnn_solver_request_cloud_mask takes beside rrtmgpnn_solver_request_active_columns; rows at
+ * or past the count are not written.  Packed words only.  The argument checks and messages of the full-extent twins;
+ * idx, nact or mask_bits NULL is RRTMGPNN_ERR_ARGUMENT; ncol == 0 is OK.  The grid is ncol: the host never reads the
+ * count, and nothing is allocated, so the calls capture into a hipGraph.  No reference counterpart. */
+int rrtmgpnn_sampled_mask_max_ran_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                         const float *cloud_frac, const int *idx, const int *nact,
+                                         unsigned int *mask_bits);
+/* As above with exponential-random overlap (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463). */
+int rrtmgpnn_sampled_mask_exp_ran_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                         const float *cloud_frac, const float *overlap_param, const int *idx,
+                                         const int *nact, unsigned int *mask_bits);
+/* As above with the random numbers drawn in the kernel, counter word (col0 + idx[j]) mod 2^32 (rrtmgp_rfmip_sw.F90:285-287,
+ * 433, 456-463). */
+int rrtmgpnn_sampled_mask_max_ran_seeded_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
+                                                const unsigned int *rng, const float *cloud_frac, const int *idx,
+                                                const int *nact, unsigned int *mask_bits);
+/* As above with exponential-random overlap (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463). */
+int rrtmgpnn_sampled_mask_exp_ran_seeded_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
+                                                const unsigned int *rng, const float *cloud_frac,
+                                                const float *overlap_param, const int *idx, const int *nact,
+                                                unsigned int *mask_bits);
 /* draw_samples / apply_cloud_mask (:36-120, :291-307): per g-point the band value (nbnd, nlay, ncol) where cloud_mask is
  * set, else 0, into (ngpt, nlay, ncol).  tau always; ssa and g when all of ssa_bnd, g_bnd, ssa, g are given (2str),
  * none of them for 1scl.  band_lims_gpt HOST (2, nbnd), every g-point in a band. */
@@ -888,7 +918,9 @@ int rrtmgpnn_daylit_plan(rrtmgpnn_context *ctx, int ncol, const float *v, int ki
                          int *nday);
 /* rrtmgpnn_gather_columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): one launch; for each of the narrays (1..16)
  * arrays of row_floats[a] floats per column, row idx[j] of src[a] goes to row j of dst[a] for j < *nday.  Rows of dst at
- * or past *nday are left as they were.  Rows need no alignment beyond a float's. */
+ * or past *nday are left as they were.  Rows need no alignment beyond a float's.  A table whose rows are all at least
+ * 256 floats (an aerosol's band arrays) runs a kernel with one block per column and array; put such arrays in a call
+ * of their own. */
 int rrtmgpnn_gather_columns(rrtmgpnn_context *ctx, int ncol, int narrays, const float *const *src, float *const *dst,
                             const int *row_floats, const int *idx, const int *nday);
 /* rrtmgpnn_scatter_columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): one launch; for each of the narrays (1..6)
@@ -914,9 +946,17 @@ int rrtmgpnn_gas_optics_sw_nn_active(rrtmgpnn_context *ctx, int ncol, int nlay, 
  * checkpointed kernel (even ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), kernel family 7 of
  * rrtmgpnn_context_get_solver_path: the instances of family 2 with option bit 2048, for g == NULL and without or with
  * the band increment.  The instance and its workspace are chosen from ncol, as without the request.
- * RRTMGPNN_ERR_ARGUMENT: every other solver entry, with a message naming the three; ncol other than the call's.
- * RRTMGPNN_ERR_UNSUPPORTED: a by-band, cloud-mask, aerosol or Jacobian request beside it, g-point outputs, a gas g
- * array, the other SW kernel modes, odd ngpt. */
+ * On rrtmgpnn_sw_solver_2stream_inc and on rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0 it is also honoured together
+ * with rrtmgpnn_solver_request_cloud_mask, rrtmgpnn_solver_request_aerosol (2str) or both (kernel family 8: a McICA
+ * step on daylit columns): the mask's and the aerosol's extents are the call's ncol, their rows those of the dense
+ * columns (rrtmgpnn_sampled_mask_*_active writes such a mask).
+ * RRTMGPNN_ERR_ARGUMENT: every other solver entry, with a message naming the three; ncol other than the call's; a mask
+ * or an aerosol of other extents than the call's.
+ * Refused: RRTMGPNN_ERR_UNSUPPORTED, every armed request cleared, nothing written -- a by-band request beside it, alone
+ * or paired with the mask (rrtmgpnn_solver_request_byband_mcica); a Jacobian request; a cloud-mask or aerosol request
+ * ahead of rrtmgpnn_sw_solver_2stream; g-point outputs; a gas g array; an aerosol on bands outside the band-pair
+ * layout; the other SW kernel modes; odd ngpt.  The clear + all-sky (_clr_all) entries take no count
+ * (RRTMGPNN_ERR_ARGUMENT). */
 int rrtmgpnn_solver_request_active_columns(rrtmgpnn_context *ctx, int ncol, const int *nact);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */

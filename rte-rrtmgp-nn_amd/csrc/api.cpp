@@ -165,15 +165,19 @@ static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
 static const char kNoMaskMsg[] = "solver_request_cloud_mask: this solver entry takes no cloud mask (the _planck_inc, "
                                  "_2stream_inc, _2stream_rfmip, _2stream_clr_all and _2stream_rfmip_clr_all entries do)";
 // ... and an armed active-column count (rrtmgpnn_solver_request_active_columns; rrtmgp_rfmip_sw.F90:285-287, 433,
-// 456-463): the three SW two-stream entries take it alone, on the call's ncol, into the call's extras
+// 456-463): the three SW two-stream entries take it on the call's ncol, into the call's extras -- alone, or (`sky`: the
+// _inc and _rfmip entries) beside a cloud-mask and / or an aerosol request, which those entries then check as ever
 static const char kNoActiveMsg[] = "solver_request_active_columns: this solver entry takes no active-column count (the "
                                    "sw_solver_2stream, sw_solver_2stream_inc and sw_solver_2stream_rfmip entries do)";
-static int take_active(const char *entry, const Requests &rq, bool honour, int ncol, SolverExtras &ex)
+static int take_active(const char *entry, const Requests &rq, bool honour, int ncol, SolverExtras &ex, bool sky = false)
 {
   if (!rq.act.armed) return RRTMGPNN_OK;
   if (!honour) return fail(RRTMGPNN_ERR_ARGUMENT, kNoActiveMsg);
   const std::string e(entry);
-  if (rq.byband || rq.mask.armed || rq.aer.armed || rq.jac.armed)
+  if (sky && (rq.byband || rq.jac.armed))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an active-column count together with a by-band (alone or paired with a "
+                                              "cloud mask) or Jacobian request");
+  if (!sky && (rq.byband || rq.mask.armed || rq.aer.armed || rq.jac.armed))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an active-column count together with a by-band, cloud-mask, aerosol or "
                                               "Jacobian request");
   if (rq.act.ncol != ncol)
@@ -259,7 +263,7 @@ static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngp
                                JacMode jac = kJacRefuse, AerMode aer = kAerRefuse, int nbnd = 0, bool active = false)
 {
   const Requests rq = take_requests(ctx, ngpt, ex);
-  if (int rc = take_active(entry, rq, active, ncol, ex)) return rc;
+  if (int rc = take_active(entry, rq, active, ncol, ex, /*sky=*/active)) return rc;
   if (rq.byband_rc) return rq.byband_rc;
   if (int rc = take_aerosol(entry, rq, aer, nbnd, nlay, ncol, ex)) return rc;
   if (int rc = take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex)) return rc;
@@ -1800,6 +1804,55 @@ int rrtmgpnn_sampled_mask_exp_ran_seeded(rrtmgpnn_context *ctx, int ngpt, int nl
 {
   return sampled_mask_seeded(ctx, "sampled_mask_exp_ran_seeded", true, ngpt, nlay, ncol, rng, cloud_frac,
                              overlap_param, cloud_mask, mask_bits);
+}
+
+// the masks of a block compacted to its daylit columns (rrtmgp_rfmip_sw.F90:285-287, 433, 456-463): the full-extent
+// twins' checks and messages, packed words only
+static int sampled_mask_active(rrtmgpnn_context *ctx, const char *who, bool exp_ran, bool seeded, int ngpt, int nlay,
+                               int ncol, const void *src, const float *cloud_frac, const float *overlap_param,
+                               const int *idx, const int *nact, unsigned int *mask_bits)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  if (seeded && !src) return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": rng is NULL");
+  if (!src || !cloud_frac || ngpt < 1 || nlay < 1 || ncol < 0 || (exp_ran && nlay > 1 && !overlap_param))
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": bad argument");
+  if (!idx || !nact || !mask_bits)
+    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(who) + ": idx, nact or mask_bits is NULL");
+  return launch_sampled_mask_active(ctx, exp_ran, seeded, ngpt, nlay, ncol, src, cloud_frac, overlap_param, idx, nact,
+                                    mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_max_ran_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                         const float *cloud_frac, const int *idx, const int *nact,
+                                         unsigned int *mask_bits)
+{
+  return sampled_mask_active(ctx, "sampled_mask_max_ran_active", false, false, ngpt, nlay, ncol, randoms, cloud_frac,
+                             nullptr, idx, nact, mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_exp_ran_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const float *randoms,
+                                         const float *cloud_frac, const float *overlap_param, const int *idx,
+                                         const int *nact, unsigned int *mask_bits)
+{
+  return sampled_mask_active(ctx, "sampled_mask_exp_ran_active", true, false, ngpt, nlay, ncol, randoms, cloud_frac,
+                             overlap_param, idx, nact, mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_max_ran_seeded_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
+                                                const unsigned int *rng, const float *cloud_frac, const int *idx,
+                                                const int *nact, unsigned int *mask_bits)
+{
+  return sampled_mask_active(ctx, "sampled_mask_max_ran_seeded_active", false, true, ngpt, nlay, ncol, rng, cloud_frac,
+                             nullptr, idx, nact, mask_bits);
+}
+
+int rrtmgpnn_sampled_mask_exp_ran_seeded_active(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol,
+                                                const unsigned int *rng, const float *cloud_frac,
+                                                const float *overlap_param, const int *idx, const int *nact,
+                                                unsigned int *mask_bits)
+{
+  return sampled_mask_active(ctx, "sampled_mask_exp_ran_seeded_active", true, true, ngpt, nlay, ncol, rng, cloud_frac,
+                             overlap_param, idx, nact, mask_bits);
 }
 
 int rrtmgpnn_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int nbnd, const int *band_lims_gpt,

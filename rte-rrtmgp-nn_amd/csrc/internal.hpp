@@ -84,8 +84,8 @@ struct SolverExtras {
   // increment) beside the all-sky problem; broadband outputs only
   float *clr_up = nullptr, *clr_dn = nullptr, *clr_dir = nullptr;
   // rrtmgpnn_solver_request_active_columns: one device word, the number of columns (the first *nact of the call's ncol)
-  // the kernel solves; only the checkpointed SW launcher has such instances (kSolverSwCkActive), for g == NULL, without
-  // any of the above
+  // the kernel solves; only the checkpointed SW launcher has such instances, for g == NULL: kSolverSwCkActive without
+  // any of the above, kSolverSwCkActiveSky beside mask_bits and / or a 2str aerosol (rows of the call's ncol both)
   const int *nact = nullptr;
 };
 
@@ -286,7 +286,8 @@ enum SolverFamily {
   kSolverLwRescl = 4,      // lw_rescl_kernel (kernels_lw_scat.hip)
   kSolverSw2Stream = 5,    // sw_2stream_kernel (kernels_rte.hip)
   kSolverSwX2 = 6,         // sw_2stream_x2_kernel (kernels_sw_x2.hip)
-  kSolverSwCkActive = 7    // sw_2stream_ck_kernel, the active-count instances (rrtmgpnn_solver_request_active_columns)
+  kSolverSwCkActive = 7,   // sw_2stream_ck_kernel, the active-count instances (rrtmgpnn_solver_request_active_columns)
+  kSolverSwCkActiveSky = 8  // ... those beside a cloud mask and / or an aerosol (a McICA step on daylit columns)
 };
 // lw_noscat_kernel
 constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand = 8, kLwOptDual = 16, kLwOptMask = 32,
@@ -295,7 +296,8 @@ constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand =
 // (kCk*Small, VSmall), else the default set
 constexpr uint32_t kSwCkHasG = 1, kSwCkInc = 2, kSwCkGpt = 4, kSwCkTn = 8, kSwCkEmk = 16, kSwCkBandPair = 32,
                    kSwCkBand = 64, kSwCkMask = 128, kSwCkAer = 256, kSwCkDual = 512, kSwCkSmall = 1024,
-                   kSwCkActive = 2048;  // the active-column count comes from a device word (family kSolverSwCkActive)
+                   kSwCkActive = 2048;  // the active-column count comes from a device word (families kSolverSwCkActive,
+                                        // kSolverSwCkActiveSky)
 // lw_rescl_planck_inc_kernel
 constexpr uint32_t kScatOptMask = 1, kScatOptAer = 2, kScatOptDual = 4;
 // lw_rescl_kernel
@@ -350,6 +352,11 @@ int launch_sampled_mask(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay,
 // the seeded route: rng is the four device words {seed low, seed high, stream, col0} (rrtmgpnn_mcica_rng_set)
 int launch_sampled_mask_seeded(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, int nlay, int ncol, const uint32_t *rng,
                                const float *cloud_frac, const float *overlap, unsigned char *mask, uint32_t *bits);
+// the mask of a block compacted to its daylit columns (rrtmgpnn_daylit_plan's idx and count): src is randoms, or rng
+// when seeded; packed words only, row j of bits from source column idx[j], rows at or past the count untouched
+int launch_sampled_mask_active(rrtmgpnn_context *ctx, bool exp_ran, bool seeded, int ngpt, int nlay, int ncol,
+                               const void *src, const float *cloud_frac, const float *overlap, const int *idx,
+                               const int *nact, uint32_t *bits);
 int launch_mcica_randoms(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const uint32_t *rng, float *randoms);
 int launch_draw_samples(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, const BandArgs &bands,
                         const unsigned char *mask, const float *tau_bnd, const float *ssa_bnd, const float *g_bnd,

@@ -119,6 +119,23 @@ __global__ void __launch_bounds__(kColThreads)
   }
 }
 
+// Long rows (an aerosol's band array: (nbnd, nlay) floats per column), where 64 columns per block would leave a block
+// hundreds of dependent steps: block (j, y) copies row idx[j] of array y to row j with its lanes side by side; blocks at
+// or past the count exit.  Chosen for a table whose rows are all at least kLongRow floats (launch_gather_columns)
+namespace {
+constexpr int kLongRow = 256;
+}
+__global__ void __launch_bounds__(kColThreads)
+    gather_rows_kernel(int ncol, ColumnTable t, const int *__restrict__ idx, const int *__restrict__ nday_p)
+{
+  const int j = blockIdx.x;
+  if (j >= min(*nday_p, ncol)) return;
+  const int a = blockIdx.y, r = t.row[a];
+  const float *__restrict__ src = t.src[a] + (size_t)idx[j] * r;
+  float *__restrict__ dst = t.dst[a] + (size_t)j * r;
+  for (int k = threadIdx.x; k < r; k += kColThreads) dst[k] = src[k];
+}
+
 // Block (x, y): columns [64 x, 64 x + 64) of array y.  Column i of out from dense row slot[i], zeros where slot[i] < 0:
 // the driver's zeroing of the unused columns, here also of flux_dir
 __global__ void __launch_bounds__(kColThreads)
@@ -151,6 +168,13 @@ int launch_daylit_plan(rrtmgpnn_context *ctx, int ncol, const float *v, int kind
 int launch_gather_columns(rrtmgpnn_context *ctx, int ncol, const ColumnTable &t, const int *idx, const int *nday)
 {
   if (ncol == 0 || t.n == 0) return RRTMGPNN_OK;
+  bool long_rows = true;
+  for (int a = 0; a < t.n; a++) long_rows = long_rows && t.row[a] >= kLongRow;
+  if (long_rows) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(ncol, t.n), dim3(kColThreads), 0, ctx->stream, ncol, t, idx, nday);
+    RRTMGPNN_LAUNCH_CHECK("gather_rows_kernel");
+    return RRTMGPNN_OK;
+  }
   const dim3 grid((ncol + kColsPerBlock - 1) / kColsPerBlock, t.n);
   hipLaunchKernelGGL(gather_columns_kernel, grid, dim3(kColThreads), 0, ctx->stream, ncol, t, idx, nday);
   RRTMGPNN_LAUNCH_CHECK("gather_columns_kernel");

@@ -6,6 +6,8 @@
 //  * draw_samples_kernel : apply_cloud_mask (:291-307): the band value where the mask is set, else 0
 //  * the seeded route (no reference counterpart): sampled_mask_kernel<kExp, true> draws its random numbers itself, and
 //    mcica_randoms_kernel writes the same stream out as an array (the generator is described below)
+//  * the compact masks (no reference counterpart): sampled_mask_kernel<kExp, kSeeded, true> samples the packed mask of
+//    a block compacted to its daylit columns (rrtmgpnn_daylit_plan), dense row j from source column idx[j]
 //
 // The extension predates this fork's layout (as mo_heating_rates does); here randoms and both masks are
 // (ngpt, nlay, ncol), cloud_frac (nlay, ncol) and overlap_param (nlay-1, ncol), first index fastest.
@@ -67,16 +69,31 @@ __device__ __forceinline__ float philox_unit(uint32_t w) { return (float)(w >> 8
 // layers of prefetched randoms become one Philox call per lane per group of kMaskPf layers, skipped by the whole block
 // where none of the group's layers is cloudy (cloud_frac is uniform over the block and a deviate is consumed only at a
 // cloudy layer, so the skip is exact).  Everything after the deviate is the same statements.
-template <bool kExp, bool kSeeded = false>
+// kCompact (the _active entries: the mask of a block compacted to its daylit columns, rrtmgpnn_daylit_plan): block j
+// samples source column idx[j] -- its cloud_frac, overlap_param, randoms and, seeded, its counter word col0 + idx[j],
+// so a column has the same clouds compacted or not -- and writes row j of the dense packed mask; blocks at or past
+// min(max(*nact, 0), ncol) return at once (ncol is the grid).  The plan takes the byte mask's argument slot (the
+// compact entries write packed words only), so the other instances keep their arguments.
+struct MaskPlan {
+  const int *idx, *nact;
+};
+using MaskBytes = unsigned char *__restrict__;
+template <bool kExp, bool kSeeded = false, bool kCompact = false>
 __global__ void __launch_bounds__(kMaskMaxT)
     sampled_mask_kernel(int ngpt, int nlay, const std::conditional_t<kSeeded, uint32_t, float> *__restrict__ src,
                         const float *__restrict__ cloud_frac, const float *__restrict__ overlap,
-                        unsigned char *__restrict__ mask, uint32_t *__restrict__ bits)
+                        std::conditional_t<kCompact, MaskPlan, MaskBytes> mask, uint32_t *__restrict__ bits)
 {
-  const int icol = blockIdx.x, nw = (ngpt + 31) / 32;
+  int icol = blockIdx.x;
+  const int nw = (ngpt + 31) / 32;
+  if constexpr (kCompact) {
+    if ((int)blockIdx.x >= min(max(*mask.nact, 0), (int)gridDim.x)) return;
+    icol = mask.idx[blockIdx.x];
+  }
   const float *cf = cloud_frac + (size_t)nlay * icol;
   const float *ov = kExp ? overlap + (size_t)(nlay - 1) * icol : nullptr;
   const size_t col = (size_t)nlay * icol;  // this column's first (layer, column) row
+  const size_t ocol = kCompact ? (size_t)nlay * blockIdx.x : col;  // ... and that of its output
   uint32_t k0 = 0, k1 = 0, stream = 0, gcol = 0;  // seeded: rng, read once per block (block-uniform loads)
   if constexpr (kSeeded) {
     k0 = src[0];
@@ -130,13 +147,14 @@ __global__ void __launch_bounds__(kMaskMaxT)
           }
           const bool m = on && cloudy && local > (1.0f - frac);
           prev = cloudy;
-          if (mask && on) mask[g + (size_t)ngpt * (col + l)] = m ? 1 : 0;
-          if (bits) {
+          if constexpr (!kCompact)
+            if (mask && on) mask[g + (size_t)ngpt * (col + l)] = m ? 1 : 0;
+          if (kCompact || bits) {
             // bit g % 32 of word g / 32: the wave's ballot holds two words, stored by its first lane
             const unsigned long long b = __ballot(m);
             if ((threadIdx.x & 63) == 0) {
               const int w = g >> 5;
-              uint32_t *o = bits + (size_t)nw * (col + l);
+              uint32_t *o = bits + (size_t)nw * (ocol + l);
               o[w] = (uint32_t)b;
               if (w + 1 < nw) o[w + 1] = (uint32_t)(b >> 32);
             }
@@ -174,6 +192,25 @@ int launch_sampled_mask_seeded(rrtmgpnn_context *ctx, bool exp_ran, int ngpt, in
     hipLaunchKernelGGL((sampled_mask_kernel<false, true>), dim3(ncol), dim3(threads), 0, ctx->stream, ngpt, nlay, rng,
                        cloud_frac, overlap, mask, bits);
   RRTMGPNN_LAUNCH_CHECK("sampled_mask_kernel (seeded)");
+  return RRTMGPNN_OK;
+}
+
+// the compact masks (kCompact): src is randoms or rng; the grid is the launch-time ncol, the count a device word
+int launch_sampled_mask_active(rrtmgpnn_context *ctx, bool exp_ran, bool seeded, int ngpt, int nlay, int ncol,
+                               const void *src, const float *cloud_frac, const float *overlap, const int *idx,
+                               const int *nact, uint32_t *bits)
+{
+  if (ncol == 0) return RRTMGPNN_OK;
+  const int threads = std::min((ngpt + 63) / 64 * 64, kMaskMaxT);
+  const MaskPlan plan{idx, nact};
+  auto go = [&](auto kern, auto *s) {
+    hipLaunchKernelGGL(kern, dim3(ncol), dim3(threads), 0, ctx->stream, ngpt, nlay, s, cloud_frac, overlap, plan, bits);
+  };
+  if (seeded && exp_ran) go(sampled_mask_kernel<true, true, true>, (const uint32_t *)src);
+  else if (seeded) go(sampled_mask_kernel<false, true, true>, (const uint32_t *)src);
+  else if (exp_ran) go(sampled_mask_kernel<true, false, true>, (const float *)src);
+  else go(sampled_mask_kernel<false, false, true>, (const float *)src);
+  RRTMGPNN_LAUNCH_CHECK("sampled_mask_kernel (compact)");
   return RRTMGPNN_OK;
 }
 

@@ -1186,11 +1186,12 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: clear + all-sky fluxes from one launch are taken by the checkpointed "
                                           "kernel only (even ngpt <= 256, the fused band increment, broadband outputs)");
   // the daylit columns of a compacted block (rrtmgpnn_solver_request_active_columns): only the checkpointed kernel reads
-  // the count (the entries refuse the other requests beside it before they get here)
-  if (ex.nact && (!ck || gpt || bb || dual || ex.mask_bits || ex.aer_tau))
+  // the count, alone or beside a cloud mask and / or an aerosol (the entries refuse the other requests beside it before
+  // they get here)
+  if (ex.nact && (!ck || gpt || bb || dual))
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count is taken by the checkpointed kernel only (even "
-                                          "ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), without other requests or "
-                                          "g-point outputs");
+                                          "ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band, g-point or "
+                                          "clear-sky outputs");
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
   // the other kernels read them from memory, formed there first by sw_boundary_kernel
   SwBcDev bcd{};

@@ -324,15 +324,18 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
   constexpr bool kTn = (O & kSwCkTn) != 0, kEmk = (O & kSwCkEmk) != 0, kBandPair = (O & kSwCkBandPair) != 0;
   constexpr bool kBand = (O & kSwCkBand) != 0, kMask = (O & kSwCkMask) != 0, kAer = (O & kSwCkAer) != 0;
   constexpr bool kDual = (O & kSwCkDual) != 0, kSmall = (O & kSwCkSmall) != 0, kActive = (O & kSwCkActive) != 0;
-  static_assert(!kActive || (!kMask && !kAer && !kDual && !kGpt && !kBand && !kHasG),
-                "the active-count instances: clear sky or the fused increment, broadband outputs");
+  static_assert(!kActive || (!kDual && !kGpt && !kBand && !kHasG),
+                "the active-count instances: clear sky or the fused increment (masked, behind an aerosol), broadband "
+                "outputs");
   // kActive (rrtmgpnn_solver_request_active_columns): the block solves columns below *nact, a device word read here,
-  // before any barrier -- the word arrives in cmask's place (no instance has both a mask and a count), so every other
-  // instance keeps its arguments.  ncol stays the launch's in everything that lays out memory (the checkpoints pW, the
-  // planes); nca bounds the columns a block works on and the flush stores
+  // before any barrier -- the word arrives in cmask's place or, in the instances that have a mask or an aerosol
+  // (family kSolverSwCkActiveSky), in clr_up's, which only the dual instances use; so every other instance keeps its
+  // arguments.  ncol stays the launch's in everything that lays out memory (the checkpoints pW, the planes, the mask's
+  // and the aerosol's rows); nca bounds the columns a block works on and the flush stores
   int nca = ncol;
   if constexpr (kActive) {
-    nca = min(max(*(const int *)cmask, 0), ncol);  // never past the allocation
+    const int *const nactp = (kMask || kAer) ? (const int *)clr_up : (const int *)cmask;
+    nca = min(max(*nactp, 0), ncol);  // never past the allocation
     if ((int)blockIdx.x * ncb >= nca) return;
   }
   // chunk length, ring levels, wave floor, pass-1 chunks per step and prefetch distance: the small-grid set or the default
@@ -866,6 +869,17 @@ using SwCkActiveInstances = SolverInstances<
     kSwCkActive | kSwCkInc | kSwCkBandPair | kSwCkPlanesInc, kSwCkActive | kSwCkInc | kSwCkBandPair,
     kSwCkActive | kSwCkInc | kSwCkPlanesInc, kSwCkActive | kSwCkInc>;
 
+// ... and the count beside a cloud mask and / or an aerosol (kSolverSwCkActiveSky): what a McICA step on compacted daylit
+// columns selects -- the masked cloud ({band pair} x {the all-sky plane}), the aerosol in front of it and the aerosol in
+// front of an unmasked cloud (band pair, with the plane and without); no gas g.  The mask's and the aerosol's rows are
+// those of the dense columns (extents of the launch-time ncol)
+using SwCkActiveSkyInstances = SolverInstances<
+    kSwCkActive | kSwCkInc | kSwCkMask | kSwCkBandPair | kSwCkPlanesInc, kSwCkActive | kSwCkInc | kSwCkMask | kSwCkBandPair,
+    kSwCkActive | kSwCkInc | kSwCkMask | kSwCkPlanesInc, kSwCkActive | kSwCkInc | kSwCkMask,
+    kSwCkActive | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc,
+    kSwCkActive | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair,
+    kSwCkActive | kSwCkInc | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc, kSwCkActive | kSwCkInc | kSwCkAer | kSwCkBandPair>;
+
 // The instance a call runs (its options value), or the refusal.  planes: the workspace with the instance family's
 // planes was allocated (launch_sw_2stream's fallback runs the plane-free twins: the same bits); small: sw_ck_small()
 static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes, bool small, uint32_t *options)
@@ -879,13 +893,27 @@ static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes,
   if (ex.nact) {
     // the daylit columns of a compacted block: the instance the same call would run without the count (chosen from the
     // launch-time ncol: the host never sees the count), from the family's own list
-    if (ex.clr_up || ex.aer_tau || ex.mask_bits || bb || gpt)
-      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count with clear-sky twins, aerosols, a cloud "
-                                            "mask, by-band or g-point outputs");
+    if (ex.clr_up || bb || gpt)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count with clear-sky twins, by-band or g-point "
+                                            "outputs");
     if (p.g)
       return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count with a gas g array (g == NULL: the NN path)");
-    o |= kSwCkActive | (bands ? (pair ? kSwCkBandPair : 0u) | (planes ? kSwCkPlanesInc : 0u)
-                              : (small ? kSwCkSmall | kSwCkPlanesSmall : (planes ? kSwCkPlanesNN : 0u)));
+    if (ex.aer_tau) {
+      // kSolverSwCkActiveSky: the rules of the aerosol branch below, then those of the mask branch
+      if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: an aerosol increment needs the fused band increment behind it");
+      if (!ex.aer_ssa || !ex.aer_g)
+        return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
+      if (!pair)
+        return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an aerosol increment needs every band to start at an odd "
+                                              "(1-based) g-point, the band-pair layout");
+      o |= kSwCkActive | kSwCkAer | kSwCkBandPair | (planes ? kSwCkPlanesInc : 0u);
+    } else if (ex.mask_bits) {
+      if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: a cloud mask needs the fused band increment");
+      o |= kSwCkActive | (pair ? kSwCkBandPair : 0u) | (planes ? kSwCkPlanesInc : 0u);
+    } else {
+      o |= kSwCkActive | (bands ? (pair ? kSwCkBandPair : 0u) | (planes ? kSwCkPlanesInc : 0u)
+                                : (small ? kSwCkSmall | kSwCkPlanesSmall : (planes ? kSwCkPlanesNN : 0u)));
+    }
   } else if (ex.clr_up) {
     // clear-sky beside all-sky fluxes (rrtmgpnn_sw_solver_2stream_clr_all): the dual instances, one column per block,
     // one g-point per lane, two rings; {gas g} x {mask} x {aerosol}, with the planes of kCkTnDual / kCkEmkDual or, when
@@ -967,15 +995,19 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
     const auto kern = sw_2stream_ck_kernel<O>;
     if (lds > 64 * 1024)
       if (int rc = raise_lds_limit((const void *)kern)) return rc;
+    // the count word in the mask's place or, beside a mask or an aerosol, in the first clear-sky output's
+    constexpr bool kCount = (O & kSwCkActive) != 0, kSky = kCount && (O & (kSwCkMask | kSwCkAer)) != 0;
     hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, ngpt, nlay, ncol, p.top_at_1, ncb, p.inc_flux,
                        p.inc_flux_dif, p.tau, p.ssa, p.g, p.mu0, p.alb_dir, p.alb_dif, b, kInc ? p.tau_bnd : nullptr,
                        kInc ? p.ssa_bnd : nullptr, kInc ? p.g_bnd : nullptr, (float *)ws, p.flux_up, p.flux_dn,
                        p.flux_dir, ex.gpt_up, ex.gpt_dn, ex.gpt_dir, bcd, bo,
-                       (O & kSwCkActive) ? (const uint32_t *)ex.nact : ex.mask_bits,  // the count word in the mask's place
-                       ex.aer_tau, ex.aer_ssa, ex.aer_g, ex.clr_up, ex.clr_dn, ex.clr_dir);
+                       (kCount && !kSky) ? (const uint32_t *)ex.nact : ex.mask_bits, ex.aer_tau, ex.aer_ssa, ex.aer_g,
+                       kSky ? (float *)ex.nact : ex.clr_up, ex.clr_dn, ex.clr_dir);
     RRTMGPNN_LAUNCH_CHECK(kDual ? "sw_2stream_ck_kernel (clear + all sky)" : "sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
+  if (ex.nact && (ex.mask_bits || ex.aer_tau))
+    return launch_listed(ctx, kSolverSwCkActiveSky, SwCkActiveSkyInstances{}, options, go);
   if (ex.nact) return launch_listed(ctx, kSolverSwCkActive, SwCkActiveInstances{}, options, go);
   return launch_listed(ctx, kSolverSwCk, SwCkInstances{}, options, go);
 }

@@ -34,6 +34,8 @@ module mo_rrtmgpnn_c
             c_rrtmgpnn_draw_samples
   public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
             c_rrtmgpnn_sampled_mask_exp_ran_seeded
+  public :: c_rrtmgpnn_sampled_mask_max_ran_active, c_rrtmgpnn_sampled_mask_exp_ran_active, &
+            c_rrtmgpnn_sampled_mask_max_ran_seeded_active, c_rrtmgpnn_sampled_mask_exp_ran_seeded_active
   public :: c_rrtmgpnn_present, c_rrtmgpnn_present_update_host, c_rrtmgpnn_present_delete  ! masks (mo_cloud_sampling)
   public :: c_rrtmgpnn_network_load, c_rrtmgpnn_compute_nn_inputs, c_rrtmgpnn_get_col_dry, &
             c_rrtmgpnn_interpolate_tlev, c_rrtmgpnn_predict_nn_lw, c_rrtmgpnn_predict_nn_sw, &
@@ -513,6 +515,31 @@ module mo_rrtmgpnn_c
         overlap_param, cloud_mask, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_exp_ran_seeded")
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, rng, cloud_frac, overlap_param, cloud_mask, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    ! the packed masks of a block compacted to its daylit columns: idx and nact are rrtmgpnn_daylit_plan's idx and nday
+    integer(c_int) function c_rrtmgpnn_sampled_mask_max_ran_active(ctx, ngpt, nlay, ncol, randoms, cloud_frac, idx, nact, &
+        mask_bits) bind(C, name="rrtmgpnn_sampled_mask_max_ran_active")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, randoms, cloud_frac, idx, nact, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_exp_ran_active(ctx, ngpt, nlay, ncol, randoms, cloud_frac, &
+        overlap_param, idx, nact, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_exp_ran_active")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, randoms, cloud_frac, overlap_param, idx, nact, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_max_ran_seeded_active(ctx, ngpt, nlay, ncol, rng, cloud_frac, idx, &
+        nact, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_max_ran_seeded_active")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rng, cloud_frac, idx, nact, mask_bits
+      integer(c_int), value :: ngpt, nlay, ncol
+    end function
+    integer(c_int) function c_rrtmgpnn_sampled_mask_exp_ran_seeded_active(ctx, ngpt, nlay, ncol, rng, cloud_frac, &
+        overlap_param, idx, nact, mask_bits) bind(C, name="rrtmgpnn_sampled_mask_exp_ran_seeded_active")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, rng, cloud_frac, overlap_param, idx, nact, mask_bits
       integer(c_int), value :: ngpt, nlay, ncol
     end function
     integer(c_int) function c_rrtmgpnn_draw_samples(ctx, ngpt, nlay, ncol, nbnd, band_lims_gpt, cloud_mask, tau_bnd, &

@@ -132,6 +132,10 @@ SIGNATURES = {
     "rrtmgpnn_mcica_randoms": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     "rrtmgpnn_sampled_mask_max_ran_seeded": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_sampled_mask_exp_ran_seeded": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rrtmgpnn_sampled_mask_max_ran_active": (c_int, [c_vp, c_int, c_int, c_int] + [c_vp] * 5),
+    "rrtmgpnn_sampled_mask_exp_ran_active": (c_int, [c_vp, c_int, c_int, c_int] + [c_vp] * 6),
+    "rrtmgpnn_sampled_mask_max_ran_seeded_active": (c_int, [c_vp, c_int, c_int, c_int] + [c_vp] * 5),
+    "rrtmgpnn_sampled_mask_exp_ran_seeded_active": (c_int, [c_vp, c_int, c_int, c_int] + [c_vp] * 6),
     "rrtmgpnn_draw_samples": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp]),
     "rrtmgpnn_sum_byband": (c_int, [c_vp, c_int, c_int, c_int, c_int, P(c_int), c_vp, c_vp]),

@@ -1046,13 +1046,19 @@ def rte_lw(optical_props, top_at_1, sources, sfc_emis, fluxes, inc_flux=None, n_
     return ""
 
 
-def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, fluxes, inc_flux_dif=None, active=None):
+def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, fluxes, inc_flux_dif=None, active=None,
+           band_inc=None):
     """rte/mo_rte_sw.F90:48-266 (fork: albedos per g-point (ncol, ngpt)).  1scl: the direct beam (sw_solver_noscat);
     2str: sw_solver_2stream.
     active: a rrtmgpnn.daylit plan, or its count word (an int32 device tensor of one element): the arrays are dense
     (daylit.gather) and only their first nday columns are solved (rrtmgpnn_solver_request_active_columns, armed right
     ahead of the solver call); flux rows at or past the count are left as they are.  Two-stream, broadband fluxes,
-    atmos.g None."""
+    atmos.g None.
+    band_inc (an extension of the reference's interface): a two-stream set by band on atmos's bands, (ncol, nlay, nband),
+    that the solver adds to atmos as it reads it (rrtmgpnn_sw_solver_2stream_inc; atmos is left as it was) -- the entry
+    that takes the requests armed ahead of this call with cloud_sampling.arm_cloud_mask (band_inc is then the cloud the
+    mask samples) and cloud_sampling.arm_aerosol, alone or beside active (then on the dense columns: a mask from
+    daylit.sampled_mask_active, a gathered aerosol).  Two-stream, no g-point fluxes."""
     if not fluxes.are_desired():
         return "rte_sw: no space allocated for fluxes"
     if not isinstance(atmos, (OpticalProps1scl, OpticalProps2str)):
@@ -1077,6 +1083,11 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
             return e
     if active is not None and (isinstance(atmos, OpticalProps1scl) or fluxes.are_desired_gpt()):
         return "rte_sw: active columns go with the two-stream solver and broadband fluxes"
+    if band_inc is not None:
+        if isinstance(atmos, OpticalProps1scl) or not isinstance(band_inc, OpticalProps2str) or fluxes.are_desired_gpt():
+            return "rte_sw: a band increment goes with the two-stream solver, without g-point fluxes"
+        if not band_inc.bands_are_equal(atmos) or tuple(band_inc.tau.shape) != (ncol, nlay, atmos.get_nband()):
+            return "rte_sw: the band increment is not defined by band on the atmosphere's bands and extents"
     if isinstance(atmos, OpticalProps1scl):
         # direct beam only (:213-222): apply_BC_factor + sw_solver_noscat; as in the reference only the direct flux
         # is written (flux_up / flux_dn / flux_net are left as they are)
@@ -1120,10 +1131,17 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
         if active is not None:
             word = getattr(active, "nday", active)
             check(_lib.lib().rrtmgpnn_solver_request_active_columns(ctx.h, ncol, _p(word)), "solver_request_active_columns")
-        check(_lib.lib().rrtmgpnn_sw_solver_2stream(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux),
-                                                    _p(inc_flux_dif), _p(atmos.tau), _p(atmos.ssa), _p(atmos.g),
-                                                    _p(mu0), _p(sfc_alb_dir_gpt), _p(sfc_alb_dif_gpt), _p(up),
-                                                    _p(dn), _p(dr)), "sw_solver_2stream")
+        if band_inc is not None:
+            check(_lib.lib().rrtmgpnn_sw_solver_2stream_inc(
+                ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux), _p(inc_flux_dif), _p(atmos.tau),
+                _p(atmos.ssa), _p(atmos.g), atmos.get_nband(), int_array(atmos.band_lims_gpt.ravel()), _p(band_inc.tau),
+                _p(band_inc.ssa), _p(band_inc.g), _p(mu0), _p(sfc_alb_dir_gpt), _p(sfc_alb_dif_gpt), _p(up), _p(dn),
+                _p(dr)), "sw_solver_2stream_inc")
+        else:
+            check(_lib.lib().rrtmgpnn_sw_solver_2stream(ctx.h, ngpt, nlay, ncol, int(bool(top_at_1)), _p(inc_flux),
+                                                        _p(inc_flux_dif), _p(atmos.tau), _p(atmos.ssa), _p(atmos.g),
+                                                        _p(mu0), _p(sfc_alb_dir_gpt), _p(sfc_alb_dif_gpt), _p(up),
+                                                        _p(dn), _p(dr)), "sw_solver_2stream")
     if bb and fluxes.bnd_flux_net is not None:
         torch.sub(fluxes.bnd_flux_dn, fluxes.bnd_flux_up, out=fluxes.bnd_flux_net)
     if fluxes.flux_net is not None:

@@ -10,8 +10,16 @@ the daylit columns instead:
     api.rte_sw(dense_atmos, ..., dense_fluxes, active=pl)        # or daylit.arm_active_columns(ctx, pl) + a C entry
     daylit.scatter(pl, [(d_flux_up, flux_up), ...])              # zeros at night
 
+With McICA-sampled clouds the packed mask is sampled for the compacted columns directly, from the full-extent cloud
+fraction, overlap parameter and random numbers (nothing is gathered for it), and armed beside the count:
+
+    daylit.sampled_mask_active(pl, randoms, cloud_frac, mask_bits, overlap_param)    # or sampled_mask_seeded_active
+    cloud_sampling.arm_cloud_mask(ctx, ngpt, mask_bits)                               # and arm_aerosol(ctx, dense_aer)
+    api.rte_sw(dense_atmos, ..., dense_fluxes, active=pl, band_inc=dense_clouds_by_band)
+
 nday never leaves the device: the network and solver kernels read it, so the sequence can be captured in a hipGraph
-once and replayed for any day / night pattern.  pipeline.ClearSkyStep(daylit=True) is this sequence as a step.
+once and replayed for any day / night pattern.  pipeline.ClearSkyStep(daylit=True) is this sequence as a step, and
+ClearSkyStep(clouds=, mcica={..., "daylit": True}) the one with sampled clouds (and aerosols).
 plan_host is the numpy restatement the tests compare with."""
 import numpy as np
 
@@ -95,6 +103,48 @@ def scatter(pl, pairs):
     src, dst, rows, n, dev = _table(pl, pairs, "scatter", MAX_SCATTER)
     check(_lib.lib().rrtmgpnn_scatter_columns(_ctx(dev).h, pl.ncol, n, src, dst, rows, pl.slot.data_ptr()),
           "scatter_columns")
+
+
+def _compact_mask(who, pl, src, cloud_frac, overlap_param, mask_bits, ngpt, ctx):
+    import torch
+    exp_ran = overlap_param is not None
+    if cloud_frac.dim() != 2 or cloud_frac.shape[0] != pl.ncol or cloud_frac.dtype != torch.float32:
+        raise ValueError("daylit.%s: cloud_frac is a float32 (ncol, nlay) tensor of the plan's ncol" % who)
+    ncol, nlay = cloud_frac.shape
+    if exp_ran and tuple(overlap_param.shape) != (ncol, nlay - 1):
+        raise ValueError("daylit.%s: overlap_param is (ncol, nlay - 1)" % who)
+    if tuple(mask_bits.shape) != (ncol, nlay, (int(ngpt) + 31) // 32) or mask_bits.element_size() != 4:
+        raise ValueError("daylit.%s: mask_bits is not (ncol, nlay, ceil(ngpt/32)) 32-bit words" % who)
+    if not all(t is None or t.is_contiguous() for t in (src, cloud_frac, overlap_param, mask_bits)):
+        raise ValueError("daylit.%s: arrays must be contiguous" % who)
+    ctx = ctx or _ctx(cloud_frac.device)
+    head = (ctx.h, int(ngpt), nlay, ncol, src.data_ptr(), cloud_frac.data_ptr())
+    tail = (pl.idx.data_ptr(), pl.nday.data_ptr(), mask_bits.data_ptr())
+    if exp_ran:
+        head += (overlap_param.data_ptr() if nlay > 1 else None,)
+    check(getattr(_lib.lib(), "rrtmgpnn_" + who)(*head, *tail), who)
+
+
+def sampled_mask_active(pl, randoms, cloud_frac, mask_bits, overlap_param=None, ctx=None):
+    """The packed McICA mask of the plan's daylit columns from the caller's randoms (ncol, nlay, ngpt): row j < nday of
+    the dense mask_bits (ncol, nlay, ceil(ngpt / 32)) is column idx[j]'s mask, sampled from that column's randoms,
+    cloud_frac (ncol, nlay) and overlap_param (ncol, nlay - 1) in place; rows at or past nday are left as they were.
+    overlap_param None: maximum-random overlap, else exponential-random.  ctx: the api.Context to launch on."""
+    import torch
+    if randoms.dim() != 3 or tuple(randoms.shape[:2]) != tuple(cloud_frac.shape) or randoms.dtype != torch.float32:
+        raise ValueError("daylit.sampled_mask_active: randoms is a float32 (ncol, nlay, ngpt) tensor")
+    who = "sampled_mask_exp_ran_active" if overlap_param is not None else "sampled_mask_max_ran_active"
+    _compact_mask(who, pl, randoms, cloud_frac, overlap_param, mask_bits, randoms.shape[2], ctx)
+
+
+def sampled_mask_seeded_active(pl, rng, cloud_frac, mask_bits, ngpt, overlap_param=None, ctx=None):
+    """As sampled_mask_active with the random numbers drawn in the kernel: rng is the 4-word device buffer of
+    rrtmgpnn_mcica_rng_set {seed low, seed high, stream, col0}, and dense column j draws with the counter word
+    col0 + idx[j] -- the clouds column idx[j] has in a block that is not compacted."""
+    if rng.numel() != 4 or rng.element_size() != 4:
+        raise ValueError("daylit.sampled_mask_seeded_active: rng is the 4-word buffer of rrtmgpnn_mcica_rng_set")
+    who = "sampled_mask_exp_ran_seeded_active" if overlap_param is not None else "sampled_mask_max_ran_seeded_active"
+    _compact_mask(who, pl, rng, cloud_frac, overlap_param, mask_bits, ngpt, ctx)
 
 
 def arm_active_columns(ctx, pl):

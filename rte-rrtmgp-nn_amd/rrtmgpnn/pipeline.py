@@ -99,6 +99,19 @@ rrtmgpnn_solver_request_active_columns and the _rfmip solver; rrtmgpnn_scatter_c
 count of daylit columns is a device word that the network and the solver read, so a captured step follows the sun:
 set_sza() between replays, no recapture.  The LW chain is untouched.  Not with mcica, aerosols, clrsky, byband, sw_dual,
 fused=False, sw=False, capture_chains or run_blocks.  Off (the default), nothing of the step changes.
+
+mcica={..., "daylit": True} (fused): the daylit-column SW chain under McICA-sampled clouds, with aerosols= and the "clrsky"
+key where given -- the configuration of a weather or climate host.  The chain is the daylit=True one with four
+differences.  The aerosol's three SW band arrays are gathered too, in a rrtmgpnn_gather_columns call of their own (their
+rows are long: the call runs the long-row gather kernel), and the other arrays take a second call where they exceed 16.  The packed mask is sampled for the compacted columns directly, by the _active twin of the step's
+mask entry: dense column j reads cloud_frac, overlap_param and the random numbers of column idx[j] in place -- none of
+them is gathered -- and, seeded, draws with the counter word col0 + idx[j], so a column has the clouds it has in the
+step without "daylit".  The solver call has the cloud-mask, the aerosol (where given) and the active-column requests
+armed together (solver family 8).  With "clrsky", the active-column request is armed again (sw_active_clr) for the clear
+launch, which takes the aerosol as its own increment or none (family 7), and one rrtmgpnn_scatter_columns writes all six
+SW flux arrays, zeros at night in each.  The LW chain is untouched: full extent, its own mask and stream.  set_sza,
+set_aerosols, set_mcica_seed and set_mcica_randoms work between graph replays without recapture.  Not with
+mcica["byband"], sw_dual, fused=False, capture_chains or run_blocks; daylit=True beside it is refused as above.
 """
 
 from types import SimpleNamespace
@@ -115,7 +128,8 @@ from .api import GAUSS_DS, GAUSS_WTS, Context
 SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "delta_scale_sw", "increment_sw",
             "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask",
             "mcica_randoms_sw", "sw_mask_byband", "sw_aerosol", "increment_aer_sw",
-            "daylit_plan", "daylit_gather", "sw_active", "daylit_scatter"}
+            "daylit_plan", "daylit_gather", "sw_active", "daylit_scatter",
+            "daylit_gather2", "daylit_gather3", "sw_active_clr"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
@@ -128,9 +142,12 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
 # (lw_upper_bc: an upper_bc=True step's boundary flux, at the head of the LW chain)
 # (daylit_plan / daylit_gather: a daylit=True step's compaction at the head of the SW chain; sw_active: its active-column
 # request, host-only, right before the solver; daylit_scatter: the fluxes back to their columns, behind it)
+# (daylit_gather2 / daylit_gather3: a mcica["daylit"] step's further gather calls, for what the first call's 16 arrays leave
+# and for the aerosol's long rows, which get a call of their own; sw_active_clr:
+# its active-column request for the clear launch sw_solver_clr, which in every other step is the chain's last call)
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "lw_upper_bc", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
-               "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "daylit_plan", "daylit_gather", "nn_inputs_sw", "cloud_optics_sw",
-               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_active", "sw_solver", "daylit_scatter"]
+               "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "daylit_plan", "daylit_gather", "daylit_gather2", "daylit_gather3", "nn_inputs_sw", "cloud_optics_sw",
+               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_active", "sw_solver", "sw_active_clr", "sw_solver_clr", "daylit_scatter"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -213,6 +230,15 @@ class ClearSkyStep:
                 raise ValueError("daylit=True with %s is not supported: the daylit-column SW chain is the fused clear-sky "
                                  "or overcast one, broadband only (the active-count network and solver instances)"
                                  % ", ".join(bad))
+        self.mcica_daylit = mcica is not None and bool(mcica.get("daylit"))
+        if self.mcica_daylit:
+            # (before any device object exists; daylit=True beside it was refused above)
+            bad = [w for w, on in (("mcica['byband']", bool(mcica.get("byband"))), ("sw_dual", bool(sw_dual)),
+                                   ("fused=False", not fused)) if on]
+            if bad:
+                raise ValueError("mcica['daylit'] with %s is not supported: the daylit-column McICA SW chain is the fused "
+                                 "one with one solver launch per sky, broadband only (the active-count masked and aerosol "
+                                 "solver instances)" % ", ".join(bad))
         self.lw_dual = bool(lw_dual)
         self.upper_bc = bool(upper_bc)
         if self.lw_dual:
@@ -405,7 +431,7 @@ class ClearSkyStep:
             if sw:
                 self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (
                     f(ncol, nlay + 1, self.kd_sw["nband"]) for _ in range(3))
-        if self.daylit:
+        if self.daylit or self.mcica_daylit:
             self._allocate_daylit()
 
     def _allocate_daylit(self):
@@ -423,7 +449,11 @@ class ClearSkyStep:
         for t, n in self._day_pairs:
             setattr(self, "d_" + n, t.clone())
         self.d_sw_up, self.d_sw_dn, self.d_sw_dir = (torch.zeros_like(self.sw_up) for _ in range(3))
-        if len(self._day_pairs) > 16:
+        self._day_pairs_aer = []
+        if self.mcica_daylit and self.clrsky:
+            self.d_sw_up_clr, self.d_sw_dn_clr, self.d_sw_dir_clr = (torch.zeros_like(self.sw_up) for _ in range(3))
+        # (a mcica["daylit"] step gathers in as many calls as its list needs: its aerosol arrays join in _allocate_aerosols)
+        if len(self._day_pairs) > 16 and not self.mcica_daylit:
             raise ValueError("daylit=True: more than 16 arrays to gather")
 
     def set_sza(self, sza):
@@ -457,6 +487,10 @@ class ClearSkyStep:
             w, q = k.split("_")
             setattr(self, "aer_%s_%s" % (q, w), torch.empty(shape, dtype=torch.float32, device=self.dev))
         self.set_aerosols(**aerosols)
+        if self.mcica_daylit:  # the SW aerosol of the daylit columns: dense twins, gathered every step
+            for n in ("aer_tau_sw", "aer_ssa_sw", "aer_g_sw"):
+                setattr(self, "d_" + n, getattr(self, n).clone())
+                self._day_pairs_aer.append((getattr(self, n), n))
 
     def set_aerosols(self, lw_tau=None, sw_tau=None, sw_ssa=None, sw_g=None):
         """Copy new aerosol properties into the step's buffers (None keeps an array) between steps or graph replays;
@@ -774,7 +808,7 @@ class ClearSkyStep:
         h2o = (self.gases["h2o"].data_ptr(),)
         delta_scale = [("delta_scale_sw", L.rrtmgpnn_delta_scale_2str,
                         (c, ncol * nlay * self.nb_sw) + ch.cld + (None,))] if self.allsky else []
-        if self.daylit:
+        if self.daylit or self.mcica_daylit:
             return self._sw_chain_daylit()
         if self.fused:
             # the boundary conditions and (all sky) clouds%increment(atmos) fused into the solver
@@ -840,6 +874,8 @@ class ClearSkyStep:
         L, c, ncol, nlay, p, ch = self.L, self.ctx.h, self.ncol, self.nlay, self._p, self._chain_sw
         bound = float(np.float32(90.0) - np.float32(2.0) * data.spacing(90.0))
         pairs = self._day_pairs
+        if self.mcica_daylit:
+            return self._sw_chain_mcica_daylit(bound)
         rows = [int(t[0].numel()) if t.dim() > 1 else 1 for t, _ in pairs]
         # (ctypes arrays the captured calls point at: kept on the step)
         self._day_src = ptr_array([t.data_ptr() for t, _ in pairs])
@@ -869,6 +905,66 @@ class ClearSkyStep:
              + p("tau_sw", "ssa_sw") + (None,) + band_inc + p("toa", "alb", "mu0", "d_sw_up", "d_sw_dn", "d_sw_dir")),
             ("daylit_scatter", L.rrtmgpnn_scatter_columns,
              (c, ncol, 3, self._day_dense, self._day_out, self._day_out_rows) + p("day_slot")),
+        ]
+
+    def _sw_chain_mcica_daylit(self, bound):
+        """A mcica["daylit"] step's SW chain (module docstring): the daylit=True chain with the aerosol gathered too, the
+        mask sampled for the compacted columns, the three requests ahead of the all-sky launch and, with clear-sky
+        outputs, the clear launch on the active columns behind it; one scatter of three or six flux arrays."""
+        L, c, ncol, nlay, p, ch = self.L, self.ctx.h, self.ncol, self.nlay, self._p, self._chain_sw
+        pairs = self._day_pairs
+        # (ctypes arrays the captured calls point at: kept on the step) -- 16 arrays per gather call; the aerosol's band
+        # arrays (rows of nband * nlay floats) in a call of their own, which then runs the long-row gather kernel
+        self._day_tables = []
+        for part in [pairs[k:k + 16] for k in range(0, len(pairs), 16)] + ([self._day_pairs_aer] if self.aerosols else []):
+            self._day_tables.append((len(part), ptr_array([t.data_ptr() for t, _ in part]),
+                                     ptr_array([getattr(self, "d_" + n).data_ptr() for _, n in part]),
+                                     int_array([int(t[0].numel()) if t.dim() > 1 else 1 for t, _ in part])))
+        if len(self._day_tables) > 3:
+            raise ValueError("mcica['daylit']: more than three gather calls")
+        sky = ("", "_clr") if self.clrsky else ("",)
+        dense = ["d_sw_%s%s" % (k, s) for s in sky for k in ("up", "dn", "dir")]
+        self._day_dense = ptr_array(list(p(*dense)))
+        self._day_out = ptr_array(list(p(*[n[2:] for n in dense])))
+        self._day_out_rows = int_array([nlay + 1] * len(dense))
+        dense_gas = {n: getattr(self, "d_gas_" + n) for n in self._day_gases}
+        g = [dense_gas.get(n) if k >= 2 else None for k, n in enumerate(self.sw_names)]
+        self._g_sw_day = ptr_array([t.data_ptr() if t is not None else None for t in g])
+        no_inc = (0, None, None, None, None)
+        aer = p("d_aer_tau_sw", "d_aer_ssa_sw", "d_aer_g_sw")
+        aer_inc = (self.nb_sw, self._lims_sw) + aer if self.aerosols else no_inc
+        solver = lambda name, inc, *out: (  # noqa: E731
+            name, L.rrtmgpnn_sw_solver_2stream_rfmip,
+            (c, self.ng_sw, nlay, ncol, self.top_at_1) + p("solar_source", "d_tsi", "d_sfc_alb", "d_sza")
+            + p("tau_sw", "ssa_sw") + (None,) + inc + p("toa", "alb", "mu0", *out))
+        # the _active twin of the step's mask entry: the plan's idx and count in place of the byte mask
+        src, sfx = (ch.rng, "_seeded") if ch.randoms is None else (ch.randoms, "")
+        exp_ran = self.overlap_param is not None
+        mask = ("mcica_mask_sw",
+                getattr(L, "rrtmgpnn_sampled_mask_%s%s_active" % ("exp_ran" if exp_ran else "max_ran", sfx)),
+                (c, ch.ngpt, nlay, ncol, src) + p("cloud_frac") + (p("overlap_param") if exp_ran else ())
+                + p("day_idx", "nday") + (ch.bits,))
+        active = lambda name: (name, L.rrtmgpnn_solver_request_active_columns, (c, ncol) + p("nday"))  # noqa: E731
+        return [
+            ("daylit_plan", L.rrtmgpnn_daylit_plan, (c, ncol) + p("sza") + (0, bound) + p("day_idx", "day_slot", "nday")),
+            *[("daylit_gather" + ("", "2", "3")[k], L.rrtmgpnn_gather_columns, (c, ncol) + t + p("day_idx", "nday"))
+              for k, t in enumerate(self._day_tables)],
+            ("predict_nn_sw", L.rrtmgpnn_gas_optics_sw_nn_active,
+             (c, ncol, nlay, self.ng_sw, self.nx_sw) + p("d_play", "d_tlay", "d_plev", "d_gas_h2o")
+             + (self._g_sw_day, self._nd_sw, self._nets_sw) + ch.props + p("nday")),
+            ("cloud_optics_sw", L.rrtmgpnn_cloud_optics_compute,
+             (c, self.cloud_sw, ncol, nlay) + p("d_lwp", "d_iwp", "d_rel", "d_rei") + ch.cld),
+            ("delta_scale_sw", L.rrtmgpnn_delta_scale_2str, (c, ncol * nlay * self.nb_sw) + ch.cld + (None,)),
+            mask,
+            *self._request(ch),
+            *([("sw_aerosol", L.rrtmgpnn_solver_request_aerosol, (c, ch.nband, nlay, ncol) + aer)]
+              if self.aerosols else []),
+            active("sw_active"),
+            solver("sw_solver", (self.nb_sw, self._lims_sw) + ch.cld, "d_sw_up", "d_sw_dn", "d_sw_dir"),
+            *([active("sw_active_clr"), solver("sw_solver_clr", aer_inc, "d_sw_up_clr", "d_sw_dn_clr", "d_sw_dir_clr")]
+              if self.clrsky else []),
+            ("daylit_scatter", L.rrtmgpnn_scatter_columns,
+             (c, ncol, len(dense), self._day_dense, self._day_out, self._day_out_rows) + p("day_slot")),
         ]
 
     def _finish(self, overlap, lw_after=None, sw_after=None, lw_net_cus=None, sw_net_cus=0):
@@ -1123,6 +1219,7 @@ class ClearSkyStep:
         between them."""
         if not (self.overlap and self.sw):
             raise ValueError("capture_chains: a step with its LW and SW chains on two streams")
+        self._refuse_blocks()
         if self.daylit:
             raise ValueError("daylit=True with capture_chains / run_blocks is not supported: a stream of blocks re-runs "
                              "one block, whose daylit columns do not change")
@@ -1140,12 +1237,18 @@ class ClearSkyStep:
             graphs.append(g)
         self.chain_graphs = tuple(graphs)
 
+    def _refuse_blocks(self):
+        if self.mcica_daylit:
+            raise ValueError("mcica['daylit'] with capture_chains / run_blocks is not supported: a stream of blocks "
+                             "re-runs one block, whose daylit columns do not change")
+
     def run_blocks(self, k):
         """k blocks streamed through the step: each chain replays k times in its own stream's order, and block b+1's
         SW chain starts as soon as block b's SW solver is done -- beside block b's LW chain -- instead of after
         block b's join.  (A stream of distinct blocks needs each block's inputs and outputs in storage of its own;
         this one re-runs the step's block, whose results are the same every time.)  Ordered after the caller's
         current stream's work and before its later work."""
+        self._refuse_blocks()
         if self.daylit:
             raise ValueError("daylit=True with capture_chains / run_blocks is not supported: a stream of blocks re-runs "
                              "one block, whose daylit columns do not change")
