@@ -8,6 +8,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "datafile.hpp"
@@ -87,19 +88,6 @@ static int check_ctx(rrtmgpnn_context *ctx)
   return RRTMGPNN_OK;
 }
 
-static int band_args(int nbnd, const int *lims, int ngpt, BandArgs &b)
-{
-  if (nbnd < 1 || nbnd > kMaxBands || !lims) return fail(RRTMGPNN_ERR_ARGUMENT, "band limits: need 1..64 bands");
-  b.nbnd = nbnd;
-  for (int i = 0; i < nbnd; i++) {
-    b.lims[2 * i] = lims[2 * i];
-    b.lims[2 * i + 1] = lims[2 * i + 1];
-    if (lims[2 * i] < 1 || lims[2 * i + 1] > ngpt || lims[2 * i] > lims[2 * i + 1])
-      return fail(RRTMGPNN_ERR_ARGUMENT, "band limits out of range [1, ngpt]");
-  }
-  return RRTMGPNN_OK;
-}
-
 // The kernels give a g-point the FIRST band that holds it and increment it once; the reference's inc_*_bybnd loop over
 // the bands and increment it once per band that holds it.  Overlapping limits would differ silently: refuse them.
 static int bands_disjoint(const BandArgs &b)
@@ -123,177 +111,11 @@ static int bands_cover(const BandArgs &b, int ngpt)
   return RRTMGPNN_OK;
 }
 
-// The requests armed on a context (rrtmgpnn_solver_request_byband / _cloud_mask) belong to its next solver call.
-// Every solver entry starts by taking them: they are copied out and cleared, whatever the entry then returns, so the
-// call after it never sees them.  The by-band request is validated against the call's ngpt into the call's
-// SolverExtras; what an entry does with the cloud mask, and whether it has by-band instances at all, is the entry's
-// part (the three functions below, or an `if` of its own).  A null context has nothing armed (check_ctx reports it).
-struct Requests {
-  bool byband = false;  // a by-band request was armed ...
-  int byband_rc = RRTMGPNN_OK;  // ... and its band limits against ngpt: ex's by-band part is filled when OK
-  rrtmgpnn_context::CloudMaskRequest mask{};
-  rrtmgpnn_context::JacobianRequest jac{};
-  rrtmgpnn_context::AerosolRequest aer{};
-  rrtmgpnn_context::ActiveRequest act{};
-};
-
-static Requests take_requests(rrtmgpnn_context *ctx, int ngpt, SolverExtras &ex)
-{
-  Requests rq;
-  if (!ctx) return rq;
-  rq.mask = ctx->cloud_mask;
-  ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
-  rq.jac = ctx->jacobian;
-  ctx->jacobian = rrtmgpnn_context::JacobianRequest{};
-  rq.aer = ctx->aerosol;
-  ctx->aerosol = rrtmgpnn_context::AerosolRequest{};
-  rq.act = ctx->active;
-  ctx->active = rrtmgpnn_context::ActiveRequest{};
-  if (!ctx->byband.armed) return rq;
-  const auto bb = ctx->byband;
-  ctx->byband = rrtmgpnn_context::BybandRequest{};
-  rq.byband = true;
-  rq.byband_rc = band_args(bb.nbnd, bb.lims, ngpt, ex.bnd);
-  if (rq.byband_rc) return rq;
-  ex.bnd_up = bb.up;
-  ex.bnd_dn = bb.dn;
-  ex.bnd_dir = bb.dir;
-  return rq;
-}
-
-// the entries without masked instances refuse an armed cloud mask
-static const char kNoMaskMsg[] = "solver_request_cloud_mask: this solver entry takes no cloud mask (the _planck_inc, "
-                                 "_2stream_inc, _2stream_rfmip, _2stream_clr_all and _2stream_rfmip_clr_all entries do)";
-// ... and an armed active-column count (rrtmgpnn_solver_request_active_columns; rrtmgp_rfmip_sw.F90:285-287, 433,
-// 456-463): the three SW two-stream entries take it on the call's ncol, into the call's extras -- alone, or (`sky`: the
-// _inc and _rfmip entries) beside a cloud-mask and / or an aerosol request, which those entries then check as ever
-static const char kNoActiveMsg[] = "solver_request_active_columns: this solver entry takes no active-column count (the "
-                                   "sw_solver_2stream, sw_solver_2stream_inc and sw_solver_2stream_rfmip entries do)";
-static int take_active(const char *entry, const Requests &rq, bool honour, int ncol, SolverExtras &ex, bool sky = false)
-{
-  if (!rq.act.armed) return RRTMGPNN_OK;
-  if (!honour) return fail(RRTMGPNN_ERR_ARGUMENT, kNoActiveMsg);
-  const std::string e(entry);
-  if (sky && (rq.byband || rq.jac.armed))
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an active-column count together with a by-band (alone or paired with a "
-                                              "cloud mask) or Jacobian request");
-  if (!sky && (rq.byband || rq.mask.armed || rq.aer.armed || rq.jac.armed))
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an active-column count together with a by-band, cloud-mask, aerosol or "
-                                              "Jacobian request");
-  if (rq.act.ncol != ncol)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested active-column count's ncol is not this call's");
-  ex.nact = rq.act.nact;
-  return RRTMGPNN_OK;
-}
-// What an entry does with an armed Jacobian request (rrtmgpnn_solver_request_jacobian): the LW entries that read source
-// arrays need its sfc_source_Jac, the fused-Planck ones form it in-kernel and take none, every other entry refuses
-// (`refusal`, or a message naming the entry).  The extents are the call's; by-band outputs do not go with it.
-enum JacMode { kJacRefuse, kJacSources, kJacFused };
-static int take_jacobian(const char *entry, const Requests &rq, JacMode mode, int ngpt, int nlay, int ncol,
-                         SolverExtras &ex, const char *refusal = nullptr)
-{
-  if (!rq.jac.armed) return RRTMGPNN_OK;
-  const std::string e(entry);
-  if (mode == kJacRefuse)
-    return fail(RRTMGPNN_ERR_ARGUMENT,
-                refusal ? std::string(refusal)
-                        : e + ": no flux Jacobian from this entry (the lw_solver_noscat, _noscat_planck, "
-                              "_noscat_planck_inc and _1rescl entries have it)");
-  if (rq.byband) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": a flux Jacobian together with by-band outputs");
-  if (rq.jac.ngpt != ngpt || rq.jac.nlay != nlay || rq.jac.ncol != ncol)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested flux Jacobian's extents (ngpt, nlay, ncol) are not this call's");
-  if (mode == kJacSources && !rq.jac.sfc_jac)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the flux Jacobian needs sfc_source_Jac beside this entry's source arrays");
-  if (mode == kJacFused && rq.jac.sfc_jac)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": sfc_source_Jac must be null, this entry forms it from the Planck fraction");
-  ex.sfc_jac = rq.jac.sfc_jac;
-  ex.jac_up = rq.jac.flux_up;
-  return RRTMGPNN_OK;
-}
-// What an entry does with an armed aerosol request (rrtmgpnn_solver_request_aerosol): the entries with aerosol
-// instances take a set of their kind (LW: 1scl, SW: 2str) on the call's own bands and extents into the call's extras, every
-// other entry refuses.  By-band outputs and the flux Jacobian do not go with it (the class layers then use the
-// materialising increment).
-enum AerMode { kAerRefuse, kAerLw, kAerSw };
-static int take_aerosol(const char *entry, const Requests &rq, AerMode mode, int nbnd, int nlay, int ncol,
-                        SolverExtras &ex)
-{
-  if (!rq.aer.armed) return RRTMGPNN_OK;
-  const std::string e(entry);
-  if (mode == kAerRefuse)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": this solver entry takes no aerosol request (the lw_solver_noscat_planck_inc, "
-                                           "_planck_clr_all, _planck_clr_all_mcica, sw_solver_2stream_inc, "
-                                           "sw_solver_2stream_rfmip, sw_solver_2stream_clr_all and "
-                                           "sw_solver_2stream_rfmip_clr_all entries do)");
-  if (rq.byband) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an aerosol increment together with by-band outputs");
-  if (rq.jac.armed) return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": an aerosol increment together with the flux Jacobian");
-  if (mode == kAerLw && (rq.aer.ssa || rq.aer.g))
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": a longwave entry takes a 1scl aerosol (ssa_aer and g_aer null)");
-  if (mode == kAerSw && (!rq.aer.ssa || !rq.aer.g))
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": a shortwave entry takes a 2str aerosol (ssa_aer and g_aer set)");
-  if (rq.aer.nbnd != nbnd || rq.aer.nlay != nlay || rq.aer.ncol != ncol)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested aerosol's extents (nbnd, nlay, ncol) are not this call's");
-  ex.aer_tau = rq.aer.tau;
-  ex.aer_ssa = rq.aer.ssa;
-  ex.aer_g = rq.aer.g;
-  return RRTMGPNN_OK;
-}
-// ... and with g-point outputs beside it
-static int jacobian_no_gpt(const char *entry, const SolverExtras &ex, const float *gpt_up, const float *gpt_dn)
-{
-  if (ex.jac_up && (gpt_up || gpt_dn))
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a flux Jacobian together with g-point outputs");
-  return RRTMGPNN_OK;
-}
-
-static int take_byband(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
-                       JacMode jac = kJacRefuse, const char *jac_refusal = nullptr, bool active = false)
-{
-  const Requests rq = take_requests(ctx, ngpt, ex);
-  if (int rc = take_active(entry, rq, active, ncol, ex)) return rc;
-  if (rq.byband_rc) return rq.byband_rc;
-  if (int rc = take_aerosol(entry, rq, kAerRefuse, 0, nlay, ncol, ex)) return rc;
-  if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, kNoMaskMsg);
-  return take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex, jac_refusal);
-}
-
-// the three that honour it, alone or paired with by-band outputs: the mask against the call's extents, then into the
-// call's extras
-static int take_byband_or_mask(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, SolverExtras &ex,
-                               JacMode jac = kJacRefuse, AerMode aer = kAerRefuse, int nbnd = 0, bool active = false)
-{
-  const Requests rq = take_requests(ctx, ngpt, ex);
-  if (int rc = take_active(entry, rq, active, ncol, ex, /*sky=*/active)) return rc;
-  if (rq.byband_rc) return rq.byband_rc;
-  if (int rc = take_aerosol(entry, rq, aer, nbnd, nlay, ncol, ex)) return rc;
-  if (int rc = take_jacobian(entry, rq, jac, ngpt, nlay, ncol, ex)) return rc;
-  if (!rq.mask.armed) return RRTMGPNN_OK;
-  // both armed: only as the pair rrtmgpnn_solver_request_byband_mcica states (a by-band request left over from an
-  // earlier call beside a fresh mask is not one)
-  if (rq.byband && !rq.mask.paired)
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(entry) + ": a cloud mask together with by-band outputs, requested "
-                                                               "separately (solver_request_byband_mcica requests the pair)");
-  if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
-    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
-                                                            "are not this call's");
-  ex.mask_bits = rq.mask.bits;
-  return RRTMGPNN_OK;
-}
-
-// the two _clr_all entries have neither by-band nor request-masked instances: `mask_msg` is the entry's refusal.  They
-// take an aerosol request, into `ex`
-static int refuse_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nbnd, int nlay, int ncol,
-                           SolverExtras &ex, const char *mask_msg)
-{
-  const Requests rq = take_requests(ctx, ngpt, ex);
-  if (int rc = take_active(entry, rq, false, ncol, ex)) return rc;
-  if (int rc = take_aerosol(entry, rq, kAerLw, nbnd, nlay, ncol, ex)) return rc;
-  if (rq.byband)
-    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(entry) + ": by-band outputs are not available from this entry (the "
-                                                            "_planck and _planck_inc entries have them)");
-  if (rq.mask.armed) return fail(RRTMGPNN_ERR_ARGUMENT, mask_msg);
-  return take_jacobian(entry, rq, kJacRefuse, ngpt, 0, 0, ex);
-}
+// The requests armed on a context (rrtmgpnn_solver_request_*) belong to its next solver call.  Every solver entry starts
+// by taking them: they are copied out and cleared, whatever the entry then returns, so the call after it never sees
+// them.  What the entry makes of them is its row of kRequestPolicies (requests.cpp), applied to the call's extents into
+// the call's SolverExtras.  A null context has nothing armed (check_ctx reports it).
+static ArmedRequests take(rrtmgpnn_context *ctx) { return ctx ? std::exchange(ctx->armed, {}) : ArmedRequests{}; }
 
 static int lw_ds_check(int nmus, const float *lw_Ds)
 {
@@ -308,8 +130,9 @@ static int lw_noscat(rrtmgpnn_context *ctx, const LwNoscat &p, const float *lay_
                      const float *sfc_source, const float *lw_Ds, float *gpt_up, float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband("lw_solver_noscat", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacSources)) return rc;
-  if (int rc = jacobian_no_gpt("lw_solver_noscat", ex, gpt_up, gpt_dn)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowLwNoscat], take(ctx), {p.ngpt, 0, p.nlay, p.ncol, gpt_up || gpt_dn},
+                              ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (int rc = lw_ds_check(p.nmus, lw_Ds)) return rc;
   if (!p.Ds || !p.wts || !p.tau || !lay_source || !lev_source || !p.sfc_emis || !sfc_source || !p.flux_up ||
@@ -336,12 +159,23 @@ static int planck_args(const char *entry, const LwNoscat &p, LwPlanckIn &in, int
   return bands_cover(in.bands, p.ngpt);
 }
 
+// the fused-Planck entries' sources from their arguments; tau_bnd: the band increment of tau, or null (planck_args
+// fills the bands)
+static LwPlanckIn planck_in(const float *tlay, const float *tlev, const float *tsfc, const float *totplnk,
+                            int nPlanckTemp, int sfc_lay, int emis_by_band, float temp_ref_min, float totplnk_delta,
+                            const float *pfrac, const float *tau_bnd)
+{
+  return {{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
+          pfrac, {}, tau_bnd};
+}
+
 static int lw_noscat_planck(rrtmgpnn_context *ctx, const LwNoscat &p, LwPlanckIn &in, int nbnd,
                             const int *band_lims_gpt, const float *lw_Ds, float *gpt_up, float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband("lw_solver_noscat_planck", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacFused)) return rc;
-  if (int rc = jacobian_no_gpt("lw_solver_noscat_planck", ex, gpt_up, gpt_dn)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowLwNoscatPlanck], take(ctx),
+                              {p.ngpt, nbnd, p.nlay, p.ncol, gpt_up || gpt_dn}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (int rc = lw_ds_check(p.nmus, lw_Ds)) return rc;
   if (int rc = planck_args("lw_solver_noscat_planck", p, in, nbnd, band_lims_gpt, false)) return rc;
@@ -356,8 +190,9 @@ static int lw_1rescl(rrtmgpnn_context *ctx, const LwNoscat &p, const float *ssa,
                      float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband("lw_solver_1rescl", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacSources)) return rc;
-  if (int rc = jacobian_no_gpt("lw_solver_1rescl", ex, gpt_up, gpt_dn)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowLw1rescl], take(ctx), {p.ngpt, 0, p.nlay, p.ncol, gpt_up || gpt_dn},
+                              ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!p.Ds || !p.wts || !p.tau || !ssa || !g || !lay_source || !lev_source || !p.sfc_emis || !sfc_source ||
       !p.flux_up || !p.flux_dn || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
@@ -373,8 +208,7 @@ static int lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
                       float *gpt_up, float *gpt_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband("lw_solver_2stream", ctx, ngpt, nlay, ncol, ex, kJacRefuse,
-                           "rte_lw: can't provide Jacobian of fluxes w.r.t surface temperature with 2-stream"))
+  if (int rc = apply_requests(kRequestPolicies[kRowLw2stream], take(ctx), {ngpt, 0, nlay, ncol, gpt_up || gpt_dn}, ex))
     return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!tau || !ssa || !g || !lev_source || !sfc_emis_gpt || !sfc_source || !flux_up || !flux_dn || ngpt < 1 ||
@@ -389,9 +223,9 @@ static int lw_2stream(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int t
 static int sw_2stream(rrtmgpnn_context *ctx, const Sw2Stream &p, float *gpt_up, float *gpt_dn, float *gpt_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband("sw_solver_2stream", ctx, p.ngpt, p.nlay, p.ncol, ex, kJacRefuse, nullptr, true)) return rc;
-  if (ex.nact && (gpt_up || gpt_dn || gpt_dir))
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw_solver_2stream: an active-column count together with g-point outputs");
+  if (int rc = apply_requests(kRequestPolicies[kRowSw2stream], take(ctx),
+                              {p.ngpt, 0, p.nlay, p.ncol, gpt_up || gpt_dn || gpt_dir}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!p.inc_flux || !p.tau || !p.ssa || !p.mu0 || !p.alb_dir || !p.alb_dif || !p.flux_up || !p.flux_dn ||
       !p.flux_dir || p.ngpt < 1 || p.nlay < 1 || p.ncol < 0)
@@ -406,7 +240,8 @@ static int sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int to
                      const float *tau, const float *mu0, float *flux_dir, float *gpt_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband("sw_solver_noscat", ctx, ngpt, nlay, ncol, ex)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowSwNoscat], take(ctx), {ngpt, 0, nlay, ncol, gpt_dir != nullptr}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !mu0 || !flux_dir || ngpt < 1 || nlay < 1 || ncol < 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_noscat: bad argument");
@@ -414,12 +249,12 @@ static int sw_noscat(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int to
   return launch_sw_noscat(ctx, ex, ngpt, nlay, ncol, top_at_1, inc_flux, tau, mu0, flux_dir);
 }
 
-// rrtmgpnn_lw_solver_noscat_planck_clr_all(_mcica): the context's mode, 0 being `mode0` -- what the measurements of
-// DESIGN.md section 3 chose, the dual kernel and the masked dual kernel
-static bool lw_clr_all_dual(const rrtmgpnn_context *ctx, int mode0)
+// the mode of a clear + all-sky entry: the context's (rrtmgpnn_context_set_*_clr_all), else the process default, 0
+// being `measured` -- what the measurements of DESIGN.md section 3 chose for the entry
+static int clr_all_mode(int ctx_mode, int process_default, int measured)
 {
-  const int mode = ctx->lw_clr_all >= 0 ? ctx->lw_clr_all : g_lw_clr_all_default;
-  return (mode == 0 ? mode0 : mode) == 1;
+  const int mode = ctx_mode >= 0 ? ctx_mode : process_default;
+  return mode == 0 ? measured : mode;
 }
 
 }  // namespace rrtmgpnn
@@ -1194,8 +1029,8 @@ int rrtmgpnn_lw_solver_noscat_planck(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      int emis_by_band, const float *sfc_emis, float *flux_up, float *flux_dn)
 {
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, nullptr};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, nullptr);
   return lw_noscat_planck(ctx, p, in, nbnd, band_lims_gpt, nullptr, nullptr, nullptr);
 }
 
@@ -1209,8 +1044,8 @@ int rrtmgpnn_lw_solver_noscat_planck_gpt(rrtmgpnn_context *ctx, int ngpt, int nl
                                          float *gpt_flux_dn)
 {
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, nullptr};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, nullptr);
   return lw_noscat_planck(ctx, p, in, nbnd, band_lims_gpt, lw_Ds, gpt_flux_up, gpt_flux_dn);
 }
 
@@ -1223,12 +1058,12 @@ int rrtmgpnn_lw_solver_noscat_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          const float *sfc_emis, float *flux_up, float *flux_dn)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("lw_solver_noscat_planck_inc", ctx, ngpt, nlay, ncol, ex, kJacFused, kAerLw, nbnd))
+  if (int rc = apply_requests(kRequestPolicies[kRowLwNoscatPlanckInc], take(ctx), {ngpt, nbnd, nlay, ncol, false}, ex))
     return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, tau_bnd};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, tau_bnd);
   if (int rc = planck_args("lw_solver_noscat_planck_inc", p, in, nbnd, band_lims_gpt, true)) return rc;
   return launch_lw_noscat_planck(ctx, ex, p, in);
 }
@@ -1246,16 +1081,17 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
                                              float *flux_up_clr, float *flux_dn_clr)
 {
   SolverExtras ex;
-  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all", ctx, ngpt, nbnd, nlay, ncol, ex, kNoMaskMsg)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowLwNoscatPlanckClrAll], take(ctx), {ngpt, nbnd, nlay, ncol, false}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, tau_bnd};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, tau_bnd);
   if (int rc = planck_args("lw_solver_noscat_planck_clr_all", p, in, nbnd, band_lims_gpt, true,
                            flux_up_clr && flux_dn_clr))
     return rc;
-  return launch_lw_noscat_planck_clr_all(ctx, ex, lw_clr_all_dual(ctx, kLwClrAllDefaultMode), p, in, flux_up_clr,
-                                         flux_dn_clr);
+  const bool dual = clr_all_mode(ctx->lw_clr_all, g_lw_clr_all_default, kLwClrAllDefaultMode) == 1;
+  return launch_lw_noscat_planck_clr_all(ctx, ex, dual, p, in, flux_up_clr, flux_dn_clr);
 }
 
 // mode 0 of rrtmgpnn_context_set_lw_clr_all for the McICA entry: the masked dual kernel
@@ -1272,21 +1108,20 @@ int rrtmgpnn_lw_solver_noscat_planck_clr_all_mcica(rrtmgpnn_context *ctx, int ng
                                                    float *flux_dn_clr, const unsigned int *mask_bits)
 {
   SolverExtras ex;
-  if (int rc = refuse_requests("lw_solver_noscat_planck_clr_all_mcica", ctx, ngpt, nbnd, nlay, ncol, ex,
-                               "lw_solver_noscat_planck_clr_all_mcica: the cloud mask is this entry's mask_bits "
-                               "argument, not a solver_request_cloud_mask request"))
+  if (int rc = apply_requests(kRequestPolicies[kRowLwNoscatPlanckClrAllMcica], take(ctx),
+                              {ngpt, nbnd, nlay, ncol, false}, ex))
     return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!mask_bits) return fail(RRTMGPNN_ERR_ARGUMENT, "lw_solver_noscat_planck_clr_all_mcica: mask_bits is null");
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, tau_bnd};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, tau_bnd);
   if (int rc = planck_args("lw_solver_noscat_planck_clr_all_mcica", p, in, nbnd, band_lims_gpt, true,
                            flux_up_clr && flux_dn_clr))
     return rc;
   ex.mask_bits = mask_bits;
-  return launch_lw_noscat_planck_clr_all(ctx, ex, lw_clr_all_dual(ctx, kLwClrAllMcicaDefaultMode), p, in, flux_up_clr,
-                                         flux_dn_clr);
+  const bool dual = clr_all_mode(ctx->lw_clr_all, g_lw_clr_all_default, kLwClrAllMcicaDefaultMode) == 1;
+  return launch_lw_noscat_planck_clr_all(ctx, ex, dual, p, in, flux_up_clr, flux_dn_clr);
 }
 
 int rrtmgpnn_lw_solver_1rescl(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1, int nmus,
@@ -1317,27 +1152,14 @@ int rrtmgpnn_lw_solver_1rescl_planck_inc(rrtmgpnn_context *ctx, int ngpt, int nl
                                          const float *totplnk, int emis_by_band, const float *sfc_emis,
                                          float *flux_up, float *flux_dn)
 {
-  // broadband fluxes of McICA-sampled (or overcast) scattering clouds: the cloud mask is the one request with an
-  // instance here; by-band outputs, the flux Jacobian and an aerosol increment are refused, naming this entry
   static const char kEntry[] = "lw_solver_1rescl_planck_inc";
   SolverExtras ex;
-  const Requests rq = take_requests(ctx, ngpt, ex);
-  if (int rc = take_active(kEntry, rq, false, ncol, ex)) return rc;
-  if (rq.byband)
-    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": by-band outputs are not available from this entry (the "
-                                                             "lw_solver_1rescl entry has them, without a mask)");
-  if (int rc = take_aerosol(kEntry, rq, kAerRefuse, nbnd, nlay, ncol, ex)) return rc;
-  if (int rc = take_jacobian(kEntry, rq, kJacRefuse, ngpt, nlay, ncol, ex)) return rc;
-  if (rq.mask.armed) {
-    if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
-      return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
-                                                               "are not this call's");
-    ex.mask_bits = rq.mask.bits;
-  }
+  if (int rc = apply_requests(kRequestPolicies[kRowLw1resclPlanckInc], take(ctx), {ngpt, nbnd, nlay, ncol, false}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, tau_bnd};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, tau_bnd);
   if (int rc = planck_args(kEntry, p, in, nbnd, band_lims_gpt, true, ssa_bnd && g_bnd)) return rc;
   return launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd);
 }
@@ -1355,32 +1177,18 @@ int rrtmgpnn_lw_solver_1rescl_planck_clr_all(rrtmgpnn_context *ctx, int ngpt, in
                                              const float *totplnk, int emis_by_band, const float *sfc_emis,
                                              float *flux_up, float *flux_dn, float *flux_up_clr, float *flux_dn_clr)
 {
-  // the cloud mask (all-sky set only) and a 1scl aerosol (both sets) have instances here; by-band outputs and the flux
-  // Jacobian are refused, naming this entry
   static const char kEntry[] = "lw_solver_1rescl_planck_clr_all";
   SolverExtras ex;
-  const Requests rq = take_requests(ctx, ngpt, ex);
-  if (int rc = take_active(kEntry, rq, false, ncol, ex)) return rc;
-  if (rq.byband)
-    return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": by-band outputs are not available from this entry (the "
-                                                             "lw_solver_1rescl entry has them, without a mask)");
-  if (int rc = take_jacobian(kEntry, rq, kJacRefuse, ngpt, nlay, ncol, ex)) return rc;
-  if (int rc = take_aerosol(kEntry, rq, kAerLw, nbnd, nlay, ncol, ex)) return rc;
-  if (rq.mask.armed) {
-    if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
-      return fail(RRTMGPNN_ERR_ARGUMENT, std::string(kEntry) + ": the requested cloud mask's extents (ngpt, nlay, ncol) "
-                                                               "are not this call's");
-    ex.mask_bits = rq.mask.bits;
-  }
+  if (int rc = apply_requests(kRequestPolicies[kRowLw1resclPlanckClrAll], take(ctx), {ngpt, nbnd, nlay, ncol, false}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   const LwNoscat p{ngpt, nlay, ncol, top_at_1, nmus, Ds, weights, inc_flux, tau, sfc_emis, flux_up, flux_dn};
-  LwPlanckIn in{{tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band != 0, temp_ref_min, totplnk_delta},
-                pfrac, {}, tau_bnd};
+  LwPlanckIn in = planck_in(tlay, tlev, tsfc, totplnk, nPlanckTemp, sfc_lay, emis_by_band, temp_ref_min, totplnk_delta,
+                            pfrac, tau_bnd);
   if (ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, std::string(kEntry) + ": more than 256 g-points");
   if (int rc = planck_args(kEntry, p, in, nbnd, band_lims_gpt, true, ssa_bnd && g_bnd && flux_up_clr && flux_dn_clr))
     return rc;
-  const int mode0 = ctx->lw_scat_clr_all >= 0 ? ctx->lw_scat_clr_all : g_lw_scat_clr_all_default;
-  const bool dual = (mode0 == 0 ? kLwScatClrAllDefaultMode : mode0) == 1;
+  const bool dual = clr_all_mode(ctx->lw_scat_clr_all, g_lw_scat_clr_all_default, kLwScatClrAllDefaultMode) == 1;
   return launch_lw_rescl_planck_clr_all(ctx, ex, dual, p, in, ssa_bnd, g_bnd, flux_up_clr, flux_dn_clr);
 }
 
@@ -1444,7 +1252,7 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
                                    float *flux_dn, float *flux_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("sw_solver_2stream_inc", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd, true))
+  if (int rc = apply_requests(kRequestPolicies[kRowSw2streamInc], take(ctx), {ngpt, nbnd, nlay, ncol, false}, ex))
     return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !tau_bnd || !ssa_bnd || !g_bnd || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt ||
@@ -1462,30 +1270,17 @@ int rrtmgpnn_sw_solver_2stream_inc(rrtmgpnn_context *ctx, int ngpt, int nlay, in
 // launches)
 static const int kSwClrAllDefaultMode = 2;
 
-// The two sw_solver_2stream_clr_all entries behind their argument checks: the requests (mask, 2str aerosol; by-band and
-// Jacobian refused), then the dual instance of the checkpointed kernel, or the two launches whose bits it has -- the
-// all-sky one with the requests, the clear one on the gases alone or with the aerosol as its band increment
-static int sw_clr_all_shape(const char *entry, int ngpt, int nbnd);
-
-// (the requests are taken first and cleared whatever follows; the entry's own shape refusals come before what it makes
-// of the requests, so that an armed request of other extents does not hide them)
-static int sw_clr_all_requests(const char *entry, rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int nbnd,
-                               SolverExtras &ex)
+// The two sw_solver_2stream_clr_all entries behind their requests and argument checks: the dual instance of the
+// checkpointed kernel, or the two launches whose bits it has -- the all-sky one with the requests, the clear one on the
+// gases alone or with the aerosol as its band increment
+// the entries' own shape refusals: after the requests are taken (and so cleared), before anything is made of them, so
+// that an armed request of other extents does not hide them
+static int sw_clr_all_shape(const char *entry, int ngpt, int nbnd)
 {
-  const Requests rq = take_requests(ctx, ngpt, ex);
   const std::string e(entry);
-  if (int rc = take_active(entry, rq, false, ncol, ex)) return rc;
-  if (int rc = sw_clr_all_shape(entry, ngpt, nbnd)) return rc;
-  if (rq.byband)
-    return fail(RRTMGPNN_ERR_ARGUMENT, e + ": by-band outputs are not available from this entry (the sw_solver_2stream_inc "
-                                           "and sw_solver_2stream_rfmip entries have them)");
-  if (int rc = take_aerosol(entry, rq, kAerSw, nbnd, nlay, ncol, ex)) return rc;
-  if (int rc = take_jacobian(entry, rq, kJacRefuse, ngpt, nlay, ncol, ex)) return rc;
-  if (rq.mask.armed) {
-    if (rq.mask.ngpt != ngpt || rq.mask.nlay != nlay || rq.mask.ncol != ncol)
-      return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the requested cloud mask's extents (ngpt, nlay, ncol) are not this call's");
-    ex.mask_bits = rq.mask.bits;
-  }
+  if (nbnd <= 0) return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the all-sky set needs the band increment (nbnd > 0)");
+  if (ngpt % 2 != 0 || ngpt > 256)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": ngpt must be even and at most 256");
   return RRTMGPNN_OK;
 }
 
@@ -1493,8 +1288,7 @@ static int sw_clr_all_launch(rrtmgpnn_context *ctx, SolverExtras &ex, const Sw2S
                              float *flux_up_clr, float *flux_dn_clr, float *flux_dir_clr)
 {
   if (p.ncol == 0) return RRTMGPNN_OK;
-  const int mode0 = ctx->sw_clr_all >= 0 ? ctx->sw_clr_all : g_sw_clr_all_default;
-  const int mode = mode0 == 0 ? kSwClrAllDefaultMode : mode0;
+  const int mode = clr_all_mode(ctx->sw_clr_all, g_sw_clr_all_default, kSwClrAllDefaultMode);
   if (mode == 1 && sw_ck_selected(ctx, p.ngpt)) {
     ex.clr_up = flux_up_clr;
     ex.clr_dn = flux_dn_clr;
@@ -1518,15 +1312,6 @@ static int sw_clr_all_launch(rrtmgpnn_context *ctx, SolverExtras &ex, const Sw2S
   return ctx->second_solver_launch(launch_sw_2stream(ctx, exc, pc, bc));
 }
 
-static int sw_clr_all_shape(const char *entry, int ngpt, int nbnd)
-{
-  const std::string e(entry);
-  if (nbnd <= 0) return fail(RRTMGPNN_ERR_ARGUMENT, e + ": the all-sky set needs the band increment (nbnd > 0)");
-  if (ngpt % 2 != 0 || ngpt > 256)
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, e + ": ngpt must be even and at most 256");
-  return RRTMGPNN_OK;
-}
-
 int rrtmgpnn_sw_solver_2stream_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay, int ncol, int top_at_1,
                                        const float *inc_flux, const float *inc_flux_dif, const float *tau,
                                        const float *ssa, const float *g, int nbnd, const int *band_lims_gpt,
@@ -1537,7 +1322,9 @@ int rrtmgpnn_sw_solver_2stream_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay
 {
   static const char entry[] = "sw_solver_2stream_clr_all";
   SolverExtras ex;
-  if (int rc = sw_clr_all_requests(entry, ctx, ngpt, nlay, ncol, nbnd, ex)) return rc;
+  const ArmedRequests taken = take(ctx);
+  if (int rc = sw_clr_all_shape(entry, ngpt, nbnd)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowSw2streamClrAll], taken, {ngpt, nbnd, nlay, ncol, false}, ex)) return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!inc_flux || !tau || !ssa || !mu0 || !sfc_alb_dir_gpt || !sfc_alb_dif_gpt || !flux_up || !flux_dn || !flux_dir ||
       !flux_up_clr || !flux_dn_clr || !flux_dir_clr || ngpt < 1 || nlay < 1 || ncol < 0 || nbnd < 0 ||
@@ -1551,25 +1338,25 @@ int rrtmgpnn_sw_solver_2stream_clr_all(rrtmgpnn_context *ctx, int ngpt, int nlay
   return sw_clr_all_launch(ctx, ex, p, nullptr, flux_up_clr, flux_dn_clr, flux_dir_clr);
 }
 
+static void arm_byband(rrtmgpnn_context *ctx, int nbnd, const int *lims, float *up, float *dn, float *dir)
+{
+  ctx->armed.byband = {true, up, dn, dir, nbnd};
+  std::memcpy(ctx->armed.byband.lims, lims, sizeof(int) * 2 * nbnd);
+}
+
 int rrtmgpnn_solver_request_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, float *bnd_flux_up,
                                    float *bnd_flux_dn, float *bnd_flux_dir)
 {
   if (int rc = check_ctx(ctx)) return rc;
-  ctx->byband = rrtmgpnn_context::BybandRequest{};
-  ctx->cloud_mask.paired = false;  // a by-band half of its own: no longer the pair of solver_request_byband_mcica
+  ctx->armed.byband = BybandRequest{};
+  ctx->armed.cloud_mask.paired = false;  // a by-band half of its own: no longer the pair of solver_request_byband_mcica
   if (!bnd_flux_up && !bnd_flux_dn && !bnd_flux_dir) return RRTMGPNN_OK;  // nothing wanted: nothing armed
   if (nbnd < 1 || nbnd > kMaxBands || !band_lims_gpt)
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband: band limits: need 1..64 bands");
   for (int i = 0; i < nbnd; i++)
     if (band_lims_gpt[2 * i] < 1 || band_lims_gpt[2 * i] > band_lims_gpt[2 * i + 1])
       return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband: band limits out of range");
-  auto &rq = ctx->byband;
-  rq.armed = true;
-  rq.up = bnd_flux_up;
-  rq.dn = bnd_flux_dn;
-  rq.dir = bnd_flux_dir;
-  rq.nbnd = nbnd;
-  std::memcpy(rq.lims, band_lims_gpt, sizeof(int) * 2 * nbnd);
+  arm_byband(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, bnd_flux_dir);
   return RRTMGPNN_OK;
 }
 
@@ -1577,16 +1364,11 @@ int rrtmgpnn_solver_request_cloud_mask(rrtmgpnn_context *ctx, int ngpt, int nlay
                                        const unsigned int *mask_bits)
 {
   if (int rc = check_ctx(ctx)) return rc;
-  ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+  ctx->armed.cloud_mask = CloudMaskRequest{};
   if (!mask_bits) return RRTMGPNN_OK;  // nothing wanted: nothing armed
   if (ngpt < 1 || nlay < 1 || ncol < 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_cloud_mask: bad extents");
-  auto &rq = ctx->cloud_mask;
-  rq.armed = true;
-  rq.ngpt = ngpt;
-  rq.nlay = nlay;
-  rq.ncol = ncol;
-  rq.bits = mask_bits;
+  ctx->armed.cloud_mask = {true, /*paired=*/false, ngpt, nlay, ncol, mask_bits};
   return RRTMGPNN_OK;
 }
 
@@ -1594,16 +1376,10 @@ int rrtmgpnn_solver_request_jacobian(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      float *flux_up_Jac)
 {
   if (int rc = check_ctx(ctx)) return rc;
-  ctx->jacobian = rrtmgpnn_context::JacobianRequest{};
+  ctx->armed.jacobian = JacobianRequest{};
   if (!flux_up_Jac) return RRTMGPNN_OK;  // nothing wanted: nothing armed
   if (ngpt < 1 || nlay < 1 || ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_jacobian: bad extents");
-  auto &rq = ctx->jacobian;
-  rq.armed = true;
-  rq.ngpt = ngpt;
-  rq.nlay = nlay;
-  rq.ncol = ncol;
-  rq.sfc_jac = sfc_source_Jac;
-  rq.flux_up = flux_up_Jac;
+  ctx->armed.jacobian = {true, ngpt, nlay, ncol, sfc_source_Jac, flux_up_Jac};
   return RRTMGPNN_OK;
 }
 
@@ -1611,21 +1387,14 @@ int rrtmgpnn_solver_request_aerosol(rrtmgpnn_context *ctx, int nbnd, int nlay, i
                                     const float *ssa_aer, const float *g_aer)
 {
   if (int rc = check_ctx(ctx)) return rc;
-  ctx->aerosol = rrtmgpnn_context::AerosolRequest{};
+  ctx->armed.aerosol = AerosolRequest{};
   if (!tau_aer && !ssa_aer && !g_aer) return RRTMGPNN_OK;  // nothing wanted: nothing armed
   if (!tau_aer) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_aerosol: tau_aer is null");
   if ((ssa_aer == nullptr) != (g_aer == nullptr))
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_aerosol: ssa_aer and g_aer are both null (1scl) or both set (2str)");
   if (nbnd < 1 || nbnd > kMaxBands || nlay < 1 || ncol < 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_aerosol: bad extents");
-  auto &rq = ctx->aerosol;
-  rq.armed = true;
-  rq.nbnd = nbnd;
-  rq.nlay = nlay;
-  rq.ncol = ncol;
-  rq.tau = tau_aer;
-  rq.ssa = ssa_aer;
-  rq.g = g_aer;
+  ctx->armed.aerosol = {true, nbnd, nlay, ncol, tau_aer, ssa_aer, g_aer};
   return RRTMGPNN_OK;
 }
 
@@ -1633,13 +1402,10 @@ int rrtmgpnn_solver_request_aerosol(rrtmgpnn_context *ctx, int nbnd, int nlay, i
 int rrtmgpnn_solver_request_active_columns(rrtmgpnn_context *ctx, int ncol, const int *nact)
 {
   if (int rc = check_ctx(ctx)) return rc;
-  ctx->active = rrtmgpnn_context::ActiveRequest{};
+  ctx->armed.active = ActiveRequest{};
   if (!nact) return RRTMGPNN_OK;  // nothing wanted: nothing armed
   if (ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_active_columns: ncol < 0");
-  auto &rq = ctx->active;
-  rq.armed = true;
-  rq.ncol = ncol;
-  rq.nact = nact;
+  ctx->armed.active = {true, ncol, nact};
   return RRTMGPNN_OK;
 }
 
@@ -1701,8 +1467,8 @@ int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const 
                                          const unsigned int *mask_bits)
 {
   if (int rc = check_ctx(ctx)) return rc;
-  ctx->byband = rrtmgpnn_context::BybandRequest{};
-  ctx->cloud_mask = rrtmgpnn_context::CloudMaskRequest{};
+  ctx->armed.byband = BybandRequest{};
+  ctx->armed.cloud_mask = CloudMaskRequest{};
   if (!mask_bits) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: mask_bits is null");
   if (!bnd_flux_up && !bnd_flux_dn && !bnd_flux_dir)
     return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: no by-band output");
@@ -1712,19 +1478,8 @@ int rrtmgpnn_solver_request_byband_mcica(rrtmgpnn_context *ctx, int nbnd, const 
   for (int i = 0; i < nbnd; i++)
     if (band_lims_gpt[2 * i] < 1 || band_lims_gpt[2 * i + 1] > ngpt || band_lims_gpt[2 * i] > band_lims_gpt[2 * i + 1])
       return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_byband_mcica: band limits out of range [1, ngpt]");
-  auto &bb = ctx->byband;
-  bb.armed = true;
-  bb.up = bnd_flux_up;
-  bb.dn = bnd_flux_dn;
-  bb.dir = bnd_flux_dir;
-  bb.nbnd = nbnd;
-  std::memcpy(bb.lims, band_lims_gpt, sizeof(int) * 2 * nbnd);
-  auto &rq = ctx->cloud_mask;
-  rq.armed = rq.paired = true;
-  rq.ngpt = ngpt;
-  rq.nlay = nlay;
-  rq.ncol = ncol;
-  rq.bits = mask_bits;
+  arm_byband(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, bnd_flux_dir);
+  ctx->armed.cloud_mask = {true, /*paired=*/true, ngpt, nlay, ncol, mask_bits};
   return RRTMGPNN_OK;
 }
 
@@ -2145,7 +1900,7 @@ int rrtmgpnn_sw_solver_2stream_rfmip(rrtmgpnn_context *ctx, int ngpt, int nlay, 
                                      float *flux_up, float *flux_dn, float *flux_dir)
 {
   SolverExtras ex;
-  if (int rc = take_byband_or_mask("sw_solver_2stream_rfmip", ctx, ngpt, nlay, ncol, ex, kJacRefuse, kAerSw, nbnd, true))
+  if (int rc = apply_requests(kRequestPolicies[kRowSw2streamRfmip], take(ctx), {ngpt, nbnd, nlay, ncol, false}, ex))
     return rc;
   if (ex.mask_bits && nbnd <= 0)
     return fail(RRTMGPNN_ERR_ARGUMENT, "sw_solver_2stream_rfmip: a cloud mask needs the band increment (nbnd > 0)");
@@ -2178,7 +1933,10 @@ int rrtmgpnn_sw_solver_2stream_rfmip_clr_all(rrtmgpnn_context *ctx, int ngpt, in
 {
   static const char entry[] = "sw_solver_2stream_rfmip_clr_all";
   SolverExtras ex;
-  if (int rc = sw_clr_all_requests(entry, ctx, ngpt, nlay, ncol, nbnd, ex)) return rc;
+  const ArmedRequests taken = take(ctx);
+  if (int rc = sw_clr_all_shape(entry, ngpt, nbnd)) return rc;
+  if (int rc = apply_requests(kRequestPolicies[kRowSw2streamRfmipClrAll], taken, {ngpt, nbnd, nlay, ncol, false}, ex))
+    return rc;
   if (int rc = check_ctx(ctx)) return rc;
   if (!solar_source || !tsi || !sfc_alb || !sza || !tau || !ssa || !toa_flux || !sfc_alb_gpt || !mu0 || !flux_up ||
       !flux_dn || !flux_dir || !flux_up_clr || !flux_dn_clr || !flux_dir_clr || ngpt < 1 || nlay < 1 || ncol < 0 ||

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/rrtmgpnn.h"
+#include "requests.hpp"
 
 namespace rrtmgpnn {
 
@@ -34,7 +35,6 @@ int fail(int code, const std::string &msg);
 
 constexpr int kMaxLayers = 7;   // network layers (excluding input)
 constexpr int kMaxInputs = 32;  // NN input features
-constexpr int kMaxBands = 64;
 extern int g_sw_kernel_default;  // rrtmgpnn_context_set_sw_kernel(NULL, mode)
 extern int g_mlp_kernel_default;  // rrtmgpnn_context_set_mlp_kernel(NULL, mode)
 extern int g_lw_clr_all_default;  // rrtmgpnn_context_set_lw_clr_all(NULL, mode)
@@ -45,49 +45,7 @@ extern int g_lw_scat_clr_all_default;  // rrtmgpnn_context_set_lw_scat_clr_all(N
 // call for a (kernel, device) pair it makes no HIP call (hipGraph captures stay attribute-free).
 int raise_lds_limit(const void *kernel);
 
-// band limits as a kernel argument: 1-based inclusive (first, last) g-point per band
-struct BandArgs {
-  int lims[2 * kMaxBands];
-  int nbnd;
-};
-
-// A solver call's options, beyond the problem itself.  The entry (api.cpp) builds one on its stack -- the by-band part
-// from the context's armed request (take_requests), the rest from its own arguments -- and hands it to the launchers,
-// which read it and nothing else: a launcher's signature says that it honours options, its body which.
-struct SolverExtras {
-  // rte_lw's lw_Ds and ty_fluxes_flexible's g-point outputs, (ngpt, nlay+1, ncol) each (the *_gpt entries)
-  const float *lw_Ds = nullptr;
-  float *gpt_up = nullptr, *gpt_dn = nullptr, *gpt_dir = nullptr;
-  // ty_fluxes_byband's by-band outputs, (nbnd, nlay+1, ncol) each, and their band limits
-  // (rrtmgpnn_solver_request_byband); every solver launch has by-band instances
-  float *bnd_up = nullptr, *bnd_dn = nullptr, *bnd_dir = nullptr;
-  BandArgs bnd{};
-  bool byband() const { return bnd_up || bnd_dn || bnd_dir; }
-  // McICA: the packed cloud mask (nw, nlay, ncol), nw = ceil(ngpt / 32), of the fused band increment
-  // (rrtmgpnn_solver_request_cloud_mask / _byband_mcica, or the _clr_all_mcica entry's argument); only the _planck_inc,
-  // _clr_all_mcica, _2stream_inc and _2stream_rfmip entries have masked instances, the three that take a request also
-  // with by-band outputs
-  const uint32_t *mask_bits = nullptr;
-  // rte_lw's flux_up_Jac (rrtmgpnn_solver_request_jacobian): d flux_up / d T_sfc, (nlay+1, ncol), carried beside the
-  // up pass from sfc_jac (ngpt, ncol) -- null on the fused-Planck path, which forms it in-kernel.  Only the LW
-  // no-scattering and rescaled launchers have Jacobian instances, without by-band or g-point outputs
-  const float *sfc_jac = nullptr;
-  float *jac_up = nullptr;
-  // rrtmgpnn_solver_request_aerosol: a second, unmasked band increment (nbnd, nlay, ncol) on the call's own bands, applied
-  // in front of the call's fused band increment (which a mask may switch; this one never).  aer_ssa / aer_g are both
-  // null for a 1scl (LW) aerosol and both set for a 2str (SW) one.  Only the fused-Planck incremented LW launchers and
-  // the checkpointed SW launcher (band-pair increment) have aerosol instances, without by-band, g-point or Jacobian
-  // outputs and without lw_Ds
-  const float *aer_tau = nullptr, *aer_ssa = nullptr, *aer_g = nullptr;
-  // the sw_solver_2stream_clr_all entries' clear-sky outputs, (nlay+1, ncol) each: set (all three), the checkpointed SW
-  // launcher runs its dual instance, which solves the clear sky (the gases and the aerosol, never the fused band
-  // increment) beside the all-sky problem; broadband outputs only
-  float *clr_up = nullptr, *clr_dn = nullptr, *clr_dir = nullptr;
-  // rrtmgpnn_solver_request_active_columns: one device word, the number of columns (the first *nact of the call's ncol)
-  // the kernel solves; only the checkpointed SW launcher has such instances, for g == NULL: kSolverSwCkActive without
-  // any of the above, kSolverSwCkActiveSky beside mask_bits and / or a 2str aerosol (rows of the call's ncol both)
-  const int *nact = nullptr;
-};
+// BandArgs, SolverExtras and the armed requests: requests.hpp
 
 // Planck inputs of the LW solvers that form the sources in-kernel from the Planck fraction (a kernel argument)
 struct LwPlanck {
@@ -161,41 +119,8 @@ struct rrtmgpnn_context {
     if (rc == RRTMGPNN_OK) solver_path[2] = 2;
     return rc;
   }
-  // rrtmgpnn_solver_request_byband: armed for the next solver call on this context, which clears it
-  struct BybandRequest {
-    bool armed = false;
-    float *up = nullptr, *dn = nullptr, *dir = nullptr;
-    int nbnd = 0;
-    int lims[2 * rrtmgpnn::kMaxBands] = {0};
-  } byband;
-  // rrtmgpnn_solver_request_cloud_mask: armed for the next solver call on this context, which clears it
-  struct CloudMaskRequest {
-    bool armed = false;
-    // armed together with the by-band request by rrtmgpnn_solver_request_byband_mcica: the pair is meant.  A later
-    // separate request of either half drops it
-    bool paired = false;
-    int ngpt = 0, nlay = 0, ncol = 0;
-    const uint32_t *bits = nullptr;
-  } cloud_mask;
-  // rrtmgpnn_solver_request_jacobian: armed for the next solver call on this context, which clears it
-  struct JacobianRequest {
-    bool armed = false;
-    int ngpt = 0, nlay = 0, ncol = 0;
-    const float *sfc_jac = nullptr;
-    float *flux_up = nullptr;
-  } jacobian;
-  // rrtmgpnn_solver_request_aerosol: armed for the next solver call on this context, which clears it
-  struct AerosolRequest {
-    bool armed = false;
-    int nbnd = 0, nlay = 0, ncol = 0;
-    const float *tau = nullptr, *ssa = nullptr, *g = nullptr;
-  } aerosol;
-  // rrtmgpnn_solver_request_active_columns: armed for the next solver call on this context, which clears it
-  struct ActiveRequest {
-    bool armed = false;
-    int ncol = 0;
-    const int *nact = nullptr;
-  } active;
+  // the requests armed for the next solver call on this context, which takes and clears them (requests.hpp)
+  rrtmgpnn::ArmedRequests armed;
   void *ws = nullptr;
   size_t ws_bytes = 0;
   bool ws_pinned = false;
