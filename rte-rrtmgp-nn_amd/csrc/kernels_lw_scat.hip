@@ -241,7 +241,8 @@ __global__ void __launch_bounds__(256) lw_rescl_kernel(int ngpt, int nlay, int n
 //  * kMask: where the g-point's bit of cmask (nw, nlay, ncol) is clear the three band operands are 0, which is what
 //    draw_samples leaves there for increment to add;
 //  * sources: lay = pfrac(l) * B_b(tlay(l)), lev(li) = pfrac(min(li, nlay-1)) * B_b(tlev(li)), sfc = pfrac(sfc_lay) *
-//    B_b(tsfc), the band Planck values interpolated once per column into LDS as lw_noscat_kernel's kFused instances do;
+//    B_b(tsfc), the band Planck values interpolated once per column into LDS by lw_planck_table (rte_device.hpp), which
+//    lw_noscat_kernel's kFused instances call too;
 //  * transport: rs_layer and the three passes of lw_rescl_kernel, the same ring and ordered flush.
 // A layer's inputs -- tau, pfrac, the neighbouring pfrac of lev(l+1), three band values (one address per band: the
 // loads broadcast), kMask: one mask word -- are loaded kPF layers ahead of the recurrence in every pass, and so is the
@@ -304,7 +305,9 @@ struct ScatDualArgs<true> {
 // extensions/mo_rrtmgp_clr_all_sky.F90:146-172).  Each lane carries the clear radiance of t_clr = tau [+ tau_aer]
 // through ns_layer: down in pass 1, up in pass 2; pass 3 has nothing to add for it.  The clear values are staged in a
 // second ring ([2][kScatRing][ngpt]: 0 = all-sky, 1 = clear) and reduced to part planes 2 (up) and 3 (dn): clear down
-// by pass 1's own flushes (the all-sky radiance stages nothing there), clear up beside all-sky up by pass 2's.
+// by pass 1's own flushes (the all-sky radiance stages nothing there), clear up beside all-sky up by pass 2's.  The
+// three passes are written once: what the clear radiance adds stands under `if constexpr (kDual)` at the points of the
+// loop where it acts, so the prefetch, the workspace reads and the flush windows are the single instances' own.
 //
 // O: the instance's options, an OR of the kScatOpt* bits (internal.hpp), named again in the first lines
 template <uint32_t O>
@@ -358,35 +361,7 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
   const float ysfc = Tpf.ld(vg, row * (uint32_t)(pl.sfc_lay - 1));
   const float e = pl.emis_by_band ? emis[b + (size_t)nbnd * icol] : emis[gc + (size_t)ngpt * icol];
   const float inc = inc_flux ? inc_flux[gc + (size_t)ngpt * icol] : 0.0f;
-  {
-    // band Planck values of this column (the table loop of lw_noscat_kernel): B_b(tlay(l)) at [b][l], B_b(tlev(l)) at
-    // [b][nlay+l], B_b(tsfc) at [nbnd*brow + b]
-    const float *tl = pl.tlay + (size_t)nlay * icol, *tv = pl.tlev + (size_t)nlev * icol;
-    constexpr int kBtabU = 8;
-    const int ntab = nbnd * (brow + 1), nrow = nbnd * brow;
-    for (int i0 = threadIdx.x; i0 < ntab; i0 += kBtabU * (int)blockDim.x) {
-      float T[kBtabU];
-      int bb[kBtabU];
-#pragma unroll
-      for (int u = 0; u < kBtabU; u++) {
-        const int i = min(i0 + u * (int)blockDim.x, ntab - 1);  // clamped: past-the-end entries are not stored
-        const int ib = i < nrow ? i / brow : i - nrow;
-        const int k = i < nrow ? i - ib * brow : -1;
-        bb[u] = ib;
-        const float *p = k < 0 ? pl.tsfc + icol : (k < nlay ? tl + k : tv + (k - nlay));
-        T[u] = *p;
-      }
-      float v[kBtabU];
-#pragma unroll
-      for (int u = 0; u < kBtabU; u++)
-        v[u] = interp1d(T[u], pl.tmin, pl.tdelta, pl.ntemp, pl.totplnk + (size_t)pl.ntemp * bb[u]);
-#pragma unroll
-      for (int u = 0; u < kBtabU; u++) {
-        const int i = i0 + u * (int)blockDim.x;
-        if (i < ntab) btab[i] = v[u];
-      }
-    }
-  }
+  lw_planck_table<false>(btab, pl, nbnd, nlay, icol);  // band Planck values of this column (rte_device.hpp)
   const float *bl = btab + (size_t)b * brow;  // this lane's band row
   __syncthreads();
   const float ss = ysfc * btab[(size_t)nbnd * brow + b];
@@ -408,133 +383,13 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
   auto lay_up = [&](int j) { return top_at_1 ? nlay - 1 - j : j; };  // j-th layer from the surface
   float *pdn = part, *pup = part + (size_t)nlev * 4;
 
-  if constexpr (kDual) {
-    // One angle.  The loops below are the single instance's with the clear radiance beside the all-sky one; kept apart
-    // from them so that the single instances compile from the text they had.  A COPY: a change to the prefetch, the
-    // workspace reads or the flush windows of the three passes after this block belongs here too, and the other way.
-    float *const ring_clr = ring + (size_t)kScatRing * ngpt;
-    float *const pup_clr = part + (size_t)2 * nlev * 4, *const pdn_clr = part + (size_t)3 * nlev * 4;
-    const float D = ang.D[0];
-    const float fac = (ngpt & 3) == 0 ? 2.0f * kPi * ang.w[0] : 1.0f;  // quirk B-5 as noscat
-    auto put = [&](float v, int r) {
-      if (on) ring[(size_t)r * ngpt + g] = v;
-    };
-    auto put_clr = [&](float v, int r) {
-      if (on) ring_clr[(size_t)r * ngpt + g] = v;
-    };
-    // the clear ring alone (pass 1), both rings (pass 2: part planes 1 and 2), the all-sky ring alone (pass 3)
-    auto flush_clr_dn = [&](int n, int lev0, int dl) {
-      ring_flush<kScatRing>(ring_clr, pdn_clr, 1, n, lev0, dl, ngpt, nlev, false);
-    };
-    auto flush_up = [&](int n, int lev0, int dl) { ring_flush<kScatRing>(ring, pup, 2, n, lev0, dl, ngpt, nlev, false); };
-    auto flush_dn = [&](int n, int lev0, int dl) { ring_flush<kScatRing>(ring, pdn, 1, n, lev0, dl, ngpt, nlev, false); };
-    RsIn pf[kPF];
-    float pw[kPF];
-    // 1: down, no scattering: the all-sky radiance with the rescaled optics into W, the clear one into its ring
-    const float I0 = inc / (2.0f * kPi * ang.w[0]);
-    float I = I0, Ic = I0;
-    if (on) W[X(top)] = I;
-#pragma unroll
-    for (int p = 0; p < kPF; p++) pf[p] = load(lay_dn(min(p, nlay - 1)));
-    put_clr(fac * Ic, 0);
-    flush_clr_dn(1, top, 1);
-    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
-#pragma unroll
-      for (int s = 0; s < kScatRing; s++) {
-        const int j = j0 + s, p = s % kPF, l = lay_dn(min(j, nlay - 1));
-        const RsIn d = pf[p];
-        pf[p] = load(lay_dn(min(j + kPF, nlay - 1)));
-        if (j < nlay) {
-          const RsLayer r = layer(d, l, D);
-          I = r.trans * I + r.sdn;
-          if (on) W[X(top_at_1 ? l + 1 : l)] = I;
-          const NsLayer c = layer_clr(d, l, D);
-          Ic = c.trans * Ic + c.sdn;
-          put_clr(fac * Ic, s);
-        }
-      }
-      flush_clr_dn(min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
-    }
-    // surface reflection and emission
-    float U = I * (1.0f - e) + e * ss;
-    float Uc = Ic * (1.0f - e) + e * ss;
-    if (on) W[X(sfcl)] = U;
-    put(fac * U, 0);
-    put_clr(fac * Uc, 0);
-    flush_up(1, sfcl, 1);
-    // 2: up
-    auto ltop_of = [&](int l) { return top_at_1 ? l : l + 1; };
-#pragma unroll
-    for (int p = 0; p < kPF; p++) {
-      const int l = lay_up(min(p, nlay - 1));
-      pf[p] = load(l);
-      pw[p] = W[X(ltop_of(l))];
-    }
-    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
-#pragma unroll
-      for (int s = 0; s < kScatRing; s++) {
-        const int j = j0 + s, p = s % kPF, l = lay_up(min(j, nlay - 1)), ltop = ltop_of(l);
-        const RsIn d = pf[p];
-        const float wd = pw[p];
-        {
-          const int ln = lay_up(min(j + kPF, nlay - 1));
-          pf[p] = load(ln);
-          pw[p] = W[X(ltop_of(ln))];
-        }
-        if (j < nlay) {
-          const RsLayer r = layer(d, l, D);
-          const float adj = r.Cn * (r.An * wd - r.trans * r.sdn - r.sup);
-          U = r.trans * U + r.sup + adj;
-          if (on) W[X(ltop)] = U;
-          put(fac * U, s);
-          const NsLayer c = layer_clr(d, l, D);
-          Uc = c.trans * Uc + c.sup;
-          put_clr(fac * Uc, s);
-        }
-      }
-      flush_up(min(kScatRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
-    }
-    // 3: down again, the all-sky radiance only
-    I = I0;
-    put(fac * I, 0);
-#pragma unroll
-    for (int p = 0; p < kPF; p++) {
-      const int l = lay_dn(min(p, nlay - 1));
-      pf[p] = load(l);
-      pw[p] = W[X(l)];
-    }
-    flush_dn(1, top, 1);
-    for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
-#pragma unroll
-      for (int s = 0; s < kScatRing; s++) {
-        const int j = j0 + s, p = s % kPF, l = lay_dn(min(j, nlay - 1));
-        const RsIn d = pf[p];
-        const float wu = pw[p];
-        {
-          const int ln = lay_dn(min(j + kPF, nlay - 1));
-          pf[p] = load(ln);
-          pw[p] = W[X(ln)];
-        }
-        if (j < nlay) {
-          const RsLayer r = layer(d, l, D);
-          const float adj = r.Cn * (r.An * wu - r.trans * r.sup - r.sdn);
-          I = r.trans * I + r.sdn + adj;
-          put(fac * I, s);
-        }
-      }
-      flush_dn(min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
-    }
-    for (int l = g; l < nlev; l += blockDim.x) {
-      flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
-      flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
-      da.flux_dn_clr[l + (size_t)nlev * icol] = combine4(pdn_clr + 4 * l);
-      da.flux_up_clr[l + (size_t)nlev * icol] = combine4(pup_clr + 4 * l);
-    }
-    return;
-  }
+  // kDual: the clear ring and its part planes (null in the single instances, whose LDS holds neither)
+  [[maybe_unused]] float *const ring_clr = kDual ? ring + (size_t)kScatRing * ngpt : nullptr;
+  [[maybe_unused]] float *const pup_clr = kDual ? part + (size_t)2 * nlev * 4 : nullptr;
+  [[maybe_unused]] float *const pdn_clr = kDual ? part + (size_t)3 * nlev * 4 : nullptr;
 
-  // (the three passes below have a copy in the kDual block above: keep the two in step)
-  for (int imu = 0; imu < ang.nmus; imu++) {
+  const int nang = kDual ? 1 : ang.nmus;
+  for (int imu = 0; imu < nang; imu++) {
     const float D = ang.D[imu];
     const float fac = (multi || (ngpt & 3) == 0) ? 2.0f * kPi * ang.w[imu] : 1.0f;  // quirk B-5 as noscat
     const bool acc = imu > 0;
@@ -548,17 +403,29 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
         ring[(size_t)r * ngpt + g] = v;
       }
     };
-    auto flush = [&](float *pq, int n, int lev0, int dl) {
-      if (!multi) ring_flush<kScatRing>(ring, pq, 1, n, lev0, dl, ngpt, nlev, false);
+    // kDual: v = fac * the clear radiance, into the second ring
+    auto put_clr = [&](float v, int r) {
+      if (on) ring_clr[(size_t)r * ngpt + g] = v;
+    };
+    // nq rings from rg on into nq part planes from pq on.  kDual: the clear ring alone (pass 1, to plane 3), both rings
+    // (pass 2, to planes 1 and 2), the all-sky ring alone (pass 3)
+    auto flush = [&](const float *rg, float *pq, int nq, int n, int lev0, int dl) {
+      if (!multi) ring_flush<kScatRing>(rg, pq, nq, n, lev0, dl, ngpt, nlev, false);
     };
     RsIn pf[kPF];
     float pw[kPF];
-    // 1: no-scattering transport down with the rescaled optics (lw_transport_noscat_dn)
+    // 1: no-scattering transport down with the rescaled optics (lw_transport_noscat_dn), radn_dn into W; kDual: the
+    //    clear radiance beside it, staged in its ring and flushed here
     const float I0 = inc / (2.0f * kPi * ang.w[imu]);
     float I = I0;
+    [[maybe_unused]] float Ic = I0;  // kDual
     if (on) W[X(top)] = I;
 #pragma unroll
     for (int p = 0; p < kPF; p++) pf[p] = load(lay_dn(min(p, nlay - 1)));
+    if constexpr (kDual) {
+      put_clr(fac * Ic, 0);
+      flush(ring_clr, pdn_clr, 1, 1, top, 1);
+    }
     for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
 #pragma unroll
       for (int s = 0; s < kScatRing; s++) {
@@ -569,16 +436,25 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
           const RsLayer r = layer(d, l, D);
           I = r.trans * I + r.sdn;
           if (on) W[X(top_at_1 ? l + 1 : l)] = I;
+          if constexpr (kDual) {
+            const NsLayer c = layer_clr(d, l, D);
+            Ic = c.trans * Ic + c.sdn;
+            put_clr(fac * Ic, s);
+          }
         }
       }
+      if constexpr (kDual) flush(ring_clr, pdn_clr, 1, min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
     }
     // surface reflection and emission
     float U = I * (1.0f - e) + e * ss;
+    [[maybe_unused]] float Uc = Ic * (1.0f - e) + e * ss;  // kDual
     if (on) W[X(sfcl)] = U;
     put(fac * U, 0, 1, sfcl);
-    flush(pup, 1, sfcl, 1);
+    if constexpr (kDual) put_clr(fac * Uc, 0);
+    flush(ring, pup, kDual ? 2 : 1, 1, sfcl, 1);
     // 2: up with the adjustment from the first-pass radiance at the layer top (lw_transport_1rescl); the layer top's
-    //    element of W is read (radn_dn), then written (radn_up)
+    //    element of W is read (radn_dn), then written (radn_up); kDual: the clear radiance up beside it, one flush of
+    //    both rings
     auto ltop_of = [&](int l) { return top_at_1 ? l : l + 1; };
 #pragma unroll
     for (int p = 0; p < kPF; p++) {
@@ -603,12 +479,17 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
           U = r.trans * U + r.sup + adj;
           if (on) W[X(ltop)] = U;
           put(fac * U, s, 1, ltop);
+          if constexpr (kDual) {
+            const NsLayer c = layer_clr(d, l, D);
+            Uc = c.trans * Uc + c.sup;
+            put_clr(fac * Uc, s);
+          }
         }
       }
-      flush(pup, min(kScatRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
+      flush(ring, pup, kDual ? 2 : 1, min(kScatRing, nlay - j0), sfcl - dl_dn * (j0 + 1), -dl_dn);
     }
     // 3: down again with the adjustment from radn_up(l) in array order: the layer top when top_at_1, the
-    //    layer bottom otherwise (:1761-1767 vs :1783-1789, reproduced)
+    //    layer bottom otherwise (:1761-1767 vs :1783-1789, reproduced); the clear radiance has nothing to add
     I = I0;
     put(fac * I, 0, 0, top);
 #pragma unroll
@@ -617,7 +498,7 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
       pf[p] = load(l);
       pw[p] = W[X(l)];
     }
-    flush(pdn, 1, top, 1);
+    flush(ring, pdn, 1, 1, top, 1);
     for (int j0 = 0; j0 < nlay; j0 += kScatRing) {
 #pragma unroll
       for (int s = 0; s < kScatRing; s++) {
@@ -636,7 +517,7 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
           put(fac * I, s, 0, top_at_1 ? l + 1 : l);
         }
       }
-      flush(pdn, min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
+      flush(ring, pdn, 1, min(kScatRing, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
     }
   }
   if (multi) {
@@ -652,6 +533,10 @@ __global__ void __launch_bounds__(256) lw_rescl_planck_inc_kernel(
   for (int l = g; l < nlev; l += blockDim.x) {
     flux_dn[l + (size_t)nlev * icol] = combine4(pdn + 4 * l);
     flux_up[l + (size_t)nlev * icol] = combine4(pup + 4 * l);
+    if constexpr (kDual) {
+      da.flux_dn_clr[l + (size_t)nlev * icol] = combine4(pdn_clr + 4 * l);
+      da.flux_up_clr[l + (size_t)nlev * icol] = combine4(pup_clr + 4 * l);
+    }
   }
 }
 
@@ -836,6 +721,28 @@ using LwResclIncInstances =
     SolverInstances<0u, kScatOptMask, kScatOptAer, kScatOptAer | kScatOptMask, kScatOptDual, kScatOptDual | kScatOptMask,
                     kScatOptDual | kScatOptAer, kScatOptDual | kScatOptAer | kScatOptMask>;
 
+// What a launch of lw_rescl_planck_inc_kernel is refused for, in this order, and the workspace it is given: the one set
+// of limits of launch_lw_rescl_planck_inc and, ahead of its clear launch, launch_lw_rescl_planck_clr_all.  flux_up_clr
+// set: the dual instance.  *lds: the launch's LDS in bytes.
+static int lw_rescl_planck_limits(rrtmgpnn_context *ctx, const SolverExtras &ex, const LwNoscat &p, int nbnd,
+                                  const float *flux_up_clr, const float *flux_dn_clr, size_t *lds, void **ws)
+{
+  if (p.nmus < 1 || p.nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
+  if (p.ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
+  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.lw_Ds)
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): broadband fluxes only");
+  const bool dual = flux_up_clr != nullptr;
+  if (dual && (!flux_dn_clr || p.nmus != 1))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): the dual instance runs one "
+                                          "angle and writes both clear-sky arrays");
+  *lds = lw_rescl_planck_lds(nbnd, p.nlay, p.ngpt, dual);
+  if (*lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
+  // the shared radn_dn / radn_up plane, and the two angle accumulators (as many as the no-scattering clear launch of
+  // launch_lw_rescl_planck_clr_all accumulates in)
+  const int planes = p.nmus > 1 ? 3 : 1;
+  return ctx->workspace(sizeof(float) * planes * (size_t)p.ngpt * (p.nlay + 1) * p.ncol, ws);
+}
+
 // in.tau_bnd, ssa_bnd, g_bnd: the band-resolved two-stream increment; ex.mask_bits, or null: the McICA mask that
 // switches it; ex.aer_tau, or null: the 1scl aerosol in front of it (from the _clr_all entry only: _1rescl_planck_inc
 // refuses the request).  flux_up_clr / flux_dn_clr set (both; one angle): the dual instance.  No other extras have an
@@ -845,23 +752,14 @@ int launch_lw_rescl_planck_inc(rrtmgpnn_context *ctx, const SolverExtras &ex, co
 {
   const int ngpt = p.ngpt, nlay = p.nlay, ncol = p.ncol, nmus = p.nmus;
   if (ncol == 0) return RRTMGPNN_OK;
-  if (nmus < 1 || nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
-  if (ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
-  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.lw_Ds)
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): broadband fluxes only");
+  size_t lds = 0;
+  void *ws = nullptr;
+  if (int rc = lw_rescl_planck_limits(ctx, ex, p, in.bands.nbnd, flux_up_clr, flux_dn_clr, &lds, &ws)) return rc;
   const bool dual = flux_up_clr != nullptr;
-  if (dual && (!flux_dn_clr || nmus != 1))
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): the dual instance runs one "
-                                          "angle and writes both clear-sky arrays");
   LwAngles a{};
   a.nmus = nmus;
   for (int i = 0; i < nmus; i++) { a.D[i] = p.Ds[i]; a.w[i] = p.wts[i]; }
   const int threads = (ngpt + 63) / 64 * 64;
-  const size_t lds = lw_rescl_planck_lds(in.bands.nbnd, nlay, ngpt, dual);
-  if (lds > 64 * 1024) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
-  void *ws = nullptr;
-  const int planes = nmus > 1 ? 3 : 1;  // the shared radn_dn / radn_up plane, and the two angle accumulators
-  if (int rc = ctx->workspace(sizeof(float) * planes * (size_t)ngpt * (nlay + 1) * ncol, &ws)) return rc;
   const uint32_t options = (ex.mask_bits ? kScatOptMask : 0u) | (ex.aer_tau ? kScatOptAer : 0u) | (dual ? kScatOptDual : 0u);
   return launch_listed(ctx, kSolverLwResclInc, LwResclIncInstances{}, options, [&](auto oc) -> int {
     constexpr uint32_t O = decltype(oc)::value;
@@ -890,18 +788,11 @@ int launch_lw_rescl_planck_clr_all(rrtmgpnn_context *ctx, const SolverExtras &ex
   if (p.ncol == 0) return RRTMGPNN_OK;
   if (dual && p.nmus == 1 && lw_rescl_planck_lds(in.bands.nbnd, p.nlay, p.ngpt, true) <= 64 * 1024)
     return launch_lw_rescl_planck_inc(ctx, ex, p, in, ssa_bnd, g_bnd, flux_up_clr, flux_dn_clr);
-  // what launch_lw_rescl_planck_inc would refuse, ahead of the clear launch
-  if (p.nmus < 1 || p.nmus > 4) return fail(RRTMGPNN_ERR_ARGUMENT, "lw solver: nmus must be 1..4");
-  if (p.ngpt > 256) return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: more than 256 g-points");
-  if (ex.byband() || ex.gpt_up || ex.gpt_dn || ex.jac_up || ex.lw_Ds)
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver (fused Planck, band increment): broadband fluxes only");
-  if (lw_rescl_planck_lds(in.bands.nbnd, p.nlay, p.ngpt, false) > 64 * 1024)
-    return fail(RRTMGPNN_ERR_UNSUPPORTED, "lw rescaled solver: too many layers for LDS partials");
   {
-    // the larger of the two launches' workspaces (the clear launch accumulates in two planes with several angles)
+    // the non-dual all-sky launch's limits and workspace, ahead of the clear launch
+    size_t lds = 0;
     void *ws = nullptr;
-    const int planes = p.nmus > 1 ? 3 : 1;
-    if (int rc = ctx->workspace(sizeof(float) * planes * (size_t)p.ngpt * (p.nlay + 1) * p.ncol, &ws)) return rc;
+    if (int rc = lw_rescl_planck_limits(ctx, ex, p, in.bands.nbnd, nullptr, nullptr, &lds, &ws)) return rc;
   }
   SolverExtras clear_ex = ex;
   clear_ex.mask_bits = nullptr;

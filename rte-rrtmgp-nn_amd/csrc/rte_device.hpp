@@ -77,6 +77,50 @@ __host__ __device__ constexpr size_t lw_btab_floats(int nbnd, int nlay, bool jac
   return ((size_t)nbnd * (2 * nlay + 2 + (jac ? 1 : 0)) + 3) & ~(size_t)3;
 }
 
+// The fused Planck table of column icol, built by the whole block into btab (lw_btab_floats(nbnd, nlay, kJac) floats of
+// LDS): band Planck values B_b(tlay(l)) at [b][l], B_b(tlev(l)) at [b][nlay+l], B_b(tsfc) at [nbnd*brow + b], with
+// brow = 2*nlay + 1; interpolate1D of compute_Planck_source_nn.  The caller's barrier comes before the first read.
+template <bool kJac>
+__device__ __forceinline__ void lw_planck_table(float *btab, const LwPlanck &pl, int nbnd, int nlay, int icol)
+{
+  const int nlev = nlay + 1, brow = 2 * nlay + 1;
+  const float *tl = pl.tlay + (size_t)nlay * icol, *tv = pl.tlev + (size_t)nlev * icol;
+  // kBtabU entries per thread per round, their loads issued together: the temperatures, then the table pairs (a
+  // loop of one entry per round waits out two dependent load latencies per entry, ~16 per block at C3)
+  constexpr int kBtabU = 8;
+  // kJac: one more row, B_b(tsfc + 1), at [nbnd*(brow+1) + b]
+  const int ntab = nbnd * (brow + (kJac ? 2 : 1)), nrow = nbnd * brow;
+  for (int i0 = threadIdx.x; i0 < ntab; i0 += kBtabU * (int)blockDim.x) {
+    float T[kBtabU];
+    int bb[kBtabU];
+#pragma unroll
+    for (int u = 0; u < kBtabU; u++) {
+      const int i = min(i0 + u * (int)blockDim.x, ntab - 1);  // clamped: past-the-end entries are not stored
+      int b = i < nrow ? i / brow : i - nrow;
+      const int k = i < nrow ? i - b * brow : -1;
+      bool plus1 = false;
+      if constexpr (kJac) {
+        plus1 = b >= nbnd;
+        if (plus1) b -= nbnd;
+      }
+      bb[u] = b;
+      const float *p = k < 0 ? pl.tsfc + icol : (k < nlay ? tl + k : tv + (k - nlay));  // one load, no branch
+      T[u] = *p;
+      if constexpr (kJac)
+        if (plus1) T[u] = T[u] + 1.0f;
+    }
+    float v[kBtabU];
+#pragma unroll
+    for (int u = 0; u < kBtabU; u++)
+      v[u] = interp1d(T[u], pl.tmin, pl.tdelta, pl.ntemp, pl.totplnk + (size_t)pl.ntemp * bb[u]);
+#pragma unroll
+    for (int u = 0; u < kBtabU; u++) {
+      const int i = i0 + u * (int)blockDim.x;
+      if (i < ntab) btab[i] = v[u];
+    }
+  }
+}
+
 // inc_2stream_by_2stream_bybnd (rte/kernels/mo_optical_props_kernels.F90:430-463) for one g-point: the
 // same expressions as increment_bybnd_kernel, so the incremented properties are bit-identical.
 __device__ __forceinline__ void inc_2str(float &t1, float &w1, float &g1, float t2, float w2, float g2)

@@ -10,7 +10,10 @@ Shapes, the smallest that reach every code path of the kernel: 3 columns;
   (256, 7)  the shipped g-points, one partial ring chunk of 8;
   (256, 11) a full chunk and a partial one;
   (72, 7)   two bands, the second wave partial, the last mask word partial;
+  (72, 8)   nlay equal to one flush ring (kScatRing = 8): the chunk walk ends on a full ring with no partial chunk behind
+            it, and the prefetch clamps on the ring boundary;
   (30, 7)   ngpt % 4 != 0: the sequential broadband sum of bare radiances (quirk B-5);
+  (30, 16)  nlay equal to two flush rings, with the sequential sum;
   (30, 1)   one layer: lev(l+1)'s Planck fraction is the layer's own (min(l+1, nlay-1)).
 Column 2 is designed (DESIGNED): a layer with tau_bnd = 0 (and a negative g_bnd in band 0: the sign of the zero g
 depends on the gas operands staying in the expression), a layer with tau_bnd * ssa_bnd < eps = 3 FLT_MIN, where
@@ -23,7 +26,7 @@ import numpy as np
 import mcica_ref as M
 
 NCOL = 3
-CASES = ((256, 7), (256, 11), (72, 7), (30, 7), (30, 1))
+CASES = ((256, 7), (256, 11), (72, 7), (72, 8), (30, 7), (30, 16), (30, 1))
 MASK_SEED = 5
 MASKS = (None, "sampled", "ones", "zeros")
 EPS = np.float32(3.0) * np.finfo(np.float32).tiny
