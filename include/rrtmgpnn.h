@@ -142,7 +142,10 @@ int rrtmgpnn_context_get_mlp_path(rrtmgpnn_context *ctx, int path[8]);
  *   8 sw_2stream_ck_kernel with that count beside a cloud mask and / or an aerosol (the requests armed together):
  *     family 2's bits, 2048 and 2 in every instance, with 128, 256 or both -- the masked cloud with and without the
  *     band-pair layout, the aerosol (band pair only) in front of the masked or the unmasked cloud, each with the
- *     transmittance plane and without.
+ *     transmittance plane and without;
+ *   9 sw_2stream_ck_kernel with the by-band sums of the surface level (rrtmgpnn_solver_request_sfc_byband): the
+ *     instance the same call runs without the request (family 2, or 8 beside an active-column count) and 4096 --
+ *     2 and 32 in every instance, 128, 256 or both, with 2048 and without, with the transmittance plane and without.
  * path[2]: the launches the call made in these families, 2 where a clear + all-sky entry ran its two launches (path[0]
  * and path[1] are then the second's).  path[3]: the number of instances the family is compiled for; an options value
  * outside that list is refused with RRTMGPNN_ERR_UNSUPPORTED.  A call that launches nothing leaves the path as it was. */
@@ -958,6 +961,29 @@ int rrtmgpnn_gas_optics_sw_nn_active(rrtmgpnn_context *ctx, int ncol, int nlay, 
  * layout; the other SW kernel modes; odd ngpt.  The clear + all-sky (_clr_all) entries take no count
  * (RRTMGPNN_ERR_ARGUMENT). */
 int rrtmgpnn_solver_request_active_columns(rrtmgpnn_context *ctx, int ncol, const int *nact);
+/* Ask this context's next solver call for the shortwave fluxes at the surface by band (ty_fluxes_byband,
+ * extensions/mo_fluxes_byband.F90, at the surface level alone): what a host hands to its land, ocean and sea-ice models.
+ * band_lims_gpt: HOST (2, nbnd), 1-based, copied by the call under the rules of rrtmgpnn_solver_request_byband.
+ * sfc_bnd_up / sfc_bnd_dn / sfc_bnd_dir: DEVICE (nbnd, ncol), band fastest; a NULL pointer is not wanted, all three NULL
+ * disarm.  Armed for one call, cleared by it whatever it returns.
+ * The values are, bit for bit, what rrtmgpnn_solver_request_byband puts at the surface level (array index nlay when
+ * top_at_1, else 0): sum_byband -- the band's first g-point, then the others one by one in increasing g -- of the
+ * g-point up flux, the total down flux (diffuse + direct, rounded once per g-point) and the direct flux.  The call's
+ * broadband outputs are those of the same call without the request.  Nothing is allocated and the pointers are kernel
+ * arguments, so an armed call can be captured in a hipGraph.
+ * Honoured by rrtmgpnn_sw_solver_2stream_inc and by rrtmgpnn_sw_solver_2stream_rfmip with nbnd > 0 on the checkpointed
+ * kernel (even ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3) for g == NULL, bands in the band-pair layout and a
+ * cloud-mask request, a 2str aerosol request or both taken by the same call, with an active-column request beside them
+ * or without (rows at or past *nact are not written): kernel family 9 of rrtmgpnn_context_get_solver_path.
+ * RRTMGPNN_ERR_ARGUMENT: every other solver entry, with a message naming the two; ncol other than the call's; nbnd or
+ * limits other than the call's increment bands.
+ * Refused: RRTMGPNN_ERR_UNSUPPORTED, every armed request cleared, nothing written -- neither a mask nor an aerosol
+ * beside it (rrtmgpnn_solver_request_byband has the surface level in its outputs); a by-band request beside it, alone or
+ * as the _byband_mcica pair; a gas g array; bands outside the band-pair layout; the other SW kernel modes; odd ngpt.  A
+ * Jacobian request beside it is refused as the two entries refuse it alone (RRTMGPNN_ERR_ARGUMENT; beside an
+ * active-column request, that request's RRTMGPNN_ERR_UNSUPPORTED): an earlier request's refusal stands. */
+int rrtmgpnn_solver_request_sfc_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, int ncol,
+                                       float *sfc_bnd_up, float *sfc_bnd_dn, float *sfc_bnd_dir);
 /* ty_optical_props_2str%delta_scale([for]) (rte/mo_optical_props.F90:576-604; kernels
  * rte/kernels/mo_optical_props_kernels.F90:41-92) on n values in place.  fwd == NULL: f = g**2. */
 int rrtmgpnn_delta_scale_2str(rrtmgpnn_context *ctx, long long n, float *tau, float *ssa, float *g, const float *fwd);

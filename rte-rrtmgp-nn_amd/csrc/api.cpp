@@ -1409,6 +1409,24 @@ int rrtmgpnn_solver_request_active_columns(rrtmgpnn_context *ctx, int ncol, cons
   return RRTMGPNN_OK;
 }
 
+// ty_fluxes_byband (extensions/mo_fluxes_byband.F90) at the surface level alone, what a host's surface models take
+int rrtmgpnn_solver_request_sfc_byband(rrtmgpnn_context *ctx, int nbnd, const int *band_lims_gpt, int ncol,
+                                       float *sfc_bnd_up, float *sfc_bnd_dn, float *sfc_bnd_dir)
+{
+  if (int rc = check_ctx(ctx)) return rc;
+  ctx->armed.sfc_byband = SfcBybandRequest{};
+  if (!sfc_bnd_up && !sfc_bnd_dn && !sfc_bnd_dir) return RRTMGPNN_OK;  // nothing wanted: nothing armed
+  if (nbnd < 1 || nbnd > kMaxBands || !band_lims_gpt)
+    return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_sfc_byband: band limits: need 1..64 bands");
+  for (int i = 0; i < nbnd; i++)
+    if (band_lims_gpt[2 * i] < 1 || band_lims_gpt[2 * i] > band_lims_gpt[2 * i + 1])
+      return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_sfc_byband: band limits out of range");
+  if (ncol < 0) return fail(RRTMGPNN_ERR_ARGUMENT, "solver_request_sfc_byband: ncol < 0");
+  ctx->armed.sfc_byband = {true, sfc_bnd_up, sfc_bnd_dn, sfc_bnd_dir, nbnd, ncol};
+  std::memcpy(ctx->armed.sfc_byband.lims, band_lims_gpt, sizeof(int) * 2 * nbnd);
+  return RRTMGPNN_OK;
+}
+
 // rrtmgp_rfmip_sw.F90:285-287 (usecol), 433 (mu0 = 1 at night), 456-463 (the zeroing): kernels_daylit.hip
 int rrtmgpnn_daylit_plan(rrtmgpnn_context *ctx, int ncol, const float *v, int kind, float bound, int *idx, int *slot,
                          int *nday)

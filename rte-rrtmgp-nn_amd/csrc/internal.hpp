@@ -212,7 +212,8 @@ enum SolverFamily {
   kSolverSw2Stream = 5,    // sw_2stream_kernel (kernels_rte.hip)
   kSolverSwX2 = 6,         // sw_2stream_x2_kernel (kernels_sw_x2.hip)
   kSolverSwCkActive = 7,   // sw_2stream_ck_kernel, the active-count instances (rrtmgpnn_solver_request_active_columns)
-  kSolverSwCkActiveSky = 8  // ... those beside a cloud mask and / or an aerosol (a McICA step on daylit columns)
+  kSolverSwCkActiveSky = 8,  // ... those beside a cloud mask and / or an aerosol (a McICA step on daylit columns)
+  kSolverSwCkSfcBand = 9  // sw_2stream_ck_kernel, the surface by-band instances (rrtmgpnn_solver_request_sfc_byband)
 };
 // lw_noscat_kernel
 constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand = 8, kLwOptDual = 16, kLwOptMask = 32,
@@ -221,8 +222,9 @@ constexpr uint32_t kLwOptFused = 1, kLwOptInc = 2, kLwOptMulti = 4, kLwOptBand =
 // (kCk*Small, VSmall), else the default set
 constexpr uint32_t kSwCkHasG = 1, kSwCkInc = 2, kSwCkGpt = 4, kSwCkTn = 8, kSwCkEmk = 16, kSwCkBandPair = 32,
                    kSwCkBand = 64, kSwCkMask = 128, kSwCkAer = 256, kSwCkDual = 512, kSwCkSmall = 1024,
-                   kSwCkActive = 2048;  // the active-column count comes from a device word (families kSolverSwCkActive,
+                   kSwCkActive = 2048,  // the active-column count comes from a device word (families kSolverSwCkActive,
                                         // kSolverSwCkActiveSky)
+                   kSwCkSfcBand = 4096;  // by-band sums of the surface level alone (family kSolverSwCkSfcBand)
 // lw_rescl_planck_inc_kernel
 constexpr uint32_t kScatOptMask = 1, kScatOptAer = 2, kScatOptDual = 4;
 // lw_rescl_kernel

@@ -1157,6 +1157,12 @@ int launch_sw_2stream(rrtmgpnn_context *ctx, const SolverExtras &ex, Sw2Stream p
     return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: an active-column count is taken by the checkpointed kernel only (even "
                                           "ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band, g-point or "
                                           "clear-sky outputs");
+  // the surface level's by-band sums (rrtmgpnn_solver_request_sfc_byband): only the checkpointed kernel has the
+  // instances (select_sw_ck holds the call to the rest of their rules)
+  if (ex.sfc_byband() && (!ck || gpt || bb || dual))
+    return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: surface by-band outputs are taken by the checkpointed kernel only "
+                                          "(even ngpt, rrtmgpnn_context_set_sw_kernel mode 0 or 3), without by-band, "
+                                          "g-point or clear-sky outputs");
   // the RFMIP boundary conditions (rrtmgpnn_sw_solver_2stream_rfmip): formed in the checkpointed kernel's prologue;
   // the other kernels read them from memory, formed there first by sw_boundary_kernel
   SwBcDev bcd{};

@@ -324,6 +324,7 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
   constexpr bool kTn = (O & kSwCkTn) != 0, kEmk = (O & kSwCkEmk) != 0, kBandPair = (O & kSwCkBandPair) != 0;
   constexpr bool kBand = (O & kSwCkBand) != 0, kMask = (O & kSwCkMask) != 0, kAer = (O & kSwCkAer) != 0;
   constexpr bool kDual = (O & kSwCkDual) != 0, kSmall = (O & kSwCkSmall) != 0, kActive = (O & kSwCkActive) != 0;
+  constexpr bool kSfcBand = (O & kSwCkSfcBand) != 0;
   static_assert(!kActive || (!kDual && !kGpt && !kBand && !kHasG),
                 "the active-count instances: clear sky or the fused increment (masked, behind an aerosol), broadband "
                 "outputs");
@@ -348,6 +349,9 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
   static_assert(!kAer || (kInc && (kBandPair || kDual) && sizeof(V) == 8 && !kGpt && !kBand),
                 "the aerosol increment goes in front of the fused band-pair increment");
   static_assert(!kMask || (kInc && sizeof(V) == 8 && !kGpt), "the cloud mask switches the fused band increment");
+  static_assert(!kSfcBand || (kInc && kBandPair && (kMask || kAer) && sizeof(V) == 8 && !kDual && !kGpt && !kBand &&
+                              !kHasG && !kSmall),
+                "the surface by-band instances: the masked cloud and / or the aerosol on the band-pair increment");
   constexpr bool kG0 = !kHasG && !kInc;  // g is the literal 0 (the NN path)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // `ncb` columns per block: lane t works on column c = t / (ngpt/NPL), g-points g .. g + NPL - 1
@@ -709,16 +713,21 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
       }
     }
   };
-  auto flush = [&](int n, int lev0, int dl, int slot0 = 0) {
+  auto flush = [&](int n, int lev0, int dl, int slot0 = 0, bool sfc = false) {
     // kBand: the by-band sums bo.up / bo.dn / bo.dir in the same barrier window; the ring keeps diffuse and direct
     // apart (the broadband bits do not move) and the band walk forms dif + dir itself (band_flush)
-    const BandOut *pb = kBand ? &bo : nullptr;
+    // kSfcBand (rrtmgpnn_solver_request_sfc_byband): the same walk over the surface level alone, the last of the
+    // levels of pass 3's last flush (sfc), into bo's (nbnd, ncol) arrays
+    const BandOut *pb = (kBand || kSfcBand) ? &bo : nullptr;
+    const int sfc_slot = (kSfcBand && sfc) ? slot0 + n - 1 : -1;
     if (kCkFlushLanes && (ngpt & 3) == 0 && 3 * ncr * n * 4 <= (int)blockDim.x)
-      ring_flush_sw_lanes<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, nca,
-                                                 flux_up, flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir);
+      ring_flush_sw_lanes<R, kGpt, kBand, kDual, kSfcBand>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0,
+                                                           nca, flux_up, flux_dn, flux_dir, rs, slot0, pb, clr_up,
+                                                           clr_dn, clr_dir, sfc_slot);
     else
-      ring_flush_sw<R, kGpt, kBand, kDual>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, nca, flux_up,
-                                           flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir);
+      ring_flush_sw<R, kGpt, kBand, kDual, kSfcBand>(smem + kExpTabFloats, ncr, n, lev0, dl, ngpt, nlev, icol0, nca,
+                                                     flux_up, flux_dn, flux_dir, rs, slot0, pb, clr_up, clr_dn, clr_dir,
+                                                     sfc_slot);
   };
   // the ring holds M = R / K chunks; the block flushes it when it is full (a barrier, the ordered sums, a barrier).
   // (Staggering the blocks' flush phases, so that blocks sharing a CU flush at different chunks, measured equal, round
@@ -784,7 +793,7 @@ __global__ void __launch_bounds__(512, sw_ck_waves(O))
       }
       if (valid && (rbase + K == R || ck == nck - 1)) {
         const int j0 = ck * K - rbase;  // first layer of this ring's levels
-        flush(min(R, nlay - j0), top + dl_dn * (j0 + 1), dl_dn);
+        flush(min(R, nlay - j0), top + dl_dn * (j0 + 1), dl_dn, 0, ck == nck - 1);  // pass 3 ends at the surface
       }
     };
     if constexpr (AHEAD == 2) {
@@ -880,6 +889,21 @@ using SwCkActiveSkyInstances = SolverInstances<
     kSwCkActive | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair,
     kSwCkActive | kSwCkInc | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc, kSwCkActive | kSwCkInc | kSwCkAer | kSwCkBandPair>;
 
+// ... and the by-band sums of the surface level (rrtmgpnn_solver_request_sfc_byband, kSolverSwCkSfcBand): each instance
+// is its twin of the first family (aerosol / masked cloud, band pair, no gas g) or of kSolverSwCkActiveSky plus the bit,
+// {the count} x {mask, mask + aerosol, aerosol} x {the all-sky plane}
+using SwCkSfcBandInstances = SolverInstances<
+    kSwCkSfcBand | kSwCkInc | kSwCkMask | kSwCkBandPair | kSwCkPlanesInc, kSwCkSfcBand | kSwCkInc | kSwCkMask | kSwCkBandPair,
+    kSwCkSfcBand | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc,
+    kSwCkSfcBand | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair,
+    kSwCkSfcBand | kSwCkInc | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc, kSwCkSfcBand | kSwCkInc | kSwCkAer | kSwCkBandPair,
+    kSwCkSfcBand | kSwCkActive | kSwCkInc | kSwCkMask | kSwCkBandPair | kSwCkPlanesInc,
+    kSwCkSfcBand | kSwCkActive | kSwCkInc | kSwCkMask | kSwCkBandPair,
+    kSwCkSfcBand | kSwCkActive | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc,
+    kSwCkSfcBand | kSwCkActive | kSwCkInc | kSwCkMask | kSwCkAer | kSwCkBandPair,
+    kSwCkSfcBand | kSwCkActive | kSwCkInc | kSwCkAer | kSwCkBandPair | kSwCkPlanesInc,
+    kSwCkSfcBand | kSwCkActive | kSwCkInc | kSwCkAer | kSwCkBandPair>;
+
 // The instance a call runs (its options value), or the refusal.  planes: the workspace with the instance family's
 // planes was allocated (launch_sw_2stream's fallback runs the plane-free twins: the same bits); small: sw_ck_small()
 static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes, bool small, uint32_t *options)
@@ -890,6 +914,26 @@ static int select_sw_ck(const SolverExtras &ex, const Sw2Stream &p, bool planes,
   bool pair = bands != nullptr;
   for (int i = 0; bands && i < bands->nbnd; i++) pair = pair && ((bands->lims[2 * i] - 1) % 2 == 0);
   uint32_t o = (p.g ? kSwCkHasG : 0u) | (bands ? kSwCkInc : 0u) | (ex.mask_bits ? kSwCkMask : 0u);
+  if (ex.sfc_byband()) {
+    // the surface level's by-band sums: the twin's rules (the branches below) hold, and on top of them no gas g, the
+    // band-pair layout (also for a masked cloud alone) and the request's bands the increment's own
+    if (ex.clr_up || bb || gpt)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: surface by-band outputs with clear-sky twins, by-band or g-point "
+                                            "outputs");
+    if (!ex.mask_bits && !ex.aer_tau)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: surface by-band outputs need a cloud mask or an aerosol increment");
+    if (p.g) return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: surface by-band outputs with a gas g array (g == NULL: the NN path)");
+    if (!bands) return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: surface by-band outputs need the fused band increment");
+    if (!pair)
+      return fail(RRTMGPNN_ERR_UNSUPPORTED, "sw solver: surface by-band outputs need every band to start at an odd "
+                                            "(1-based) g-point, the band-pair layout");
+    bool same = ex.sfc_bnd.nbnd == bands->nbnd;
+    for (int i = 0; same && i < 2 * bands->nbnd; i++) same = ex.sfc_bnd.lims[i] == bands->lims[i];
+    if (!same)
+      return fail(RRTMGPNN_ERR_ARGUMENT, "sw solver: the requested surface by-band outputs' bands are not this call's "
+                                         "increment bands");
+    o |= kSwCkSfcBand;
+  }
   if (ex.nact) {
     // the daylit columns of a compacted block: the instance the same call would run without the count (chosen from the
     // launch-time ncol: the host never sees the count), from the family's own list
@@ -973,7 +1017,9 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
   const SwBcDev nobc{};  // tsi == NULL: the caller's inc_flux, mu0 and albedos
   const SwBcDev &bcd = bc ? *bc : nobc;
   const bool gpt = ex.gpt_up || ex.gpt_dn || ex.gpt_dir;
-  const BandOut bo = ex.byband() ? band_out(ex) : BandOut{};
+  const BandOut bo = ex.byband()       ? band_out(ex)
+                     : ex.sfc_byband() ? BandOut{ex.sfc_bnd_up, ex.sfc_bnd_dn, ex.sfc_bnd_dir, ex.sfc_bnd}
+                                       : BandOut{};
   uint32_t options = 0;
   if (int rc = select_sw_ck(ex, p, planes, sw_ck_small(ctx, ngpt, ncol, p.g != nullptr, p.bands != nullptr, gpt), &options))
     return rc;
@@ -1006,6 +1052,7 @@ int launch_sw_2stream_ck(rrtmgpnn_context *ctx, const SolverExtras &ex, const Sw
     RRTMGPNN_LAUNCH_CHECK(kDual ? "sw_2stream_ck_kernel (clear + all sky)" : "sw_2stream_ck_kernel");
     return RRTMGPNN_OK;
   };
+  if (ex.sfc_byband()) return launch_listed(ctx, kSolverSwCkSfcBand, SwCkSfcBandInstances{}, options, go);
   if (ex.nact && (ex.mask_bits || ex.aer_tau))
     return launch_listed(ctx, kSolverSwCkActiveSky, SwCkActiveSkyInstances{}, options, go);
   if (ex.nact) return launch_listed(ctx, kSolverSwCkActive, SwCkActiveInstances{}, options, go);

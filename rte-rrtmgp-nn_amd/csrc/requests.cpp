@@ -10,6 +10,8 @@ static constexpr char kMaskIsArgumentMsg[] = "lw_solver_noscat_planck_clr_all_mc
                                              "mask_bits argument, not a solver_request_cloud_mask request";
 static constexpr char kNoActiveMsg[] = "solver_request_active_columns: this solver entry takes no active-column count (the "
                                        "sw_solver_2stream, sw_solver_2stream_inc and sw_solver_2stream_rfmip entries do)";
+static constexpr char kNoSfcBybandMsg[] = "solver_request_sfc_byband: this solver entry takes no surface by-band request "
+                                          "(the sw_solver_2stream_inc and sw_solver_2stream_rfmip entries do)";
 static constexpr char kNoJacobianTail[] = ": no flux Jacobian from this entry (the lw_solver_noscat, _noscat_planck, "
                                           "_noscat_planck_inc and _1rescl entries have it)";
 static constexpr char kNoJacobian2streamMsg[] = "rte_lw: can't provide Jacobian of fluxes w.r.t surface temperature with "
@@ -26,7 +28,7 @@ static constexpr char kNoBybandSw[] = ": by-band outputs are not available from 
                                       "sw_solver_2stream_rfmip entries have them)";
 
 // The table: the only statement of which entry honours which request.  A row reads entry; by-band; cloud mask; flux
-// Jacobian and its refusal; aerosol; active-column count; (aerosol ahead of by-band).
+// Jacobian and its refusal; aerosol; active-column count; (aerosol ahead of by-band; surface by-band outputs).
 using J = TakeJacobian;
 using A = TakeAerosol;
 using N = TakeActive;
@@ -55,11 +57,11 @@ constexpr RequestPolicy kRequestPolicies[kNumPolicyRows] = {
     // sw_solver_noscat (rte/kernels/mo_rte_solver_kernels.F90:496-532)
     {"sw_solver_noscat", kTake, kNoMaskMsg, J::kRefuse, nullptr, A::kRefuse, N::kRefuse},
     // sw_solver_2stream behind inc_2stream_by_2stream_bybnd (rte/kernels/mo_optical_props_kernels.F90:430-463)
-    {"sw_solver_2stream_inc", kTake, kTake, J::kRefuse, nullptr, A::k2str, N::kBesideSky},
+    {"sw_solver_2stream_inc", kTake, kTake, J::kRefuse, nullptr, A::k2str, N::kBesideSky, false, true},
     // rte_sw twice, clear and all sky (extensions/mo_rrtmgp_clr_all_sky.F90:283-304)
     {"sw_solver_2stream_clr_all", kNoBybandSw, kTake, J::kRefuse, nullptr, A::k2str, N::kRefuse},
     // sw_solver_2stream_inc behind the RFMIP driver's boundary conditions (rrtmgp_rfmip_sw.F90:403-441)
-    {"sw_solver_2stream_rfmip", kTake, kTake, J::kRefuse, nullptr, A::k2str, N::kBesideSky},
+    {"sw_solver_2stream_rfmip", kTake, kTake, J::kRefuse, nullptr, A::k2str, N::kBesideSky, false, true},
     // ... twice, clear and all sky (extensions/mo_rrtmgp_clr_all_sky.F90:283-304)
     {"sw_solver_2stream_rfmip_clr_all", kNoBybandSw, kTake, J::kRefuse, nullptr, A::k2str, N::kRefuse},
 };
@@ -169,10 +171,37 @@ int apply_mask(const RequestPolicy &p, const ArmedRequests &rq, const CallDims &
   return RRTMGPNN_OK;
 }
 
+// the surface level's by-band sums: beside a taken cloud mask and / or aerosol, never beside the full by-band outputs
+// (whose surface level they equal) or a flux Jacobian; on the call's own bands and columns
+int apply_sfc_byband(const RequestPolicy &p, const ArmedRequests &rq, const CallDims &d, SolverExtras &ex)
+{
+  const SfcBybandRequest &s = rq.sfc_byband;
+  if (!s.armed) return RRTMGPNN_OK;
+  if (!p.sfc_byband) return fail(RRTMGPNN_ERR_ARGUMENT, kNoSfcBybandMsg);
+  if (rq.byband.armed)
+    return refuse(RRTMGPNN_ERR_UNSUPPORTED, p, ": surface by-band outputs together with a by-band request (alone or paired "
+                                               "with a cloud mask), whose surface level they are");
+  if (rq.jacobian.armed)
+    return refuse(RRTMGPNN_ERR_UNSUPPORTED, p, ": surface by-band outputs together with a Jacobian request");
+  if (!ex.mask_bits && !ex.aer_tau)
+    return refuse(RRTMGPNN_ERR_UNSUPPORTED, p, ": surface by-band outputs need a cloud mask or an aerosol request beside "
+                                               "them (rrtmgpnn_solver_request_byband has the surface level in its outputs)");
+  if (s.ncol != d.ncol)
+    return refuse(RRTMGPNN_ERR_ARGUMENT, p, ": the requested surface by-band outputs' ncol is not this call's");
+  if (s.nbnd != d.nbnd)
+    return refuse(RRTMGPNN_ERR_ARGUMENT, p, ": the requested surface by-band outputs' bands are not this call's increment "
+                                            "bands");
+  if (int rc = band_args(s.nbnd, s.lims, d.ngpt, ex.sfc_bnd)) return rc;
+  ex.sfc_bnd_up = s.up;
+  ex.sfc_bnd_dn = s.dn;
+  ex.sfc_bnd_dir = s.dir;
+  return RRTMGPNN_OK;
+}
+
 }  // namespace
 
 // The order of the checks, the same for every entry: active-column count, by-band, aerosol, cloud mask, flux Jacobian,
-// then the g-point outputs beside what was taken.  Each request is first refused where the row refuses it, then checked
+// then the g-point outputs beside what was taken, then the surface by-band outputs.  Each request is first refused where the row refuses it, then checked
 // against the other armed requests, then against the call's extents, then taken into `ex`.  (Of the orders that keep
 // every answer one the ladders this replaced gave for the same requests or a part of them, this one changes the fewest;
 // DESIGN.md, "Solver dispatch".  The one departure, RequestPolicy::aerosol_ahead_of_byband, swaps the second and third
@@ -192,7 +221,7 @@ int apply_requests(const RequestPolicy &p, const ArmedRequests &rq, const CallDi
     return refuse(RRTMGPNN_ERR_UNSUPPORTED, p, ": a flux Jacobian together with g-point outputs");
   if (ex.nact && d.gpt_outputs)
     return refuse(RRTMGPNN_ERR_UNSUPPORTED, p, ": an active-column count together with g-point outputs");
-  return RRTMGPNN_OK;
+  return apply_sfc_byband(p, rq, d, ex);
 }
 
 }  // namespace rrtmgpnn

@@ -55,6 +55,12 @@ struct SolverExtras {
   // the kernel solves; only the checkpointed SW launcher has such instances, for g == NULL: kSolverSwCkActive without
   // any of the above, kSolverSwCkActiveSky beside mask_bits and / or a 2str aerosol (rows of the call's ncol both)
   const int *nact = nullptr;
+  // rrtmgpnn_solver_request_sfc_byband: the by-band sums of the surface level alone, (nbnd, ncol) each, on the call's own
+  // increment bands; only the checkpointed SW launcher has such instances (kSolverSwCkSfcBand), for g == NULL, the
+  // band-pair layout and a cloud mask and / or a 2str aerosol, with nact or without
+  float *sfc_bnd_up = nullptr, *sfc_bnd_dn = nullptr, *sfc_bnd_dir = nullptr;
+  BandArgs sfc_bnd{};
+  bool sfc_byband() const { return sfc_bnd_up || sfc_bnd_dn || sfc_bnd_dir; }
 };
 
 // The requests: each is armed on a context for its next solver call, which takes and clears all of them whatever it
@@ -94,13 +100,24 @@ struct ActiveRequest {
   int ncol = 0;
   const int *nact = nullptr;
 };
+// rrtmgpnn_solver_request_sfc_byband
+struct SfcBybandRequest {
+  bool armed = false;
+  float *up = nullptr, *dn = nullptr, *dir = nullptr;
+  int nbnd = 0, ncol = 0;
+  int lims[2 * kMaxBands] = {0};
+};
 struct ArmedRequests {
   BybandRequest byband;
   CloudMaskRequest cloud_mask;
   JacobianRequest jacobian;
   AerosolRequest aerosol;
   ActiveRequest active;
-  bool any() const { return byband.armed || cloud_mask.armed || jacobian.armed || aerosol.armed || active.armed; }
+  SfcBybandRequest sfc_byband;
+  bool any() const
+  {
+    return byband.armed || cloud_mask.armed || jacobian.armed || aerosol.armed || active.armed || sfc_byband.armed;
+  }
 };
 
 // What one solver entry does with each kind of request: one row of kRequestPolicies per entry (a *_gpt twin shares its
@@ -119,6 +136,8 @@ struct RequestPolicy {
   TakeActive active;
   // the aerosol is looked at ahead of the by-band request (the two lw_solver_noscat_planck_clr_all rows)
   bool aerosol_ahead_of_byband = false;
+  // the entry takes rrtmgpnn_solver_request_sfc_byband (beside a taken cloud mask and / or aerosol)
+  bool sfc_byband = false;
 };
 
 // the call's extents, and whether it has g-point outputs (a *_gpt entry given at least one): neither a flux Jacobian

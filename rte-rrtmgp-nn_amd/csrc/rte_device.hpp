@@ -312,11 +312,14 @@ __device__ __forceinline__ float combine4(const float *p) { return ((p[0] + p[1]
 // kBand: also the by-band sums (band_flush), the down value formed as dif + dir per g-point unless kTotal
 // kSkies (the dual clear + all-sky instances, ncb = 2): the two "columns" of the ring are the two skies of column icol0
 // -- ring column 0 stores to o_up / o_dn / o_dir, ring column 1 to c_up / c_dn / c_dir, both at column icol0
-template <int R, bool kTotal = false, bool kBand = false, bool kSkies = false>
+// kSfc (rrtmgpnn_solver_request_sfc_byband): the by-band sums of the one level in slot sfc_slot (the surface; < 0: not
+// among this flush's levels) into bo's (nbnd, ncol) arrays -- band_flush of that slot alone, with n = 1 and nlev = 1
+template <int R, bool kTotal = false, bool kBand = false, bool kSkies = false, bool kSfc = false>
 __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n, int lev0, int dl, int ngpt, int nlev,
                                               int icol0, int ncol, float *o_up, float *o_dn, float *o_dir,
                                               int stride = 0, int slot0 = 0, const BandOut *bo = nullptr,
-                                              float *c_up = nullptr, float *c_dn = nullptr, float *c_dir = nullptr)
+                                              float *c_up = nullptr, float *c_dn = nullptr, float *c_dir = nullptr,
+                                              int sfc_slot = -1)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -358,6 +361,10 @@ __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n,
   if constexpr (kBand)
     band_flush(ring, rs, R * rs, 3 * R * rs, ncb, 3, n, slot0, lev0, dl, nlev, icol0, ncol, kTotal ? -1 : 1, bo->up,
                bo->dn, bo->dir, bo->b, (3 * ncb * n + 63) & ~63);
+  if constexpr (kSfc)
+    if (sfc_slot >= 0)
+      band_flush(ring, rs, R * rs, 3 * R * rs, ncb, 3, 1, sfc_slot, 0, 0, 1, icol0, ncol, 1, bo->up, bo->dn, bo->dir,
+                 bo->b, (3 * ncb * n + 63) & ~63);
   __syncthreads();
 }
 
@@ -371,13 +378,13 @@ __device__ __forceinline__ void ring_flush_sw(const float *ring, int ncb, int n,
 // (the SW launchers refuse more before launching)
 constexpr int kFlushLanesMaxCols = 4;
 
-// kSkies: as ring_flush_sw's
-template <int R, bool kTotal = false, bool kBand = false, bool kSkies = false>
+// kSkies, kSfc: as ring_flush_sw's
+template <int R, bool kTotal = false, bool kBand = false, bool kSkies = false, bool kSfc = false>
 __device__ __forceinline__ void ring_flush_sw_lanes(const float *ring, int ncb, int n, int lev0, int dl, int ngpt,
                                                     int nlev, int icol0, int ncol, float *o_up, float *o_dn,
                                                     float *o_dir, int stride, int slot0 = 0,
                                                     const BandOut *bo = nullptr, float *c_up = nullptr,
-                                                    float *c_dn = nullptr, float *c_dir = nullptr)
+                                                    float *c_dn = nullptr, float *c_dir = nullptr, int sfc_slot = -1)
 {
   __syncthreads();
   const int t = threadIdx.x;
@@ -414,6 +421,10 @@ __device__ __forceinline__ void ring_flush_sw_lanes(const float *ring, int ncb, 
   if constexpr (kBand)
     band_flush(ring, stride, R * stride, 3 * R * stride, ncb, 3, n, slot0, lev0, dl, nlev, icol0, ncol,
                kTotal ? -1 : 1, bo->up, bo->dn, bo->dir, bo->b, (3 * per_q + 63) & ~63);
+  if constexpr (kSfc)
+    if (sfc_slot >= 0)
+      band_flush(ring, stride, R * stride, 3 * R * stride, ncb, 3, 1, sfc_slot, 0, 0, 1, icol0, ncol, 1, bo->up, bo->dn,
+                 bo->dir, bo->b, (3 * per_q + 63) & ~63);
   __syncthreads();
 }
 

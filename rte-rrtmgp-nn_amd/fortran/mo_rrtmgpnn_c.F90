@@ -30,6 +30,7 @@ module mo_rrtmgpnn_c
   public :: c_rrtmgpnn_solver_request_aerosol
   public :: c_rrtmgpnn_daylit_plan, c_rrtmgpnn_gather_columns, c_rrtmgpnn_scatter_columns, &
             c_rrtmgpnn_gas_optics_sw_nn_active, c_rrtmgpnn_solver_request_active_columns
+  public :: c_rrtmgpnn_solver_request_sfc_byband
   public :: c_rrtmgpnn_solver_request_cloud_mask, c_rrtmgpnn_sampled_mask_max_ran, c_rrtmgpnn_sampled_mask_exp_ran, &
             c_rrtmgpnn_draw_samples
   public :: c_rrtmgpnn_mcica_rng_set, c_rrtmgpnn_mcica_randoms, c_rrtmgpnn_sampled_mask_max_ran_seeded, &
@@ -462,6 +463,15 @@ module mo_rrtmgpnn_c
       import :: c_int, c_ptr
       type(c_ptr), value :: ctx, nact
       integer(c_int), value :: ncol
+    end function
+    ! ty_fluxes_byband at the surface level alone: outputs (nbnd, ncol) of the next SW solver call that takes a cloud mask
+    ! and / or an aerosol; band_lims_gpt on the host, the outputs device pointers (c_null_ptr: not wanted)
+    integer(c_int) function c_rrtmgpnn_solver_request_sfc_byband(ctx, nbnd, band_lims_gpt, ncol, sfc_bnd_up, &
+        sfc_bnd_dn, sfc_bnd_dir) bind(C, name="rrtmgpnn_solver_request_sfc_byband")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, sfc_bnd_up, sfc_bnd_dn, sfc_bnd_dir
+      integer(c_int), value :: nbnd, ncol
+      integer(c_int), dimension(*), intent(in) :: band_lims_gpt
     end function
     ! the two requests above as a pair: by-band outputs of the next solver call under its McICA mask
     integer(c_int) function c_rrtmgpnn_solver_request_byband_mcica(ctx, nbnd, band_lims_gpt, bnd_flux_up, bnd_flux_dn, &

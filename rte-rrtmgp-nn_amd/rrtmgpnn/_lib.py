@@ -167,6 +167,7 @@ SIGNATURES = {
     "rrtmgpnn_gas_optics_sw_nn_active": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, P(c_vp),
                                                  P(c_int), P(c_vp), c_vp, c_vp, c_vp, c_vp]),
     "rrtmgpnn_solver_request_active_columns": (c_int, [c_vp, c_int, c_vp]),
+    "rrtmgpnn_solver_request_sfc_byband": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
     "rrtmgpnn_file_open": (c_int, [c_char_p, P(c_vp)]),
     "rrtmgpnn_file_close": (c_int, [c_vp]),
     "rrtmgpnn_file_nvars": (c_int, [c_vp, P(c_int)]),

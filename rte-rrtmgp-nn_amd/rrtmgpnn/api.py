@@ -1058,7 +1058,10 @@ def rte_sw(atmos, top_at_1, mu0, inc_flux, sfc_alb_dir_gpt, sfc_alb_dif_gpt, flu
     that the solver adds to atmos as it reads it (rrtmgpnn_sw_solver_2stream_inc; atmos is left as it was) -- the entry
     that takes the requests armed ahead of this call with cloud_sampling.arm_cloud_mask (band_inc is then the cloud the
     mask samples) and cloud_sampling.arm_aerosol, alone or beside active (then on the dense columns: a mask from
-    daylit.sampled_mask_active, a gathered aerosol).  Two-stream, no g-point fluxes."""
+    daylit.sampled_mask_active, a gathered aerosol).  Beside either of the two, cloud_sampling.arm_sfc_byband asks the
+    same call for the by-band fluxes at the surface, (ncol, nband) each (rrtmgpnn_solver_request_sfc_byband: atmos.g
+    None, bands in the band-pair layout; with active, rows at or past the count are left as they are).  Two-stream, no
+    g-point fluxes."""
     if not fluxes.are_desired():
         return "rte_sw: no space allocated for fluxes"
     if not isinstance(atmos, (OpticalProps1scl, OpticalProps2str)):

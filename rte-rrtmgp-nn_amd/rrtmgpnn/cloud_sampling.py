@@ -233,6 +233,24 @@ def arm_aerosol(ctx, aer_props):
         _p(getattr(aer_props, "g", None))), "solver_request_aerosol")
 
 
+def arm_sfc_byband(ctx, band_lims_gpt, sfc_up, sfc_dn, sfc_dir=None):
+    """Arm the by-band fluxes at the surface, outputs (ncol, nband) over band_lims_gpt (nband, 2; 1-based, inclusive: the
+    call's own increment bands), for the next solver call on ctx (rrtmgpnn_solver_request_sfc_byband); that call clears
+    it.  Taken by the fused shortwave call (api.rte_sw with band_inc=) beside arm_cloud_mask, arm_aerosol or both, also
+    with active=; the values are the surface level of the by-band fluxes of the same problem.  An output that is None
+    is not written; all three None disarm."""
+    outs = [o for o in (sfc_up, sfc_dn, sfc_dir) if o is not None]
+    if not outs:
+        check(_lib.lib().rrtmgpnn_solver_request_sfc_byband(ctx.h, 0, None, 0, None, None, None), "solver_request_sfc_byband")
+        return
+    lims = [int(v) for pair in band_lims_gpt for v in pair]
+    ncol, nbnd = outs[0].shape
+    if nbnd != len(lims) // 2 or any(tuple(o.shape) != (ncol, nbnd) for o in outs):
+        raise ValueError("arm_sfc_byband: the outputs are (ncol, nband) on the bands of band_lims_gpt")
+    check(_lib.lib().rrtmgpnn_solver_request_sfc_byband(
+        ctx.h, nbnd, int_array(lims), ncol, _p(sfc_up), _p(sfc_dn), _p(sfc_dir)), "solver_request_sfc_byband")
+
+
 def arm_cloud_mask_byband(ctx, ngpt, mask_bits, band_lims_gpt, bnd_up, bnd_dn, bnd_dir=None):
     """Arm the packed mask mask_bits (ncol, nlay, ceil(ngpt / 32)) together with by-band outputs (ncol, nlay + 1, nbnd)
     over band_lims_gpt (nbnd, 2; 1-based, inclusive) for the next solver call on ctx

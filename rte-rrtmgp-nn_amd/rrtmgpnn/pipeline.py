@@ -112,6 +112,16 @@ launch, which takes the aerosol as its own increment or none (family 7), and one
 SW flux arrays, zeros at night in each.  The LW chain is untouched: full extent, its own mask and stream.  set_sza,
 set_aerosols, set_mcica_seed and set_mcica_randoms work between graph replays without recapture.  Not with
 mcica["byband"], sw_dual, fused=False, capture_chains or run_blocks; daylit=True beside it is refused as above.
+
+sfc_byband=True (fused, clouds= with mcica= and / or aerosols=): the step also owns the SW fluxes at the surface by band,
+sw_sfc_bnd_up / sw_sfc_bnd_dn / sw_sfc_bnd_dir, (ncol, nband) each (sfc_byband_fluxes()) -- what a host hands to its land,
+ocean and sea-ice models.  rrtmgpnn_solver_request_sfc_byband (sw_sfc_byband, host-only) is armed right before the
+all-sky SW launch, beside its mask and aerosol requests, and that launch forms the band sums of its surface level
+(solver family 9); the clear launch is as it was.  With mcica["daylit"] the solver writes dense rows and a
+rrtmgpnn_scatter_columns call of their own (daylit_scatter_sfc, rows of nband floats) puts them back, zeros at night.
+The values are the surface level of the by-band fluxes of the same step.  Not with byband, mcica["byband"], sw_dual,
+fused=False, sw=False, daylit=True, nor without clouds= and one of mcica= and aerosols=.  Off (the default), nothing of
+the step changes.
 """
 
 from types import SimpleNamespace
@@ -129,7 +139,7 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
             "sw_byband", "sw_solver", "sw_solver_clr", "mcica_mask_sw", "draw_samples_sw", "sw_mask",
             "mcica_randoms_sw", "sw_mask_byband", "sw_aerosol", "increment_aer_sw",
             "daylit_plan", "daylit_gather", "sw_active", "daylit_scatter",
-            "daylit_gather2", "daylit_gather3", "sw_active_clr"}
+            "daylit_gather2", "daylit_gather3", "sw_active_clr", "sw_sfc_byband", "daylit_scatter_sfc"}
 
 
 # issue order of the fused step (stable sort; names not listed keep their place at the end)
@@ -145,9 +155,12 @@ SW_CHAIN = {"sw_boundary", "nn_inputs_sw", "predict_nn_sw", "cloud_optics_sw", "
 # (daylit_gather2 / daylit_gather3: a mcica["daylit"] step's further gather calls, for what the first call's 16 arrays leave
 # and for the aerosol's long rows, which get a call of their own; sw_active_clr:
 # its active-column request for the clear launch sw_solver_clr, which in every other step is the chain's last call)
+# (sw_sfc_byband: a sfc_byband=True step's request, host-only, right before the all-sky solver; daylit_scatter_sfc: its
+# dense rows back to their columns in a mcica["daylit"] step)
 FUSED_ORDER = ["sw_boundary", "get_col_dry", "expand_emis", "lw_upper_bc", "nn_inputs_lw", "cloud_optics_lw", "mcica_mask_lw",
                "predict_nn_lw", "lw_solver_clr", "lw_byband", "lw_mask", "lw_mask_byband", "lw_jacobian", "lw_aerosol", "lw_solver", "daylit_plan", "daylit_gather", "daylit_gather2", "daylit_gather3", "nn_inputs_sw", "cloud_optics_sw",
-               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_active", "sw_solver", "sw_active_clr", "sw_solver_clr", "daylit_scatter"]
+               "delta_scale_sw", "mcica_mask_sw", "predict_nn_sw", "sw_byband", "sw_mask", "sw_mask_byband", "sw_aerosol", "sw_active", "sw_sfc_byband", "sw_solver", "sw_active_clr", "sw_solver_clr", "daylit_scatter",
+               "daylit_scatter_sfc"]
 
 
 def issue_order(calls, fused, lw_after=""):
@@ -212,14 +225,29 @@ class ClearSkyStep:
     aerosols: aerosol optical properties by band, {"lw_tau": (ncol, nlay, nband_lw), "sw_tau", "sw_ssa", "sw_g": (ncol,
     nlay, nband_sw)} (the SW keys only with sw=True), in step-owned device buffers (aer_tau_lw, aer_tau_sw, aer_ssa_sw,
     aer_g_sw) that set_aerosols refills between steps or replays: added to the gas properties ahead of the clear solve,
-    so the clear-sky fluxes are those of gases plus aerosols; refused with byband, jacobian and mcica["byband"]."""
+    so the clear-sky fluxes are those of gases plus aerosols; refused with byband, jacobian and mcica["byband"].
+    sfc_byband: the step also owns the SW fluxes at the surface by band (sw_sfc_bnd_up / sw_sfc_bnd_dn / sw_sfc_bnd_dir,
+    (ncol, nband); sfc_byband_fluxes()), formed by the all-sky SW launch of a fused step with clouds= and mcica= and / or
+    aerosols= (module docstring); refused with byband, mcica["byband"], sw_dual, fused=False, sw=False and daylit=True."""
 
     def __init__(self, prob, device=0, nmus=1, ctx=None, lw_models=("lw_abs", "lw_pfrac"),
                  sw_models=("sw_abs", "sw_ray"), fused=True, clouds=None, icergh=2, cloud_lut=True, overlap=True,
                  sw=True, lw_after=None, sw_after=None, sw_priority=0, lw_net_cus=None, sw_net_cus=0, byband=False,
                  clrsky=False, mcica=None, jacobian=False, aerosols=None, lw_scattering=False, sw_dual=False,
-                 lw_dual=False, upper_bc=False, spectral=None, daylit=False):
+                 lw_dual=False, upper_bc=False, spectral=None, daylit=False, sfc_byband=False):
         lw_models, sw_models = self._resolve_spectral(spectral, lw_models, sw_models)
+        self.sfc_byband = bool(sfc_byband)
+        if self.sfc_byband:
+            # (ahead of the other option checks, so that the refusal names this option)
+            bad = [w for w, on in (("byband", bool(byband)),
+                                   ("mcica['byband']", mcica is not None and bool(mcica.get("byband"))),
+                                   ("sw_dual", bool(sw_dual)), ("fused=False", not fused), ("sw=False", not sw),
+                                   ("daylit=True", bool(daylit)), ("no clouds", clouds is None),
+                                   ("neither mcica nor aerosols", mcica is None and aerosols is None)) if on]
+            if bad:
+                raise ValueError("sfc_byband=True with %s is not supported: the surface by-band fluxes come from the fused "
+                                 "all-sky SW launch under a McICA mask and / or behind an aerosol request (the by-band "
+                                 "outputs of byband=True hold the surface level)" % ", ".join(bad))
         self.daylit = bool(daylit)
         if self.daylit:
             # (ahead of the other option checks, so that the refusal names this option)
@@ -431,6 +459,9 @@ class ClearSkyStep:
             if sw:
                 self.sw_bnd_up, self.sw_bnd_dn, self.sw_bnd_dir = (
                     f(ncol, nlay + 1, self.kd_sw["nband"]) for _ in range(3))
+        if self.sfc_byband:
+            self.sw_sfc_bnd_up, self.sw_sfc_bnd_dn, self.sw_sfc_bnd_dir = (
+                f(ncol, self.kd_sw["nband"]).zero_() for _ in range(3))
         if self.daylit or self.mcica_daylit:
             self._allocate_daylit()
 
@@ -452,6 +483,9 @@ class ClearSkyStep:
         self._day_pairs_aer = []
         if self.mcica_daylit and self.clrsky:
             self.d_sw_up_clr, self.d_sw_dn_clr, self.d_sw_dir_clr = (torch.zeros_like(self.sw_up) for _ in range(3))
+        if self.sfc_byband:
+            self.d_sw_sfc_bnd_up, self.d_sw_sfc_bnd_dn, self.d_sw_sfc_bnd_dir = (
+                torch.zeros_like(self.sw_sfc_bnd_up) for _ in range(3))
         # (a mcica["daylit"] step gathers in as many calls as its list needs: its aerosol arrays join in _allocate_aerosols)
         if len(self._day_pairs) > 16 and not self.mcica_daylit:
             raise ValueError("daylit=True: more than 16 arrays to gather")
@@ -638,6 +672,15 @@ class ClearSkyStep:
             return []
         return [("increment_aer_" + ch.sfx, self.L.rrtmgpnn_increment_bybnd,
                  (self.ctx.h, self.ncol, self.nlay, ch.ngpt, ch.nband, ch.lims) + ch.props + ch.aer)]
+
+    def _sfc_byband_request(self, ch, dense=False):
+        """A sfc_byband=True step's request, armed right before the all-sky SW solver call beside its mask and aerosol
+        requests: the surface level's band sums into sw_sfc_bnd_* (dense: a mcica["daylit"] step's dense twins)."""
+        if not self.sfc_byband:
+            return []
+        out = ["%ssw_sfc_bnd_%s" % ("d_" if dense else "", k) for k in ("up", "dn", "dir")]
+        return [("sw_sfc_byband", self.L.rrtmgpnn_solver_request_sfc_byband,
+                 (self.ctx.h, ch.nband, ch.lims, self.ncol) + self._p(*out))]
 
     def _jacobian_request(self):
         """A jacobian=True step's request, armed right before the LW solver call (after the chain's other request, which
@@ -830,6 +873,7 @@ class ClearSkyStep:
                 *self._clouds_in(ch),
                 *self._request(ch),
                 *self._aerosol_request(ch),
+                *self._sfc_byband_request(ch),
             ]
             if self.sw_dual:
                 # both flux sets from one call (rrtmgpnn_sw_solver_2stream_rfmip_clr_all): the same requests ahead of
@@ -945,6 +989,15 @@ class ClearSkyStep:
                 (c, ch.ngpt, nlay, ncol, src) + p("cloud_frac") + (p("overlap_param") if exp_ran else ())
                 + p("day_idx", "nday") + (ch.bits,))
         active = lambda name: (name, L.rrtmgpnn_solver_request_active_columns, (c, ncol) + p("nday"))  # noqa: E731
+        sfc_scatter = []
+        if self.sfc_byband:
+            # the surface rows (nband floats) back to their columns, zeros at night: a scatter call of their own
+            sfc = ["sw_sfc_bnd_%s" % k for k in ("up", "dn", "dir")]
+            self._day_sfc_dense = ptr_array(list(p(*["d_" + n for n in sfc])))
+            self._day_sfc_out = ptr_array(list(p(*sfc)))
+            self._day_sfc_rows = int_array([self.nb_sw] * 3)
+            sfc_scatter = [("daylit_scatter_sfc", L.rrtmgpnn_scatter_columns,
+                            (c, ncol, 3, self._day_sfc_dense, self._day_sfc_out, self._day_sfc_rows) + p("day_slot"))]
         return [
             ("daylit_plan", L.rrtmgpnn_daylit_plan, (c, ncol) + p("sza") + (0, bound) + p("day_idx", "day_slot", "nday")),
             *[("daylit_gather" + ("", "2", "3")[k], L.rrtmgpnn_gather_columns, (c, ncol) + t + p("day_idx", "nday"))
@@ -960,11 +1013,13 @@ class ClearSkyStep:
             *([("sw_aerosol", L.rrtmgpnn_solver_request_aerosol, (c, ch.nband, nlay, ncol) + aer)]
               if self.aerosols else []),
             active("sw_active"),
+            *self._sfc_byband_request(ch, dense=True),
             solver("sw_solver", (self.nb_sw, self._lims_sw) + ch.cld, "d_sw_up", "d_sw_dn", "d_sw_dir"),
             *([active("sw_active_clr"), solver("sw_solver_clr", aer_inc, "d_sw_up_clr", "d_sw_dn_clr", "d_sw_dir_clr")]
               if self.clrsky else []),
             ("daylit_scatter", L.rrtmgpnn_scatter_columns,
              (c, ncol, len(dense), self._day_dense, self._day_out, self._day_out_rows) + p("day_slot")),
+            *sfc_scatter,
         ]
 
     def _finish(self, overlap, lw_after=None, sw_after=None, lw_net_cus=None, sw_net_cus=0):
@@ -1303,6 +1358,12 @@ class ClearSkyStep:
         if self.allsky:
             ins += [self.lwp, self.iwp, self.rel, self.rei]
         return ins, [self.lw_up, self.lw_dn, self.sw_up, self.sw_dn, self.sw_dir]
+
+    def sfc_byband_fluxes(self):
+        """Host copies of a sfc_byband step's SW fluxes at the surface by band, (ncol, nband) each."""
+        if not self.sfc_byband:
+            raise ValueError("sfc_byband_fluxes: the step was built without sfc_byband=True")
+        return {k: getattr(self, k).cpu().numpy() for k in ("sw_sfc_bnd_up", "sw_sfc_bnd_dn", "sw_sfc_bnd_dir")}
 
     def byband_fluxes(self):
         """Host copies of a byband step's by-band fluxes, (ncol, nlay+1, nband) each."""
